@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- train-step throughput of the hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,12 @@ clip, SGD-Nesterov) on the reference's own synthetic benchmark batch
 3d_fullres, 6 stages, 31.2 M parameters, 4 modalities, 128^3 patch, fp32, batch 2 per GPU (weak scaling: the global
 batch is 2*N, split by the reference's rule nnUNetTrainer.py:304-349).  Inputs are resident in HBM before the timed
 region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (the headline only).  --full adds what takes runs
+of its own: the roofline kernels (isolated and inside eager steps), the CPU baseline and, for the default fp32
+configs[1] run, the same workload in bf16 (`secondary.bf16`); --no-roofline / --no-cpu-baseline / --no-secondary drop
+parts of it.  --dump-outputs DIR writes what the last timed step produced (dump_outputs) for output-for-output
+comparison of two builds: inputs and initial weights are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -283,6 +289,24 @@ def dominant_kernel_roofline(torch, dev):
     return roof
 
 
+DUMP_PARAM_DRAWS = 1 << 22   # seeded draws of parameter indices (unique ones kept): <= 16 MB of the 125 MB of weights
+
+
+def dump_outputs(directory, net, last):
+    """What the last timed step returned (its loss) and what it left behind (the parameters after its update), as
+    float32 DIR/<name>.npy: `loss.npy` and `params_sample.npy` = the parameters, flattened in net.parameters() order,
+    at the sorted unique indices of DUMP_PARAM_DRAWS draws from np.random.default_rng(0)."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "loss.npy"), np.asarray(last["loss"], dtype=np.float32))
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_PARAM_DRAWS))
+        sample = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    np.save(os.path.join(directory, "params_sample.npy"), sample)
+
+
 def usable_cores():
     """Host cores this process may actually use: CPU affinity capped by the cgroup quota (the GPU box exposes all
     host CPUs to os.cpu_count() but grants a share of them)."""
@@ -363,12 +387,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: roofline kernels, CPU baseline, the bf16 steps of a default run")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's loss and a seeded sample of the updated parameters as DIR/*.npy")
     ap.add_argument("--roofline-only", action="store_true",
                     help="profiling aid: only the isolated launches of the roofline kernels (rocprofv3 --kernel-trace then "
                          "shows the timed layer alone)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the bf16 steps a default (configs[1], fp32) run appends")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the bf16 steps a --full (configs[1], fp32) run appends")
     ap.add_argument("--no-graph", action="store_true", help="A/B aid: eager steps (one launch per kernel) instead of the "
                                                             "hipGraph replay")
     ap.add_argument("--patch", type=int, nargs=3, default=list(PATCH), help="debug only; the metric is quoted at 128^3")
@@ -381,6 +409,8 @@ def main():
                     help="auto = what BASELINE.json names for the config (fp32 for cfg2/cfg3, bf16 for cfg4/cfg5); bf16 = "
                          "bf16 activations on the bf16 MFMA engine, fp32 master weights/statistics/losses/optimizer")
     args = ap.parse_args()
+    if not args.full:   # a plain run measures the headline only
+        args.no_roofline = args.no_cpu_baseline = args.no_secondary = True
     if args.precision == "auto":
         args.precision = "bf16" if args.config in ("cfg4", "cfg5") else "fp32"
     if args.config == "cfg5" and tuple(args.patch) == PATCH:
@@ -453,6 +483,8 @@ def main():
 
     tr = build_trainer(args.config, args.precision)
     dt, last = timed_steps(tr, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr.network, last)
     graphed = tr._step_graph is not None and tr._step_graph.get("graph") is not None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)

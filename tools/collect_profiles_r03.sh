@@ -26,8 +26,8 @@ plain() {  # tag, bench args...
   python3 $ROOT/bench.py "$@" > $OUT/plain_$tag.json 2> $OUT/plain_$tag.err || echo "plain $tag failed"
   tail -1 $OUT/plain_$tag.json | cut -c1-200
 }
-plain default --gpus 1 --steps 20 --warmup 5
-plain bf16 --precision bf16 --steps 20 --warmup 5 --no-cpu-baseline
+plain default --gpus 1 --steps 20 --warmup 5 --full
+plain bf16 --precision bf16 --steps 20 --warmup 5 --full --no-cpu-baseline
 plain cfg3 --config cfg3 --steps 10 --warmup 5 --no-cpu-baseline --no-roofline
 plain cfg4 --config cfg4 --steps 10 --warmup 5 --no-cpu-baseline --no-roofline
 plain cfg5 --config cfg5 --steps 10 --warmup 5 --no-cpu-baseline --no-roofline

@@ -644,10 +644,53 @@ def persistence_fixtures():
     print("wrote persistence_grid.json cc_label.json")
 
 
+# ------------------------------------------------------------------ the cases tests/test_oracle.py once ran the reference on
+def oracle_check_fixtures():
+    """Inputs and outputs of three reference modules (soft_skeleton, robust_ce_loss, network_initialization) and of the
+    reference's C++ persistence extension, on the small cases tests/test_oracle.py pins the oracle to."""
+    g = gen(5)
+    x = torch.rand(1, 2, 9, 8, 7, generator=g)
+    sk = ref_module("training/loss/soft_skeleton.py", "ref_skel_live")
+    skel = {f"skel_iter{it}": sk.soft_skel(x, it) for it in (0, 2, 5)}
+    rce = ref_module("training/loss/robust_ce_loss.py", "ref_rce_live")
+    logits = torch.randn(2, 4, 3, 3, 3, generator=g)
+    tgt = torch.round(torch.rand(2, 1, 3, 3, 3, generator=g) * 3)
+    loss = rce.RobustCrossEntropyLoss()(logits, tgt)
+    init = ref_module("utilities/network_initialization.py", "ref_init_live")
+    torch.manual_seed(11)
+    conv = torch.nn.Conv3d(4, 8, 3)
+    conv.apply(init.InitWeights_He(1e-2))
+    save("reference_modules.npz", source="reference soft_skeleton.py:6-37, robust_ce_loss.py:6-16, "
+                                         "network_initialization.py:4-12", x=x, logits=logits, target=tgt, ce_loss=loss,
+         he_seed=11, he_weight=conv.weight, **skel)
+
+    m = build_ref.load()
+    assert m is not None, "run `python oracle/build_ref.py` first"
+    rng = np.random.default_rng(9)
+    D, H, W = 3, 4, 5
+    f = (np.round(rng.random((D, H, W)) * 8) / 8).astype(np.float32)  # ties on purpose
+    s = m.SimplicialComplex()
+    for i in range(D * H * W):
+        s.append([i])
+    for z in range(D):
+        for y in range(H):
+            for x in range(W):
+                for dz, dy, dx in ((0, 0, 1), (0, 1, 0), (1, 0, 0)):
+                    if z + dz < D and y + dy < H and x + dx < W:
+                        s.append([(z * H + y) * W + x, ((z + dz) * H + y + dy) * W + x + dx])
+    s.initialize()
+    s.extendFloat(torch.from_numpy(f.reshape(-1).copy()))
+    save("ref_persistence_3x4x5.npz", source="reference C++ persistence (hom.cpp) compiled into oracle/_ref", f=f,
+         dgm0=m.persistenceForwardHom(s, 0, 0)[0])
+
+
 if __name__ == "__main__":
     torch.set_num_threads(4)
     if len(sys.argv) > 1 and sys.argv[1] == "extracted":  # only the fixtures compiled out of reference function bodies
         extracted_reference_fixtures()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "oracle-checks":  # only the cases tests/test_oracle.py pins the oracle to
+        oracle_check_fixtures()
         sys.exit(0)
     conv_fixtures()
     instnorm_fixtures()
@@ -657,3 +700,4 @@ if __name__ == "__main__":
     unet_step_fixture()
     mvd_step_fixture()
     persistence_fixtures()
+    oracle_check_fixtures()
