@@ -96,6 +96,32 @@ int mvd_conv3d_fwd_wino_stats(const float *x1, int C1, const float *x2, int C2, 
 int mvd_conv3d_dgrad_wino(const float *dy, const float *wb, const float *ub, float *dx1, int C1, float *dx2, int C2, int N,
                           int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes,
                           void *stream);
+/* F(2x2x2,3x3x3) engine: Winograd F(2,3) along D as well -- 8 multiply-adds per output and channel pair instead of the
+ * 12 of F(2x2,3x3) -- same coefficients (1 and 1/2), same results within fp32 round-off.  It refines the F(2x2,3x3)
+ * engine: mvd_conv_wino3_applicable returns the bits of mvd_conv_wino_applicable for which the 3-D kernel also has
+ * its own minimum of work items PER SAMPLE (4x8x8 voxels x 32 output channels, default 128: the choice does not
+ * depend on the batch size; mvd_set_wino3_min_items, < 0 restores the default) and is on (env MVD_WINO3=0 turns it off; the F(2x2,3x3) entries above keep their meaning in every case).
+ * mvd_pack_weight_wino3: torch weight -> vf (forward) / vb (input gradient), mvd_wino3_weight_elems(C, K) = 64*C*K
+ * floats each.  mvd_pack_weights_batch3: mvd_pack_weights_batch with the 3-D tables vf / vb as well (null entries are
+ * skipped), still one launch.  The *_wino3 conv entries take the 3-D table in place of uf / ub and fall back to the
+ * direct engines (same results) where the 3-D kernel does not run; the statistics epilogue writes the layout of
+ * mvd_conv3d_fwd_wino_stats. */
+int mvd_set_wino3_min_items(long n);
+int mvd_conv_wino3_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]);
+size_t mvd_wino3_weight_elems(int C, int K);
+int mvd_pack_weight_wino3(const float *w, float *vf, float *vb, int K, int C, void *stream);
+int mvd_pack_weights_batch3(int n, const float *const *w, float *const *wf, float *const *wb, float *const *uf,
+                            float *const *ub, float *const *vf, float *const *vb, const int *K, const int *C,
+                            const int *T, const int *transposed, void *stream);
+int mvd_conv3d_fwd_wino3(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *vf,
+                         const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
+                         const int stride[3], void *ws, size_t ws_bytes, void *stream);
+int mvd_conv3d_fwd_wino3_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *vf,
+                               const float *bias, float *y, float *stats, int *stats_done, int N, int D, int H, int W,
+                               int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream);
+int mvd_conv3d_dgrad_wino3(const float *dy, const float *wb, const float *vb, float *dx1, int C1, float *dx2, int C2,
+                           int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
+                           size_t ws_bytes, void *stream);
 size_t mvd_conv3d_wgrad_workspace_bytes(int C, int K, int T, int N, int Do, int Ho, int Wo);
 int mvd_conv3d_wgrad(const float *x1, int C1, const float *x2, int C2, const float *dy, float *dw, float *dbias,
                      int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,

@@ -45,6 +45,17 @@ SIGNATURES = {
                                           _I3, _I3, _P, c_size_t, _P]),
     "mvd_conv3d_dgrad_wino": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
                                       c_size_t, _P]),
+    "mvd_set_wino3_min_items": (c_int, [c_long]),
+    "mvd_conv_wino3_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
+    "mvd_wino3_weight_elems": (c_size_t, [c_int, c_int]),
+    "mvd_pack_weight_wino3": (c_int, [_P, _P, _P, c_int, c_int, _P]),
+    "mvd_pack_weights_batch3": (c_int, [c_int] + [_P] * 11 + [_P]),
+    "mvd_conv3d_fwd_wino3": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
+                                     c_size_t, _P]),
+    "mvd_conv3d_fwd_wino3_stats": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
+                                           _I3, _I3, _P, c_size_t, _P]),
+    "mvd_conv3d_dgrad_wino3": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
+                                       c_size_t, _P]),
     "mvd_conv3d_wgrad_bf16": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
                                       c_size_t, _P]),
     "mvd_convT3d_wgrad_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _P, c_size_t,

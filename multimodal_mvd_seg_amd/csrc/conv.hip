@@ -12,6 +12,14 @@ static int g_engine_mode = 0;  // 0 auto, 1 scalar only
 // MVD_TRANSP=0: transposed convs through the gathered-tap engines (debug / A-B)
 static const int g_transp_off = getenv("MVD_TRANSP") ? (atoi(getenv("MVD_TRANSP")) == 0) : 0;
 static long g_wino_min_items = getenv("MVD_WINO_MIN") ? atol(getenv("MVD_WINO_MIN")) : 256;
+// the F(2x2x2,3x3x3) engine (MVD_WINO3=0: off) takes a Winograd layer when it has at least this many 4x8x8-voxel x
+// 32-channel work items PER SAMPLE (one workgroup per CU).  Per sample, so that the engine of a layer does not depend on
+// the batch size: a data-parallel step (one sample per rank) then runs the engines of the single-process step.
+// Measured it beats k_fwd_wino2 on every stride-1 layer of the flagship down to 16^3 x 256 channels = 128 items per
+// sample
+static const long kWino3MinItemsDefault = 128;
+static long g_wino3_min_items = getenv("MVD_WINO3_MIN") ? atol(getenv("MVD_WINO3_MIN")) : kWino3MinItemsDefault;
+static long wino3_items(int D, int H, int W, int K) { return (long)((D + 3) / 4) * ((H + 7) / 8) * ((W + 7) / 8) * (K / 32); }
 
 // =============================================================================================== scalar forward-type
 // one thread per (n, o, k); k fastest so weight reads and output writes are coalesced and A is a wave broadcast
@@ -303,10 +311,21 @@ static void conv_fwd_geom(FwdGeom &g, int N, int D, int H, int W, int C1, int C2
 
 // u (optional): Winograd-domain weights of mvd_pack_weight_wino for this pass (uf for the forward, ub for the input
 // gradient); used for plain 3x3x3 stride-1 problems with enough tiles to fill the chip, the direct engines otherwise
+// u3d: u is the F(2x2x2,3x3x3) table of mvd_pack_weight_wino3 (the 3-D engine runs when it has enough work items,
+// the direct engines otherwise)
 static int run_fwd(const FwdGeom &g, const float *a1, const float *a2, const float *w, const float *bias, float *y1,
                    float *y2, void *ws, size_t ws_bytes, hipStream_t s, const float *u = nullptr, float *stats = nullptr,
-                   int *stats_done = nullptr) {
+                   int *stats_done = nullptr, bool u3d = false) {
     if (stats_done) *stats_done = 0;
+    if (u3d) {
+        if (g_engine_mode == 0 && u && !g_wino_off && wino3_enabled() &&
+            wino3_items(g.Do, g.Ho, g.Wo, g.K1 + g.K2) >= g_wino3_min_items) {
+            int r = fwd_wino3(g, a1, a2, u, bias, y1, y2, s, stats, stats_done);
+            if (r >= 0) return r;
+            if (stats_done) *stats_done = 0;
+        }
+        u = nullptr;
+    }
     if (g_engine_mode == 0 && u && !g_wino_off) {
         const long tiles = (long)g.N * ((g.Do + 3) / 4) * ((g.Ho + 3) / 4) * ((g.Wo + 7) / 8) * ((g.K1 + g.K2) / 32);
         if (tiles >= g_wino_min_items) {
@@ -383,13 +402,13 @@ size_t mvd_conv_fwd_workspace_bytes(int N, long out_voxels, int K) { return fwd_
 static int conv3d_fwd_impl(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *uf,
                            const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
                            const int stride[3], void *ws, size_t ws_bytes, void *stream, float *stats = nullptr,
-                           int *stats_done = nullptr) {
+                           int *stats_done = nullptr, bool u3d = false) {
     MVD_REQUIRE(x1 && wf && y && C1 > 0 && C2 >= 0 && (C2 == 0 || x2), "conv3d_fwd: null pointer / bad channels");
     MVD_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && K > 0, "conv3d_fwd: bad shape");
     if (check_ks(ksize, stride, "conv3d_fwd")) return 2;
     FwdGeom g;
     conv_fwd_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
-    return run_fwd(g, x1, x2, wf, bias, y, nullptr, ws, ws_bytes, as_stream(stream), uf, stats, stats_done);
+    return run_fwd(g, x1, x2, wf, bias, y, nullptr, ws, ws_bytes, as_stream(stream), uf, stats, stats_done, u3d);
 }
 
 int mvd_conv3d_fwd(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *bias, float *y, int N,
@@ -452,9 +471,62 @@ int mvd_pack_weight_wino(const float *w, float *uf, float *ub, int K, int C, voi
     return pack_weight_wino(w, uf, ub, K, C, as_stream(stream));
 }
 
+// ------------------------------------------------------------------------------------- F(2x2x2,3x3x3) engine (3-D)
+int mvd_set_wino3_min_items(long n) {
+    g_wino3_min_items = n < 0 ? kWino3MinItemsDefault : n;
+    return 0;
+}
+
+int mvd_conv_wino3_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
+    if (!wino3_enabled()) return 0;
+    const int two = mvd_conv_wino_applicable(N, D, H, W, C1, C2, K, ksize, stride);
+    return two & ((wino3_items(D, H, W, K) >= g_wino3_min_items ? 1 : 0) |
+                  (wino3_items(D, H, W, C1 + C2) >= g_wino3_min_items ? 2 : 0));
+}
+
+size_t mvd_wino3_weight_elems(int C, int K) { return (size_t)64 * C * K; }
+
+int mvd_pack_weight_wino3(const float *w, float *uf, float *ub, int K, int C, void *stream) {
+    MVD_REQUIRE(w && (uf || ub) && K > 0 && C > 0, "pack_weight_wino3: bad arguments");
+    MVD_REQUIRE(K % 32 == 0 && C % 32 == 0, "pack_weight_wino3: needs C %% 32 == 0 and K %% 32 == 0");
+    return pack_weight_wino3(w, uf, ub, K, C, as_stream(stream));
+}
+
+int mvd_pack_weights_batch3(int n, const float *const *w, float *const *wf, float *const *wb, float *const *uf,
+                            float *const *ub, float *const *vf, float *const *vb, const int *K, const int *C,
+                            const int *T, const int *transposed, void *stream) {
+    MVD_REQUIRE(n > 0 && w && wf && wb && uf && ub && vf && vb && K && C && T && transposed,
+                "pack_weights_batch3: null table");
+    for (int q = 0; q < n; q++) {
+        MVD_REQUIRE(w[q] && (wf[q] || wb[q] || uf[q] || ub[q] || vf[q] || vb[q]),
+                    "pack_weights_batch3: job without source or destination");
+        MVD_REQUIRE(K[q] > 0 && C[q] > 0 && T[q] > 0 && T[q] <= MVD_MAX_TAPS, "pack_weights_batch3: bad K / C / T");
+        if (uf[q] || ub[q]) MVD_REQUIRE(wino_mode() == 2, "pack_weights_batch3: Winograd tables need MVD_WINO=2");
+        if (uf[q] || ub[q] || vf[q] || vb[q])
+            MVD_REQUIRE(T[q] == 27 && !transposed[q] && K[q] % 32 == 0 && C[q] % 32 == 0,
+                        "pack_weights_batch3: Winograd tables need a 3x3x3 conv with C %% 32 == 0 and K %% 32 == 0");
+    }
+    return pack_weights_batch(n, w, wf, wb, uf, ub, K, C, T, transposed, as_stream(stream), vf, vb);
+}
+
+int mvd_conv3d_fwd_wino3(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *vf,
+                         const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
+                         const int stride[3], void *ws, size_t ws_bytes, void *stream) {
+    return conv3d_fwd_impl(x1, C1, x2, C2, wf, vf, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, nullptr,
+                           nullptr, true);
+}
+
+int mvd_conv3d_fwd_wino3_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *vf,
+                               const float *bias, float *y, float *stats, int *stats_done, int N, int D, int H, int W,
+                               int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {
+    MVD_REQUIRE(stats_done, "conv3d_fwd_wino3_stats: stats_done is required");
+    return conv3d_fwd_impl(x1, C1, x2, C2, wf, vf, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, stats,
+                           stats_done, true);
+}
+
 static int conv3d_dgrad_impl(const float *dy, const float *wb, const float *ub, float *dx1, int C1, float *dx2, int C2,
                              int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
-                             size_t ws_bytes, void *stream);
+                             size_t ws_bytes, void *stream, bool u3d = false);
 
 int mvd_conv3d_dgrad(const float *dy, const float *wb, float *dx1, int C1, float *dx2, int C2, int N, int D, int H, int W,
                      int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {
@@ -467,9 +539,15 @@ int mvd_conv3d_dgrad_wino(const float *dy, const float *wb, const float *ub, flo
     return conv3d_dgrad_impl(dy, wb, ub, dx1, C1, dx2, C2, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream);
 }
 
+int mvd_conv3d_dgrad_wino3(const float *dy, const float *wb, const float *vb, float *dx1, int C1, float *dx2, int C2,
+                           int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
+                           size_t ws_bytes, void *stream) {
+    return conv3d_dgrad_impl(dy, wb, vb, dx1, C1, dx2, C2, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, true);
+}
+
 static int conv3d_dgrad_impl(const float *dy, const float *wb, const float *ub, float *dx1, int C1, float *dx2, int C2,
                              int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
-                             size_t ws_bytes, void *stream) {
+                             size_t ws_bytes, void *stream, bool u3d) {
     MVD_REQUIRE(dy && wb && dx1 && C1 > 0 && C2 >= 0 && (C2 == 0 || dx2), "conv3d_dgrad: null pointer / bad channels");
     MVD_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && K > 0, "conv3d_dgrad: bad shape");
     if (check_ks(ksize, stride, "conv3d_dgrad")) return 2;
@@ -529,7 +607,8 @@ static int conv3d_dgrad_impl(const float *dy, const float *wb, const float *ub, 
                 g.ntaps = nt;
                 g.T = ksize[0] * ksize[1] * ksize[2];
                 if (nt == 0) continue;
-                int r = run_fwd(g, dy, nullptr, wb, nullptr, dx1, dx2, ws, ws_bytes, as_stream(stream), ub);
+                int r = run_fwd(g, dy, nullptr, wb, nullptr, dx1, dx2, ws, ws_bytes, as_stream(stream), ub, nullptr, nullptr,
+                                u3d);
                 if (r) return r;
             }
     return 0;

@@ -81,6 +81,12 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
 int fwd_wino(const FwdGeom &g, const float *a1, const float *a2, const float *u, const float *bias, float *y1, float *y2,
              hipStream_t s, float *stats = nullptr, int *stats_done = nullptr);
 int pack_weight_wino(const float *w, float *uf, float *ub, int K, int C, hipStream_t s);
+// F(2x2x2,3x3x3) engine (conv_wino3.hip): same contract as fwd_wino with the 3-D table of pack_weight_wino3
+// (64*C*K floats); the statistics come out in the same 4x4x8-tile layout
+int fwd_wino3(const FwdGeom &g, const float *a1, const float *a2, const float *u, const float *bias, float *y1, float *y2,
+              hipStream_t s, float *stats = nullptr, int *stats_done = nullptr);
+int pack_weight_wino3(const float *w, float *uf, float *ub, int K, int C, hipStream_t s);
+int wino3_enabled();  // MVD_WINO3: 0 off, 1 (default) on
 int dgrad32s(int N, int D, int H, int W, int C, int K, int Do, int Ho, int Wo, const float *dy, const float *wb, float *dx,
              hipStream_t s, int accumulate = 0);
 // bf16 twin (conv_bf16.hip): all eight parity classes of a 3x3x3 stride-2 conv's input gradient from one staged dy tile
@@ -104,7 +110,8 @@ int wgrad16zs(const WgradGeom &g, const unsigned short *a1, const unsigned short
               size_t ws_bytes, int *nsplit_out, hipStream_t s);
 void wgrad16z_enable(int on);
 int pack_weights_batch(int n, const float *const *w, float *const *wf, float *const *wb, float *const *uf, float *const *ub,
-                       const int *K, const int *C, const int *T, const int *transposed, hipStream_t s);
+                       const int *K, const int *C, const int *T, const int *transposed, hipStream_t s,
+                       float *const *vf = nullptr, float *const *vb = nullptr);
 int wino_mode();                          // MVD_WINO: 0 off, 1 F(2,3) along W, 2 F(2x2,3x3) (default)
 size_t wino_weight_elems(int C, int K);   // floats of one uf / ub buffer in the active mode
 

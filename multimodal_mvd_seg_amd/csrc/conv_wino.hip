@@ -20,6 +20,7 @@
 //   * the output transform runs on the accumulators in the epilogue; bias is added there.
 #include "common.h"
 #include "conv_geom.h"
+#include "wino_common.h"
 
 namespace mvd {
 
@@ -312,12 +313,12 @@ __global__ void k_pack_wino2(const float *__restrict__ w, float *__restrict__ uf
 // scalar scan over the (at most PACK_MAX_JOBS) block ranges.
 struct PackJob {
     const float *w;
-    float *wf, *wb, *uf, *ub;
+    float *wf, *wb, *uf, *ub, *vf, *vb;  // vf / vb: the F(2x2x2,3x3x3) tables (conv_wino3.hip)
     int K, C, T, transposed;
     unsigned blk_begin;
     int tiled;  // 1: 3x3x3 conv with C % 32 == 0 and K % 32 == 0 -> one workgroup per 16 k x 16 c tile (through LDS)
 };
-constexpr int PACK_MAX_JOBS = 48;
+constexpr int PACK_MAX_JOBS = 44;  // 88-byte jobs: the batch stays inside the 4 KB kernel-argument segment
 struct PackBatch {
     int n;
     PackJob j[PACK_MAX_JOBS];
@@ -390,11 +391,14 @@ __global__ __launch_bounds__(256) void k_pack_batch(const PackBatch pb) {
             }
         }
     }
+    if (J.vf || J.vb) pack_wino3_tile(tile, J.vf, J.vb, K, C, k0, c0, tid);
 }
 
-// jobs: host arrays of n entries.  uf / ub entries may be null (no Winograd pack for that layer).
+// jobs: host arrays of n entries.  uf / ub / vf / vb entries may be null (no Winograd pack of that kind for that layer);
+// vf / vb themselves may be null (no 3-D tables at all).
 int pack_weights_batch(int n, const float *const *w, float *const *wf, float *const *wb, float *const *uf, float *const *ub,
-                       const int *K, const int *C, const int *T, const int *transposed, hipStream_t s) {
+                       const int *K, const int *C, const int *T, const int *transposed, hipStream_t s,
+                       float *const *vf, float *const *vb) {
     int done = 0;
     while (done < n) {
         PackBatch pb;
@@ -405,6 +409,7 @@ int pack_weights_batch(int n, const float *const *w, float *const *wf, float *co
             const int q = done + m;
             PackJob &J = pb.j[m];
             J.w = w[q]; J.wf = wf[q]; J.wb = wb[q]; J.uf = uf[q]; J.ub = ub[q];
+            J.vf = vf ? vf[q] : nullptr; J.vb = vb ? vb[q] : nullptr;
             J.K = K[q]; J.C = C[q]; J.T = T[q]; J.transposed = transposed[q];
             J.blk_begin = blocks;
             J.tiled = (J.T == 27 && !J.transposed && J.K % 32 == 0 && J.C % 32 == 0) ? 1 : 0;
@@ -430,42 +435,11 @@ __device__ inline float4 f4_axpy(float s, const float4 b, const float4 a) {  // 
 __device__ inline float4 f4_sub(const float4 a, const float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ inline float4 f4_add(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
-// Packed fp32 VALU through inline asm.  On gfx950 every fp32 VALU instruction takes ~3 cycles away from the fp32 MFMA
-// pipe of its SIMD (tools/probes/valu_mix_probe.hip: they do not overlap, not even across waves), so the input transform
-// is written with v_pk_fma_f32 / v_pk_add_f32 on the register pairs ds_read_b128 delivers -- 16 instead of 32 VALU
-// instructions per 16 MFMAs.  Plain <2 x float> arithmetic does not survive: the backend's pre-emit peephole unpacks
-// packed F32 instructions it finds behind an MFMA.
-// HAZARD: a VALU write needs 2 wait states before an MFMA reads the register as SrcA/B, and the compiler's hazard
-// recognizer does not look inside inline asm -- hence the trailing s_nop 1 of every block whose results feed MFMAs.
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-// One half (two of the four channels of a float4) of the F(2x2,3x3) input transform of a step:
-//   R_c = a_c + sg * b_c (c = 0..3: the four patch columns);  V0 = R0 - R2, V1 = R1 + R2, V2 = R2 - R1, V3 = R1 - R3
-// in place: a0 -> V0, a2 -> V2, a3 -> V3; V1 is returned (a1 is consumed as scratch for R1).
-__device__ __forceinline__ v2f wino2_input_transform(v2f sg, v2f &a0, v2f a1, v2f &a2, v2f &a3, v2f b0, v2f b1, v2f b2,
-                                                     v2f b3) {
-    v2f t;
-    asm("v_pk_fma_f32 %0, %5, %6, %0\n\t"
-        "v_pk_fma_f32 %1, %5, %7, %1\n\t"
-        "v_pk_fma_f32 %2, %5, %8, %2\n\t"
-        "v_pk_fma_f32 %3, %5, %9, %3\n\t"
-        "v_pk_add_f32 %0, %0, %2 neg_lo:[0,1] neg_hi:[0,1]\n\t"  // V0 = R0 - R2
-        "v_pk_add_f32 %3, %1, %3 neg_lo:[0,1] neg_hi:[0,1]\n\t"  // V3 = R1 - R3
-        "v_pk_add_f32 %4, %1, %2\n\t"                            // V1 = R1 + R2
-        "v_pk_add_f32 %2, %2, %1 neg_lo:[0,1] neg_hi:[0,1]\n\t"  // V2 = R2 - R1
-        "s_nop 1"
-        : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=&v"(t)
-        : "v"(sg), "v"(b0), "v"(b1), "v"(b2), "v"(b3));
-    return t;
-}
-
 #ifndef MVD_W2B
 #define MVD_W2B 12
 #endif
 constexpr int W2B = MVD_W2B;  // staging loads in flight per thread before the LDS stores
 constexpr int W2EH = 6, W2EW = 10, W2EHW = 60;  // halo of the 4 x 4 x 8 tile: 6 x 6 x 10 slots
-__device__ __forceinline__ constexpr int w2_coff(int c) { return (c >> 1) + 5 * (c & 1); }  // slot offset of patch column c
 
 #ifndef MVD_WINO_DBG
 #define MVD_WINO_DBG 0

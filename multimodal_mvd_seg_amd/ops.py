@@ -158,7 +158,7 @@ def _check_pack_generation(saved, what):
 
 
 class _PackEntry:
-    __slots__ = ("transposed", "K", "C", "T", "wf", "wb", "uf", "ub", "stamp", "gen")
+    __slots__ = ("transposed", "K", "C", "T", "wf", "wb", "uf", "ub", "vf", "vb", "stamp", "gen")
 
 
 def _flat_of(w, owner=None):
@@ -173,20 +173,26 @@ def _pack_stamp(w, owner=None):
             flat._version if flat is not None else -1)
 
 
-def _packed(weight, transposed, want_uf=False, want_ub=False):
+def _packed(weight, transposed, want_uf=False, want_ub=False, want_vf=False, want_vb=False):
+    """uf / ub: the F(2x2,3x3) tables (mvd_pack_weight_wino), vf / vb: the F(2x2x2,3x3x3) tables (mvd_pack_weight_wino3)."""
     w = weight.detach()
     if not w.is_contiguous():  # no cache for a strided view: pack a contiguous copy
         e = _PackEntry()
         e.gen = 0
         e.wf, e.wb = pack_weight(weight, transposed)
-        e.uf = e.ub = None
+        e.uf = e.ub = e.vf = e.vb = None
+        wc = w.contiguous()
+        K, C = wc.shape[:2]
         if want_uf or want_ub:
-            wc = w.contiguous()
-            K, C = wc.shape[:2]
             n = query("mvd_wino_weight_elems", C, K)
             e.uf = torch.empty((n,), dtype=torch.float32, device=w.device) if want_uf else None
             e.ub = torch.empty((n,), dtype=torch.float32, device=w.device) if want_ub else None
             call("mvd_pack_weight_wino", _p(wc), _p(e.uf), _p(e.ub), K, C, _stream())
+        if want_vf or want_vb:
+            n = query("mvd_wino3_weight_elems", C, K)
+            e.vf = torch.empty((n,), dtype=torch.float32, device=w.device) if want_vf else None
+            e.vb = torch.empty((n,), dtype=torch.float32, device=w.device) if want_vb else None
+            call("mvd_pack_weight_wino3", _p(wc), _p(e.vf), _p(e.vb), K, C, _stream())
         return e
     e = getattr(weight, "_mvd_pack", None)
     stale = False
@@ -200,7 +206,7 @@ def _packed(weight, transposed, want_uf=False, want_ub=False):
         e.T = w[0, 0].numel()
         e.wf = torch.empty((e.T, e.C, e.K), dtype=torch.float32, device=w.device)
         e.wb = torch.empty((e.T, e.K, e.C), dtype=torch.float32, device=w.device)
-        e.uf = e.ub = None
+        e.uf = e.ub = e.vf = e.vb = None
         e.stamp = None
         e.gen = 0
         weight._mvd_pack = e
@@ -216,13 +222,24 @@ def _packed(weight, transposed, want_uf=False, want_ub=False):
         if want_ub and e.ub is None:
             e.ub = torch.empty((n,), dtype=torch.float32, device=w.device)
         new_wino = True
+    new_wino3 = False
+    if (want_vf and e.vf is None) or (want_vb and e.vb is None):
+        n = query("mvd_wino3_weight_elems", e.C, e.K)
+        if want_vf and e.vf is None:
+            e.vf = torch.empty((n,), dtype=torch.float32, device=w.device)
+        if want_vb and e.vb is None:
+            e.vb = torch.empty((n,), dtype=torch.float32, device=w.device)
+        new_wino3 = True
     if stale or e.stamp != _pack_stamp(w, weight):
-        e.gen += 1  # wf / wb / uf / ub are overwritten in place
+        e.gen += 1  # wf / wb / uf / ub / vf / vb are overwritten in place
         call("mvd_pack_weight", _p(w), _p(e.wf), _p(e.wb), e.K, e.C, e.T, 1 if transposed else 0, _stream())
         new_wino = e.uf is not None or e.ub is not None
+        new_wino3 = e.vf is not None or e.vb is not None
         e.stamp = _pack_stamp(w, weight)
     if new_wino:
         call("mvd_pack_weight_wino", _p(w), _p(e.uf), _p(e.ub), e.K, e.C, _stream())
+    if new_wino3:
+        call("mvd_pack_weight_wino3", _p(w), _p(e.vf), _p(e.vb), e.K, e.C, _stream())
     return e
 
 
@@ -343,13 +360,15 @@ def repack_all(fp=None):
     wb_ = PA(*[ptr(e.wb) for _, e, _w in jobs])
     uf_ = PA(*[ptr(e.uf) for _, e, _w in jobs])
     ub_ = PA(*[ptr(e.ub) for _, e, _w in jobs])
+    vf_ = PA(*[ptr(e.vf) for _, e, _w in jobs])
+    vb_ = PA(*[ptr(e.vb) for _, e, _w in jobs])
     K_ = IA(*[e.K for _, e, _w in jobs])
     C_ = IA(*[e.C for _, e, _w in jobs])
     T_ = IA(*[e.T for _, e, _w in jobs])
     tr_ = IA(*[1 if e.transposed else 0 for _, e, _w in jobs])
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    call("mvd_pack_weights_batch", n, cast(w_), cast(wf_), cast(wb_), cast(uf_), cast(ub_), cast(K_), cast(C_), cast(T_),
-         cast(tr_), _stream())
+    call("mvd_pack_weights_batch3", n, cast(w_), cast(wf_), cast(wb_), cast(uf_), cast(ub_), cast(vf_), cast(vb_), cast(K_),
+         cast(C_), cast(T_), cast(tr_), _stream())
     for d, e, w in jobs:
         e.stamp = _pack_stamp(d, w)
         e.gen += 1
@@ -504,19 +523,25 @@ class Conv3dFn(Function):
         else:
             # fp32 3x3x3 stride-1 layers with enough tiles run the Winograd kernels (4/9 of the MFMA work); the packed
             # weights come from the per-weight cache (re-packed once per optimizer step, see repack_all)
+            # F(2x2x2,3x3x3) (mvd_conv_wino3_applicable: 2/3 of the F(2x2,3x3) MFMA work) where it has enough work items,
+            # F(2x2,3x3) on the other Winograd layers, the direct engines on the rest
             wino = query("mvd_conv_wino_applicable", N, D, H, W, C1, C2, K, i3(ks), i3(stride)) if len(ks) == 3 else 0
-            pk = _packed(weight, False, bool(wino & 1), bool(wino & 2))
+            wino3 = query("mvd_conv_wino3_applicable", N, D, H, W, C1, C2, K, i3(ks), i3(stride)) if wino else 0
+            wino2 = wino & ~wino3
+            pk = _packed(weight, False, bool(wino2 & 1), bool(wino2 & 2), bool(wino3 & 1), bool(wino3 & 2))
             wf, wb = pk.wf, pk.wb
-            uf = pk.uf if wino & 1 else None
-            ub = pk.ub if wino & 2 else None
+            uf = pk.vf if wino3 & 1 else (pk.uf if wino2 & 1 else None)
+            ub = pk.vb if wino3 & 2 else (pk.ub if wino2 & 2 else None)
+            sfx3 = "3" if wino3 & 1 else ""
+            ctx.ub3 = bool(wino3 & 2)
             if uf is not None:
                 # the Winograd kernel also emits the per-tile (sum, sum of squares) of its output: the InstanceNorm that
                 # follows (InstanceNormLeakyReLUFn picks them up from the tensor) skips its statistics pass
                 ntiles = query("mvd_conv_stats_tiles", od[0], od[1], od[2])
                 stats = torch.empty((N, ntiles, K, 2), dtype=torch.float32, device=x1.device)
                 done = ctypes.c_int(0)
-                call("mvd_conv3d_fwd_wino_stats", _p(x1), C1, _p(x2), C2, _p(wf), _p(uf), _p(bias), _p(y), _p(stats),
-                     ctypes.byref(done), N, D, H, W, K, i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
+                call("mvd_conv3d_fwd_wino" + sfx3 + "_stats", _p(x1), C1, _p(x2), C2, _p(wf), _p(uf), _p(bias), _p(y),
+                     _p(stats), ctypes.byref(done), N, D, H, W, K, i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
                 if done.value:
                     y._mvd_tile_stats = (stats, ntiles)
             else:
@@ -570,8 +595,8 @@ class Conv3dFn(Function):
                 call("mvd_conv3d_dgrad_bf16", _p(dy), _p(wb), _p(dx1), C1, _p(dx2), C2, N, D, H, W, K, i3(ks), i3(stride),
                      _p(ws), ws.numel(), _stream())
             else:
-                call("mvd_conv3d_dgrad_wino", _p(dy), _p(wb), _p(ub), _p(dx1), C1, _p(dx2), C2, N, D, H, W, K, i3(ks),
-                     i3(stride), _p(ws), ws.numel(), _stream())
+                call("mvd_conv3d_dgrad_wino3" if ctx.ub3 else "mvd_conv3d_dgrad_wino", _p(dy), _p(wb), _p(ub), _p(dx1), C1,
+                     _p(dx2), C2, N, D, H, W, K, i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
             if need1:
                 _publish(ctx.share1, dx1)
             if need2:
