@@ -122,6 +122,15 @@ int mvd_conv3d_fwd_wino3_stats(const float *x1, int C1, const float *x2, int C2,
 int mvd_conv3d_dgrad_wino3(const float *dy, const float *wb, const float *vb, float *dx1, int C1, float *dx2, int C2,
                            int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
                            size_t ws_bytes, void *stream);
+/* F(2x2x2,3x3x3) weight gradient: mvd_conv3d_wgrad runs it for fp32 3x3x3 stride-1 convs with 32-multiple channels
+ * (two inputs included) that have at least the minimum of work items PER SAMPLE (2x8x8 dy voxels x 32 input x 32
+ * output channels; mvd_set_wgrad_wino3_min_items, < 0 restores the default) unless MVD_WGRAD_WINO3=0 or MVD_WINO=0.
+ * mvd_conv_wgrad_wino3_applicable: 1 when it would run for that shape, else 0.  mvd_wgrad_wino3_launches: its launches
+ * since the library was loaded (a workspace too small for it falls back to F(2x2,3x3) without an error). */
+int mvd_set_wgrad_wino3_min_items(long n);
+int mvd_conv_wgrad_wino3_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3],
+                                    const int stride[3]);
+long mvd_wgrad_wino3_launches(void);
 size_t mvd_conv3d_wgrad_workspace_bytes(int C, int K, int T, int N, int Do, int Ho, int Wo);
 int mvd_conv3d_wgrad(const float *x1, int C1, const float *x2, int C2, const float *dy, float *dw, float *dbias,
                      int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,

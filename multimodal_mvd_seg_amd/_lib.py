@@ -56,6 +56,9 @@ SIGNATURES = {
                                            _I3, _I3, _P, c_size_t, _P]),
     "mvd_conv3d_dgrad_wino3": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
                                        c_size_t, _P]),
+    "mvd_set_wgrad_wino3_min_items": (c_int, [c_long]),
+    "mvd_conv_wgrad_wino3_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
+    "mvd_wgrad_wino3_launches": (c_long, []),
     "mvd_conv3d_wgrad_bf16": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
                                       c_size_t, _P]),
     "mvd_convT3d_wgrad_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _P, c_size_t,

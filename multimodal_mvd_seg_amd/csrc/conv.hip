@@ -648,6 +648,23 @@ size_t mvd_conv3d_wgrad_workspace_bytes(int C, int K, int T, int N, int Do, int 
     return max_sz(a, colsum_ws((long)N * Do * Ho * Wo, K));
 }
 
+int mvd_set_wgrad_wino3_min_items(long n) {
+    set_wgrad_wino3_min_items(n);
+    return 0;
+}
+
+int mvd_conv_wgrad_wino3_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3],
+                                    const int stride[3]) {
+    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || K <= 0 || !ksize || !stride) return 0;
+    for (int a = 0; a < 3; a++)
+        if (ksize[a] != 3 || stride[a] != 1) return 0;
+    WgradGeom g;
+    conv_wgrad_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
+    return wgrad_wino3_selected(g) ? 1 : 0;
+}
+
+long mvd_wgrad_wino3_launches(void) { return wgrad_wino3_launches(); }
+
 int mvd_conv3d_wgrad(const float *x1, int C1, const float *x2, int C2, const float *dy, float *dw, float *dbias, int N,
                      int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes,
                      void *stream) {

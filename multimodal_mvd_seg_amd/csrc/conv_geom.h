@@ -113,6 +113,18 @@ int pack_weights_batch(int n, const float *const *w, float *const *wf, float *co
                        const int *K, const int *C, const int *T, const int *transposed, hipStream_t s,
                        float *const *vf = nullptr, float *const *vb = nullptr);
 int wino_mode();                          // MVD_WINO: 0 off, 1 F(2,3) along W, 2 F(2x2,3x3) (default)
+// F(2x2x2,3x3x3) weight gradient (conv_wgrad_wino3.hip): plain 3x3x3 stride-1 conv, 32-multiple channels; -1 = not
+// run (shape, workspace), else the contract of wgrad_mfma.  wgrad_wino3_selected: the engine is on and the layer has the
+// minimum of work items per sample; wgrad_wino3_ws: partials + bias rows for nsplit splits
+int wgrad_wino3(const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws, size_t ws_bytes,
+                int nsplit, hipStream_t s, float *dbias, int *dbias_done);
+bool wgrad_wino3_selected(const WgradGeom &g);
+size_t wgrad_wino3_ws(int nsplit, int C, int K);
+int wgrad_wino3_enabled();  // MVD_WGRAD_WINO3: 0 off, 1 (default) on
+void set_wgrad_wino3_min_items(long n);
+long wgrad_wino3_launches();  // launches of k_wgrad_wino3 since the library was loaded
+// dbias[k] = fp64 sum of the rows pbias[0..nrows)[k] in a fixed order (k_dbias_reduce, conv_mfma.hip)
+int dbias_reduce(const float *pbias, float *dbias, int K, int nrows, hipStream_t s);
 size_t wino_weight_elems(int C, int K);   // floats of one uf / ub buffer in the active mode
 
 // ConvTranspose3d (kernel == stride) as LDS-free GEMMs (conv_transp.hip); -1 = shape not covered

@@ -1999,6 +1999,11 @@ __global__ __launch_bounds__(1024) void k_dbias_reduce(const float *__restrict__
     dbias[k] = (float)t;
 }
 
+int dbias_reduce(const float *pbias, float *dbias, int K, int nrows, hipStream_t s) {
+    hipLaunchKernelGGL(k_dbias_reduce, dim3(cdiv(K, 64)), dim3(1024), 0, s, pbias, dbias, K, nrows);
+    return check_launch("conv wgrad dbias reduce");
+}
+
 template <int NA, int NB>
 __global__ __launch_bounds__(256, 1) void k_wgrad_wino2(const WgradGeom g, const WgTile tg, const float *__restrict__ a1,
                                                         const float *__restrict__ a2, const float *__restrict__ b,
@@ -2773,7 +2778,14 @@ static bool wgrad_mfma_ok(const WgradGeom &g) {
 size_t wgrad_mfma_ws(const WgradGeom &g) {
     if (!wgrad_mfma_ok(g)) return 0;
     // split-K partials + the bias-gradient rows (two lane halves per partial)
-    return (size_t)wgrad_max_split(g) * (g.ntaps * (size_t)(g.C1 + g.C2) + 2) * g.K * sizeof(float) + 256;
+    size_t ws = (size_t)wgrad_max_split(g) * (g.ntaps * (size_t)(g.C1 + g.C2) + 2) * g.K * sizeof(float) + 256;
+    // the F(2x2x2,3x3x3) kernel: 64 positions at the fp32 split count (one workgroup per CU)
+    const int C = g.C1 + g.C2;
+    if (g.ntaps == 27 && C % 32 == 0 && g.K % 32 == 0) {
+        const size_t w3 = wgrad_wino3_ws(wgrad_max_split(g, 1), C, g.K) + 256;
+        if (w3 > ws) ws = w3;
+    }
+    return ws;
 }
 
 // k_wgrad16z + the split reduce.  -1 = not that kernel's problem.  in_scale / in_shift (optional, [N][C1] fp32): the loader
@@ -3022,6 +3034,10 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
         for (int t = 0; t < 27 && plain; t++)
             plain = g.wt[t] == t && g.off[t][0] == t / 9 - 1 && g.off[t][1] == (t / 3) % 3 - 1 && g.off[t][2] == t % 3 - 1 &&
                     g.ob[t][0] == 0 && g.ob[t][1] == 0 && g.ob[t][2] == 0;
+        if (plain && wgrad_wino3_selected(g)) {  // F(2x2x2,3x3x3): 64 positions over octets (conv_wgrad_wino3.hip)
+            const int r3 = wgrad_wino3(g, a1, a2, b, dw, ws, ws_bytes, wgrad_max_split(g, 1), s, dbias, dbias_done);
+            if (r3 >= 0) return r3;
+        }
         const size_t need_w = (size_t)tg.nsplit * 36 * C * g.K * sizeof(float);
         if (plain && need_w <= ws_bytes) {
             // Winograd F(2,3)-transposed weight gradient: 36 position tiles over pairs instead of 27 taps over voxels
