@@ -503,6 +503,24 @@ int mvd_feed_crop_pad_seg_i16(const int16_t *seg, float *out, int C, int D, int 
  * nearest neighbour == skimage.transform.resize(order=0) == scipy.ndimage.zoom(order=0, grid_mode=True)) */
 int mvd_feed_downsample_seg(const float *in, float *out, long BC, int D, int H, int W, int d, int h, int w, void *stream);
 
+/* SpatialTransform of the feed (nnUNetTrainer.py:703-714: batchgenerators augment_spatial, rotation + scaling, order 3
+ * data / order 1 seg, border mode 'constant'), on the initial patch [C][D][H][W] cut by mvd_feed_crop_pad_* (data pad 0,
+ * seg pad -1).  Pinned to scipy.ndimage.
+ * mvd_feed_bspline_prefilter_f32: in place, spline_filter1d(order=3, mode='mirror') along the axes of axis_mask (bit 0:
+ *   D, 1: H, 2: W; W <= 16383), all C channels per launch; a length-1 axis is left unchanged.
+ * mvd_feed_warp_data_f32: out[C][fd][fh][fw] = map_coordinates(coef, p, order=3, mode='constant', cval) with coef the
+ *   prefiltered patch and p(o) = A (o - (f-1)/2) + off; affine12 is a HOST array {A row-major (9), off (3)} copied into
+ *   the kernel arguments (no device copy: the call is capturable).  flip_mask mirrors the OUTPUT (MirrorTransform).
+ * mvd_feed_warp_seg: the same p with 8 linear taps: out = the largest label whose indicator reaches 0.5, 0 where none
+ *   does and outside [0, n-1] (interpolate_img(order=1, cval=-1, is_seg=True)); then replace_from -> replace_to when
+ *   `replace` != 0 (RemoveLabelTransform(-1, 0)).  seg holds integer labels as float32. */
+int mvd_feed_bspline_prefilter_f32(float *x, int C, int D, int H, int W, int axis_mask, void *stream);
+int mvd_feed_warp_data_f32(const float *coef, float *out, int C, int D, int H, int W, int fd, int fh, int fw,
+                           const double *affine12, int flip_mask, float cval, void *stream);
+int mvd_feed_warp_seg(const float *seg, float *out, int C, int D, int H, int W, int fd, int fh, int fw,
+                      const double *affine12, int flip_mask, int replace, int replace_from, int replace_to,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

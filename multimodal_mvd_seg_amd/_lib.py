@@ -166,6 +166,9 @@ SIGNATURES = {
     "mvd_feed_crop_pad_f32": (c_int, [_P, _P] + [c_int] * 11 + [c_float, _P]),
     "mvd_feed_crop_pad_seg_i16": (c_int, [_P, _P] + [c_int] * 15 + [_P]),
     "mvd_feed_downsample_seg": (c_int, [_P, _P, c_long] + [c_int] * 6 + [_P]),
+    "mvd_feed_bspline_prefilter_f32": (c_int, [_P] + [c_int] * 5 + [_P]),
+    "mvd_feed_warp_data_f32": (c_int, [_P, _P] + [c_int] * 7 + [_P, c_int, c_float, _P]),
+    "mvd_feed_warp_seg": (c_int, [_P, _P] + [c_int] * 7 + [_P] + [c_int] * 4 + [_P]),
 }
 
 _lib = None

@@ -22,9 +22,13 @@ import torch.distributed as dist
 from torch import nn
 
 from . import losses, ops
+from .dataloading import DeviceDataLoader3D, get_patch_size
 from .network import InitWeights_He, MI355PlainConvUNet, MVDDualBranchNet, set_precision
 from .optim import FlatParams, FusedSGDNesterov, PolyLRScheduler
 from .parallel import BucketedGradReducer, broadcast_parameters, ddp_batch_split
+
+
+ANISO_THRESHOLD = 3  # configuration.py:7
 
 
 # ------------------------------------------------------------------------------------------------ plans (input contract)
@@ -330,6 +334,38 @@ class nnUNetTrainerMI355(object):
         if not captured_now:
             self.optimizer.note_replayed_step()
         return sg['loss']
+
+    # -- training feed (nnUNetTrainer.py:377-434 and :600-630, fed from HBM by dataloading.DeviceDataLoader3D) ----
+    def configure_rotation_dummyDA_mirroring_and_inital_patch_size(self):
+        """The 3-D branch of nnUNetTrainer.py:377-434 (ANISO_THRESHOLD = 3, configuration.py:7)."""
+        patch_size = self.configuration_manager.patch_size
+        dim = len(patch_size)
+        if dim != 3:
+            raise NotImplementedError("configure_rotation_dummyDA_mirroring_and_inital_patch_size: 3-D plans only")
+        do_dummy_2d_data_aug = (max(patch_size) / patch_size[0]) > ANISO_THRESHOLD
+        if do_dummy_2d_data_aug:
+            rotation_for_DA = {'x': (-180. / 360 * 2. * np.pi, 180. / 360 * 2. * np.pi), 'y': (0, 0), 'z': (0, 0)}
+        else:
+            rotation_for_DA = {ax: (-30. / 360 * 2. * np.pi, 30. / 360 * 2. * np.pi) for ax in ('x', 'y', 'z')}
+        mirror_axes = (0, 1, 2)
+        # the reference sizes the initial patch with (0.85, 1.25), not the (0.7, 1.4) the transform draws from
+        initial_patch_size = get_patch_size(patch_size[-dim:], *rotation_for_DA.values(), (0.85, 1.25))
+        if do_dummy_2d_data_aug:
+            initial_patch_size[0] = patch_size[0]
+        self.inference_allowed_mirroring_axes = mirror_axes
+        return rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, mirror_axes
+
+    def get_device_dataloader(self, dataset_tr, device=None):
+        """The training loader of get_dataloaders (:600-630) with its transforms' geometric part on the device: initial
+        patch, SpatialTransform (rotation, scaling 0.7-1.4), mirroring, RemoveLabel and the deep-supervision targets."""
+        rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, mirror_axes = \
+            self.configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+        return DeviceDataLoader3D(dataset_tr, self.batch_size, [int(i) for i in initial_patch_size],
+                                  self.configuration_manager.patch_size, self.label_manager,
+                                  oversample_foreground_percent=self.oversample_foreground_percent,
+                                  mirror_axes=mirror_axes, deep_supervision_scales=self._get_deep_supervision_scales(),
+                                  device=self.device if device is None else device, rotation_for_DA=rotation_for_DA,
+                                  scale_range=(0.7, 1.4), do_dummy_2d_data_aug=do_dummy_2d_data_aug)
 
     def train_step(self, batch: dict, return_device_loss: bool = False) -> dict:
         data, target = batch['data'], batch['target']
