@@ -521,6 +521,40 @@ int mvd_feed_warp_seg(const float *seg, float *out, int C, int D, int H, int W, 
                       const double *affine12, int flip_mask, int replace, int replace_from, int replace_to,
                       void *stream);
 
+/* Intensity augmentations of the feed (nnUNetTrainer.py:719-736: GaussianNoise, GaussianBlur, BrightnessMultiplicative,
+ * ContrastAugmentation, SimulateLowResolution, Gamma (inverted), Gamma) and MaskTransform, on the batch patch
+ * [C][D][H][W] (V = D*H*W voxels per channel, C <= 16, bit c of chmask selects channel c).  Per-channel parameters are
+ * HOST arrays of C values copied into the kernel arguments (capturable calls); statistics stay on the device.  Pinned
+ * to numpy / scipy.ndimage.
+ * mvd_feed_channel_stats_f32: stats[c] = {mean, std (ddof 0), min, max} (fp64) of channel c, fixed-order two-level
+ *   reduction through ws (mvd_feed_stats_workspace_bytes(C)); pre_op 2 / 3 takes them of the gamma map y of x / of -x
+ *   (params: gamma per channel, pre_stats: the channel's own stats).
+ * mvd_feed_intensity_apply_f32: in place, op 0 x *= p[c]; 1 clip((x - mean) p[c] + mean, min, max) (stats_a);
+ *   2 / 3 augment_gamma(retain_stats=True) with gamma p[c] on x / on -x (stats_a of x, stats_b of y); 4 clip(x, min,
+ *   max) of stats_a.
+ * mvd_feed_gaussian_blur_f32: in place, gaussian_filter(x[c], sigma[c]) (mode 'reflect', truncate 4, sigma <= 1.1) for
+ *   every channel with sigma[c] > 0; ws: 2 * (selected channels) * V floats.
+ * mvd_feed_gaussian_noise_f32: x[k] += sigma * N(raw_k), k = c V + v the stored voxel, raw_k the k-th output of
+ *   numpy.random.Philox(key=key0 + 2^64 key1).random_raw(); N: u1 = (2 (raw >> 41) + 1) 2^-24,
+ *   u2 = (2 ((raw >> 18) & (2^23 - 1)) + 1) 2^-24, sqrt(-2 ln u1) cos(2 pi u2).
+ * mvd_feed_lowres_gather_f32: dpad [td+2pad][th+2pad][tw+2pad] = zoom(x', (td,th,tw)/(D,H,W), order=0, mode='nearest',
+ *   grid_mode=True) edge-padded by pad, with x' the single channel x un-mirrored on flip_mask (SimulateLowResolution's
+ *   downsample; the upsample is mvd_feed_bspline_prefilter_f32 + mvd_feed_warp_data_f32 with a diagonal affine).
+ * mvd_feed_mask_remove_label: data[c] = 0 where seg[0] < 0 for the channels of chmask (MaskTransform), then
+ *   replace_from -> replace_to in all Cs seg channels when `replace` != 0 (RemoveLabelTransform). */
+size_t mvd_feed_stats_workspace_bytes(int C);
+int mvd_feed_channel_stats_f32(const float *x, double *stats, double *ws, int C, long V, int chmask, int pre_op,
+                               const float *params, const double *pre_stats, void *stream);
+int mvd_feed_intensity_apply_f32(float *x, int C, long V, int chmask, int op, const float *params,
+                                 const double *stats_a, const double *stats_b, void *stream);
+int mvd_feed_gaussian_blur_f32(float *x, float *ws, int C, int D, int H, int W, const double *sigma, void *stream);
+int mvd_feed_gaussian_noise_f32(float *x, int C, long V, int chmask, uint64_t key0, uint64_t key1, float sigma,
+                                void *stream);
+int mvd_feed_lowres_gather_f32(const float *x, float *dpad, int D, int H, int W, int td, int th, int tw, int pad,
+                               int flip_mask, void *stream);
+int mvd_feed_mask_remove_label(float *data, float *seg, int C, int Cs, long V, int chmask, int replace,
+                               int replace_from, int replace_to, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ The product path has NO fallback: if the shared library is missing or a call fai
 """
 import ctypes
 import os
-from ctypes import c_float, c_int, c_long, c_size_t, c_void_p
+from ctypes import c_float, c_int, c_long, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmvdseg_hip.so")
@@ -169,6 +169,13 @@ SIGNATURES = {
     "mvd_feed_bspline_prefilter_f32": (c_int, [_P] + [c_int] * 5 + [_P]),
     "mvd_feed_warp_data_f32": (c_int, [_P, _P] + [c_int] * 7 + [_P, c_int, c_float, _P]),
     "mvd_feed_warp_seg": (c_int, [_P, _P] + [c_int] * 7 + [_P] + [c_int] * 4 + [_P]),
+    "mvd_feed_stats_workspace_bytes": (c_size_t, [c_int]),
+    "mvd_feed_channel_stats_f32": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_int, _P, _P, _P]),
+    "mvd_feed_intensity_apply_f32": (c_int, [_P, c_int, c_long, c_int, c_int, _P, _P, _P, _P]),
+    "mvd_feed_gaussian_blur_f32": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P]),
+    "mvd_feed_gaussian_noise_f32": (c_int, [_P, c_int, c_long, c_int, c_uint64, c_uint64, c_float, _P]),
+    "mvd_feed_lowres_gather_f32": (c_int, [_P, _P] + [c_int] * 8 + [_P]),
+    "mvd_feed_mask_remove_label": (c_int, [_P, _P, c_int, c_int, c_long] + [c_int] * 4 + [_P]),
 }
 
 _lib = None

@@ -9,16 +9,18 @@ NumpyToTensor('float') (nnUNetTrainer.py:738-768) -- runs here as three HIP kern
 (csrc/feed.hip) on volumes that stay in HBM (288 GB holds a whole preprocessed dataset); there is no CPU fallback.
 The rotation / scaling SpatialTransform (:703-714) runs on the device too when the loader is given `rotation_for_DA`
 (csrc/feed_spatial.hip): its resampling is pinned to scipy.ndimage, its batchgenerators glue (draws,
-coordinate mesh, rotation matrices) is restated.  The intensity augmentations (:715-737: noise, blur, brightness,
-contrast, low-resolution simulation, gamma) live in batchgenerators, which is absent from the reference tree; they are
-not part of this slice.
+coordinate mesh, rotation matrices) is restated.  The intensity augmentations (:719-736: noise, blur, brightness,
+contrast, low-resolution simulation, the two gammas) and MaskTransform run on the device when the loader is given
+`intensity_augmentation=True` / `mask_channels` (csrc/feed_intensity.hip): their numeric cores are pinned to
+numpy / scipy.ndimage, their batchgenerators glue (which values are drawn, in which order) is restated in
+`draw_intensity`.
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from ._lib import call
+from ._lib import call, query
 
 
 def _p(t):
@@ -143,6 +145,137 @@ def spatial_transform_seg(seg, out, affine, flip_mask=0, replace=None):
          _affine_arg(affine), int(flip_mask), int(replace is not None), int(rf), int(rt), _stream())
 
 
+def _dev_f32(t, name, dim=4):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == dim):
+        raise RuntimeError(f"{name}: contiguous float32 device tensor of {dim} dims")
+
+
+def _chmask(C, channels):
+    if C > 16:
+        raise ValueError("intensity kernels take at most 16 channels")
+    if channels is None:
+        return (1 << C) - 1
+    m = 0
+    for c in channels:
+        if not 0 <= int(c) < C:
+            raise ValueError(f"channel {c} out of range for {C} channels")
+        m |= 1 << int(c)
+    return m
+
+
+def _chan_arg(vals, C, ctype=ctypes.c_float):
+    vals = [0.0 if v is None else float(v) for v in vals]
+    if len(vals) != C:
+        raise ValueError(f"one value per channel ({C}) expected, got {len(vals)}")
+    return (ctype * C)(*vals)
+
+
+STAT_MEAN, STAT_STD, STAT_MIN, STAT_MAX = range(4)
+OP_BRIGHTNESS, OP_CONTRAST, OP_GAMMA, OP_GAMMA_INVERTED, OP_CLIP = range(5)
+LOWRES_PAD = 12  # scipy zoom's edge pad in front of the order-3 prefilter (_prepad_for_spline_filter, mode 'nearest')
+
+
+def stats_workspace(C, device):
+    """The first-level partials buffer of channel_stats (float64, on `device`)."""
+    nbytes = int(query("mvd_feed_stats_workspace_bytes", int(C)))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def channel_stats(x, stats, ws, channels=None, pre_op=0, gammas=None, pre_stats=None):
+    """stats[c] <- (mean, std (ddof 0), min, max) in fp64 of each selected channel of x [C,D,H,W], or of its gamma map
+    (pre_op OP_GAMMA / OP_GAMMA_INVERTED, gammas per channel, pre_stats = the channel's own stats).  Deterministic."""
+    _dev_f32(x, "channel_stats")
+    C = int(x.shape[0])
+    if not (stats.is_cuda and stats.dtype == torch.float64 and stats.numel() >= 4 * C and stats.is_contiguous()):
+        raise RuntimeError("channel_stats: stats is a contiguous float64 device tensor of >= 4 C values")
+    if not (ws.is_cuda and ws.dtype == torch.float64 and ws.numel() * 8 >= query("mvd_feed_stats_workspace_bytes", C)):
+        raise RuntimeError("channel_stats: ws too small (stats_workspace)")
+    if pre_op and (pre_stats is None or gammas is None or pre_stats.dtype != torch.float64 or pre_stats.numel() < 4 * C):
+        raise RuntimeError("channel_stats: the gamma map needs gammas and float64 pre_stats")
+    call("mvd_feed_channel_stats_f32", _p(x), _p(stats), _p(ws), C, x[0].numel(), _chmask(C, channels), int(pre_op),
+         _chan_arg(gammas, C) if pre_op else None, _p(pre_stats) if pre_op else None, _stream())
+
+
+def intensity_apply(x, op, params=None, stats_a=None, stats_b=None, channels=None):
+    """In place on the selected channels of x [C,D,H,W]: OP_BRIGHTNESS x *= p; OP_CONTRAST clip((x - mean) p + mean, min,
+    max) with stats_a; OP_GAMMA / OP_GAMMA_INVERTED augment_gamma(retain_stats=True) with gamma p (stats_a of x,
+    stats_b of its gamma map); OP_CLIP clip(x, min, max) of stats_a."""
+    _dev_f32(x, "intensity_apply")
+    C = int(x.shape[0])
+    for st in (stats_a, stats_b):
+        if st is not None and not (st.is_cuda and st.dtype == torch.float64 and st.numel() >= 4 * C):
+            raise RuntimeError("intensity_apply: stats are float64 device tensors of >= 4 C values")
+    call("mvd_feed_intensity_apply_f32", _p(x), C, x[0].numel(), _chmask(C, channels), int(op),
+         _chan_arg(params, C) if params is not None else None, _p(stats_a) if stats_a is not None else None,
+         _p(stats_b) if stats_b is not None else None, _stream())
+
+
+def gaussian_blur(x, sigmas, ws):
+    """In place: scipy.ndimage.gaussian_filter(x[c], sigmas[c]) (mode 'reflect', truncate 4) for every channel of x
+    [C,D,H,W] whose sigma is not None; ws: float32 device scratch of >= 2 * (selected channels) * D*H*W values."""
+    _dev_f32(x, "gaussian_blur")
+    C = int(x.shape[0])
+    nsel = sum(s is not None for s in sigmas)
+    if not (ws.is_cuda and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= 2 * nsel * x[0].numel()):
+        raise RuntimeError("gaussian_blur: ws is a float32 device tensor of >= 2 * selected * D*H*W values")
+    if any(s is not None and not 0 < float(s) <= 1.1 for s in sigmas):
+        raise ValueError("gaussian_blur: 0 < sigma <= 1.1")
+    call("mvd_feed_gaussian_blur_f32", _p(x), _p(ws), C, *[int(v) for v in x.shape[1:]],
+         _chan_arg(sigmas, C, ctypes.c_double), _stream())
+
+
+def gaussian_noise(x, sigma, key, channels=None):
+    """In place: x += sigma * N on the selected channels of x [C,D,H,W]; N of stored voxel k = c*D*H*W + v from the
+    k-th numpy.random.Philox(key=key).random_raw() output (Box-Muller, see include/mvdseg_hip.h)."""
+    _dev_f32(x, "gaussian_noise")
+    key = int(key)
+    if not 0 <= key < 2 ** 128:
+        raise ValueError("gaussian_noise: key in [0, 2^128)")
+    call("mvd_feed_gaussian_noise_f32", _p(x), int(x.shape[0]), x[0].numel(), _chmask(int(x.shape[0]), channels),
+         key & (2 ** 64 - 1), key >> 64, float(sigma), _stream())
+
+
+def lowres_gather(x, dpad, target_shape, flip_mask=0, pad=LOWRES_PAD):
+    """dpad [td+2pad, th+2pad, tw+2pad] <- zoom(x', target/shape, order=0, mode='nearest', grid_mode=True) edge-padded
+    by pad, with x' the single channel x [D,H,W] un-mirrored on flip_mask."""
+    _dev_f32(x, "lowres_gather", 3)
+    _dev_f32(dpad, "lowres_gather", 3)
+    t = [int(v) for v in target_shape]
+    if list(dpad.shape) != [v + 2 * pad for v in t]:
+        raise RuntimeError("lowres_gather: dpad must be target_shape + 2 pad")
+    call("mvd_feed_lowres_gather_f32", _p(x), _p(dpad), *[int(v) for v in x.shape], *t, int(pad), int(flip_mask),
+         _stream())
+
+
+def mask_remove_label(data, seg, channels, replace=(-1, 0)):
+    """MaskTransform (data[c] = 0 where seg[0] < 0, c in channels) then RemoveLabelTransform(replace) on seg, in place;
+    data [C,D,H,W], seg [Cs,D,H,W] float32."""
+    _dev_f32(data, "mask_remove_label")
+    _dev_f32(seg, "mask_remove_label")
+    if tuple(data.shape[1:]) != tuple(seg.shape[1:]):
+        raise RuntimeError("mask_remove_label: data and seg differ in spatial shape")
+    rf, rt = (replace if replace is not None else (0, 0))
+    call("mvd_feed_mask_remove_label", _p(data), _p(seg), int(data.shape[0]), int(seg.shape[0]), data[0].numel(),
+         _chmask(int(data.shape[0]), channels), int(replace is not None), int(rf), int(rt), _stream())
+
+
+def lowres_target_shape(shape, zoom):
+    """np.round(shape * zoom) (augment_linear_downsampling_scipy), at least 1 per axis (the reference cannot resize a
+    length-1 axis to 0 either)."""
+    return [max(1, int(v)) for v in np.round(np.asarray(shape, dtype=np.float64) * zoom).astype(int)]
+
+
+def lowres_affine(shape, target):
+    """The diagonal map p = s (o - (n-1)/2) + off of scipy's order-3 zoom t -> n on the pad-12 array:
+    p = (o + 0.5) t/n - 0.5 + 12."""
+    s = [t / n for n, t in zip(shape, target)]
+    a = [s[0], 0., 0., 0., s[1], 0., 0., 0., s[2]]
+    return a + [si * n / 2. - 0.5 + LOWRES_PAD for si, n in zip(s, shape)]
+
+
+INTENSITY_KEYS = ('noise', 'blur', 'brightness', 'contrast', 'lowres', 'gamma_inverted', 'gamma')
+
+
 class DeviceDataLoader3D:
     """nnUNetDataLoader3D with the per-batch work on the GPU.  `data` is an nnUNetDataset-like object: `.keys()` and
     `.load_case(key) -> (data [C,D,H,W] float32, seg [1,D,H,W] integer, properties)` with
@@ -152,7 +285,10 @@ class DeviceDataLoader3D:
     def __init__(self, data, batch_size, patch_size, final_patch_size, label_manager, oversample_foreground_percent=0.0,
                  sampling_probabilities=None, pad_sides=None, probabilistic_oversampling=False, mirror_axes=None,
                  deep_supervision_scales=None, device="cuda:0", rotation_for_DA=None, scale_range=(0.7, 1.4),
-                 p_rot_per_sample=0.2, p_scale_per_sample=0.2, p_rot_per_axis=1.0, do_dummy_2d_data_aug=False):
+                 p_rot_per_sample=0.2, p_scale_per_sample=0.2, p_rot_per_axis=1.0, do_dummy_2d_data_aug=False,
+                 intensity_augmentation=False, mask_channels=None, p_noise=0.1, p_blur=0.2, p_blur_per_channel=0.5,
+                 p_brightness=0.15, p_contrast=0.15, p_lowres=0.25, p_lowres_per_channel=0.5, p_gamma_inverted=0.1,
+                 p_gamma=0.3):
         self._data = data
         self.batch_size = int(batch_size)
         self.indices = list(data.keys())
@@ -174,6 +310,17 @@ class DeviceDataLoader3D:
                                       "Convert3DTo2DTransform) is not implemented")
         if self.rotation_for_DA is not None and any(p < f for p, f in zip(self.patch_size, self.final_patch_size)):
             raise ValueError("DeviceDataLoader3D: patch_size must not be smaller than final_patch_size")
+        # the intensity stage (nnUNetTrainer.py:719-736) with its per-sample / per-channel probabilities, and
+        # MaskTransform: mask_channels is the plans' use_mask_for_norm (one bool per input channel)
+        self.intensity_augmentation = bool(intensity_augmentation)
+        self.p_noise, self.p_blur, self.p_blur_per_channel = float(p_noise), float(p_blur), float(p_blur_per_channel)
+        self.p_brightness, self.p_contrast = float(p_brightness), float(p_contrast)
+        self.p_lowres, self.p_lowres_per_channel = float(p_lowres), float(p_lowres_per_channel)
+        self.p_gamma_inverted, self.p_gamma = float(p_gamma_inverted), float(p_gamma)
+        self.mask_channels = None if mask_channels is None else [i for i, m in enumerate(mask_channels) if m]
+        if self.mask_channels == []:
+            self.mask_channels = None  # MaskTransform is only added when some channel uses it
+        self._istate = None  # intensity scratch (statistics, blur / low-res buffers), reused across batches
         self.list_of_keys = list(data.keys())
         self.need_to_pad = (np.array(patch_size) - np.array(final_patch_size)).astype(int)  # base_data_loader.py:33
         if pad_sides is not None:
@@ -307,10 +454,63 @@ class DeviceDataLoader3D:
             modified = True
         return (float(rot[0]), float(rot[1]), float(rot[2]), float(sc)) if modified else None
 
+    def draw_intensity(self, nsamples, nchannels):
+        """The intensity transforms' draws for a batch (batchgenerators, absent from the reference tree -- restated from
+        its published source with nnU-Net's arguments, nnUNetTrainer.py:719-736).  Transform by transform, each over
+        all samples (as Compose runs them); every transform first draws `np.random.uniform() < p_per_sample`:
+          noise       sigma ~ U(0, 0.1); per channel a uniform (< p_per_channel = 1); then ONE key for the device field
+                      (np.random.randint(0, 2^63), in place of the reference's np.random.normal field)
+          blur        per channel a uniform (<= 0.5), then sigma ~ U(0.5, 1) for a selected channel
+          brightness  one multiplier that is drawn and discarded, then one ~ U(0.75, 1.25) per channel
+          contrast    per channel a uniform (< 1), a uniform (< 0.5: U(0.75, 1), else U(1, 1.25))
+          low-res     per channel a uniform (< 0.5), then the zoom ~ U(0.5, 1) for a selected channel
+          gamma inv.  per channel a uniform (< 0.5: U(0.7, 1), else U(1, 1.5))
+          gamma       the same
+        The reference takes the noise level and get_range_val's values (blur sigma) from Python's `random` module;
+        here every draw is np.random's, so a seeded run is reproducible with np.random.seed alone.  RNG-stream parity
+        with the reference is not a goal.  Returns one dict per sample with the keys INTENSITY_KEYS: None
+        when the transform skips the sample, else noise (sigma, key), blur / low-res a per-channel list of sigma /
+        zoom or None, the others a per-channel list of the factor."""
+        out = [dict.fromkeys(INTENSITY_KEYS) for _ in range(nsamples)]
+        u = np.random.uniform
+
+        def two_sided(lo, hi):  # contrast / gamma: (lo, 1) or (1, hi) with probability 1/2 each
+            return u(lo, 1) if np.random.random() < 0.5 and lo < 1 else u(max(lo, 1), hi)
+
+        for it in out:
+            if u() < self.p_noise:
+                sigma = u(0, 0.1)
+                for _ in range(nchannels):
+                    u()  # p_per_channel = 1
+                it['noise'] = (float(sigma), int(np.random.randint(0, 2 ** 63, dtype=np.int64)))
+        for it in out:
+            if u() < self.p_blur:
+                it['blur'] = [float(u(0.5, 1.)) if u() <= self.p_blur_per_channel else None for _ in range(nchannels)]
+        for it in out:
+            if u() < self.p_brightness:
+                u(0.75, 1.25)
+                it['brightness'] = [float(u(0.75, 1.25)) for _ in range(nchannels)]
+        def per_channel_factor(lo, hi):  # contrast: a selection uniform (p_per_channel = 1) before each factor
+            u()
+            return float(two_sided(lo, hi))
+
+        for it in out:
+            if u() < self.p_contrast:
+                it['contrast'] = [per_channel_factor(0.75, 1.25) for _ in range(nchannels)]
+        for it in out:
+            if u() < self.p_lowres:
+                it['lowres'] = [float(u(0.5, 1)) if u() < self.p_lowres_per_channel else None for _ in range(nchannels)]
+        for key, p in (('gamma_inverted', self.p_gamma_inverted), ('gamma', self.p_gamma)):
+            for it in out:
+                if u() < p:
+                    it[key] = [float(two_sided(0.7, 1.5)) for _ in range(nchannels)]
+        return out
+
     # ------------------------------------------------------------------ the batch
     def plan_batch(self):
         """The host decisions of one batch, in the reference's RNG order: keys, then per sample (oversample?, bbox),
-        then per sample the SpatialTransform draws (only with rotation_for_DA), then per sample the mirror draw."""
+        then per sample the SpatialTransform draws (only with rotation_for_DA), then the intensity draws (only with
+        intensity_augmentation, draw_intensity), then per sample the mirror draw."""
         keys = self.get_indices()
         boxes = []
         for j, k in enumerate(keys):
@@ -318,6 +518,11 @@ class DeviceDataLoader3D:
             data, _, properties = self._case(k)
             lbs, _ = self.get_bbox(tuple(data.shape[1:]), force_fg, properties['class_locations'])
             boxes.append([int(v) for v in lbs])
+        if self.intensity_augmentation:
+            spatial = [self.draw_spatial() if self.rotation_for_DA is not None else None for _ in keys]
+            intensity = self.draw_intensity(len(keys), self.data_shape[1])
+            flips = [self.draw_mirror() for _ in keys]
+            return list(keys), boxes, spatial, intensity, flips
         if self.rotation_for_DA is None:
             flips = [self.draw_mirror() for _ in keys]
             return list(keys), boxes, flips
@@ -332,13 +537,67 @@ class DeviceDataLoader3D:
                              torch.empty((seg.shape[0], *self.patch_size), dtype=torch.float32, device=self.device))
         return self._scratch[1], self._scratch[2]
 
+    def _intensity_state(self, C, V):
+        st = self._istate
+        if st is None or st['C'] != C:
+            n = [v + 2 * LOWRES_PAD for v in self.final_patch_size]
+            st = {'C': C, 'stats': torch.empty((2, C, 4), dtype=torch.float64, device=self.device),
+                  'stats1': torch.empty((2, 4), dtype=torch.float64, device=self.device),
+                  'ws': stats_workspace(C, self.device),
+                  'blur': torch.empty(2 * C * V, dtype=torch.float32, device=self.device),
+                  'dpad': torch.empty(int(np.prod(n)), dtype=torch.float32, device=self.device)}
+            self._istate = st
+        return st
+
+    def apply_intensity(self, x, it, flip_mask):
+        """The intensity stage on one sample x [C,D,H,W] (already mirrored on flip_mask, as the feed's crop / warp
+        kernels store it), in the reference order noise, blur, brightness, contrast, low-res, gamma (inverted), gamma.
+        Every transform but the noise (indexed by stored voxel) and the low-res downsample (un-mirrored in its gather,
+        re-mirrored by the warp) commutes with the mirror."""
+        C = int(x.shape[0])
+        shape = tuple(int(v) for v in x.shape[1:])
+        st = self._intensity_state(C, x[0].numel())
+        sa, sb = st['stats'][0], st['stats'][1]
+        if it['noise'] is not None:
+            gaussian_noise(x, it['noise'][0], it['noise'][1])
+        if it['blur'] is not None and any(v is not None for v in it['blur']):
+            gaussian_blur(x, it['blur'], st['blur'])
+        if it['brightness'] is not None:
+            intensity_apply(x, OP_BRIGHTNESS, it['brightness'])
+        if it['contrast'] is not None:
+            channel_stats(x, sa, st['ws'])
+            intensity_apply(x, OP_CONTRAST, it['contrast'], sa)
+        if it['lowres'] is not None:
+            for c, z in enumerate(it['lowres']):
+                if z is None:
+                    continue
+                t = lowres_target_shape(shape, z)
+                dpad = st['dpad'][:int(np.prod([v + 2 * LOWRES_PAD for v in t]))].view(
+                    *[v + 2 * LOWRES_PAD for v in t])
+                lowres_gather(x[c], dpad, t, flip_mask)
+                d4 = dpad.unsqueeze(0)
+                channel_stats(d4, st['stats1'][0], st['ws'])
+                bspline_prefilter(d4, 7)
+                spatial_transform_data(d4, x[c:c + 1], lowres_affine(shape, t), flip_mask, 0.0)
+                intensity_apply(x[c:c + 1], OP_CLIP, None, st['stats1'][0])
+        for key, op in (('gamma_inverted', OP_GAMMA_INVERTED), ('gamma', OP_GAMMA)):
+            if it[key] is not None:
+                channel_stats(x, sa, st['ws'])
+                channel_stats(x, sb, st['ws'], pre_op=op, gammas=it[key], pre_stats=sa)
+                intensity_apply(x, op, it[key], sa, sb)
+
     def generate_train_batch(self, plan=None):
         plan = plan if plan is not None else self.plan_batch()
+        intensity = None
         if len(plan) == 3:
             keys, boxes, flips = plan
             spatial = [None] * len(keys)
-        else:
+        elif len(plan) == 4:
             keys, boxes, spatial, flips = plan
+        else:
+            keys, boxes, spatial, intensity, flips = plan
+        # MaskTransform reads the seg before RemoveLabel: keep the -1 in the stores and replace in the mask pass
+        remove = (-1, 0) if self.mask_channels is None else None
         data_all = torch.empty(self.data_shape, dtype=torch.float32, device=self.device)
         target = torch.empty(self.seg_shape, dtype=torch.float32, device=self.device)
         # an unmodified sample is the centre crop of the initial patch at (n - f) // 2 (center_crop_aug): cut straight
@@ -350,7 +609,7 @@ class DeviceDataLoader3D:
             if spatial[j] is None:
                 lbs = [b + s for b, s in zip(boxes[j], shift)]
                 crop_pad_data(data, data_all[j], lbs, flips[j], 0.0)
-                crop_pad_seg(seg, target[j], lbs, flips[j], -1, replace=(-1, 0))
+                crop_pad_seg(seg, target[j], lbs, flips[j], -1, replace=remove)
             else:
                 pdata, pseg = self._scratch_for(data, seg)
                 crop_pad_data(data, pdata, boxes[j], 0, 0.0)
@@ -358,7 +617,11 @@ class DeviceDataLoader3D:
                 bspline_prefilter(pdata, 7)
                 affine = spatial_affine(spatial[j], self.patch_size)
                 spatial_transform_data(pdata, data_all[j], affine, flips[j], 0.0)
-                spatial_transform_seg(pseg, target[j], affine, flips[j], replace=(-1, 0))
+                spatial_transform_seg(pseg, target[j], affine, flips[j], replace=remove)
+            if intensity is not None:
+                self.apply_intensity(data_all[j], intensity[j], flips[j])
+            if self.mask_channels is not None:
+                mask_remove_label(data_all[j], target[j], self.mask_channels, replace=(-1, 0))
             props.append(properties)
         if self.deep_supervision_scales is not None:
             target = [downsample_seg(target, s) for s in self.deep_supervision_scales]

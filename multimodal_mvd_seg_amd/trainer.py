@@ -355,17 +355,22 @@ class nnUNetTrainerMI355(object):
         self.inference_allowed_mirroring_axes = mirror_axes
         return rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, mirror_axes
 
-    def get_device_dataloader(self, dataset_tr, device=None):
+    def get_device_dataloader(self, dataset_tr, device=None, intensity_augmentation=False):
         """The training loader of get_dataloaders (:600-630) with its transforms' geometric part on the device: initial
-        patch, SpatialTransform (rotation, scaling 0.7-1.4), mirroring, RemoveLabel and the deep-supervision targets."""
+        patch, SpatialTransform (rotation, scaling 0.7-1.4), mirroring, RemoveLabel and the deep-supervision targets.
+        intensity_augmentation=True adds the intensity transforms (:719-736) and, where the plans set
+        use_mask_for_norm, MaskTransform: the reference's whole training recipe."""
         rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, mirror_axes = \
             self.configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+        use_mask_for_norm = getattr(self.configuration_manager, 'use_mask_for_norm', None)
+        mask_channels = use_mask_for_norm if intensity_augmentation and use_mask_for_norm else None
         return DeviceDataLoader3D(dataset_tr, self.batch_size, [int(i) for i in initial_patch_size],
                                   self.configuration_manager.patch_size, self.label_manager,
                                   oversample_foreground_percent=self.oversample_foreground_percent,
                                   mirror_axes=mirror_axes, deep_supervision_scales=self._get_deep_supervision_scales(),
                                   device=self.device if device is None else device, rotation_for_DA=rotation_for_DA,
-                                  scale_range=(0.7, 1.4), do_dummy_2d_data_aug=do_dummy_2d_data_aug)
+                                  scale_range=(0.7, 1.4), do_dummy_2d_data_aug=do_dummy_2d_data_aug,
+                                  intensity_augmentation=intensity_augmentation, mask_channels=mask_channels)
 
     def train_step(self, batch: dict, return_device_loss: bool = False) -> dict:
         data, target = batch['data'], batch['target']
