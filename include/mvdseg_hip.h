@@ -555,6 +555,34 @@ int mvd_feed_lowres_gather_f32(const float *x, float *dpad, int D, int H, int W,
 int mvd_feed_mask_remove_label(float *data, float *seg, int C, int Cs, long V, int chmask, int replace,
                                int replace_from, int replace_to, void *stream);
 
+/* Segmentation export and evaluation after sliding-window inference (the tail of perform_actual_validation,
+ * nnUNetTrainer.py:1135-1260).  logits: float [K][d][h][w] in network space.  The resampled size (D,H,W), the
+ * pre-crop volume `full`, the lower bbox corner `lo` (HOST int[3] each) are per NETWORK axis; perm = transpose_backward
+ * (HOST int[3]): output axis j holds network axis perm[j], and the output is the contiguous volume of extents
+ * full[perm[0..2]].  Per-axis interpolation comes as three DEVICE tables of D + H + W entries (axis D first): value =
+ * lerp(x[idx0], x[idx1], weight), evaluated with fp32 fmaf along W, then H, then D.  A linear axis (order 1) has
+ * c = clamp((o + 0.5) n_in / n_out - 0.5, 0, n_in - 1), idx0 = floor(c), idx1 = min(idx0 + 1, n_in - 1), weight = c - idx0;
+ * a nearest axis (order 0, the separate-z axis) idx0 = idx1 = clamp(floor(c + 0.5), 0, n_in - 1), weight 0; an axis of
+ * unchanged size is the identity.  Pinned to scipy.ndimage.zoom(order=1, mode='nearest', grid_mode=True) and
+ * map_coordinates(order=0, mode='nearest').  Indices are clamped to the logits' extent again in the kernel.
+ * mvd_export_resize_argmax_u8: out = uint8 label volume (K <= 255): argmax over the K interpolated channels, the lowest
+ *   index on an exact tie, 0 outside the bbox; every output byte is written once, the K x (D,H,W) floats never exist.
+ * mvd_export_resize_softmax_f32: out = float [K] planes of the same volume; apply_softmax != 0: fp32 softmax over K,
+ *   outside the bbox plane 0 is 1 and the others 0 (label_handling.py:199-205); == 0: the interpolated logits, 0 outside.
+ * mvd_seg_confusion_counts: counts[r] = {TP, FP, FN, TN} (int64, device) of label set r (label_sets: HOST int32 [R][16],
+ *   set_sizes: HOST int [R], 1..16 labels of 0..255 each, R <= 32) between pred (uint8) and gt (uint8, or int16 when
+ *   gt_is_i16), over the voxels whose gt is not ignore_label (when has_ignore).  Integer sums: exact and run-to-run
+ *   identical.  Both volumes 16-byte aligned. */
+int mvd_export_resize_argmax_u8(const float *logits, unsigned char *out, const int *idx0, const int *idx1,
+                                const float *weight, int K, int d, int h, int w, int D, int H, int W, const int *full,
+                                const int *lo, const int *perm, void *stream);
+int mvd_export_resize_softmax_f32(const float *logits, float *out, const int *idx0, const int *idx1, const float *weight,
+                                  int K, int d, int h, int w, int D, int H, int W, const int *full, const int *lo,
+                                  const int *perm, int apply_softmax, void *stream);
+int mvd_seg_confusion_counts(const unsigned char *pred, const void *gt, int gt_is_i16, long n, const int32_t *label_sets,
+                             const int *set_sizes, int R, int has_ignore, int ignore_label, long long *counts,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,9 @@ SIGNATURES = {
     "mvd_feed_gaussian_noise_f32": (c_int, [_P, c_int, c_long, c_int, c_uint64, c_uint64, c_float, _P]),
     "mvd_feed_lowres_gather_f32": (c_int, [_P, _P] + [c_int] * 8 + [_P]),
     "mvd_feed_mask_remove_label": (c_int, [_P, _P, c_int, c_int, c_long] + [c_int] * 4 + [_P]),
+    "mvd_export_resize_argmax_u8": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P]),
+    "mvd_export_resize_softmax_f32": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, c_int, _P]),
+    "mvd_seg_confusion_counts": (c_int, [_P, _P, c_int, c_long, _P, _P, c_int, c_int, c_int, _P, _P]),
 }
 
 _lib = None

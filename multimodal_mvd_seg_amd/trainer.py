@@ -44,6 +44,29 @@ class ConfigurationManager:
             return cfg[k]
         raise AttributeError(k)
 
+    # plans_handler.py:68-69, :139-148 -- what the segmentation export reads (export.py)
+    @property
+    def spacing(self):
+        if 'spacing' not in self.configuration:
+            raise AttributeError("the configuration has no 'spacing' (needed to export a prediction)")
+        return self.configuration['spacing']
+
+    @property
+    def resampling_fn_probabilities_kwargs(self):
+        # the default plans' values (experiment_planning/experiment_planners/default_experiment_planner.py)
+        kw = {'is_seg': False, 'order': 1, 'order_z': 0, 'force_separate_z': None}
+        kw.update(self.configuration.get('resampling_fn_probabilities_kwargs', {}))
+        return kw
+
+    @property
+    def resampling_fn_probabilities(self):
+        from functools import partial
+        from . import export
+        name = self.configuration.get('resampling_fn_probabilities', 'resample_data_or_seg_to_shape')
+        if name != 'resample_data_or_seg_to_shape':
+            raise NotImplementedError(f"resampling_fn_probabilities '{name}': only resample_data_or_seg_to_shape")
+        return partial(export.resample_data_or_seg_to_shape, **self.resampling_fn_probabilities_kwargs)
+
 
 class LabelManager:
     """label_handling.py:21,230-234 for the plain-labels case (no regions, no ignore label)."""
@@ -61,6 +84,10 @@ class LabelManager:
     def num_segmentation_heads(self):
         return len(self.all_labels)
 
+    @property
+    def foreground_labels(self):
+        return [i for i in self.all_labels if i != 0]
+
 
 class PlansManager:
     def __init__(self, plans: dict):
@@ -77,6 +104,15 @@ class PlansManager:
 
     def get_label_manager(self, dataset_json):
         return LabelManager(dataset_json['labels'])
+
+    # plans_handler.py:252-257; plans without the keys keep the axis order
+    @property
+    def transpose_forward(self):
+        return list(self.plans.get('transpose_forward', [0, 1, 2]))
+
+    @property
+    def transpose_backward(self):
+        return list(self.plans.get('transpose_backward', [0, 1, 2]))
 
 
 def determine_num_input_channels(plans_manager, configuration_manager, dataset_json):
@@ -396,6 +432,69 @@ class nnUNetTrainerMI355(object):
             counts = ops.argmax_counts(output, target).cpu().numpy()
         tp_hard, fp_hard, fn_hard = counts[1:, 0], counts[1:, 1], counts[1:, 2]  # [1:] removes background (:996-1002)
         return {'loss': l.detach().cpu().numpy(), 'tp_hard': tp_hard, 'fp_hard': fp_hard, 'fn_hard': fn_hard}
+
+    # -- final validation (nnUNetTrainer.py:1135-1260) for in-memory cases, everything on the device ---------------
+    def perform_actual_validation(self, cases, save_probabilities: bool = False, pp_fns=None, pp_fn_kwargs=None,
+                                  tile_step_size: float = 0.5, use_gaussian: bool = True, use_mirroring: bool = True,
+                                  return_segmentations: bool = False):
+        """`cases`: dicts {'data': preprocessed image [C, d, h, w], 'properties': the case's properties dict
+        (shape_before_cropping, bbox_used_for_cropping, shape_after_cropping_and_before_resampling, spacing), 'seg':
+        ground truth in the original space (uint8 / int16, [D, H, W] or [1, D, H, W])}.  Per case: sliding-window
+        prediction (tile step 0.5, Gaussian, mirroring: the reference's settings :1140-1142) -> segmentation export
+        (export.py) -> optional postprocessing.apply_postprocessing(pp_fns, pp_fn_kwargs) -> confusion counts, with one
+        host synchronisation per case (the counts).  Returns compute_metrics_on_folder's {'metric_per_case', 'mean',
+        'foreground_mean'}; with return_segmentations also the list of device segmentations (and with
+        save_probabilities the list of probability volumes).  Deep supervision is off for the duration and restored.
+        Files, the next-stage export and the worker pool are out of scope."""
+        from . import evaluation, export, postprocessing
+        from .inference import SlidingWindowPredictor
+        if not hasattr(self, 'inference_allowed_mirroring_axes'):
+            self.configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+        ds_holder = self.network.decoder if hasattr(self.network, 'decoder') else self.network
+        ds_attr = 'deep_supervision' if hasattr(self.network, 'decoder') else 'do_ds'
+        ds_before = getattr(ds_holder, ds_attr)
+        was_training = self.network.training
+        self.set_deep_supervision_enabled(False)
+        self.network.eval()
+        labels = self.label_manager.foreground_labels
+        results, segs, probs = [], [], []
+        try:
+            predictor = SlidingWindowPredictor(self.network, self.configuration_manager.patch_size,
+                                               self.label_manager.num_segmentation_heads, tile_step_size=tile_step_size,
+                                               use_gaussian=use_gaussian, use_mirroring=use_mirroring,
+                                               allowed_mirroring_axes=self.inference_allowed_mirroring_axes,
+                                               device=self.device)
+            for case in cases:
+                prediction = predictor.predict_sliding_window_return_logits(case['data'])
+                out = export.convert_predicted_logits_to_segmentation_with_correct_shape(
+                    prediction, self.plans_manager, self.configuration_manager, self.label_manager, case['properties'],
+                    return_probabilities=save_probabilities)
+                seg = out[0] if save_probabilities else out
+                del prediction
+                if pp_fns:
+                    seg = postprocessing.apply_postprocessing(seg, pp_fns, pp_fn_kwargs)
+                ref = case['seg']
+                ref = torch.from_numpy(np.ascontiguousarray(ref)) if isinstance(ref, np.ndarray) else ref
+                ref = ref.to(self.device, non_blocking=True)
+                if ref.dim() == 4:
+                    ref = ref[0]
+                if tuple(ref.shape) != tuple(seg.shape):
+                    raise RuntimeError(f"ground truth {tuple(ref.shape)} and exported segmentation {tuple(seg.shape)} "
+                                       f"differ in shape")
+                results.append(evaluation.compute_metrics(ref, seg, labels, self.label_manager.ignore_label))
+                if return_segmentations:
+                    segs.append(seg)
+                    if save_probabilities:
+                        probs.append(out[1])
+        finally:
+            setattr(ds_holder, ds_attr, ds_before)
+            self.network.train(was_training)
+        if not results:
+            raise ValueError("perform_actual_validation: no cases")
+        metrics = evaluation.aggregate_metrics(results, labels)
+        if return_segmentations:
+            return (metrics, segs, probs) if save_probabilities else (metrics, segs)
+        return metrics
 
     @staticmethod
     def dice_from_counts(tp, fp, fn):
