@@ -583,6 +583,35 @@ int mvd_seg_confusion_counts(const unsigned char *pred, const void *gt, int gt_i
                              const int *set_sizes, int R, int has_ignore, int ignore_label, long long *counts,
                              void *stream);
 
+/* Surface distances of two segmentations: medpy's __surface_distances, as evaluation/Hausdorff.py and
+ * evaluation/metrics.py:312-382 of the reference use it.  Volumes are [D][H][W], every extent 1..1024.
+ * mvd_surf_border: masks A = {a in label_set}, B = {b in label_set} (a, b: uint8, or int16 when *_is_i16; label_set: HOST,
+ *   1..16 labels of 0..255).  border[v] bit 0 / bit 1: v belongs to A / B and one of its footprint neighbours
+ *   (|dz| + |dy| + |dx| <= connectivity, 1..3) is 0 or lies outside the volume (scipy's binary_erosion, border_value 0).
+ *   stats: DEVICE int32[10] = {|A|, |B|, |border A|, |border B|, 1024 - min z, 1024 - min y, 1024 - min x, max z + 1,
+ *   max y + 1, max x + 1} with the extrema over the union of A and B (all 0 when both are empty).  Integer atomics.
+ * mvd_edt_squared: exact squared Euclidean distance of every voxel of `box` (HOST int[6]: lower corner z, y, x, then
+ *   extents) to the nearest site INSIDE the box; a site is a voxel with (vol[v] & bit) != 0, or == 0 when zero_is_site.
+ *   spacing == NULL: int32 squared voxel distance (INT32_MAX when the box holds no site); spacing = HOST double[3]: fp64
+ *   ((dx sx)^2 + (dy sy)^2) + (dz sz)^2 (+inf without a site).  The result, contiguous over the box, is left at the
+ *   START of `workspace` (mvd_edt_workspace_bytes(box extents, spaced) device bytes, 16-byte aligned).
+ * mvd_edt_root: out[i] = correctly rounded fp64 root of sq[i] (int32, or double when spaced), +inf for "no site".
+ * mvd_surf_gather: the roots at the box voxels whose border byte has `bit`, compacted into out[0 .. capacity) in an
+ *   UNSPECIFIED order (slots from an integer counter, DEVICE int32, which ends as the number of such voxels).
+ * mvd_surf_reduce: out (DEVICE double[6]) = {sum s0, sum s1, s0[n0 - 1], s1[n1 - 1], all[lo], all[hi]}; the sums are
+ *   formed in a fixed order by one block: bit-identical from run to run for identical input. */
+int mvd_surf_border(const void *a, int a_is_i16, const void *b, int b_is_i16, int D, int H, int W,
+                    const int32_t *label_set, int nlabels, int connectivity, unsigned char *border, int32_t *stats,
+                    void *stream);
+size_t mvd_edt_workspace_bytes(int bd, int bh, int bw, int spaced);
+int mvd_edt_squared(const unsigned char *vol, int bit, int zero_is_site, int D, int H, int W, const int *box,
+                    const double *spacing, void *workspace, size_t workspace_bytes, void *stream);
+int mvd_edt_root(const void *sq, int spaced, long n, double *out, void *stream);
+int mvd_surf_gather(const void *sq, int spaced, const unsigned char *border, int bit, int D, int H, int W, const int *box,
+                    double *out, int capacity, int32_t *counter, void *stream);
+int mvd_surf_reduce(const double *s0, int n0, const double *s1, int n1, const double *all, int lo, int hi, double *out,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,12 @@ SIGNATURES = {
     "mvd_export_resize_argmax_u8": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P]),
     "mvd_export_resize_softmax_f32": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, c_int, _P]),
     "mvd_seg_confusion_counts": (c_int, [_P, _P, c_int, c_long, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "mvd_surf_border": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P]),
+    "mvd_edt_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mvd_edt_squared": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "mvd_edt_root": (c_int, [_P, c_int, c_long, _P, _P]),
+    "mvd_surf_gather": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
+    "mvd_surf_reduce": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, _P, _P]),
 }
 
 _lib = None

@@ -148,3 +148,12 @@ def compute_metrics_on_cases(cases: Iterable[Tuple], regions_or_labels, ignore_l
     if not results:
         raise ValueError("no cases")
     return aggregate_metrics(results, regions_or_labels)
+
+
+def compute_surface_metrics(seg_ref, seg_pred, labels_or_regions, spacing=None, connectivity: int = 1,
+                            ignore_label: Optional[int] = None) -> dict:
+    """{label_or_region: {'HD', 'HD95', 'ASSD'}}: the surface distances of evaluation/Hausdorff.py and
+    evaluation/metrics.py:312-382 (medpy's hd, hd95, assd with the reference's NaN rule) per label or region of two label
+    volumes, on the device (surface.py).  Opt-in: nothing else in this module calls it."""
+    from . import surface
+    return surface.compute_surface_metrics(seg_ref, seg_pred, labels_or_regions, spacing, connectivity, ignore_label)

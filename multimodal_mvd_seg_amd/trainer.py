@@ -436,7 +436,8 @@ class nnUNetTrainerMI355(object):
     # -- final validation (nnUNetTrainer.py:1135-1260) for in-memory cases, everything on the device ---------------
     def perform_actual_validation(self, cases, save_probabilities: bool = False, pp_fns=None, pp_fn_kwargs=None,
                                   tile_step_size: float = 0.5, use_gaussian: bool = True, use_mirroring: bool = True,
-                                  return_segmentations: bool = False):
+                                  return_segmentations: bool = False, surface_metrics: bool = False,
+                                  surface_connectivity: int = 1):
         """`cases`: dicts {'data': preprocessed image [C, d, h, w], 'properties': the case's properties dict
         (shape_before_cropping, bbox_used_for_cropping, shape_after_cropping_and_before_resampling, spacing), 'seg':
         ground truth in the original space (uint8 / int16, [D, H, W] or [1, D, H, W])}.  Per case: sliding-window
@@ -444,7 +445,9 @@ class nnUNetTrainerMI355(object):
         (export.py) -> optional postprocessing.apply_postprocessing(pp_fns, pp_fn_kwargs) -> confusion counts, with one
         host synchronisation per case (the counts).  Returns compute_metrics_on_folder's {'metric_per_case', 'mean',
         'foreground_mean'}; with return_segmentations also the list of device segmentations (and with
-        save_probabilities the list of probability volumes).  Deep supervision is off for the duration and restored.
+        save_probabilities the list of probability volumes).  surface_metrics adds 'HD', 'HD95' and 'ASSD' (evaluation.
+        compute_surface_metrics, spacing = properties['spacing'], footprint surface_connectivity) to every per-case,
+        per-label dict, and with them to the means.  Deep supervision is off for the duration and restored.
         Files, the next-stage export and the worker pool are out of scope."""
         from . import evaluation, export, postprocessing
         from .inference import SlidingWindowPredictor
@@ -482,6 +485,11 @@ class nnUNetTrainerMI355(object):
                     raise RuntimeError(f"ground truth {tuple(ref.shape)} and exported segmentation {tuple(seg.shape)} "
                                        f"differ in shape")
                 results.append(evaluation.compute_metrics(ref, seg, labels, self.label_manager.ignore_label))
+                if surface_metrics:
+                    surf = evaluation.compute_surface_metrics(ref, seg, labels, case['properties']['spacing'],
+                                                              surface_connectivity, self.label_manager.ignore_label)
+                    for key, m in surf.items():
+                        results[-1]['metrics'][key].update(m)
                 if return_segmentations:
                     segs.append(seg)
                     if save_probabilities:
