@@ -612,6 +612,70 @@ int mvd_surf_gather(const void *sq, int spaced, const unsigned char *border, int
 int mvd_surf_reduce(const double *s0, int n0, const double *s1, int n1, const double *all, int lo, int hi, double *out,
                     void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Region-based training and the ignore label (csrc/loss_region.hip).
+ * Region loss = DC_and_BCE_loss({}, {batch_dice, do_bg, smooth, ddp}, use_ignore_label) of upstream nnU-Net 2.1.1 (the
+ * class is missing from the fork: parity unpinned, pinned to torch.nn.functional in fp64 by tests/region_loss_ref.py).
+ * logits planar [N,R,V], R <= 8 sigmoid heads.  Targets, `target_form`:
+ *   0  label map float [N,V] + lut (HOST uint32[256]): bit r of lut[label] = the label belongs to region r, bit 31 = the
+ *      label is the ignore label (the mvd_seg_label_mask convention).  Labels truncate like .long(), clamped to 0..255.
+ *   1  planes float [N,R,V] (ConvertSegmentationToRegionsTransform's output), a value >= 0.5 is a member voxel; lut unused.
+ *   2  planes float [N,R+1,V], the ignore plane last.
+ * With m = 1 on the voxels that are not ignored: stats[N][3R+2] = per head (sum m s y, sum m s, sum m y), s = sigmoid(z),
+ * then sum m * sum_r bce_r with bce = max(z,0) - z y + log1p(exp(-|z|)) (fp32), then sum m.  fp64 accumulation in a fixed
+ * order, no float atomics: run-to-run bit-identical, and forms 0 and 1/2 give identical bits for equivalent targets.
+ * The sums are rounded once to the fp32 stats (the mvd_dcce_fwd convention), so sum m y and the valid-voxel count sum m --
+ * from which the BCE / CE denominator c is formed -- are exact integers only up to 2^24 voxels per sample (256^3); beyond
+ * that they carry fp32's relative error of 6e-8, as torch's own fp32 mask.sum() does.
+ * finalize: dc = (2I+s)/clip(G+P+s,1e-8) as mvd_dcce_finalize; BCE = sum / (N R V) without the ignore label and sum /
+ * clip(sum m, 1e-8) with it (voxels, not voxels x heads: upstream's own normalisation).  loss[4] = {w_ce*BCE + w_dice*dice,
+ * BCE, dice, c} where c is the factor of the backward; coef[Nd][R][2] as mvd_dcce_finalize.
+ * bwd: dlogits[n,r,v] = m ? g * ( w_ce c (s - y) + s (1 - s) (coefI[n,r] y + coefP[n,r]) ) : 0 (an exact zero).
+ *
+ * mvd_dcce_masked_*: DC_and_CE_loss(ignore_label = L) for softmax heads: m = (t != L), the Dice target has L -> 0, I, P, G
+ * masked by m, CE = cross_entropy(ignore_index = L) = sum / sum m, and 0 when no voxel is valid (decided on the device).
+ * stats[N][3K+2], loss[4] and coef as above; the gradient is mvd_dcce_bwd's with m applied and 1/(N V) replaced by c.
+ *
+ * Online evaluation (nnUNetTrainer.py:969-1002), int64 counts[R or K][3] = (tp, fp, fn), integer sums, exact:
+ * mvd_sigmoid_counts: head r predicts a voxel iff z_r > 0, over m.  "sigmoid(z) > 0.5" is decided as z > 0 everywhere in
+ *   this library: exact in real arithmetic; torch's fp32 sigmoid rounds 0 < z < ~1.2e-7 to exactly 0.5 and so calls those
+ *   voxels "off".  A logit of exactly 0 is "off" under both.
+ * mvd_argmax_counts_masked: mvd_argmax_counts over m, the target's L counted nowhere.
+ * mvd_seg_to_regions: planes float [N,R(+1),V] of a label map (region_based_training.py:23-38; the ignore plane last). */
+size_t mvd_dcbce_workspace_bytes(int N, long V, int R);
+int mvd_dcbce_fwd(const float *logits, const float *target, int target_form, const uint32_t *lut_host, float *stats, int N,
+                  long V, int R, void *ws, size_t ws_bytes, void *stream);
+int mvd_dcbce_finalize(const float *stats, int N, const float *dstats, int Nd, float *loss, float *coef, long V, int R,
+                       int batch_dice, int do_bg, int use_ignore_label, float smooth, float w_ce, float w_dice,
+                       void *stream);
+int mvd_dcbce_bwd(const float *logits, const float *target, int target_form, const uint32_t *lut_host, const float *coef,
+                  const float *loss, const float *gscale_dev, float gscale_host, float *dlogits, int N, long V, int R,
+                  float w_ce, void *stream);
+size_t mvd_dcce_masked_workspace_bytes(int N, long V, int K);
+int mvd_dcce_masked_fwd(const float *logits, const float *target, float *stats, int N, long V, int K, int ignore_label,
+                        void *ws, size_t ws_bytes, void *stream);
+int mvd_dcce_masked_finalize(const float *stats, int N, const float *dstats, int Nd, float *loss, float *coef, long V, int K,
+                             int batch_dice, int do_bg, float smooth, float w_ce, float w_dice, void *stream);
+int mvd_dcce_masked_bwd(const float *logits, const float *target, const float *coef, const float *loss,
+                        const float *gscale_dev, float gscale_host, float *dlogits, int N, long V, int K, float w_ce,
+                        int ignore_label, void *stream);
+int mvd_sigmoid_counts(const float *logits, const float *target, int target_form, const uint32_t *lut_host,
+                       long long *counts, int N, long V, int R, void *stream);
+int mvd_argmax_counts_masked(const float *logits, const float *target, long long *counts, int N, long V, int K,
+                             int ignore_label, void *stream);
+int mvd_seg_to_regions(const float *seg, const uint32_t *lut_host, float *planes, int N, long V, int R, int with_ignore,
+                       void *stream);
+/* Region export (label_handling.py:163-171, :199-205), same tables / lerp order / walk as mvd_export_resize_argmax_u8:
+ * mvd_export_resize_regions_u8: the label starts at 0; for i = 0..R-1 a voxel whose interpolated head i is > 0 (see
+ *   mvd_sigmoid_counts for the rule) becomes class_order[i] (HOST int[R], 0..255): the last matching head wins.
+ * mvd_export_resize_sigmoid_f32: out = float [K] planes, 1 / (1 + exp(-z)) in fp32; every plane is 0 outside the bbox. */
+int mvd_export_resize_regions_u8(const float *logits, unsigned char *out, const int *idx0, const int *idx1,
+                                 const float *weight, int R, int d, int h, int w, int D, int H, int W, const int *full,
+                                 const int *lo, const int *perm, const int *class_order, void *stream);
+int mvd_export_resize_sigmoid_f32(const float *logits, float *out, const int *idx0, const int *idx1, const float *weight,
+                                  int K, int d, int h, int w, int D, int H, int W, const int *full, const int *lo,
+                                  const int *perm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,21 @@ SIGNATURES = {
     "mvd_edt_root": (c_int, [_P, c_int, c_long, _P, _P]),
     "mvd_surf_gather": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
     "mvd_surf_reduce": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, _P, _P]),
+    "mvd_dcbce_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
+    "mvd_dcbce_fwd": (c_int, [_P, _P, c_int, _P, _P, c_int, c_long, c_int, _P, c_size_t, _P]),
+    "mvd_dcbce_finalize": (c_int, [_P, c_int, _P, c_int, _P, _P, c_long, c_int, c_int, c_int, c_int, c_float, c_float,
+                                   c_float, _P]),
+    "mvd_dcbce_bwd": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_float, _P, c_int, c_long, c_int, c_float, _P]),
+    "mvd_dcce_masked_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
+    "mvd_dcce_masked_fwd": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_int, _P, c_size_t, _P]),
+    "mvd_dcce_masked_finalize": (c_int, [_P, c_int, _P, c_int, _P, _P, c_long, c_int, c_int, c_int, c_float, c_float,
+                                         c_float, _P]),
+    "mvd_dcce_masked_bwd": (c_int, [_P, _P, _P, _P, _P, c_float, _P, c_int, c_long, c_int, c_float, c_int, _P]),
+    "mvd_sigmoid_counts": (c_int, [_P, _P, c_int, _P, _P, c_int, c_long, c_int, _P]),
+    "mvd_argmax_counts_masked": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_int, _P]),
+    "mvd_seg_to_regions": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_int, _P]),
+    "mvd_export_resize_regions_u8": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P, _P]),
+    "mvd_export_resize_sigmoid_f32": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P]),
 }
 
 _lib = None

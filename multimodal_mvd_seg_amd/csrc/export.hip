@@ -139,6 +139,75 @@ __global__ void __launch_bounds__(256) k_export_resize_f32(const float *__restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- region export
+// Region-based labels (label_handling.py:163-171): the segmentation starts at 0 and, head after head in
+// regions_class_order order, voxels whose head is "on" take that head's label -- the last matching head wins.  A head is
+// on iff its interpolated logit is > 0, i.e. sigma(z) > 0.5 in exact arithmetic (see mvdseg_hip.h).  Same tables, lerp
+// order and one-writer linear walk as k_export_resize_argmax_u8.
+struct RegionOrder {
+    int c[8];
+};
+
+__global__ void __launch_bounds__(256) k_export_resize_regions_u8(const float *__restrict__ logits, uint8_t *__restrict__ out,
+                                                                  const int *__restrict__ i0, const int *__restrict__ i1,
+                                                                  const float *__restrict__ tw, ExportGeom g, long total,
+                                                                  RegionOrder ord) {
+    const long nquad = (total + 3) >> 2;
+    const size_t dhw = (size_t)g.d * g.h * g.w;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (long)gridDim.x * blockDim.x) {
+        const long lin = q << 2;
+        long r = lin / g.O2;
+        int a2 = (int)(lin - r * g.O2);
+        int a0 = (int)(r / g.O1);
+        int a1 = (int)(r - (long)a0 * g.O1);
+        const int nv = total - lin < 4 ? (int)(total - lin) : 4;
+        unsigned pack = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (j < nv) {
+                Taps t;
+                unsigned label = 0;
+                if (export_taps(g, i0, i1, tw, a0, a1, a2, t)) {
+#pragma unroll
+                    for (int k = 0; k < 8; k++)  // static index into the by-value order (no run-time-indexed kernel argument)
+                        if (k < g.K && export_interp(logits + (size_t)k * dhw, t) > 0.f) label = (unsigned)ord.c[k];
+                }
+                pack |= label << (8 * j);
+                if (++a2 == g.O2) {
+                    a2 = 0;
+                    if (++a1 == g.O1) {
+                        a1 = 0;
+                        ++a0;
+                    }
+                }
+            }
+        }
+        if (nv == 4) {
+            *reinterpret_cast<unsigned *>(out + lin) = pack;
+        } else {
+            for (int j = 0; j < nv; j++) out[lin + j] = (uint8_t)(pack >> (8 * j));
+        }
+    }
+}
+
+// apply_nonlin = sigmoid: 1 / (1 + exp(-z)) of the interpolated logits, every plane 0 outside the bbox (no probs[0] = 1:
+// label_handling.py:204-205)
+__global__ void __launch_bounds__(256) k_export_resize_sigmoid_f32(const float *__restrict__ logits, float *__restrict__ out,
+                                                                   const int *__restrict__ i0, const int *__restrict__ i1,
+                                                                   const float *__restrict__ tw, ExportGeom g, long total) {
+    const size_t dhw = (size_t)g.d * g.h * g.w;
+    for (long lin = (long)blockIdx.x * blockDim.x + threadIdx.x; lin < total; lin += (long)gridDim.x * blockDim.x) {
+        const long r = lin / g.O2;
+        const int a2 = (int)(lin - r * g.O2);
+        const int a0 = (int)(r / g.O1);
+        const int a1 = (int)(r - (long)a0 * g.O1);
+        Taps t;
+        const bool in = export_taps(g, i0, i1, tw, a0, a1, a2, t);
+        for (int k = 0; k < g.K; k++)
+            out[(size_t)k * total + lin] = in ? 1.0f / (1.0f + expf(-export_interp(logits + (size_t)k * dhw, t))) : 0.f;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- confusion counts
 struct RegionLut {
     uint32_t m[256];  // bit r of m[label]: label belongs to label set r
@@ -300,6 +369,37 @@ int mvd_export_resize_softmax_f32(const float *logits, float *out, const int *id
     hipLaunchKernelGGL(k_export_resize_f32, dim3(export_grid(total)), dim3(256), 0, as_stream(stream), logits, out, idx0,
                        idx1, weight, g, total, apply_softmax ? 1 : 0);
     return check_launch("export_resize_softmax_f32");
+}
+
+int mvd_export_resize_regions_u8(const float *logits, unsigned char *out, const int *idx0, const int *idx1,
+                                 const float *weight, int R, int d, int h, int w, int D, int H, int W, const int *full,
+                                 const int *lo, const int *perm, const int *class_order, void *stream) {
+    MVD_REQUIRE(logits && out && idx0 && idx1 && weight && class_order, "export_resize_regions_u8: null pointer");
+    MVD_REQUIRE(R >= 1 && R <= 8, "export_resize_regions_u8: 1..8 region heads");
+    MVD_REQUIRE(((uintptr_t)out & 3) == 0, "export_resize_regions_u8: the output must be 4-byte aligned");
+    RegionOrder ord;
+    for (int i = 0; i < 8; i++) {
+        ord.c[i] = i < R ? class_order[i] : 0;  // host array
+        MVD_REQUIRE(ord.c[i] >= 0 && ord.c[i] <= 255, "export_resize_regions_u8: label %d does not fit a uint8", ord.c[i]);
+    }
+    ExportGeom g;
+    long total = 0;
+    if (int rc = export_geom("export_resize_regions_u8", g, R, d, h, w, D, H, W, full, lo, perm, &total)) return rc;
+    hipLaunchKernelGGL(k_export_resize_regions_u8, dim3(export_grid(cdiv(total, 4))), dim3(256), 0, as_stream(stream), logits,
+                       out, idx0, idx1, weight, g, total, ord);
+    return check_launch("export_resize_regions_u8");
+}
+
+int mvd_export_resize_sigmoid_f32(const float *logits, float *out, const int *idx0, const int *idx1, const float *weight,
+                                  int K, int d, int h, int w, int D, int H, int W, const int *full, const int *lo,
+                                  const int *perm, void *stream) {
+    MVD_REQUIRE(logits && out && idx0 && idx1 && weight, "export_resize_sigmoid_f32: null pointer");
+    ExportGeom g;
+    long total = 0;
+    if (int rc = export_geom("export_resize_sigmoid_f32", g, K, d, h, w, D, H, W, full, lo, perm, &total)) return rc;
+    hipLaunchKernelGGL(k_export_resize_sigmoid_f32, dim3(export_grid(total)), dim3(256), 0, as_stream(stream), logits, out,
+                       idx0, idx1, weight, g, total);
+    return check_launch("export_resize_sigmoid_f32");
 }
 
 int mvd_seg_confusion_counts(const unsigned char *pred, const void *gt, int gt_is_i16, long n, const int32_t *label_sets,

@@ -153,12 +153,24 @@ def resample_data_or_seg_to_shape(data: torch.Tensor, new_shape: Sequence[int], 
 
 def resize_logits_to_segmentation(logits: torch.Tensor, new_shape: Sequence[int], shape_before_cropping: Sequence[int],
                                   bbox_lower: Sequence[int], transpose_backward: Sequence[int] = (0, 1, 2),
-                                  separate_z_axis: Optional[int] = None, return_probabilities: bool = False):
+                                  separate_z_axis: Optional[int] = None, return_probabilities: bool = False,
+                                  regions_class_order: Optional[Sequence[int]] = None):
     """The fused core: logits [K, d, h, w] -> uint8 labels of shape shape_before_cropping[transpose_backward] (resized to
     new_shape, argmax, pasted at bbox_lower, axes permuted), and with return_probabilities the float32 [K, ...] softmax
-    volume laid out the same way (channel 0 is 1 outside the bbox)."""
+    volume laid out the same way (channel 0 is 1 outside the bbox).
+    regions_class_order given (region-based labels, label_handling.py:163-171, :199-205): the K channels are sigmoid heads;
+    the label starts at 0 and head i, where its interpolated logit is > 0, writes regions_class_order[i] -- the last
+    matching head wins; the probabilities are the sigmoid planes, all 0 outside the bbox."""
     x = _device_logits(logits)
     K = int(x.shape[0])
+    if regions_class_order is not None:
+        order = [int(c) for c in regions_class_order]
+        if len(order) != K:
+            raise ValueError(f"regions_class_order has {len(order)} entries for {K} heads")
+        if K > 8:
+            raise NotImplementedError(f"{K} region heads: the device export holds at most 8")
+        if min(order) < 0 or max(order) > 255:
+            raise NotImplementedError("region labels outside 0..255 need a uint16 segmentation, which is not built")
     if K > 255:
         raise NotImplementedError("255 or more foreground labels need a uint16 segmentation, which is not built")
     new_shape = [int(v) for v in new_shape]
@@ -173,6 +185,15 @@ def resize_logits_to_segmentation(logits: torch.Tensor, new_shape: Sequence[int]
     i0, i1, w = _device_tables(x.shape[1:], new_shape, _axis_modes(separate_z_axis), x.device)
     out_shape = [full[a] for a in tb]
     seg = torch.empty(out_shape, dtype=torch.uint8, device=x.device)
+    if regions_class_order is not None:
+        call("mvd_export_resize_regions_u8", _p(x), _p(seg), _p(i0), _p(i1), _p(w), K, *x.shape[1:], *new_shape, i3(full),
+             i3(lo), i3(tb), (ctypes.c_int * K)(*order), _stream())
+        if not return_probabilities:
+            return seg
+        prob = torch.empty((K, *out_shape), dtype=torch.float32, device=x.device)
+        call("mvd_export_resize_sigmoid_f32", _p(x), _p(prob), _p(i0), _p(i1), _p(w), K, *x.shape[1:], *new_shape, i3(full),
+             i3(lo), i3(tb), _stream())
+        return seg, prob
     call("mvd_export_resize_argmax_u8", _p(x), _p(seg), _p(i0), _p(i1), _p(w), K, *x.shape[1:], *new_shape, i3(full),
          i3(lo), i3(tb), _stream())
     if not return_probabilities:
@@ -191,9 +212,10 @@ def convert_predicted_logits_to_segmentation_with_correct_shape(predicted_logits
     """export_prediction.py:15-67 on the device.  Returns the uint8 segmentation in the original axis order (and the
     float32 probabilities [K, ...] when asked) as device tensors.  `num_threads_torch` is accepted for signature parity;
     no host threads are involved."""
-    if getattr(label_manager, 'has_regions', False):
-        raise NotImplementedError("region-based labels are outside the device export")
-    if label_manager.num_segmentation_heads - 1 >= 255:
+    has_regions = bool(getattr(label_manager, 'has_regions', False))
+    if has_regions and label_manager.regions_class_order is None:
+        raise RuntimeError("if region-based training is requested then you need to define regions_class_order!")
+    if not has_regions and label_manager.num_segmentation_heads - 1 >= 255:
         raise NotImplementedError("255 or more foreground labels need a uint16 segmentation, which is not built")
     shape_after = [int(v) for v in properties_dict['shape_after_cropping_and_before_resampling']]
     if len(shape_after) != 3:
@@ -211,4 +233,5 @@ def convert_predicted_logits_to_segmentation_with_correct_shape(predicted_logits
                              f"{shape_after}")
     return resize_logits_to_segmentation(predicted_logits, shape_after, properties_dict['shape_before_cropping'],
                                          [b[0] for b in bbox], plans_manager.transpose_backward, axis,
-                                         return_probabilities)
+                                         return_probabilities,
+                                         label_manager.regions_class_order if has_regions else None)

@@ -34,8 +34,13 @@ class _FusedDCCE(nn.Module):
         from .parallel import gather_dice_stats
         return gather_dice_stats
 
+    def _fused_apply(self, weights, targets, outputs):
+        """All levels as one autograd node; the label modes of DESIGN 17 override this.  (Not named `_apply`: that is
+        nn.Module's own method behind .to() / .float() / .cuda().)"""
+        return ops.DeepSupervisedDCCEFn.apply(weights, self._cfg(), self._gather(), targets, *outputs)
+
     def forward(self, net_output, target):
-        return ops.DeepSupervisedDCCEFn.apply([1.0], self._cfg(), self._gather(), [target], net_output)
+        return self._fused_apply([1.0], [target], [net_output])
 
 
 class RobustCrossEntropyLoss(_FusedDCCE):
@@ -56,13 +61,52 @@ class MemoryEfficientSoftDiceLoss(_FusedDCCE):
 class DC_and_CE_loss(_FusedDCCE):
     def __init__(self, soft_dice_kwargs, ce_kwargs, weight_ce=1, weight_dice=1, ignore_label=None,
                  dice_class=MemoryEfficientSoftDiceLoss):
-        if ignore_label is not None:
-            raise NotImplementedError("ignore_label is not on the benchmarked path (SURVEY 8 a-6)")
         if ce_kwargs:
             raise NotImplementedError("ce_kwargs is {} at the reference call site (nnUNetTrainer.py:360)")
         kw = dict(batch_dice=False, do_bg=True, smooth=1., ddp=True)
         kw.update(soft_dice_kwargs)
         super().__init__(kw['batch_dice'], kw['do_bg'], kw['smooth'], kw['ddp'], float(weight_ce), float(weight_dice))
+        self.ignore_label = None if ignore_label is None else int(ignore_label)
+
+    def _fused_apply(self, weights, targets, outputs):
+        if self.ignore_label is None:
+            return super()._fused_apply(weights, targets, outputs)
+        # upstream 2.1.1 DC_and_CE_loss(ignore_label=L): mask = target != L for both terms (parity unpinned)
+        return ops.DeepSupervisedMaskedFn.apply(weights, ('ce', *self._cfg(), self.ignore_label), self._gather(), targets,
+                                                *outputs)
+
+
+class DC_and_BCE_loss(_FusedDCCE):
+    """Upstream 2.1.1 DC_and_BCE_loss for region-based training (nnUNetTrainer.py:352-357): sigmoid heads, BCE-with-logits
+    + soft Dice over the R regions; with use_ignore_label both terms are masked and the BCE sum is divided by the number
+    of valid VOXELS (upstream's own normalisation).  The class is missing from the fork: parity unpinned, semantics pinned
+    by tests/region_loss_ref.py.
+    Targets: `regions` given (a list of labels / label tuples, one per head) -> the float label map [N,1,...] the feed
+    produces, converted per voxel through a label table (`ignore_label` marks the ignored voxels); `regions` absent -> the
+    reference's binary planes [N,R(+1),...] from ConvertSegmentationToRegionsTransform, the ignore plane last."""
+
+    def __init__(self, bce_kwargs, soft_dice_kwargs, weight_ce=1, weight_dice=1, use_ignore_label: bool = False,
+                 dice_class=MemoryEfficientSoftDiceLoss, regions=None, ignore_label=None):
+        if bce_kwargs:
+            raise NotImplementedError("bce_kwargs is {} at the reference call site (nnUNetTrainer.py:353)")
+        kw = dict(batch_dice=False, do_bg=True, smooth=1., ddp=True)
+        kw.update(soft_dice_kwargs)
+        super().__init__(kw['batch_dice'], kw['do_bg'], kw['smooth'], kw['ddp'], float(weight_ce), float(weight_dice))
+        self.use_ignore_label = bool(use_ignore_label)
+        if regions is not None:
+            if self.use_ignore_label != (ignore_label is not None):
+                raise ValueError("label-map targets: use_ignore_label and ignore_label must be given together")
+            if len(regions) > ops.REGION_KMAX:
+                raise NotImplementedError(f"{len(regions)} regions: the fused loss kernels hold at most {ops.REGION_KMAX}")
+            self._extra = (0, ops.region_label_table(regions, ignore_label), self.use_ignore_label)
+        else:
+            if ignore_label is not None:
+                raise ValueError("plane targets carry the ignore label as their last plane; ignore_label needs `regions`")
+            self._extra = (2 if self.use_ignore_label else 1, None, self.use_ignore_label)
+
+    def _fused_apply(self, weights, targets, outputs):
+        return ops.DeepSupervisedMaskedFn.apply(weights, ('bce', *self._cfg(), self._extra), self._gather(), targets,
+                                                *outputs)
 
 
 class DeepSupervisionWrapper(nn.Module):
@@ -78,7 +122,7 @@ class DeepSupervisionWrapper(nn.Module):
     def forward(self, net_output, target):
         assert isinstance(net_output, (tuple, list)) and isinstance(target, (tuple, list))
         w = [1.0] * len(net_output) if self.weight_factors is None else [float(i) for i in self.weight_factors]
-        return ops.DeepSupervisedDCCEFn.apply(w, self.loss._cfg(), self.loss._gather(), list(target), *net_output)
+        return self.loss._fused_apply(w, list(target), list(net_output))
 
 
 def ds_weights(n_scales):

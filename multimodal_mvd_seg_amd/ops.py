@@ -8,6 +8,7 @@ import ctypes
 import os
 import weakref
 
+import numpy as np
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -1218,6 +1219,185 @@ def argmax_counts(logits, target):
     counts = torch.empty((K, 3), dtype=torch.int64, device=x.device)
     call("mvd_argmax_counts", _p(x), _p(t), _p(counts), N, V, K, _stream())
     return counts
+
+
+# ------------------------------------------------------------------------------- regions / ignore label
+REGION_KMAX = 8  # heads of the fused loss kernels (KMAX in csrc/loss.hip, RKMAX in csrc/loss_region.hip)
+IGNORE_BIT = 1 << 31
+
+
+def region_label_table(regions, ignore_label=None):
+    """label -> bitmask table of the region kernels, uint32 [256]: bit r is set when the label belongs to regions[r] (an
+    int or a tuple / list of ints), bit 31 when it is the ignore label (region_based_training.py:23-38 as a lookup)."""
+    if len(regions) > 31:
+        raise NotImplementedError(f"{len(regions)} regions: the label table holds 31")
+    lut = np.zeros(256, dtype=np.uint32)
+    for r, reg in enumerate(regions):
+        for l in (reg if isinstance(reg, (list, tuple)) else (reg,)):
+            l = int(l)
+            if not 0 <= l <= 255:
+                raise NotImplementedError(f"label {l} outside 0..255")
+            lut[l] |= np.uint32(1 << r)
+    if ignore_label is not None:
+        if not 0 <= int(ignore_label) <= 255:
+            raise NotImplementedError(f"ignore label {ignore_label} outside 0..255")
+        lut[int(ignore_label)] |= np.uint32(IGNORE_BIT)
+    return lut
+
+
+def _lut_p(lut):
+    return None if lut is None else lut.ctypes.data_as(ctypes.c_void_p)
+
+
+def _region_target(t, N, R, V, form):
+    """form 0: float label map -> [N,V]; 1 / 2: planes [N,R(+1),...] -> [N,R(+1),V]."""
+    if form == 0:
+        return _flat_target(t, N, V)
+    TP = R + (1 if form == 2 else 0)
+    if t.dim() < 3 or t.shape[0] != N or t.shape[1] != TP or t[0, 0].numel() != V:
+        raise RuntimeError(f"region target must be [{N}, {TP}, ...] planes with {V} voxels each (the ignore plane last), "
+                           f"got {tuple(t.shape)}")
+    t = t.reshape(N, TP, V)
+    return (t if t.dtype == torch.float32 else t.float()).contiguous()
+
+
+def _check_heads(K):
+    if K > REGION_KMAX:
+        raise NotImplementedError(f"{K} segmentation heads: the fused loss kernels hold at most {REGION_KMAX}")
+
+
+class DeepSupervisedMaskedFn(Function):
+    """DeepSupervisedDCCEFn's sibling for the two label modes it does not cover, again one autograd node over all levels:
+    cfg = ('bce', batch_dice, do_bg, smooth, w_ce, w_dice, (target_form, lut, use_ignore_label)): DC_and_BCE_loss over
+    sigmoid heads (mvd_dcbce_*);  ('ce', ..., ignore_label): DC_and_CE_loss(ignore_label=) (mvd_dcce_masked_*).
+    Stats are [N, 3K+2]; `gather` as in DeepSupervisedDCCEFn (parallel.gather_dice_stats is width-agnostic)."""
+
+    @staticmethod
+    def forward(ctx, weights, cfg, gather, targets, *logits):
+        mode, batch_dice, do_bg, smooth, w_ce, w_dice, extra = cfg
+        dev = logits[0].device
+        total = torch.zeros((1,), dtype=torch.float32, device=dev)
+        saved = []
+        ctx.levels = []
+        for i, (x, t) in enumerate(zip(logits, targets)):
+            if weights[i] == 0:
+                ctx.levels.append(None)
+                continue
+            _require_cuda(x, t)
+            x = x.contiguous()
+            N, K = x.shape[:2]
+            _check_heads(K)
+            V = x[0, 0].numel()
+            stats = torch.empty((N, 3 * K + 2), dtype=torch.float32, device=dev)
+            if mode == 'bce':
+                form, lut, use_ignore = extra
+                t = _region_target(t, N, K, V, form)
+                ws = _Workspace.get(query("mvd_dcbce_workspace_bytes", N, V, K), dev)
+                call("mvd_dcbce_fwd", _p(x), _p(t), form, _lut_p(lut), _p(stats), N, V, K, _p(ws), ws.numel(), _stream())
+            else:
+                t = _flat_target(t, N, V)
+                ws = _Workspace.get(query("mvd_dcce_masked_workspace_bytes", N, V, K), dev)
+                call("mvd_dcce_masked_fwd", _p(x), _p(t), _p(stats), N, V, K, int(extra), _p(ws), ws.numel(), _stream())
+            dstats, off, mult = (stats, 0, 1.0)
+            if gather is not None and batch_dice:
+                dstats, off, mult = gather(stats)
+            Nd = dstats.shape[0]
+            loss = torch.empty((4,), dtype=torch.float32, device=dev)
+            coef = torch.empty((Nd, K, 2), dtype=torch.float32, device=dev)
+            if mode == 'bce':
+                call("mvd_dcbce_finalize", _p(stats), N, _p(dstats), Nd, _p(loss), _p(coef), V, K, int(batch_dice),
+                     int(do_bg), int(use_ignore), float(smooth), float(w_ce), float(w_dice), _stream())
+            else:
+                call("mvd_dcce_masked_finalize", _p(stats), N, _p(dstats), Nd, _p(loss), _p(coef), V, K, int(batch_dice),
+                     int(do_bg), float(smooth), float(w_ce), float(w_dice), _stream())
+            call("mvd_axpy", _p(total), _p(loss), float(weights[i]), 1, _stream())
+            saved += [x, t, coef[off:off + N].contiguous() if (off or Nd != N) else coef, loss]
+            ctx.levels.append((N, K, V, float(weights[i]), float(mult)))
+        ctx.save_for_backward(*saved)
+        ctx.mode, ctx.extra, ctx.w_ce = mode, extra, float(w_ce)
+        ctx.shapes = [tuple(x.shape) for x in logits]
+        return total.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        g = g.contiguous()
+        grads = []
+        j = 0
+        for lvl, shp in zip(ctx.levels, ctx.shapes):
+            if lvl is None:
+                grads.append(torch.zeros(shp, dtype=torch.float32, device=g.device))
+                continue
+            N, K, V, w, mult = lvl
+            x, t, coef, loss = saved[j:j + 4]
+            j += 4
+            if mult != 1.0:
+                coef = coef * mult
+            dl = torch.empty(shp, dtype=torch.float32, device=g.device)
+            if ctx.mode == 'bce':
+                form, lut, _ = ctx.extra
+                call("mvd_dcbce_bwd", _p(x), _p(t), form, _lut_p(lut), _p(coef), _p(loss), _p(g), w, _p(dl), N, V, K,
+                     ctx.w_ce, _stream())
+            else:
+                call("mvd_dcce_masked_bwd", _p(x), _p(t), _p(coef), _p(loss), _p(g), w, _p(dl), N, V, K, ctx.w_ce,
+                     int(ctx.extra), _stream())
+            grads.append(dl)
+        return (None, None, None, None, *grads)
+
+
+def argmax_counts_masked(logits, target, ignore_label):
+    """validation_step with an ignore label and softmax heads (nnUNetTrainer.py:980-990): argmax_counts over the voxels
+    whose target is not ignore_label.  int64 [K,3]."""
+    _require_cuda(logits, target)
+    x = logits.contiguous()
+    N, K = x.shape[:2]
+    _check_heads(K)
+    V = x[0, 0].numel()
+    t = _flat_target(target, N, V)
+    counts = torch.empty((K, 3), dtype=torch.int64, device=x.device)
+    call("mvd_argmax_counts_masked", _p(x), _p(t), _p(counts), N, V, K, int(ignore_label), _stream())
+    return counts
+
+
+def sigmoid_counts(logits, target, regions=None, ignore_label=None, has_ignore_plane=False):
+    """validation_step for region heads (:969-990): head r predicts a voxel where its logit is > 0 (sigmoid > 0.5); int64
+    [R,3] = (tp, fp, fn) per region over the voxels that are not ignored.  `regions` given: target is the float label map
+    and ignore_label its ignore label; absent: target holds the [N,R(+1),...] planes (has_ignore_plane: the last one)."""
+    _require_cuda(logits, target)
+    x = logits.contiguous()
+    N, R = x.shape[:2]
+    _check_heads(R)
+    V = x[0, 0].numel()
+    if regions is not None:
+        if len(regions) != R:
+            raise RuntimeError(f"{len(regions)} regions for {R} heads")
+        form, lut = 0, region_label_table(regions, ignore_label)
+    else:
+        form, lut = (2 if has_ignore_plane else 1), None
+    t = _region_target(target, N, R, V, form)
+    counts = torch.empty((R, 3), dtype=torch.int64, device=x.device)
+    call("mvd_sigmoid_counts", _p(x), _p(t), form, _lut_p(lut), _p(counts), N, V, R, _stream())
+    return counts
+
+
+def convert_seg_to_regions(seg, regions, ignore_label=None):
+    """ConvertSegmentationToRegionsTransform (region_based_training.py:23-38) on the device: label map [N,1,...] or
+    [N,...] -> float32 planes [N, R(+1), ...], the ignore label's plane last (nnUNetTrainer.py:759-763)."""
+    _require_cuda(seg)
+    if seg.dim() >= 3 and seg.shape[1] == 1:
+        spatial = tuple(seg.shape[2:])
+    else:
+        spatial = tuple(seg.shape[1:])
+    N = seg.shape[0]
+    V = int(np.prod(spatial))
+    t = _flat_target(seg, N, V)
+    R = len(regions)
+    TP = R + (1 if ignore_label is not None else 0)
+    out = torch.empty((N, TP, *spatial), dtype=torch.float32, device=seg.device)
+    call("mvd_seg_to_regions", _p(t), _lut_p(region_label_table(regions, ignore_label)), _p(out), N, V, R,
+         int(ignore_label is not None), _stream())
+    return out
 
 
 def _kl_strides(t):

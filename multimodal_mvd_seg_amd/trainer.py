@@ -69,24 +69,105 @@ class ConfigurationManager:
 
 
 class LabelManager:
-    """label_handling.py:21,230-234 for the plain-labels case (no regions, no ignore label)."""
+    """label_handling.py:21-234: plain labels, overlapping regions (sigmoid heads, `regions_class_order`) and the ignore
+    label.  The inference nonlinearity is not held here: export.py takes the regions branch from `has_regions`."""
 
-    def __init__(self, label_dict: dict):
+    def __init__(self, label_dict: dict, regions_class_order=None, force_use_labels: bool = False):
+        self._sanity_check(label_dict)
         self.label_dict = label_dict
-        self.all_labels = sorted(int(v) for v in label_dict.values() if not isinstance(v, (list, tuple)))
-        self.has_regions = any(isinstance(v, (list, tuple)) and len(v) > 1 for v in label_dict.values())
-        self.ignore_label = label_dict.get('ignore')
-        self.has_ignore_label = self.ignore_label is not None
-        if self.has_regions or self.has_ignore_label:
-            raise NotImplementedError("regions / ignore label are outside the benchmarked path (SURVEY 8 a-6)")
+        self.regions_class_order = regions_class_order
+        self._force_use_labels = force_use_labels
+        self._has_regions = False if force_use_labels else any(
+            isinstance(i, (tuple, list)) and len(i) > 1 for i in label_dict.values())
+        self._ignore_label = self._determine_ignore_label()
+        self._all_labels = self._get_all_labels()
+        self._regions = self._get_regions()
+        if self.has_ignore_label:
+            assert self.ignore_label == max(self.all_labels) + 1, \
+                'If you use the ignore label it must have the highest label value! It cannot be 0 or in between other ' \
+                'labels.'
+
+    @staticmethod
+    def _sanity_check(label_dict: dict):
+        if 'background' not in label_dict.keys():
+            raise RuntimeError('Background label not declared (remember that this should be label 0!)')
+        bg_label = label_dict['background']
+        if isinstance(bg_label, (tuple, list)):
+            raise RuntimeError(f"Background label must be 0. Not a list. Not a tuple. Your background label: {bg_label}")
+        assert int(bg_label) == 0, f"Background label must be 0. Your background label: {bg_label}"
+
+    def _get_all_labels(self):
+        all_labels = []
+        for k, r in self.label_dict.items():
+            if k == 'ignore':
+                continue
+            if isinstance(r, (tuple, list)):
+                all_labels += [int(ri) for ri in r]
+            else:
+                all_labels.append(int(r))
+        return sorted(set(all_labels))
+
+    def _get_regions(self):
+        if not self._has_regions or self._force_use_labels:
+            return None
+        assert self.regions_class_order is not None, \
+            'if region-based training is requested then you need to define regions_class_order!'
+        regions = []
+        for k, r in self.label_dict.items():
+            if k == 'ignore':
+                continue
+            if (np.isscalar(r) and r == 0) or \
+                    (isinstance(r, (tuple, list)) and len(np.unique(r)) == 1 and np.unique(r)[0] == 0):
+                continue  # regions that are background
+            regions.append(tuple(r) if isinstance(r, list) else r)
+        assert len(self.regions_class_order) == len(regions), \
+            'regions_class_order must have as many entries as there are regions'
+        return regions
+
+    def _determine_ignore_label(self):
+        ignore_label = self.label_dict.get('ignore')
+        if ignore_label is not None:
+            assert isinstance(ignore_label, int), \
+                f'Ignore label has to be an integer. It cannot be a region (list/tuple). Got {type(ignore_label)}.'
+        return ignore_label
 
     @property
-    def num_segmentation_heads(self):
-        return len(self.all_labels)
+    def has_regions(self) -> bool:
+        return self._has_regions
+
+    @property
+    def has_ignore_label(self) -> bool:
+        return self.ignore_label is not None
+
+    @property
+    def all_regions(self):
+        return self._regions
+
+    @property
+    def all_labels(self):
+        return self._all_labels
+
+    @property
+    def ignore_label(self):
+        return self._ignore_label
+
+    @staticmethod
+    def filter_background(classes_or_regions):
+        return [i for i in classes_or_regions if
+                ((not isinstance(i, (tuple, list))) and i != 0) or
+                (isinstance(i, (tuple, list)) and not (len(np.unique(i)) == 1 and np.unique(i)[0] == 0))]
+
+    @property
+    def foreground_regions(self):
+        return self.filter_background(self.all_regions)
 
     @property
     def foreground_labels(self):
-        return [i for i in self.all_labels if i != 0]
+        return self.filter_background(self.all_labels)
+
+    @property
+    def num_segmentation_heads(self):
+        return len(self.foreground_regions) if self.has_regions else len(self.all_labels)
 
 
 class PlansManager:
@@ -103,7 +184,7 @@ class PlansManager:
         return ConfigurationManager(cfg)
 
     def get_label_manager(self, dataset_json):
-        return LabelManager(dataset_json['labels'])
+        return LabelManager(dataset_json['labels'], regions_class_order=dataset_json.get('regions_class_order'))
 
     # plans_handler.py:252-257; plans without the keys keep the axis order
     @property
@@ -254,10 +335,28 @@ class nnUNetTrainerMI355(object):
             self.oversample_foreground_percent = ov[dist.get_rank()]
 
     def _build_loss(self):
-        loss = losses.DC_and_CE_loss({'batch_dice': self.configuration_manager.batch_dice, 'smooth': 1e-5,
-                                      'do_bg': False, 'ddp': self.is_ddp}, {}, weight_ce=1, weight_dice=1,
-                                     ignore_label=self.label_manager.ignore_label,
-                                     dice_class=losses.MemoryEfficientSoftDiceLoss)
+        if getattr(self.configuration_manager, 'previous_stage_name', None) is not None:
+            raise NotImplementedError("cascade configurations (previous_stage_name) and their transforms are not built")
+        if (self.label_manager.has_regions or self.label_manager.has_ignore_label) and \
+                self.label_manager.num_segmentation_heads > ops.REGION_KMAX:
+            # the limit is the loss kernels'; a network with more heads can still be built for inference and export, and
+            # the plain-label loss keeps refusing in mvd_dcce_fwd as before
+            raise NotImplementedError(f"{self.label_manager.num_segmentation_heads} segmentation heads: the fused loss "
+                                      f"kernels hold at most {ops.REGION_KMAX}")
+        if self.label_manager.has_regions:
+            # (:352-357) the targets stay the feed's float label map: the loss converts label -> regions per voxel, which
+            # commutes with the order-0 deep-supervision resize
+            loss = losses.DC_and_BCE_loss({}, {'batch_dice': self.configuration_manager.batch_dice, 'do_bg': True,
+                                               'smooth': 1e-5, 'ddp': self.is_ddp},
+                                          use_ignore_label=self.label_manager.ignore_label is not None,
+                                          dice_class=losses.MemoryEfficientSoftDiceLoss,
+                                          regions=self.label_manager.foreground_regions,
+                                          ignore_label=self.label_manager.ignore_label)
+        else:
+            loss = losses.DC_and_CE_loss({'batch_dice': self.configuration_manager.batch_dice, 'smooth': 1e-5,
+                                          'do_bg': False, 'ddp': self.is_ddp}, {}, weight_ce=1, weight_dice=1,
+                                         ignore_label=self.label_manager.ignore_label,
+                                         dice_class=losses.MemoryEfficientSoftDiceLoss)
         if self.enable_deep_supervision:
             deep_supervision_scales = self._get_deep_supervision_scales()
             weights = np.array([1 / (2 ** i) for i in range(len(deep_supervision_scales))])
@@ -324,8 +423,12 @@ class nnUNetTrainerMI355(object):
         return (tuple(data.shape), data.dtype, tuple((tuple(t.shape), t.dtype) for t in tl), isinstance(target, list),
                 self.precision, self.network.training, self._graph_flags())
 
+    def _label_mode(self):
+        lm = self.label_manager
+        return (lm.has_regions, tuple(lm.foreground_regions) if lm.has_regions else None, lm.ignore_label)
+
     def _graph_flags(self):
-        return (bool(self.network.decoder.deep_supervision),)
+        return (bool(self.network.decoder.deep_supervision), self._label_mode())
 
     def _graphed_step(self, data, target):
         key = self._graph_key(data, target)
@@ -429,8 +532,14 @@ class nnUNetTrainerMI355(object):
             l, output = self._forward_loss(data, target)
             if self.enable_deep_supervision:
                 output, target = output[0], target[0]
-            counts = ops.argmax_counts(output, target).cpu().numpy()
-        tp_hard, fp_hard, fn_hard = counts[1:, 0], counts[1:, 1], counts[1:, 2]  # [1:] removes background (:996-1002)
+            lm = self.label_manager
+            if lm.has_regions:     # (:969-970, :985-989) sigmoid heads, every head is foreground: no [1:]
+                counts = ops.sigmoid_counts(output, target, lm.foreground_regions, lm.ignore_label).cpu().numpy()
+            elif lm.has_ignore_label:   # (:980-984)
+                counts = ops.argmax_counts_masked(output, target, lm.ignore_label).cpu().numpy()[1:]
+            else:
+                counts = ops.argmax_counts(output, target).cpu().numpy()[1:]  # [1:] removes background (:996-1002)
+        tp_hard, fp_hard, fn_hard = counts[:, 0], counts[:, 1], counts[:, 2]
         return {'loss': l.detach().cpu().numpy(), 'tp_hard': tp_hard, 'fp_hard': fp_hard, 'fn_hard': fn_hard}
 
     # -- final validation (nnUNetTrainer.py:1135-1260) for in-memory cases, everything on the device ---------------
@@ -459,7 +568,8 @@ class nnUNetTrainerMI355(object):
         was_training = self.network.training
         self.set_deep_supervision_enabled(False)
         self.network.eval()
-        labels = self.label_manager.foreground_labels
+        labels = self.label_manager.foreground_regions if self.label_manager.has_regions \
+            else self.label_manager.foreground_labels
         results, segs, probs = [], [], []
         try:
             predictor = SlidingWindowPredictor(self.network, self.configuration_manager.patch_size,
@@ -533,6 +643,9 @@ class ContrastiveTrainerMI355(nnUNetTrainerMI355):
     def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=torch.device('cuda'),
                  specified_cfg=''):
         super().__init__(plans, configuration, fold, dataset_json, unpack_dataset, device, specified_cfg)
+        if self.label_manager.has_regions or self.label_manager.has_ignore_label:
+            raise NotImplementedError("ContrastiveTrainerMI355 with regions or an ignore label: its vessel-channel terms "
+                                      "(softmax channel select, KL, soft-clDice) are defined for softmax heads only")
         self.lambda1, self.lambda2, self.lambda3 = 0.5, 0.1, 1  # MVDTrainer.py:132-134
         self.vessel_channel = 2                                 # :897-898, :907-908
         self.use_topo, self.skel_iter, self.feat_kl, self.kl_T = True, 3, True, 1
@@ -586,4 +699,4 @@ class ContrastiveTrainerMI355(nnUNetTrainerMI355):
 
     def _graph_flags(self):
         return (bool(self.network.do_ds), self.use_topo, self.topo_cc, self.skel_iter, self.feat_kl, self.kl_T,
-                self.lambda1, self.lambda3, self.vessel_channel)
+                self.lambda1, self.lambda3, self.vessel_channel, self._label_mode())

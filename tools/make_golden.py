@@ -180,7 +180,8 @@ def ref_function(rel, func_name, class_name=None, **ns):
     body = tree.body
     if class_name is not None:
         body = next(n for n in body if isinstance(n, ast.ClassDef) and n.name == class_name).body
-    node = next(n for n in body if isinstance(n, ast.FunctionDef) and n.name == func_name)
+    # (a ClassDef of that name is picked whole: LabelManager, ConvertSegmentationToRegionsTransform)
+    node = next(n for n in body if isinstance(n, (ast.FunctionDef, ast.ClassDef)) and n.name == func_name)
     node.decorator_list = []
     code = compile(ast.Module(body=[node], type_ignores=[]), path, "exec")
     glob = {"np": np, "torch": torch, "F": F, "Union": typing.Union, "Tuple": typing.Tuple, "List": typing.List}
@@ -684,8 +685,87 @@ def oracle_check_fixtures():
          dgm0=m.persistenceForwardHom(s, 0, 0)[0])
 
 
+# ------------------------------------------------------------------ regions / ignore label
+def region_label_fixtures():
+    """tests/golden/label_manager.json: the reference's own LabelManager (label_handling.py) and
+    ConvertSegmentationToRegionsTransform (region_based_training.py) -- both need only numpy and torch once
+    AbstractTransform, bounding_box_to_slice and softmax_helper_dim0 are stubbed -- executed on small inputs."""
+    LM, lm_src = ref_function("utilities/label_handling/label_handling.py", "LabelManager",
+                              softmax_helper_dim0=lambda x: torch.softmax(x, 0),
+                              bounding_box_to_slice=lambda bb: tuple(slice(*i) for i in bb))
+    TR, tr_src = ref_function("training/data_augmentation/custom_transforms/region_based_training.py",
+                              "ConvertSegmentationToRegionsTransform", AbstractTransform=object)
+
+    def plain(v):
+        if isinstance(v, (list, tuple)):
+            return [plain(i) for i in v]
+        return int(v) if isinstance(v, (int, np.integer)) else v
+
+    dicts = [
+        ({"background": 0, "a": 1, "b": 2}, None),
+        ({"background": 0, "a": 1}, None),
+        ({"background": 0, "a": 1, "b": 2, "c": 3, "d": 4}, None),
+        ({"background": 0, "a": 1, "b": 2, "ignore": 3}, None),
+        ({"background": 0, "whole": [1, 2, 3], "core": [2, 3], "enh": 3}, [1, 2, 3]),
+        ({"background": 0, "whole": (1, 2, 3), "core": (2, 3), "enh": 3}, [1, 2, 3]),
+        ({"background": 0, "whole": [1, 2, 3], "core": [2, 3], "enh": 3, "ignore": 4}, [1, 2, 3]),
+        ({"background": 0, "whole": [1, 2, 3], "core": [2, 3], "enh": 3}, [3, 1, 2]),
+        ({"background": 0, "with_bg": [0, 1], "b": 2}, [1, 2]),
+        ({"background": 0, "zeros": [0, 0], "ab": [1, 2], "b": 2}, [1, 2]),
+        ({"background": 0, "single": [1], "pair": (1, 2)}, [2, 1]),
+        ({"background": 0, "a": 1, "bc": [2, 3], "c": 3, "d": [4], "ignore": 5}, [1, 2, 3, 4]),
+    ]
+    managers = []
+    for d, order in dicts:
+        m = LM(d, order)
+        managers.append({"label_dict": plain({k: v for k, v in d.items()}),
+                         "is_tuple": {k: isinstance(v, tuple) for k, v in d.items()},
+                         "regions_class_order": order, "has_regions": bool(m.has_regions),
+                         "has_ignore_label": bool(m.has_ignore_label), "ignore_label": m.ignore_label,
+                         "all_labels": plain(m.all_labels),
+                         "all_regions": None if m.all_regions is None else plain(m.all_regions),
+                         "foreground_regions": plain(m.foreground_regions) if m.has_regions else None,
+                         "foreground_labels": plain(m.foreground_labels),
+                         "num_segmentation_heads": int(m.num_segmentation_heads)})
+    rejected = []
+    for d, order in (({"background": 0, "a": 1, "ignore": 3}, None), ({"background": 0, "a": 1, "b": 2, "ignore": 1}, None),
+                     ({"a": 1}, None), ({"background": [0, 1], "a": 2}, None), ({"background": 0, "r": [1, 2]}, None),
+                     ({"background": 0, "r": [1, 2], "s": 2}, [1])):
+        try:
+            LM(d, order)
+            raise SystemExit(f"the reference accepted {d}")
+        except (AssertionError, RuntimeError) as e:
+            rejected.append({"label_dict": plain(d), "regions_class_order": order, "error": type(e).__name__})
+    rng = np.random.RandomState(17)
+    conv = []
+    d3 = {"background": 0, "whole": [1, 2, 3], "core": [2, 3], "enh": 3}
+    for order in ([1, 2, 3], [3, 2, 1], [2, 3, 1], [1, 3, 2], [7, 5, 9]):
+        m = LM(d3, order)
+        p = rng.rand(3, 4, 5, 6).astype(np.float32)
+        p.flat[rng.choice(p.size, 12, replace=False)] = 0.5   # exactly 0.5 is "off"
+        conv.append({"regions_class_order": order, "probabilities": p.tolist(),
+                     "segmentation": m.convert_probabilities_to_segmentation(p).astype(np.int64).tolist()})
+    planes = []
+    for regions, ign, nlab in ((d3, None, 4), (d3, 4, 5), ({"background": 0, "with_bg": [0, 1], "b": 2}, None, 3),
+                               ({"background": 0, "a": 1, "bc": [2, 3], "c": 3, "d": [4]}, 5, 6)):
+        m = LM(dict(regions, **({"ignore": ign} if ign is not None else {})), list(range(1, len(regions))))
+        seg = rng.randint(0, nlab, size=(2, 1, 3, 4, 5)).astype(np.float32)
+        regs = list(m.foreground_regions) + [ign] if ign is not None else m.foreground_regions   # nnUNetTrainer.py:759-763
+        out = TR(regs, 'target', 'target')(target=seg)['target']
+        planes.append({"foreground_regions": plain(m.foreground_regions), "ignore_label": ign, "seg": seg.tolist(),
+                       "planes": out.tolist()})
+    json.dump({"source": f"reference {lm_src} and {tr_src} (classes executed with AbstractTransform, "
+                         f"bounding_box_to_slice and softmax_helper_dim0 stubbed)",
+               "managers": managers, "rejected": rejected, "convert_probabilities_to_segmentation": conv,
+               "regions_transform": planes}, open(os.path.join(OUT, "label_manager.json"), "w"))
+    print("wrote label_manager.json")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == "regions":  # only tests/golden/label_manager.json
+        region_label_fixtures()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "extracted":  # only the fixtures compiled out of reference function bodies
         extracted_reference_fixtures()
         sys.exit(0)
@@ -696,6 +776,7 @@ if __name__ == "__main__":
     instnorm_fixtures()
     reference_fixtures()
     extracted_reference_fixtures()
+    region_label_fixtures()
     loss_fixtures()
     unet_step_fixture()
     mvd_step_fixture()
