@@ -160,6 +160,11 @@ int mvd_pack_weight_bf16(const float *w, uint16_t *wf, uint16_t *wb, int K, int 
  * mvd_pack_weights_batch for the fp32 layouts): host tables of n jobs, outputs bit-identical to mvd_pack_weight_bf16. */
 int mvd_pack_weights_bf16_batch(int n, const float *const *w, uint16_t *const *wf, uint16_t *const *wb, const int *K,
                                 const int *C, const int *T, const int *transposed, void *stream);
+/* The same launch with a source channel count per job: job q reads a [K][Csrc][T] weight and packs it as the [K][C][T]
+ * weight whose reduce channels Csrc .. C-1 are zero (the 4-modality input conv, run on the 32-channel engines) --
+ * bit-identical to mvd_pack_weight_bf16 of the zero-padded tensor.  Csrc == C: the plain job; Csrc < C: conv weights only. */
+int mvd_pack_weights_bf16_batch_pad(int n, const float *const *w, uint16_t *const *wf, uint16_t *const *wb, const int *K,
+                                    const int *C, const int *T, const int *transposed, const int *Csrc, void *stream);
 int mvd_conv3d_fwd_bf16(const uint16_t *x1, int C1, const uint16_t *x2, int C2, const uint16_t *wf, const float *bias,
                         uint16_t *y, int N, int D, int H, int W, int K, const int ksize[3], const int stride[3],
                         void *ws, size_t ws_bytes, void *stream);

@@ -810,7 +810,22 @@ int mvd_pack_weights_bf16_batch(int n, const float *const *w, uint16_t *const *w
         MVD_REQUIRE(!wb[q] || K[q] % 32 == 0, "pack_weights_bf16_batch: wb needs K %% 32 == 0");
     }
     return pack_weights16_batch(n, w, reinterpret_cast<unsigned short *const *>(wf), reinterpret_cast<unsigned short *const *>(wb),
-                                K, C, T, transposed, as_stream(stream));
+                                K, C, T, transposed, nullptr, as_stream(stream));
+}
+
+int mvd_pack_weights_bf16_batch_pad(int n, const float *const *w, uint16_t *const *wf, uint16_t *const *wb, const int *K,
+                                    const int *C, const int *T, const int *transposed, const int *Csrc, void *stream) {
+    MVD_REQUIRE(n > 0 && w && wf && wb && K && C && T && transposed && Csrc, "pack_weights_bf16_batch_pad: null table");
+    for (int q = 0; q < n; q++) {
+        MVD_REQUIRE(w[q] && (wf[q] || wb[q]), "pack_weights_bf16_batch_pad: job without source or destination");
+        MVD_REQUIRE(K[q] > 0 && C[q] > 0 && T[q] > 0 && T[q] <= MVD_MAX_TAPS, "pack_weights_bf16_batch_pad: bad K / C / T");
+        MVD_REQUIRE(Csrc[q] > 0 && Csrc[q] <= C[q], "pack_weights_bf16_batch_pad: needs 0 < Csrc <= C");
+        MVD_REQUIRE(Csrc[q] == C[q] || !transposed[q], "pack_weights_bf16_batch_pad: no padding for transposed-conv weights");
+        MVD_REQUIRE(!wf[q] || C[q] % 32 == 0, "pack_weights_bf16_batch_pad: wf needs C %% 32 == 0");
+        MVD_REQUIRE(!wb[q] || K[q] % 32 == 0, "pack_weights_bf16_batch_pad: wb needs K %% 32 == 0");
+    }
+    return pack_weights16_batch(n, w, reinterpret_cast<unsigned short *const *>(wf), reinterpret_cast<unsigned short *const *>(wb),
+                                K, C, T, transposed, Csrc, as_stream(stream));
 }
 
 int mvd_conv3d_fwd_bf16(const uint16_t *x1, int C1, const uint16_t *x2, int C2, const uint16_t *wf, const float *bias, uint16_t *y, int N,

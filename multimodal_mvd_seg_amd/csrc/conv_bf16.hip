@@ -1933,6 +1933,7 @@ struct Pack16Job {
     const float *w;
     unsigned short *wf, *wb;
     int K, C, T, transposed;
+    int Cs;     // reduce channels the source holds (<= C): channels Cs .. C-1 are packed as zeros (the padded input conv)
     unsigned blk_begin;
     int tiled;  // 1: 3x3x3 conv -> one workgroup per 16 k x 16 c tile (through LDS)
 };
@@ -1960,7 +1961,8 @@ __global__ __launch_bounds__(256) void k_pack16_batch(const Pack16Batch pb) {
         const int k = (int)(i % J.K);
         const int c = (int)((i / J.K) % J.C);
         const int t = (int)(i / ((long)J.K * J.C));
-        const float v = J.transposed ? J.w[((size_t)c * J.K + k) * J.T + t] : J.w[((size_t)k * J.C + c) * J.T + t];
+        const float v = J.transposed ? J.w[((size_t)c * J.K + k) * J.T + t]
+                                     : (c < J.Cs ? J.w[((size_t)k * J.Cs + c) * J.T + t] : 0.f);
         const unsigned short b = f2bf(v);
         if (J.wf) J.wf[widx16(J.T, J.K, t, c, k)] = b;
         if (J.wb) J.wb[widx16(J.T, J.C, t, k, c)] = b;
@@ -1989,7 +1991,7 @@ __global__ __launch_bounds__(256) void k_pack16_batch(const Pack16Batch pb) {
 }
 
 int pack_weights16_batch(int n, const float *const *w, unsigned short *const *wf, unsigned short *const *wb, const int *K,
-                         const int *C, const int *T, const int *transposed, hipStream_t s) {
+                         const int *C, const int *T, const int *transposed, const int *Csrc, hipStream_t s) {
     int done = 0;
     while (done < n) {
         Pack16Batch pb;
@@ -2001,8 +2003,9 @@ int pack_weights16_batch(int n, const float *const *w, unsigned short *const *wf
             Pack16Job &J = pb.j[m];
             J.w = w[q]; J.wf = wf[q]; J.wb = wb[q];
             J.K = K[q]; J.C = C[q]; J.T = T[q]; J.transposed = transposed[q];
+            J.Cs = Csrc ? Csrc[q] : J.C;
             J.blk_begin = blocks;
-            J.tiled = (J.T == 27 && !J.transposed && J.K % 32 == 0 && J.C % 32 == 0) ? 1 : 0;
+            J.tiled = (J.T == 27 && !J.transposed && J.K % 32 == 0 && J.C % 32 == 0 && J.Cs == J.C) ? 1 : 0;
             blocks += J.tiled ? (unsigned)((J.K / 16) * (J.C / 16)) : (unsigned)cdiv((long)J.K * J.C * J.T, 256);
         }
         pb.n = m;

@@ -168,6 +168,6 @@ int fwd_bf16_prologue_ok(const FwdGeom &g);
 int pack_weight16(const float *w, unsigned short *wf, unsigned short *wb, int K, int C, int T, int transposed,
                   hipStream_t s);
 int pack_weights16_batch(int n, const float *const *w, unsigned short *const *wf, unsigned short *const *wb, const int *K,
-                         const int *C, const int *T, const int *transposed, hipStream_t s);
+                         const int *C, const int *T, const int *transposed, const int *Csrc, hipStream_t s);
 
 }  // namespace mvd

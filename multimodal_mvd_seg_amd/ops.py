@@ -6,6 +6,7 @@ arithmetic operation of the hot path runs in libmvdseg_hip.so.  Activations are 
 """
 import ctypes
 import os
+import typing
 import weakref
 
 import numpy as np
@@ -142,6 +143,7 @@ def pack_weight(weight, transposed):
 _PACK_EPOCH = [0]
 _PACK_LIVE = []
 _PACK16_LIVE = []
+_PACK16PAD_LIVE = []   # weights carrying the zero-padded pack of the narrow input conv (_mvd_pack16pad)
 
 
 def invalidate_packs():
@@ -259,27 +261,73 @@ def _live(refs, attr, fp):
     return out
 
 
+def _pack16_launch(jobs, dev):
+    """One mvd_pack_weights_bf16_batch_pad launch: jobs = (fp32 source, wf16, wb16, K, C, T, transposed, Csrc)."""
+    n = len(jobs)
+    PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
+    cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
+    col = lambda i: cast(IA(*[int(j[i]) for j in jobs]))
+    with torch.cuda.device(dev):
+        call("mvd_pack_weights_bf16_batch_pad", n, cast(PA(*[j[0].data_ptr() for j in jobs])),
+             cast(PA(*[j[1].data_ptr() for j in jobs])), cast(PA(*[j[2].data_ptr() for j in jobs])),
+             col(3), col(4), col(5), col(6), col(7), _stream())
+
+
+class _Pack16(typing.NamedTuple):
+    """A cached bf16 pack (`_mvd_pack16`: key = (stamp, transposed, device); `_mvd_pack16pad`: key = (stamp, padded reduce
+    channels, device)).  inplace: wf / wb are views of the persistent buffer of a hipGraph trainer's FlatParams."""
+    key: tuple
+    wf: torch.Tensor
+    wb: torch.Tensor
+    inplace: bool = False
+
+
+def _pack16_shape(d, transposed=False, cpad=None):
+    """(K, C, T, transposed, Csrc) of the pack job of weight `d`; cpad: the conv weight packed as if it had cpad reduce
+    channels, the ones beyond its own being zero."""
+    if cpad is not None:
+        return d.shape[0], int(cpad), d[0, 0].numel(), 0, d.shape[1]
+    (C, K) = d.shape[:2] if transposed else (d.shape[1], d.shape[0])
+    return K, C, d[0, 0].numel(), 1 if transposed else 0, C
+
+
+def _pack16_rewrite(weight, e, shape):
+    """A stale bf16 entry whose tensors are views of the persistent buffer of a hipGraph trainer (e.inplace): the captured
+    forward reads THOSE addresses, so the on-the-spot pack writes into them (re-pointing the entry at fresh tensors would
+    leave the replay on the old weights and every later eager forward on tensors no replay rewrites).  Only THIS weight's
+    pack changes, so only its own generation moves: the guards other layers took earlier in the same forward stay valid."""
+    d = weight.detach()
+    _pack16_launch([(d, e.wf, e.wb) + shape], d.device)
+    _pack16_own_gen(weight)[0] += 1
+    return _Pack16((_pack_stamp(d, weight),) + e.key[1:], e.wf, e.wb, True)
+
+
 def _repack_all_bf16(fp=None):
-    """The bf16 packs of the live weights (of `fp`, or all) that have them, in one launch (mvd_pack_weights_bf16_batch)
-    into views of ONE buffer per device.  Default: a FRESH buffer per call -- the tensors an autograd graph saved for
-    backward keep their old buffer alive, exactly as with the per-layer packs (fresh tensors per stamp).  With
-    `fp.pack16_inplace` (set by a trainer that replays its step as a hipGraph: the captured forward must read the addresses
-    the captured repack of the previous replay wrote) the buffer is owned by `fp`, persists and is rewritten in place;
-    `fp.pack16_gen` then guards saved autograd graphs the way the fp32 entries' generations do."""
-    jobs = []
+    """The bf16 packs of the live weights (of `fp`, or all) that have them -- the zero-padded pack of the input conv
+    included -- in one launch (mvd_pack_weights_bf16_batch_pad) into views of ONE buffer per device.  Default: a FRESH
+    buffer per call -- the tensors an autograd graph saved for backward keep their old buffer alive, exactly as with the
+    per-layer packs (fresh tensors per stamp).  With `fp.pack16_inplace` (set by a trainer that replays its step as a
+    hipGraph: the captured forward must read the addresses the captured repack of the previous replay wrote) the buffer is
+    owned by `fp`, persists and is rewritten in place; `fp.pack16_gen` then guards saved autograd graphs the way the fp32
+    entries' generations do."""
+    jobs = []   # (weight data, weight, cache attribute, job shape)
     for w, e in _live(_PACK16_LIVE, "_mvd_pack16", fp):
         d = w.detach()
-        if d.is_cuda and d.dtype == torch.float32 and d.is_contiguous() and d.device == e[0][2]:
-            jobs.append((d, e[0][1], w))
+        if d.is_cuda and d.dtype == torch.float32 and d.is_contiguous() and d.device == e.key[2]:
+            jobs.append((d, w, "_mvd_pack16", _pack16_shape(d, transposed=e.key[1])))
+    for w, e in _live(_PACK16PAD_LIVE, "_mvd_pack16pad", fp):
+        d = w.detach()
+        if d.is_cuda and d.dtype == torch.float32 and d.is_contiguous() and d.device == e.key[2]:
+            jobs.append((d, w, "_mvd_pack16pad", _pack16_shape(d, cpad=e.key[1])))
     inplace = fp is not None and getattr(fp, "pack16_inplace", False)
-    for dev in {d.device for d, _, _w in jobs}:
+    for dev in {j[0].device for j in jobs}:
         js = [j for j in jobs if j[0].device == dev]
-        sizes = [d.numel() for d, _, _w in js]
+        sizes = [q[0] * q[1] * q[2] for _d, _w, _a, q in js]
         pad = lambda n: (n + 127) // 128 * 128  # 256-byte aligned views
         total = 2 * sum(pad(n) for n in sizes)
         buf = None
         if inplace:
-            sig = (dev, tuple((id(w), n) for (_d, _t, w), n in zip(js, sizes)))
+            sig = (dev, tuple((id(w), attr, n) for (_d, w, attr, _q), n in zip(js, sizes)))
             held = getattr(fp, "_pack16_buf", None)
             if held is not None and held[0] == sig:
                 buf = held[1]
@@ -293,31 +341,32 @@ def _repack_all_bf16(fp=None):
         for n in sizes:
             views.append((buf[o:o + n], buf[o + pad(n):o + pad(n) + n]))
             o += 2 * pad(n)
-        n = len(js)
-        PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
-        shp = []
-        for (d, tr, _w) in js:
-            (C, K) = d.shape[:2] if tr else (d.shape[1], d.shape[0])
-            shp.append((K, C, d[0, 0].numel()))
-        cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-        with torch.cuda.device(dev):
-            call("mvd_pack_weights_bf16_batch", n, cast(PA(*[d.data_ptr() for d, _, _w in js])),
-                 cast(PA(*[v[0].data_ptr() for v in views])), cast(PA(*[v[1].data_ptr() for v in views])),
-                 cast(IA(*[q[0] for q in shp])), cast(IA(*[q[1] for q in shp])), cast(IA(*[q[2] for q in shp])),
-                 cast(IA(*[1 if tr else 0 for _, tr, _w in js])), _stream())
-        for (d, tr, w), v in zip(js, views):
-            w._mvd_pack16 = ((_pack_stamp(d, w), tr, d.device), v[0], v[1])
+        _pack16_launch([(d, v[0], v[1]) + q for (d, _w, _a, q), v in zip(js, views)], dev)
+        for (d, w, attr, _q), v in zip(js, views):
+            setattr(w, attr, _Pack16((_pack_stamp(d, w),) + getattr(w, attr).key[1:], v[0], v[1], inplace))
+
+
+def _pack16_own_gen(weight):
+    """generation of the weight's OWN in-place bf16 pack: moved by an on-the-spot rewrite of that one pack"""
+    own = getattr(weight, "_mvd_pack16_own_gen", None)
+    if own is None:
+        own = weight._mvd_pack16_own_gen = [0]
+    return own
 
 
 def _pack16_guard(weight):
-    """(generation holder, generation now) of the in-place bf16 packs `weight` takes part in, or None."""
+    """((generation holders), (generations now)) of the in-place bf16 packs `weight` takes part in, or None: the flat
+    buffer's generation (the batched repack rewrites every pack of it) and the weight's own (_pack16_rewrite)."""
     flat = _flat_of(weight)
     holder = getattr(flat, "_mvd_pack16_gen", None) if flat is not None else None
-    return (holder, holder[0]) if holder is not None else None
+    if holder is None:
+        return None
+    own = _pack16_own_gen(weight)
+    return ((holder, own), (holder[0], own[0]))
 
 
 def _check_pack16_generation(saved, what):
-    if saved is not None and saved[0][0] != saved[1]:
+    if saved is not None and tuple(h[0] for h in saved[0]) != saved[1]:
         raise RuntimeError(f"{what}: the weights were updated (optimizer.step()) between the forward and the backward pass "
                            "of this graph; the bf16 packed copies saved for backward were rewritten in place")
 
@@ -329,9 +378,10 @@ def packs_stale(fp):
     for w, e in _live(_PACK_LIVE, "_mvd_pack", fp):
         if e.stamp != _pack_stamp(w.detach(), w):
             return True
-    for w, e in _live(_PACK16_LIVE, "_mvd_pack16", fp):
-        if e[0][0] != _pack_stamp(w.detach(), w):
-            return True
+    for attr, live in (("_mvd_pack16", _PACK16_LIVE), ("_mvd_pack16pad", _PACK16PAD_LIVE)):
+        for w, e in _live(live, attr, fp):
+            if e.key[0] != _pack_stamp(w.detach(), w):
+                return True
     return False
 
 
@@ -394,19 +444,24 @@ def pack_weight_bf16(weight, transposed):
 def _packed_bf16(weight, transposed):
     """bf16 packs cached on the weight tensor under the same (epoch, version) stamp as the fp32 ones: inference packs
     once; in training the fused optimizer re-packs every registered weight in one launch after its update
-    (repack_all -> mvd_pack_weights_bf16_batch); a stale or missing entry is packed here, per layer."""
+    (repack_all -> mvd_pack_weights_bf16_batch_pad); a stale or missing entry is packed here, per layer -- into fresh
+    tensors, or IN PLACE when the entry's tensors are views of a hipGraph trainer's persistent buffer (_pack16_rewrite)."""
     w = weight.detach()
     if not w.is_contiguous():
         return pack_weight_bf16(weight, transposed)
     e = getattr(weight, "_mvd_pack16", None)
-    if e is None or e[0] != (_pack_stamp(w, weight), transposed, w.device):
+    key = (_pack_stamp(w, weight), transposed, w.device)
+    if e is None or e.key != key:
         if e is None:
             if len(_PACK16_LIVE) >= 4096:
                 _PACK16_LIVE[:] = [r for r in _PACK16_LIVE if r() is not None]
             _PACK16_LIVE.append(weakref.ref(weight))
-        e = ((_pack_stamp(w, weight), transposed, w.device),) + tuple(pack_weight_bf16(weight, transposed))
+        if e is not None and e.inplace and e.key[1:] == key[1:]:
+            e = _pack16_rewrite(weight, e, _pack16_shape(w, transposed=transposed))
+        else:
+            e = _Pack16(key, *pack_weight_bf16(weight, transposed))
         weight._mvd_pack16 = e
-    return e[1], e[2]
+    return e.wf, e.wb
 
 
 def _out_dim(i, k, s):
@@ -622,17 +677,33 @@ class Conv3dFn(Function):
 
 
 def _padded_pack_bf16(weight, cpad):
-    """bf16 packs of a [K][C][3][3][3] weight zero-padded to cpad reduce channels, cached under the usual stamp."""
+    """bf16 packs of a [K][C][3][3][3] weight zero-padded to cpad reduce channels, cached under the usual stamp and
+    registered like the plain bf16 packs: the fused optimizer rebuilds them in its batched repack, packs_stale() watches
+    them, and in hipGraph mode they live in the persistent buffer.  The kernel pads while it packs (Csrc < C)."""
     w = weight.detach()
+
+    def fresh(src):
+        K, T = src.shape[0], src[0, 0].numel()
+        wf = torch.empty((T * cpad * K,), dtype=BF16, device=src.device)
+        wb = torch.empty((T * cpad * K,), dtype=BF16, device=src.device)
+        _pack16_launch([(src, wf, wb) + _pack16_shape(src, cpad=cpad)], src.device)
+        return wf, wb
+
+    if not w.is_contiguous() or w.dtype != torch.float32:  # no cache for a strided view (the kernel reads plain fp32)
+        return fresh(w.float().contiguous())
     e = getattr(weight, "_mvd_pack16pad", None)
     key = (_pack_stamp(w, weight), cpad, w.device)
-    if e is None or e[0] != key:
-        K, C = w.shape[:2]
-        wp = torch.zeros((K, cpad, *w.shape[2:]), dtype=torch.float32, device=w.device)
-        wp[:, :C] = w
-        e = (key,) + tuple(pack_weight_bf16(wp, False))
+    if e is None or e.key != key:
+        if e is None:
+            if len(_PACK16PAD_LIVE) >= 4096:
+                _PACK16PAD_LIVE[:] = [r for r in _PACK16PAD_LIVE if r() is not None]
+            _PACK16PAD_LIVE.append(weakref.ref(weight))
+        if e is not None and e.inplace and e.key[1:] == key[1:]:
+            e = _pack16_rewrite(weight, e, _pack16_shape(w, cpad=cpad))
+        else:
+            e = _Pack16(key, *fresh(w))
         weight._mvd_pack16pad = e
-    return e[1], e[2]
+    return e.wf, e.wb
 
 
 class NarrowInputConv3dBf16Fn(Function):

@@ -5,6 +5,7 @@ nesterov).step()` (nnUNet/nnunetv2/training/nnUNetTrainer/nnUNetTrainer.py:473-4
 PolyLRScheduler (nnUNet/nnunetv2/training/lr_scheduler/polylr.py:4-20).
 """
 import ctypes
+import math
 
 import torch
 
@@ -20,14 +21,18 @@ class FlatParams:
     ALIGN = 4  # floats
 
     def __init__(self, params):
-        self.params = [p for p in params if p.requires_grad]
+        # `params`: parameters, or (name, parameter) pairs -- the names go into layout() so that a saved optimizer state
+        # can be matched to the parameters of a differently ordered buffer
+        pairs = [q if isinstance(q, (tuple, list)) else (None, q) for q in params]
+        pairs = [(n, p) for n, p in pairs if p.requires_grad]
         # de-duplicate shared parameters (decoder.encoder.* aliases) preserving order
         seen, uniq = set(), []
-        for p in self.params:
+        for n, p in pairs:
             if id(p) not in seen:
                 seen.add(id(p))
-                uniq.append(p)
-        self.params = uniq
+                uniq.append((n, p))
+        self.names = [n for n, _ in uniq]
+        self.params = [p for _, p in uniq]
         dev = self.params[0].device
         self.offsets, off = [], 0
         for p in self.params:
@@ -58,6 +63,11 @@ class FlatParams:
                 p.data = view
                 p._mvd_flat = self.flat   # ops' packed-weight cache also watches the flat buffer's version counter
         self.attach_grads()
+
+    def layout(self):
+        """What a flat state buffer (the momentum) has to agree on to be loaded here: per parameter (name or None,
+        shape, offset), in buffer order."""
+        return [(n, tuple(p.shape), o) for n, p, o in zip(self.names, self.params, self.offsets)]
 
     def invalidate_packs(self):
         """Call after writing parameter memory behind torch's back (`p.data.copy_()`, a raw-pointer kernel): the
@@ -170,11 +180,40 @@ class FusedSGDNesterov:
         ops.repack_all(self.fp)
 
     def state_dict(self):
-        return {'momentum_buffer': self.momentum_buffer.clone(), 'steps': self._steps,
+        return {'momentum_buffer': self.momentum_buffer.clone(), 'steps': self._steps, 'layout': self.fp.layout(),
                 'param_groups': [{k: v for k, v in self.param_groups[0].items() if k != 'params'}]}
 
     def load_state_dict(self, sd):
-        self.momentum_buffer.copy_(sd['momentum_buffer'])
+        """The momentum is ONE flat buffer laid out like FlatParams.flat, so it only means something together with its
+        layout.  Same layout: copied.  Another layout with unique names on both sides that cover the same parameters
+        (same names and shapes, another order): every parameter's slice is moved to its place here.  Anything else
+        raises.  A state without 'layout' (written before the signature existed) is TRUSTED when its size matches."""
+        src, mine = sd['momentum_buffer'], self.fp.layout()
+        theirs = sd.get('layout')
+        theirs = [(n, tuple(shape), int(o)) for n, shape, o in theirs] if theirs is not None else None
+        if theirs is None or theirs == mine:
+            if src.numel() != self.momentum_buffer.numel():
+                raise ValueError(f"optimizer state: momentum buffer of {src.numel()} elements, this parameter layout "
+                                 f"has {self.momentum_buffer.numel()}")
+            self.momentum_buffer.copy_(src)
+        else:
+            by_name = {n: (shape, o) for n, shape, o in theirs}
+            names = [n for n, _, _ in mine]
+            if None in by_name or None in names or len(by_name) != len(theirs) or len(set(names)) != len(names) or \
+                    set(by_name) != set(names) or any(by_name[n][0] != shape for n, shape, _ in mine):
+                raise ValueError("optimizer state: parameter layout mismatch -- the momentum buffer was saved under another "
+                                 "parameter order or other shapes, and the two layouts cannot be matched by name "
+                                 f"(saved: {[(n, s) for n, s, _ in theirs][:4]}..., here: {[(n, s) for n, s, _ in mine][:4]}...)")
+            need = max(o + math.prod(shape) for _n, shape, o in theirs)
+            if src.numel() < need:
+                raise ValueError(f"optimizer state: parameter layout mismatch -- the saved layout covers {need} elements, "
+                                 f"the saved momentum buffer has {src.numel()}")
+            src = src.to(self.momentum_buffer.device)
+            new = torch.zeros_like(self.momentum_buffer)
+            for n, shape, o in mine:
+                k, so = math.prod(shape), by_name[n][1]
+                new[o:o + k] = src[so:so + k]
+            self.momentum_buffer.copy_(new)
         self._steps = sd['steps']
         self.param_groups[0].update(sd['param_groups'][0])
 

@@ -314,7 +314,8 @@ class nnUNetTrainerMI355(object):
         # contiguous slices cut from the end -- then complete in backward order (parallel.BucketedGradReducer)
         order = getattr(self.network, "parameters_in_execution_order", None)
         params = order() if order is not None else list(self.network.parameters())
-        optimizer = FusedSGDNesterov(FlatParams(params), self.initial_lr,
+        name_of = {id(p): n for n, p in self.network.named_parameters()}   # (the layout signature of the optimizer state)
+        optimizer = FusedSGDNesterov(FlatParams([(name_of.get(id(p)), p) for p in params]), self.initial_lr,
                                      weight_decay=self.weight_decay, momentum=0.99, nesterov=True, max_grad_norm=12)
         lr_scheduler = PolyLRScheduler(optimizer, self.initial_lr, self.num_epochs)
         return optimizer, lr_scheduler
@@ -430,11 +431,27 @@ class nnUNetTrainerMI355(object):
     def _graph_flags(self):
         return (bool(self.network.decoder.deep_supervision), self._label_mode())
 
+    def _graph_side_outputs(self):
+        """Device tensors the step body leaves on the trainer beside the loss (none here), collected after the capture."""
+        return None
+
+    def _restore_graph_side_outputs(self, side):
+        """Called after every replay with what _graph_side_outputs() returned: a replay runs no Python, and an eager
+        forward in between (validation_step) may have re-pointed the attributes at its own tensors."""
+
     def _graphed_step(self, data, target):
         key = self._graph_key(data, target)
         sg = self._step_graph
         if sg is None or sg['key'] != key:
             sg = self._step_graph = {'key': key, 'graph': None, 'warm': 0}
+        # Invariant: every packed weight a replay reads is either rewritten by the replay itself (the captured repack, for
+        # the NEXT replay) or refreshed before it.  load_state_dict / invalidate_packs since the last step leave stale
+        # stamps -> repack first: before a replay, before the capture (no pack kernel may be captured by accident) and
+        # before a warm-up step (one batched launch instead of a rewrite per layer).  An eager forward in between
+        # (validation_step) that met a stale entry has packed it IN PLACE into the persistent buffer
+        # (ops._pack16_rewrite), so a current stamp always means a current buffer.
+        if ops.packs_stale(self.optimizer.fp):
+            ops.repack_all(self.optimizer.fp)
         if sg['graph'] is None:
             if sg['warm'] < self.hip_graph_warmup:
                 sg['warm'] += 1   # eager first: allocator steady state, the optimizer's first-step flag, pack caches
@@ -455,6 +472,7 @@ class nnUNetTrainerMI355(object):
                 warnings.warn(f"hipGraph capture of the train step failed ({type(e).__name__}: {e}); running eagerly")
                 return self._step_body(data, target)
             sg['graph'] = g
+            sg['side'] = self._graph_side_outputs()
             captured_now = True    # (the capture ran the body's Python once: the optimizer's step counter already moved)
         else:
             captured_now = False
@@ -467,9 +485,8 @@ class nnUNetTrainerMI355(object):
             elif sg['target'].data_ptr() != target.data_ptr():
                 sg['target'].copy_(target, non_blocking=True)
         self.optimizer.sync_hyper()
-        if ops.packs_stale(self.optimizer.fp):   # load_state_dict / invalidate_packs since the last step: the captured
-            ops.repack_all(self.optimizer.fp)    # forward reads the persistent pack buffers -> refresh them first
         sg['graph'].replay()
+        self._restore_graph_side_outputs(sg['side'])
         if not captured_now:
             self.optimizer.note_replayed_step()
         return sg['loss']
@@ -520,7 +537,9 @@ class nnUNetTrainerMI355(object):
             target = target.to(self.device, non_blocking=True)
         l = self._graphed_step(data, target) if self._graph_allowed() else self._step_body(data, target)
         if return_device_loss:
-            return {'loss': l}
+            # the graph's loss is ONE static tensor that every replay overwrites: hand out a copy, as the eager step does
+            sg = self._step_graph
+            return {'loss': l.clone() if sg is not None and l is sg.get('loss') else l}
         return {'loss': l.cpu().numpy()}  # the reference syncs here every step (:925)
 
     def validation_step(self, batch: dict) -> dict:
@@ -696,6 +715,15 @@ class ContrastiveTrainerMI355(nnUNetTrainerMI355):
             ct.append(ops.cc_label(ops.threshold_mask(tmask[n, 0], 0.5, ge=True), 26)[1])
         cp, ct = torch.cat(cp), torch.cat(ct)
         return {'cc_pred': cp, 'cc_true': ct, 'betti0_error': (cp - ct).abs()}
+
+    def _graph_side_outputs(self):
+        """`last_topology` of a replayed step: the graph's static tensors, overwritten by the next train step (clone
+        what has to outlive it); after an eager step or a validation_step it holds that forward's own fresh tensors."""
+        return self.last_topology if (self.use_topo and self.topo_cc) else None
+
+    def _restore_graph_side_outputs(self, side):
+        if side is not None:
+            self.last_topology = side
 
     def _graph_flags(self):
         return (bool(self.network.do_ds), self.use_topo, self.topo_cc, self.skel_iter, self.feat_kl, self.kl_T,

@@ -134,7 +134,7 @@ def test_narrow_input_conv_bf16_exact_integer_data(N, C, sp, planar):
 
 def test_bf16_packs_follow_the_fused_optimizer_in_one_launch():
     """After FusedSGDNesterov.step() (raw-pointer update of the flat buffer) every registered bf16 pack is rebuilt by ONE
-    batched launch (ops.repack_all -> mvd_pack_weights_bf16_batch) into fresh tensors: the cached entry must carry the
+    batched launch (ops.repack_all -> mvd_pack_weights_bf16_batch_pad) into fresh tensors: the cached entry must carry the
     new stamp without a per-layer pack, equal the per-layer pack of the updated weight bit for bit (conv and transposed
     conv layouts), and the tensors a graph saved before the step must be untouched."""
     from multimodal_mvd_seg_amd import ops, optim
@@ -158,6 +158,94 @@ def test_bf16_packs_follow_the_fused_optimizer_in_one_launch():
     assert conv.weight._mvd_pack16[1].data_ptr() != old[1].data_ptr()
     assert torch.equal(old[1], old_wf)  # the pre-step pack is still what the old graph saw
     assert not torch.equal(conv.weight._mvd_pack16[1], old_wf)
+
+
+def _pack16_layout_ref(w, C, transposed):
+    """wf16 / wb16 of a [K][Csrc][T] conv (or [C][K][T] transposed-conv) weight restated with plain tensor indexing: reduce
+    channels zero-padded to C, rounded to bf16 by torch, element (chunk of 32 reduce channels, tap, 16-half, 8-half,
+    produce channel, 8 reduce channels) -- the layout include/mvdseg_hip.h documents for mvd_pack_weight_bf16."""
+    w = w.flatten(2)
+    if transposed:
+        w = w.permute(1, 0, 2)
+    K, Cs, T = w.shape
+    wp = torch.zeros((K, C, T), dtype=torch.float32)
+    wp[:, :Cs] = w
+    wp = wp.to(torch.bfloat16)
+    wf = wp.view(K, C // 32, 2, 2, 8, T).permute(1, 5, 2, 3, 0, 4).reshape(-1) if C % 32 == 0 else None
+    wb = wp.view(K // 32, 2, 2, 8, C, T).permute(0, 5, 1, 2, 4, 3).reshape(-1) if K % 32 == 0 else None
+    return wf, wb
+
+
+def test_batched_bf16_pack_entries_against_the_layout_and_the_per_layer_pack_with_padded_reduce_channels():
+    """mvd_pack_weights_bf16_batch_pad packs a [K][Csrc][T] weight as the [K][C][T] weight whose reduce channels
+    Csrc .. C-1 are zero.  One launch holds padded jobs over the range NarrowInputConv3dBf16Fn admits (Csrc 1 .. 8, K a
+    multiple of 32; one tap and 27; wf only, wb only, both; a C of two chunks) next to plain jobs (the LDS-tiled 3x3x3
+    path, a transposed-conv weight): every output must equal, bit for bit, the layout restated in plain indexing AND
+    mvd_pack_weight_bf16 of the zero-padded tensor, and a destination that was not asked for stays untouched.  The plain
+    jobs also go through mvd_pack_weights_bf16_batch, the entry without the pad field (kept in the ABI)."""
+    from multimodal_mvd_seg_amd._lib import call
+    g = torch.Generator().manual_seed(31)
+    #        K, Csrc,  C, taps, transposed, wf, wb
+    jobs = [(32, 1, 32, (3, 3, 3), 0, 1, 1), (64, 3, 32, (3, 3, 3), 0, 1, 0), (96, 8, 32, (3, 3, 3), 0, 0, 1),
+            (32, 5, 64, (3, 3, 3), 0, 1, 1), (32, 4, 32, (1, 1, 1), 0, 1, 1), (64, 32, 32, (3, 3, 3), 0, 1, 1),
+            (32, 64, 64, (2, 2, 2), 1, 1, 1), (64, 7, 32, (3, 3, 3), 0, 1, 1)]
+    FILL = 0x7FC1   # a bf16 NaN pattern no pack produces
+    host, src, dst = [], [], []
+    for K, Cs, C, ks, tr, want_f, want_b in jobs:
+        shape = (Cs, K, *ks) if tr else (K, Cs, *ks)
+        w = torch.randn(shape, generator=g)
+        host.append(w)
+        src.append(w.to(DEV).contiguous())
+        T = ks[0] * ks[1] * ks[2]
+        dst.append(tuple(torch.full((T * C * K,), FILL, dtype=torch.int16, device=DEV).view(torch.bfloat16) for _ in range(2)))
+
+    def launch(entry, idx, with_csrc):
+        n = len(idx)
+        PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
+        cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
+        col = lambda f: cast(IA(*[f(jobs[q]) for q in idx]))
+        args = [n, cast(PA(*[src[q].data_ptr() for q in idx])),
+                cast(PA(*[dst[q][0].data_ptr() if jobs[q][5] else None for q in idx])),
+                cast(PA(*[dst[q][1].data_ptr() if jobs[q][6] else None for q in idx])),
+                col(lambda j: j[0]), col(lambda j: j[2]), col(lambda j: j[3][0] * j[3][1] * j[3][2]), col(lambda j: j[4])]
+        if with_csrc:
+            args.append(col(lambda j: j[1]))
+        call(entry, *args, _stream())
+
+    def check(idx, what):
+        torch.cuda.synchronize()
+        for q in idx:
+            K, Cs, C, ks, tr, want_f, want_b = jobs[q]
+            T = ks[0] * ks[1] * ks[2]
+            rf, rb = _pack16_layout_ref(host[q], C, tr)
+            wp = torch.zeros((K, C, *ks), dtype=torch.float32, device=DEV)
+            if tr:
+                kf = torch.empty(T * C * K, dtype=torch.bfloat16, device=DEV)
+                kb = torch.empty_like(kf)
+                call("mvd_pack_weight_bf16", _p(src[q]), _p(kf), _p(kb), K, C, T, 1, _stream())
+            else:
+                wp[:, :Cs] = src[q]
+                kf = torch.empty(T * C * K, dtype=torch.bfloat16, device=DEV)
+                kb = torch.empty_like(kf)
+                call("mvd_pack_weight_bf16", _p(wp), _p(kf), _p(kb), K, C, T, 0, _stream())
+            for name, got, ref, kern, want in (("wf", dst[q][0], rf, kf, want_f), ("wb", dst[q][1], rb, kb, want_b)):
+                bits = got.view(torch.int16).cpu()
+                if not want:
+                    assert bool((bits == torch.tensor(FILL, dtype=torch.int16)).all()), f"{what} job {q}: {name} was written"
+                    continue
+                assert torch.equal(bits, ref.view(torch.int16)), f"{what} job {q} {jobs[q]}: {name} differs from the layout"
+                assert torch.equal(bits, kern.view(torch.int16).cpu()), f"{what} job {q} {jobs[q]}: {name} differs from the per-layer pack"
+
+    every = list(range(len(jobs)))
+    launch("mvd_pack_weights_bf16_batch_pad", every, True)
+    check(every, "batch_pad")
+    plain = [q for q in every if jobs[q][1] == jobs[q][2]]
+    assert len(plain) == 2
+    for q in plain:
+        for t in dst[q]:
+            t.view(torch.int16).fill_(FILL)
+    launch("mvd_pack_weights_bf16_batch", plain, False)
+    check(plain, "batch")
 
 
 @pytest.mark.parametrize("C,K,sp,N", [(64, 32, (4, 5, 6), 2), (320, 256, (2, 2, 2), 2),

@@ -371,3 +371,64 @@ def test_flat_layout_follows_execution_order_and_the_last_reduced_bucket_is_smal
     # buckets are contiguous and ordered from the end of the buffer
     for (s0, e0, _), (s1, e1, _) in zip(red.buckets[:-1], red.buckets[1:]):
         assert e1 == s0
+
+
+def _momentum_constants(opt):
+    """fill the momentum slice of parameter i with i + 1; return {id(parameter): constant}"""
+    fp, want = opt.fp, {}
+    for i, (p, o) in enumerate(zip(fp.params, fp.offsets)):
+        opt.momentum_buffer[o:o + p.numel()] = float(i + 1)
+        want[id(p)] = float(i + 1)
+    return want
+
+
+def test_optimizer_state_carries_its_parameter_layout_and_is_never_misassigned_silently():
+    """FusedSGDNesterov.state_dict() holds the momentum as ONE flat buffer in FlatParams order.  A buffer saved under
+    another parameter order has the same numel (the per-tensor padding does not depend on the order), so without a layout
+    signature it loads onto the wrong parameters without a word.  With names (what the trainers pass) the slices are moved
+    to their parameters; without names the mismatch raises.  A state WITHOUT 'layout' (the format before the signature) still
+    loads when its numel matches -- it is then trusted, nothing can be checked."""
+    net = nn.Sequential(nn.Linear(3, 5), nn.Linear(5, 5), nn.Linear(5, 2))   # two (5,) biases: shapes alone cannot tell them apart
+    named = list(net.named_parameters())
+    a = optim.FusedSGDNesterov(optim.FlatParams(named))
+    want = _momentum_constants(a)
+    sd = a.state_dict()
+    assert [n for n, _s, _o in sd['layout']] == [n for n, _ in named]
+    assert [o for _n, _s, o in sd['layout']] == a.fp.offsets
+    # (FlatParams re-homes p.data: a second optimizer over the same module simply re-homes it again)
+    b = optim.FusedSGDNesterov(optim.FlatParams(named[::-1]))
+    assert b.fp.numel == a.fp.numel
+    assert sd['momentum_buffer'].numel() == b.momentum_buffer.numel()     # the trap: nothing in the sizes gives it away
+    b.load_state_dict(sd)
+    assert b._steps == sd['steps']
+    for p, o in zip(b.fp.params, b.fp.offsets):
+        got = b.momentum_buffer[o:o + p.numel()]
+        assert torch.equal(got, torch.full_like(got, want[id(p)])), "momentum landed on another parameter"
+    # the same layout round-trips untouched, padding included
+    a2 = optim.FusedSGDNesterov(optim.FlatParams(named))
+    a2.load_state_dict(sd)
+    assert torch.equal(a2.momentum_buffer, sd['momentum_buffer'])
+    # without names the two layouts cannot be matched: loud, and the message names the cause
+    plain = [p for _, p in named]
+    c = optim.FusedSGDNesterov(optim.FlatParams(plain))
+    _momentum_constants(c)
+    d = optim.FusedSGDNesterov(optim.FlatParams(plain[::-1]))
+    before = d.momentum_buffer.clone()
+    with pytest.raises(ValueError, match="layout mismatch"):
+        d.load_state_dict(c.state_dict())
+    assert torch.equal(d.momentum_buffer, before) and d._steps == 0       # nothing half-loaded
+    # names that do not cover the same parameters do not match either
+    e = optim.FusedSGDNesterov(optim.FlatParams([("x." + n, p) for n, p in named[::-1]]))
+    with pytest.raises(ValueError, match="layout mismatch"):
+        e.load_state_dict(sd)
+    # a buffer shorter than the layout it comes with: the same error, not a slice-shape complaint
+    cut = dict(sd, momentum_buffer=sd['momentum_buffer'][:-4])
+    with pytest.raises(ValueError, match="layout mismatch"):
+        b.load_state_dict(cut)
+    # the old format: no signature -> trusted when the size matches, refused when it does not
+    old = {k: v for k, v in sd.items() if k != 'layout'}
+    d.load_state_dict(old)
+    assert torch.equal(d.momentum_buffer, sd['momentum_buffer'])
+    old['momentum_buffer'] = torch.zeros(sd['momentum_buffer'].numel() + 4)
+    with pytest.raises(ValueError, match="momentum buffer"):
+        d.load_state_dict(old)
