@@ -52,7 +52,7 @@ struct PerDeviceFlag {
 // A value loaded from memory, made "arrived" HERE: the empty volatile asm is a use the compiler must wait for, once and
 // unconditionally.  Without it a bias loaded at the top of an epilogue has its first use inside the predicated store
 // blocks, every such block gets an s_waitcnt vmcnt(0), and that also waits for the previous block's STORE: the stores
-// of a tile run as serialised write round trips (k_fwd_wino2: 23 of a tile's 85 kilocycles, tools/stamps_wino.py).
+// of a tile run as serialised write round trips (k_fwd_wino2: 23 of a tile's 85 kilocycles in s_memtime stamps).
 __device__ __forceinline__ float settled(float v) {
     asm volatile("" : "+v"(v));
     return v;

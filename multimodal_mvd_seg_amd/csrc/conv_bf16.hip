@@ -77,17 +77,14 @@ struct Fwd16Tile {
     int nitems;
     int K;
     int toff[27];
-    signed char tdy[28];  // halo row shift of tap t (off[t][1] - min_off[1]): selects the XOR swizzle of the read
+    signed char tdy[28];  // unused (read only by the removed XOR-swizzled halo layout); kept so the argument layout stays
 };
 
 // XR: uint4 (8 bf16) per thread of the halo tile = ceil(nslots*4/256)
-// SWZ (unit gather stride in every axis): halo slots are the bare 64-byte voxel rows with the four 16-byte parts XOR-swizzled
-// by (halo y-row & 3) -- conflict-free ds_read_b128 for every tap (see k_fwd16q); the padded 80-byte slots of the
-// strided layers are 3-way conflicted on unit-stride problems (PMC round 2: as many conflict cycles as access cycles).
-#ifndef MVD_F16_DBG
-#define MVD_F16_DBG 0
-#endif
-template <int NT, int MT, int TG, int XR, bool SWZ, int NW = 4>
+// Halo slots are padded to 80 bytes: 3-way conflicted on unit-stride problems (PMC round 2: as many conflict cycles as
+// access cycles), but the conflict-free XOR-swizzled 64-byte layout measured 12-15 % SLOWER here (two workgroups per CU:
+// the kernel is bound by instruction issue, and the swizzle is arithmetic per read) and was removed.
+template <int NT, int MT, int TG, int XR, int NW = 4>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeom g, const Fwd16Tile tg, const unsigned short *__restrict__ a1,
                                                   const unsigned short *__restrict__ a2,
                                                   const unsigned short *__restrict__ w, const float *__restrict__ bias,
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
     extern __shared__ __attribute__((aligned(16))) unsigned char lds8[];
     constexpr int KT = 32 * NT;
     constexpr int TPB = NW * 64;                 // threads: wave w owns output plane od0 + w of the NW x (4 MT) x 8 tile
-    constexpr int XS = SWZ ? 64 : 80;            // bytes per halo slot (64 + 16 pad when not swizzled)
+    constexpr int XS = 80;                       // bytes per halo slot (64 + 16 pad)
     constexpr int WROW = 16;                     // bytes per (tap, s, h, k) weight fragment
     constexpr int WR = TG * 4 * KT / TPB;        // uint4 per thread per weight group (TG*2*2*KT fragments)
     constexpr int WBUF = TG * 4 * KT * WROW;     // bytes per weight buffer
@@ -137,9 +134,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
     int sbase[MT];
 #pragma unroll
     for (int m = 0; m < MT; m++)
-        sbase[m] = (((wave * g.sa[0]) * tg.EH + (4 * m + (i >> 3)) * g.sa[1]) * tg.EW + (i & 7) * g.sa[2]) * XS +
-                   (SWZ ? 0 : h * 16);
-    const int ylq = (i >> 3) & 3;  // (row of this lane inside its M tile) & 3; M tiles start at multiples of 4 rows
+        sbase[m] = (((wave * g.sa[0]) * tg.EH + (4 * m + (i >> 3)) * g.sa[1]) * tg.EW + (i & 7) * g.sa[2]) * XS + h * 16;
     f32x16 acc[MT][NT];
 #pragma unroll
     for (int m = 0; m < MT; m++)
@@ -186,10 +181,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
     // step: the tap groups are taken in an order rotated by the work item, so that at any time the CUs of an XCD ask for
     // different lines (ablation round 2: the weight path was 64 of the 118 us this kernel needs WITHOUT its MFMAs on
     // 64 -> 64 @64^3 -- 450 MB of L2 reads per launch)
-#if (MVD_F16_DBG & 64)
-    long long *stamps = reinterpret_cast<long long *>(part);  // diagnostic build only: in-kernel s_memtime stamps of one wave
-    int nst = 0;
-#endif
     // halo of one 32-channel chunk into registers (XR x 16 bytes per thread)
     constexpr bool PREF = NW == 8;
     uint4 hv[XR];
@@ -211,7 +202,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
                 const int ez = (slot * tg.magHW) >> 20, rem = slot - ez * EHW;
                 const int ey = (rem * tg.magW) >> 20, ex = rem - ey * tg.EW;
                 const int id = iz0 + ez, ih = iy0 + ey, iw = ix0 + ex;
-                if (!(MVD_F16_DBG & 16) && id >= 0 && id < g.Di && ih >= 0 && ih < g.Hi && iw >= 0 && iw < g.Wi)
+                if (id >= 0 && id < g.Di && ih >= 0 && ih < g.Hi && iw >= 0 && iw < g.Wi)
                     hv[u] = *reinterpret_cast<const uint4 *>(
                         src + ((((size_t)n * g.Di + id) * g.Hi + ih) * g.Wi + iw) * Cs + cofs + (tid & 3) * 8);
             }
@@ -227,13 +218,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
 #pragma unroll
         for (int u = 0; u < XR; u++) {
             const int idx = u * TPB + tid;
-            int part = idx & 3;
-            if (SWZ) {
-                const int slot = idx >> 2;
-                const int ez = (slot * tg.magHW) >> 20, rem = slot - ez * EHW;
-                part ^= ((rem * tg.magW) >> 20) & 3;  // halo y-row of the slot
-            }
-            *reinterpret_cast<uint4 *>(Xs + (size_t)(idx >> 2) * XS + part * 16) = hv[u];
+            *reinterpret_cast<uint4 *>(Xs + (size_t)(idx >> 2) * XS + (idx & 3) * 16) = hv[u];
         }
         // PREF (one workgroup per CU: nothing else hides the fetch): the next chunk's halo travels while this chunk's 27 taps run
         if (PREF && cc + 1 < cc_end) load_halo(cc + 1);
@@ -252,8 +237,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
             auto read_ops = [&](int j, int buf) {
                 const int tl = j >> 1, s = j & 1;
                 const int to = to3[tl];
-                const int t = gi * TG + tl < g.ntaps ? gi * TG + tl : g.ntaps - 1;  // (SWZ only)
-                const int xo = SWZ ? ((((s << 1) | h) ^ ((ylq + tg.tdy[t]) & 3)) << 4) : s * 32;
+                const int xo = s * 32;
 #pragma unroll
                 for (int m = 0; m < MT; m++) {
                     uint4 q = *reinterpret_cast<const uint4 *>(Xs + sbase[m] + to + xo);
@@ -265,20 +249,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
                     bfr[buf][q_] = *reinterpret_cast<bf16x8 *>(&q);
                 }
             };
-#if (MVD_F16_DBG & 4)
-            if (gi == 0)
-#endif
-            {
 #pragma unroll
-                for (int j = 0; j < RA && j < 2 * TG; j++) read_ops(j, j % NBUF);
-            }
+            for (int j = 0; j < RA && j < 2 * TG; j++) read_ops(j, j % NBUF);
 #pragma unroll
             for (int j = 0; j < 2 * TG; j++) {
-#if (MVD_F16_DBG & 4)
-                if (gi == 0)
-#endif
                 if (j + RA < 2 * TG) read_ops(j + RA, (j + RA) % NBUF);
-#if !(MVD_F16_DBG & 2)
                 if (fullg || gi * TG + (j >> 1) < g.ntaps) {  // block-uniform
 #pragma unroll
                     for (int m = 0; m < MT; m++)
@@ -286,7 +261,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
                         for (int q_ = 0; q_ < NT; q_++)
                             acc[m][q_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[j % NBUF][q_], af[j % NBUF][m], acc[m][q_], 0, 0, 0);
                 }
-#endif
             }
         };
         // group gi: its weights (loaded two groups ago into register set gi & 1) go to LDS buffer gi & 1 -- last read by
@@ -294,35 +268,16 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
         // With one register set the loads of group gi+1 had only group gi's 24 MFMAs (~0.4 us) to come back from L2.
         int gr = rot, gr2 = rot + 2 >= ngroups ? rot + 2 - ngroups : rot + 2;  // rotated indices of groups gj and gj + 2
         if (gr2 >= ngroups) gr2 -= ngroups;                                     // (ngroups == 1)
-#if (MVD_F16_DBG & 64)
-#define MVD_STAMP(K) { if (stamp_on) { stamps[nst * 8 + (K)] = __builtin_amdgcn_s_memtime(); } }
-#else
-#define MVD_STAMP(K)
-#endif
         // one group: PAR = its LDS buffer / register set (two named arrays: an array of arrays went to scratch memory)
-#define MVD_F16_GROUP(PAR, WRX)                                                        \
-        {                                                                              \
-            MVD_F16_STAMP_ON                                                           \
-            MVD_STAMP(0)                                                               \
-            if (!(MVD_F16_DBG & 8)) store_w(PAR, WRX);                                 \
-            MVD_STAMP(1)                                                               \
-            if (!(MVD_F16_DBG & 1)) __syncthreads(); /* B2 */                          \
-            MVD_STAMP(2)                                                               \
-            if (!(MVD_F16_DBG & 8) && gj + 2 < ngroups) load_w(cc, gr2, WRX);          \
-            MVD_STAMP(3)                                                               \
-            group_mfmas(gr, PAR);                                                      \
-            MVD_STAMP(4)                                                               \
-            MVD_F16_STAMP_NEXT                                                         \
-            gr = gr + 1 == ngroups ? 0 : gr + 1;                                       \
-            gr2 = gr2 + 1 == ngroups ? 0 : gr2 + 1;                                    \
+#define MVD_F16_GROUP(PAR, WRX)                                  \
+        {                                                        \
+            store_w(PAR, WRX);                                   \
+            __syncthreads(); /* B2 */                            \
+            if (gj + 2 < ngroups) load_w(cc, gr2, WRX);          \
+            group_mfmas(gr, PAR);                                \
+            gr = gr + 1 == ngroups ? 0 : gr + 1;                 \
+            gr2 = gr2 + 1 == ngroups ? 0 : gr2 + 1;              \
         }
-#if (MVD_F16_DBG & 64)
-#define MVD_F16_STAMP_ON const bool stamp_on = item == 64 && wave == 0 && lane == 0 && nst < 40;
-#define MVD_F16_STAMP_NEXT if (stamp_on) nst++;
-#else
-#define MVD_F16_STAMP_ON
-#define MVD_F16_STAMP_NEXT
-#endif
         for (int gj = 0; gj < ngroups;) {
             MVD_F16_GROUP(0, wrA)
             if (++gj >= ngroups) break;
@@ -330,9 +285,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
             ++gj;
         }
 #undef MVD_F16_GROUP
-#undef MVD_F16_STAMP_ON
-#undef MVD_F16_STAMP_NEXT
-#undef MVD_STAMP
     }
     // epilogue.  The MFMA operands are swapped (D^T = W^T X^T): column (lane & 31) = voxel of the M tile, rows = output
     // channels (r & 3) + 8 * (r >> 2) + 4 * h -- a lane holds 4 x 4 consecutive channels of ONE voxel and stores them as
@@ -381,7 +333,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_fwd16(const FwdGeo
                     }
                     const uint4 img = pair_store_image(pk[0], pk[1]);
                     const int k = kb * KT + q * 32 + 16 * kp + 8 * h;  // first of this lane's 8 consecutive channels
-                    if (inside && !(MVD_F16_DBG & 32)) {
+                    if (inside) {
                         if (k < g.K1) {
                             uint4 *dst = reinterpret_cast<uint4 *>(y1 + ov * g.K1 + k);
                             *dst = g.acc ? add_bf16x8(img, *dst) : img;   // (block-uniform)
@@ -591,12 +543,12 @@ int dgrad16s(int N, int D, int H, int W, int C, int K, int Do, int Ho, int Wo, c
 
 static const size_t LDS_LIMIT16 = 160 * 1024;
 
-template <int NT, int MT, int TG, int XR, bool SWZ, int NW = 4>
+template <int NT, int MT, int TG, int XR, int NW = 4>
 static int launch_fwd16(const FwdGeom &g, Fwd16Tile &tg, const unsigned short *a1, const unsigned short *a2,
                         const unsigned short *w, const float *bias, unsigned short *y1, unsigned short *y2, void *ws,
                         size_t ws_bytes, hipStream_t s) {
-    auto kern = k_fwd16<NT, MT, TG, XR, SWZ, NW>;
-    const size_t lds = (size_t)XR * (NW * 16) * (SWZ ? 64 : 80) + 2 * (size_t)TG * 4 * (32 * NT) * 16 + 256;  // + tap tables
+    auto kern = k_fwd16<NT, MT, TG, XR, NW>;
+    const size_t lds = (size_t)XR * (NW * 16) * 80 + 2 * (size_t)TG * 4 * (32 * NT) * 16 + 256;  // + tap tables
     if (lds > LDS_LIMIT16) return -1;
     static PerDeviceFlag configured;
     if (!configured()) {
@@ -638,609 +590,24 @@ static int launch_fwd16(const FwdGeom &g, Fwd16Tile &tg, const unsigned short *a
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ persistent kernel
-// 3x3x3 stride-1 layers with 32 reduce and 32 produce channels at high resolution (enc0.conv1, dec5.conv1 and their
-// input gradients: 537 MB of activations, 232 GFLOP each).  A 256-voxel tile is only 108 bf16 MFMAs per wave (3.5k
-// cycles) -- less than one L2 round trip -- so the one-tile-per-workgroup kernel above spends its time waiting for the
-// halo.  Here one workgroup per CU walks its XCD's tiles; all 27 taps' weights (55 KB) stay in LDS for the whole walk,
-// the halo of tile t+1 is fetched into registers while tile t's MFMAs run and lands in the other of two LDS halo buffers
-// (one barrier per tile); B fragments are kept in registers for a filter plane (9 taps x 2 k-steps) so the LDS feeds one
-// A fragment per MFMA.
-constexpr int P_TPB = 512;    // 8 waves: d-plane = wave & 3, row block (4 rows) = wave >> 2; two waves per SIMD
-constexpr int P_XR = 5;       // uint4 per thread: 600 slots x 4 / 512
-constexpr int P_XS = 80;      // bytes per halo slot (64 + 16 pad)
-constexpr int P_HALO = 600 * P_XS;
-constexpr int P_WB = 27 * 2 * 2 * 32 * 16;  // bytes of the resident weights
-
-__global__ __launch_bounds__(512, 2) void k_fwd16p(const FwdGeom g, const Fwd16Tile tg, const unsigned short *__restrict__ a1,
-                                                   const unsigned short *__restrict__ w, const float *__restrict__ bias,
-                                                   unsigned short *__restrict__ y1, int dbg) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds8[];
-    unsigned char *Wsm = lds8;                 // [tap][s][h][k][16 B]
-    unsigned char *Xs0 = lds8 + P_WB;          // two halo buffers
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i = lane & 31, h = lane >> 5;
-    const int per_xcd = (tg.nitems + 7) >> 3;
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3, nlocal = gridDim.x >> 3;
-    const int EHW = tg.EH * tg.EW;
-    const int nx = tg.nslots * 4;
-
-    // resident weights: 27 taps x 128 fragments of 16 B, in tap order (the tap -> weight index map is g.wt)
-    for (int f = tid; f < 27 * 128; f += P_TPB) {
-        const int t = f >> 7, r = f & 127;  // r = (s*2 + hh)*32 + k
-        *reinterpret_cast<uint4 *>(Wsm + (size_t)f * 16) =
-            *reinterpret_cast<const uint4 *>(w + ((size_t)g.wt[t] * 128 + r) * 8);
-    }
-    // tile-independent decode of this thread's staging slots
-    int rel[P_XR], cz[P_XR];
-#pragma unroll
-    for (int u = 0; u < P_XR; u++) {
-        const int idx = u * P_TPB + tid;
-        const int slot = idx >> 2;
-        const int ez = slot / EHW, rem = slot - ez * EHW;
-        const int ey = rem / tg.EW, ex = rem - ey * tg.EW;
-        rel[u] = ((ez * g.Hi + ey) * g.Wi + ex) * 32 + (idx & 3) * 8;
-        cz[u] = idx < nx ? ((ez << 16) | (ey << 8) | ex) : -1;
-    }
-    uint4 v[P_XR];
-    int n_, od0, oh0, ow0;
-    auto decode = [&](int it) {
-        unsigned r_ = (unsigned)(xcd * per_xcd + it);
-        ow0 = (int)(r_ % (unsigned)tg.ntw) * 8; r_ /= (unsigned)tg.ntw;
-        oh0 = (int)(r_ % (unsigned)tg.nth) * 8; r_ /= (unsigned)tg.nth;
-        od0 = (int)(r_ % (unsigned)tg.ntd) * 4;
-        n_ = (int)(r_ / (unsigned)tg.ntd);
-    };
-    auto valid = [&](int it) { return it < per_xcd && xcd * per_xcd + it < tg.nitems; };
-    auto load_halo = [&]() {  // of the tile in (n_, od0, oh0, ow0)
-        const int z0 = od0 - 1, y0 = oh0 - 1, x0 = ow0 - 1;
-        const unsigned short *base = a1 + ((((long)n_ * g.Di + z0) * g.Hi + y0) * g.Wi + x0) * 32L;
-#pragma unroll
-        for (int u = 0; u < P_XR; u++) {
-            const int id = z0 + (cz[u] >> 16), ih = y0 + ((cz[u] >> 8) & 255), iw = x0 + (cz[u] & 255);
-            v[u] = make_uint4(0, 0, 0, 0);
-            if (cz[u] >= 0 && !(dbg & 1) && id >= 0 && id < g.Di && ih >= 0 && ih < g.Hi && iw >= 0 && iw < g.Wi)
-                v[u] = *reinterpret_cast<const uint4 *>(base + rel[u]);
-        }
-    };
-    auto store_halo = [&](unsigned char *Xs) {
-#pragma unroll
-        for (int u = 0; u < P_XR; u++) {
-            const int idx = u * P_TPB + tid;
-            if (idx < nx) *reinterpret_cast<uint4 *>(Xs + (size_t)(idx >> 2) * P_XS + (idx & 3) * 16) = v[u];
-        }
-    };
-    const int wd = wave & 3, wm = wave >> 2;
-    const int sbase = ((wd * tg.EH + 4 * wm + (i >> 3)) * tg.EW + (i & 7)) * P_XS + h * 16;
-    const unsigned char *wl = Wsm + ((size_t)h * 32 + i) * 16;  // + ((t*2 + s)*2)*32*16 = (t*2 + s) * 1024
-
-    int it = local;
-    if (!valid(it)) return;  // whole workgroup
-    decode(it);
-    load_halo();
-    store_halo(Xs0);
-    __syncthreads();  // weights + first halo visible
-    int cur = 0;
-    while (true) {
-        const int itn = it + nlocal;
-        const bool more = valid(itn);  // block-uniform
-        const int cn = n_, cod0 = od0, coh0 = oh0, cow0 = ow0;
-        if (more) {
-            decode(itn);
-            load_halo();  // in flight during this tile's MFMAs
-        }
-        const unsigned char *Xs = Xs0 + (size_t)cur * P_HALO;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[r] = 0.f;
-#pragma unroll 1
-        for (int gz = 0; gz < ((dbg & 2) ? 0 : 3); gz++) {
-            bf16x8 bw[9][2];  // this filter plane's B fragments
-#pragma unroll
-            for (int t9 = 0; t9 < 9; t9++)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; s2++) {
-                    uint4 q = *reinterpret_cast<const uint4 *>(wl + (size_t)((gz * 9 + t9) * 2 + s2) * 1024);
-                    bw[t9][s2] = *reinterpret_cast<bf16x8 *>(&q);
-                }
-            bf16x8 af[2][2];  // [buffer][k-step]
-            auto read_a = [&](int t9, int buf) {
-                const int to = tg.toff[gz * 9 + t9] * P_XS;
-#pragma unroll
-                for (int s2 = 0; s2 < 2; s2++) {
-                    uint4 q = *reinterpret_cast<const uint4 *>(Xs + sbase + to + s2 * 32);
-                    af[buf][s2] = *reinterpret_cast<bf16x8 *>(&q);
-                }
-            };
-            read_a(0, 0);
-#pragma unroll
-            for (int t9 = 0; t9 < 9; t9++) {
-                if (t9 + 1 < 9) read_a(t9 + 1, (t9 + 1) & 1);
-#pragma unroll
-                for (int s2 = 0; s2 < 2; s2++)
-                        // operands swapped (D^T = W^T X^T): a lane ends up with 4 x 4 CONSECUTIVE output channels of one
-                        // voxel, i.e. 8-byte bf16 stores instead of sixteen 2-byte ones (the 2-byte stores cost more than
-                        // the tile's MFMAs)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[t9][s2], af[t9 & 1][s2], acc, 0, 0, 0);
-            }
-        }
-        // epilogue of the current tile: D^T layout -- column (lane & 31) = voxel of the M tile, rows = output channels
-        // (r & 3) + 8 * (r >> 2) + 4 * h
-        const int od = cod0 + wd;
-        if (od < g.Do && !(dbg & 4)) {
-            {
-                const int oh = coh0 + 4 * wm + (i >> 3), ow = cow0 + (i & 7);
-                if (oh < g.Ho && ow < g.Wo) {
-                    unsigned short *yo = y1 + ((((size_t)cn * g.Dy + od) * g.Hy + oh) * g.Wy + ow) * 32 + 4 * h;
-#pragma unroll
-                    for (int rg = 0; rg < 4; rg++) {
-                        const int k = 8 * rg + 4 * h;
-                        float bv[4] = {0.f, 0.f, 0.f, 0.f};
-                        if (bias) {
-                            const float4 b4 = *reinterpret_cast<const float4 *>(bias + k);
-                            bv[0] = b4.x; bv[1] = b4.y; bv[2] = b4.z; bv[3] = b4.w;
-                        }
-                        uint2 q;
-                        q.x = (unsigned)f2bf(acc[rg * 4 + 0] + bv[0]) | ((unsigned)f2bf(acc[rg * 4 + 1] + bv[1]) << 16);
-                        q.y = (unsigned)f2bf(acc[rg * 4 + 2] + bv[2]) | ((unsigned)f2bf(acc[rg * 4 + 3] + bv[3]) << 16);
-                        *reinterpret_cast<uint2 *>(yo + 8 * rg) = q;
-                    }
-                }
-            }
-        }
-        if (!more) break;
-        store_halo(Xs0 + (size_t)(cur ^ 1) * P_HALO);  // the other buffer: nobody reads it during this tile
-        __syncthreads();
-        cur ^= 1;
-        it = itn;
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------ k_fwd16q (round 2)
-// Same shape class as k_fwd16p (3x3x3 stride 1, 32 -> 32 channels, >= 4 tiles per CU) with the two things its ablation
-// blamed removed: (1) the 3-way LDS bank conflicts of the A-operand reads -- halo slots are now the bare
-// 64-byte voxel rows and the four 16-byte parts of a row are XOR-swizzled with (halo y-row & 3): a ds_read_b128 lane
-// group covers 4 x-runs of 4 consecutive voxels in 4 consecutive y-rows, so x & 3 picks the bank quad inside a row group
-// and the swizzle separates the rows -- conflict-free for every tap (tools: brute force over layouts, round 2);
-// (2) the B-operand traffic: LDS carried two reads per MFMA (A and B), i.e. it was the bound even conflict-free.  Now a
-// workgroup is 4 waves (one per SIMD, 512 registers each) and every lane keeps ALL 27 taps' B fragments (its 54 16-byte
-// weight fragments, 216 VGPRs) for the whole walk; a wave owns one z-plane of the 4x8x8 tile = two 32-voxel M tiles that
-// share each B fragment: one LDS read per MFMA, issued a tap ahead; tap offsets are immediates.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-// B fragments live in the ACCUMULATOR half of the register file for the whole walk (216 + 32 accumulator registers = 248
-// of 256 AGPRs) and the MFMA reads them there: with the builtin hipcc parks them in AGPRs anyway but copies each one to a
-// VGPR before use (179 v_accvgpr_read + 141 v_mov per tile, PMC: 672 VALU per 108 MFMAs).  `s_nop 1`: a VALU-written
-// A fragment (a compiler copy) needs two wait states before the MFMA reads it and nothing inside an asm string is
-// padded; accumulate chains on the same registers need none (guide 5.7 item 2).
-#define MVD_MFMA16_AB(ACC, BFRAG, AFRAG) \
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(ACC) : "a"(BFRAG), "v"(AFRAG))
-#define MVD_MFMA16_AB_NONOP(ACC, BFRAG, AFRAG) \
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(ACC) : "a"(BFRAG), "v"(AFRAG))
-constexpr int Q_TPB = 256;
-constexpr int Q_XR = 10;                 // uint4 per thread: 600 slots x 4 parts / 256
-constexpr int Q_HALO = 600 * 64;
-
-struct Fwd16QTile {
-    int ntd, nth, ntw, nitems;
-    int wsel[27];  // weight tap index of the raster tap (dz, dy, dx) = offsets -1..1
-};
-
-// DBG (compile time; 0 in production): ablation switches for tools/bench_conv.py -- 1 no halo traffic after the first
-// tile, 2 no MFMAs, 4 no output stores (results are then wrong by construction)
-//
-// One wave per SIMD has nobody to hide behind, so everything else is threaded through the 108-MFMA stream of a tile by
-// hand and kept cheap in VALU terms (PMC, round 2: the first version spent 613 VALU instructions per tile and wave on
-// address arithmetic, clamps and selects -- more than the ~540 issue slots the MFMAs leave free):
-//   * halo loads of the NEXT tile at the head of the tile; interior tiles (72 % at 128^3) use scalar-base + precomputed
-//     32-bit lane offsets, no bounds arithmetic at all; border tiles clamp the coordinates and zero on the way to LDS;
-//   * its ten LDS writes one per tap behind taps 14..23 into the other halo buffer, a barrier behind tap 24 (counted
-//     lgkmcnt: the A reads in flight are not drained), and the first two fragment groups of the next tile are already
-//     fetched under taps 25/26 -- no LDS fill bubble at the tile boundary;
-//   * the accumulators start from the bias and move to VGPRs when the tile is done; the conversion to bf16 and the
-//     eight 8-byte stores go between the first taps of the next tile.
-template <int DBG>
-__global__ __launch_bounds__(256, 1) void k_fwd16q(const FwdGeom g, const Fwd16QTile tg, const unsigned short *__restrict__ a1,
-                                                   const unsigned short *__restrict__ w, const float *__restrict__ bias,
-                                                   unsigned short *__restrict__ y1) {
-    constexpr int dbg = DBG;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds8[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i = lane & 31, h = lane >> 5;
-    const int per_xcd = (tg.nitems + 7) >> 3;
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3, nlocal = gridDim.x >> 3;
-
-    // resident B fragments: raster tap p, k-step s -> 16 bytes of lane (i, h)
-    i32x4 bw[27][2];
-#pragma unroll
-    for (int p = 0; p < 27; p++)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; s2++) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(w + ((size_t)tg.wsel[p] * 128 + (s2 * 2 + h) * 32 + i) * 8);
-            bw[p][s2] = *reinterpret_cast<const i32x4 *>(&q);
-        }
-    // staging slots of this thread (tile independent): byte offset from the tile's first halo voxel, LDS byte offset
-    unsigned rel[Q_XR];
-    int wa[Q_XR];
-#pragma unroll
-    for (int u = 0; u < Q_XR; u++) {
-        const int idx = u * Q_TPB + tid;
-        const int slot = idx < 2400 ? (idx >> 2) : 599;  // slots >= 600 (last pass, tid >= 96) are loaded, never stored
-        const int ez = slot / 100, rem = slot - ez * 100;
-        const int ey = rem / 10, ex = rem - ey * 10;
-        rel[u] = (unsigned)(((ez * g.Hi + ey) * g.Wi + ex) * 64 + (idx & 3) * 16);
-        wa[u] = slot * 64 + (((idx & 3) ^ (ey & 3)) << 4);
-    }
-    // A-operand read addresses: M tile m (rows 4m..4m+3), halo row shift dy, k-step s (the tap offset is an immediate)
-    int ra[2][3][2];
-#pragma unroll
-    for (int m = 0; m < 2; m++) {
-        const int yl = 4 * m + (i >> 3);
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++)
-                ra[m][dy][s2] = ((wave * 10 + yl) * 10 + (i & 7)) * 64 + ((((s2 << 1) | h) ^ ((yl + dy) & 3)) << 4);
-    }
-    // the bias in accumulator layout (register r <-> output channel (r & 3) + 8 * (r >> 2) + 4 * h): C operand of tap 0
-    f32x16 biasv;
-#pragma unroll
-    for (int rg = 0; rg < 4; rg++) {
-        float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (bias) b4 = *reinterpret_cast<const float4 *>(bias + 8 * rg + 4 * h);
-        biasv[rg * 4 + 0] = b4.x; biasv[rg * 4 + 1] = b4.y; biasv[rg * 4 + 2] = b4.z; biasv[rg * 4 + 3] = b4.w;
-    }
-    uint4 v[Q_XR];
-    int n_, od0, oh0, ow0;
-    unsigned inb = ~0u;  // bit u: slot u of this thread lies inside the volume (border tiles only)
-    auto decode = [&](int it) {
-        unsigned r_ = (unsigned)(xcd * per_xcd + it);
-        ow0 = (int)(r_ % (unsigned)tg.ntw) * 8; r_ /= (unsigned)tg.ntw;
-        oh0 = (int)(r_ % (unsigned)tg.nth) * 8; r_ /= (unsigned)tg.nth;
-        od0 = (int)(r_ % (unsigned)tg.ntd) * 4;
-        n_ = (int)(r_ / (unsigned)tg.ntd);
-    };
-    auto valid = [&](int it) { return it < per_xcd && xcd * per_xcd + it < tg.nitems; };
-    auto load_halo = [&]() {
-        const int z0 = od0 - 1, y0 = oh0 - 1, x0 = ow0 - 1;
-        const bool interior = z0 >= 0 && z0 + 6 <= g.Di && y0 >= 0 && y0 + 10 <= g.Hi && x0 >= 0 && x0 + 10 <= g.Wi;
-        if (interior) {  // block-uniform: scalar base + per-lane constant offset
-            const char *tb = reinterpret_cast<const char *>(a1) + ((((long)n_ * g.Di + z0) * g.Hi + y0) * g.Wi + x0) * 64L;
-            inb = ~0u;
-#pragma unroll
-            for (int u = 0; u < Q_XR; u++) v[u] = *reinterpret_cast<const uint4 *>(tb + rel[u]);
-        } else {
-            const unsigned short *base = a1 + (long)n_ * g.Di * g.Hi * g.Wi * 32L + (tid & 3) * 8;
-            inb = 0;
-#pragma unroll
-            for (int u = 0; u < Q_XR; u++) {
-                const int idx = u * Q_TPB + tid;
-                const int slot = idx < 2400 ? (idx >> 2) : 599;
-                const int ez = slot / 100, rem = slot - ez * 100;
-                const int ey = rem / 10, ex = rem - ey * 10;
-                const int id = z0 + ez, ih = y0 + ey, iw = x0 + ex;
-                const bool in = id >= 0 && id < g.Di && ih >= 0 && ih < g.Hi && iw >= 0 && iw < g.Wi;
-                inb |= in ? (1u << u) : 0u;
-                const int cd = min(max(id, 0), g.Di - 1), ch = min(max(ih, 0), g.Hi - 1), cw = min(max(iw, 0), g.Wi - 1);
-                v[u] = *reinterpret_cast<const uint4 *>(base + ((cd * g.Hi + ch) * g.Wi + cw) * 32);
-            }
-        }
-    };
-    auto store_halo_piece = [&](unsigned char *Xs, int u) {
-        const bool in = (inb >> u) & 1u;
-        uint4 q;
-        q.x = in ? v[u].x : 0u; q.y = in ? v[u].y : 0u; q.z = in ? v[u].z : 0u; q.w = in ? v[u].w : 0u;
-        if (u < Q_XR - 1 || tid < 96) *reinterpret_cast<uint4 *>(Xs + wa[u]) = q;  // 600 slots: the last pass is partial
-    };
-
-    int it = local;
-    if (!valid(it)) return;  // whole workgroup
-    decode(it);
-    load_halo();
-#pragma unroll
-    for (int u = 0; u < Q_XR; u++) store_halo_piece(lds8, u);
-    // the weight fragments are consumed by asm statements only: make their loads complete HERE, once -- otherwise the
-    // wait for them lands at the loop head as `s_waitcnt vmcnt(0)` and drains the output stores every tile
-#pragma unroll
-    for (int p = 0; p < 27; p++) asm volatile("" : "+a"(bw[p][0]), "+a"(bw[p][1]));
-    __syncthreads();
-    int cur = 0;
-    float pe[2][16];
-    unsigned short *pyo[2] = {nullptr, nullptr};  // output address of this lane's voxel in M tile m (nullptr: outside)
-    bool have_prev = false;
-    auto epilogue_piece = [&](int m, int kp) {  // channel groups 2kp, 2kp+1 of M tile m: one 16-byte store per lane
-        const int k = 2 * kp;
-        const uint4 q = pair_store_image(
-            pack_bf16x4(pe[m][k * 4 + 0], pe[m][k * 4 + 1], pe[m][k * 4 + 2], pe[m][k * 4 + 3]),
-            pack_bf16x4(pe[m][k * 4 + 4], pe[m][k * 4 + 5], pe[m][k * 4 + 6], pe[m][k * 4 + 7]));
-        if (pyo[m] && !(dbg & 4)) *reinterpret_cast<uint4 *>(pyo[m] + 8 * k) = q;
-    };
-    i32x4 af[3][2][2];  // ring of 3 tap groups x [m][k-step]: fragments are fetched TWO taps (8 MFMAs) ahead, across tiles
-    auto read_a = [&](const unsigned char *Xs, int p, int buf) {
-        const int dz = p / 9, dy = (p / 3) % 3, dx = p % 3;
-        const int to = ((dz * 10 + dy) * 10 + dx) * 64;
-#pragma unroll
-        for (int m = 0; m < 2; m++)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) {
-                const uint4 q = *reinterpret_cast<const uint4 *>(Xs + ra[m][dy][s2] + to);
-                af[buf][m][s2] = *reinterpret_cast<const i32x4 *>(&q);
-            }
-    };
-    read_a(lds8, 0, 0);
-    read_a(lds8, 1, 1);
-    while (true) {
-        const int itn = it + nlocal;
-        const bool more = valid(itn);  // block-uniform
-        const int cn = n_, cod0 = od0, coh0 = oh0, cow0 = ow0;
-        if (more) {
-            decode(itn);
-            if (!(dbg & 1)) load_halo();  // in flight during this tile's MFMAs
-        }
-        const unsigned char *Xs = lds8 + (size_t)cur * Q_HALO;
-        unsigned char *Xn = lds8 + (size_t)(cur ^ 1) * Q_HALO;
-        f32x16 acc[2] = {biasv, biasv};  // (C and D of an MFMA share one register file: the bias cannot be a VGPR C operand)
-#pragma unroll
-        for (int p = 0; p < 27; p++) {
-            if (p + 2 < 27) read_a(Xs, p + 2, (p + 2) % 3);
-            else if (more && !(dbg & 8)) read_a(Xn, p + 2 - 27, (p + 2) % 3);  // next tile's taps 0, 1 (behind the barrier of tap 24)
-            if ((p == 1 || p == 3 || p == 5 || p == 7) && have_prev) epilogue_piece((p - 1) >> 2, ((p - 1) >> 1) & 1);
-            if (!(dbg & 8) && p >= 14 && p <= 23 && more && !(dbg & 1)) store_halo_piece(Xn, p - 14);
-            if ((dbg & 8) && p >= 17 && p <= 26 && more && !(dbg & 1)) store_halo_piece(Xn, p - 17);
-            if (!(dbg & 8) && p == 24 && more) {
-                // every wave's halo writes (the newest: tap 23, four LDS reads ago) done and visible; the A reads in
-                // flight stay in flight
-                asm volatile("s_waitcnt lgkmcnt(4)\n\ts_barrier" ::: "memory");
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++)
-#pragma unroll
-                for (int m = 0; m < 2; m++)
-                    // operands swapped (D^T = W^T X^T): a lane ends with 4 x 4 consecutive output channels of one voxel
-                    if (!(dbg & 2)) MVD_MFMA16_AB(acc[m], bw[p][s2], af[p % 3][m][s2]);
-        }
-        // an MFMA result needs 12 wait states before anything but an accumulating MFMA touches it
-        asm volatile("s_nop 7\n\ts_nop 4" : "+a"(acc[0]), "+a"(acc[1]));
-        {
-            const int od = cod0 + wave;
-#pragma unroll
-            for (int m = 0; m < 2; m++) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) pe[m][r] = acc[m][r];
-                const int oh = coh0 + 4 * m + (i >> 3), ow = cow0 + (i & 7);
-                pyo[m] = (od < g.Do && oh < g.Ho && ow < g.Wo)
-                             ? y1 + ((((size_t)cn * g.Dy + od) * g.Hy + oh) * g.Wy + ow) * 32 + 8 * h
-                             : nullptr;
-            }
-            have_prev = true;
-        }
-        if (!more) break;
-        if (dbg & 8) {  // experiment: staging at the very end of the tile, plain barrier, LDS fill bubble
-            __syncthreads();
-            read_a(Xn, 0, 0);
-            read_a(Xn, 1, 1);
-        }
-        cur ^= 1;
-        it = itn;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) epilogue_piece(j >> 1, j & 1);  // the last tile
-}
-
-// ------------------------------------------------------------------------------------------------ k_fwd16r (round 2)
-// EXPERIMENT, not the default path (MVD_FWD16R=1 selects it; measured 9 % slower than k_fwd16q, see launch_fwd16p):
-// k_fwd16q with the halo moved by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write, nothing for the
-// wave to issue but ten 1-KB pieces per tile).  Why it was tried: the ablation of k_fwd16q (tools/bench_conv.py, MVD_FWD16Q_DBG)
-// showed its phases ADDING UP -- MFMA + LDS reads 0.16 ms, halo path +0.065, stores +0.043 -- however the instructions
-// were interleaved: a CU's vector-memory pipe moves ~10 B/clk, a burst of ten register loads per lane fills its queue,
-// and the one wave per SIMD then sits in the VMEM issue stage instead of issuing MFMAs.  Here the pieces of tile t+2 are
-// issued one every other tap of tile t (the pipe's own pace), land in the third of three halo buffers while tile t+1's
-// buffer is complete, and are retired by a counted vmcnt behind tap 24 (the ten newest operations of a wave at that
-// point are exactly its ten pieces of tile t+2; everything older -- tile t+1's pieces, tile t-1's stores -- is done).
-// LDS image: lane-linear per piece (wave-uniform base + 16 * lane), so the XOR swizzle of the 16-byte parts is applied
-// on the SOURCE address: the lane that fills part position pp of a slot fetches part pp ^ (halo row & 3) of that voxel.
-// Zero padding: out-of-volume lanes fetch from a 16-byte zero page.
-__device__ uint4 g_zero_page16 = {0u, 0u, 0u, 0u};
-constexpr int R_BUF = 40 * 1024;  // 600 slots x 64 B rounded up to 40 pieces of 1 KB (4 waves x 10 pieces)
-
-__global__ __launch_bounds__(256, 1) void k_fwd16r(const FwdGeom g, const Fwd16QTile tg, const unsigned short *__restrict__ a1,
-                                                   const unsigned short *__restrict__ w, const float *__restrict__ bias,
-                                                   unsigned short *__restrict__ y1) {
-    extern __shared__ __attribute__((aligned(1024))) unsigned char lds8[];
-    typedef __attribute__((address_space(3))) unsigned char lds_byte;
-    typedef const __attribute__((address_space(1))) unsigned char glb_byte;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i = lane & 31, h = lane >> 5;
-    const int per_xcd = (tg.nitems + 7) >> 3;
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3, nlocal = gridDim.x >> 3;
-
-    i32x4 bw[27][2];
-#pragma unroll
-    for (int p = 0; p < 27; p++)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; s2++) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(w + ((size_t)tg.wsel[p] * 128 + (s2 * 2 + h) * 32 + i) * 8);
-            bw[p][s2] = *reinterpret_cast<const i32x4 *>(&q);
-        }
-    // piece u of this wave fills LDS bytes [(u * 4 + wave) * 1024 + 16 * lane, +16): slot = that / 64, part position pp
-    unsigned rel[Q_XR];   // source byte offset from the tile's first halo voxel (interior tiles)
-    int cz[Q_XR];         // halo coordinates of the slot (border tiles), -1: beyond the 600 slots
-#pragma unroll
-    for (int u = 0; u < Q_XR; u++) {
-        const int unit = (u * 4 + wave) * 64 + lane;
-        const int slot = unit >> 2, pp = unit & 3;
-        const int sl = slot < 600 ? slot : 599;
-        const int ez = sl / 100, rem = sl - ez * 100;
-        const int ey = rem / 10, ex = rem - ey * 10;
-        const int q = pp ^ (ey & 3);
-        rel[u] = (unsigned)(((ez * g.Hi + ey) * g.Wi + ex) * 64 + q * 16);
-        cz[u] = slot < 600 ? ((ez << 16) | (ey << 8) | ex | (q << 24)) : -1;
-    }
-    int ra[2][3][2];
-#pragma unroll
-    for (int m = 0; m < 2; m++) {
-        const int yl = 4 * m + (i >> 3);
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++)
-                ra[m][dy][s2] = ((wave * 10 + yl) * 10 + (i & 7)) * 64 + ((((s2 << 1) | h) ^ ((yl + dy) & 3)) << 4);
-    }
-    f32x16 biasv;
-#pragma unroll
-    for (int rg = 0; rg < 4; rg++) {
-        float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (bias) b4 = *reinterpret_cast<const float4 *>(bias + 8 * rg + 4 * h);
-        biasv[rg * 4 + 0] = b4.x; biasv[rg * 4 + 1] = b4.y; biasv[rg * 4 + 2] = b4.z; biasv[rg * 4 + 3] = b4.w;
-    }
-    struct TileC { int n, od0, oh0, ow0; };
-    auto decode = [&](int it) {
-        TileC t;
-        unsigned r_ = (unsigned)(xcd * per_xcd + it);
-        t.ow0 = (int)(r_ % (unsigned)tg.ntw) * 8; r_ /= (unsigned)tg.ntw;
-        t.oh0 = (int)(r_ % (unsigned)tg.nth) * 8; r_ /= (unsigned)tg.nth;
-        t.od0 = (int)(r_ % (unsigned)tg.ntd) * 4;
-        t.n = (int)(r_ / (unsigned)tg.ntd);
-        return t;
-    };
-    auto valid = [&](int it) { return it < per_xcd && xcd * per_xcd + it < tg.nitems; };
-    const glb_byte *zero_page = (glb_byte *)(const void *)&g_zero_page16;
-    // one 1-KB piece of tile T's halo into halo buffer `buf`
-    auto dma_piece = [&](const TileC &T, int buf, int u) {
-        const int z0 = T.od0 - 1, y0 = T.oh0 - 1, x0 = T.ow0 - 1;
-        const bool interior = z0 >= 0 && z0 + 6 <= g.Di && y0 >= 0 && y0 + 10 <= g.Hi && x0 >= 0 && x0 + 10 <= g.Wi;
-        const glb_byte *src;
-        if (interior) {  // block-uniform
-            const glb_byte *tb = (glb_byte *)(const void *)a1 + ((((long)T.n * g.Di + z0) * g.Hi + y0) * g.Wi + x0) * 64L;
-            src = tb + rel[u];
-        } else {
-            const int c = cz[u];
-            const int id = z0 + ((c >> 16) & 255), ih = y0 + ((c >> 8) & 255), iw = x0 + (c & 255);
-            const bool in = c >= 0 && id >= 0 && id < g.Di && ih >= 0 && ih < g.Hi && iw >= 0 && iw < g.Wi;
-            const glb_byte *vb = (glb_byte *)(const void *)a1 +
-                                 ((((long)T.n * g.Di + id) * g.Hi + ih) * g.Wi + iw) * 64L + ((c >> 24) & 3) * 16;
-            src = in ? vb : zero_page;
-        }
-        // inline asm, not __builtin_amdgcn_global_load_lds: hipcc (ROCm 7.2) drains every piece with `s_waitcnt vmcnt(0)`
-        // in front of the next ds_read (it models the DMA as an LDS write), which is exactly the serialisation this
-        // kernel exists to remove.  M0 = LDS byte address of the piece, saved / restored around the instruction.
-        lds_byte *dst = (lds_byte *)(lds8 + (size_t)buf * R_BUF + (size_t)(u * 4 + wave) * 1024);
-        const unsigned dsta = __builtin_amdgcn_readfirstlane((unsigned)(size_t)dst);
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(dsta) : "memory");
-    };
-
-    int it = local;
-    if (!valid(it)) return;  // whole workgroup
-    TileC cur_t = decode(it);
-    TileC nxt_t = cur_t, nx2_t = cur_t;
-    bool more = valid(it + nlocal), more2 = valid(it + 2 * nlocal);
-    if (more) nxt_t = decode(it + nlocal);
-#pragma unroll
-    for (int u = 0; u < Q_XR; u++) dma_piece(cur_t, 0, u);
-    if (more) {
-#pragma unroll
-        for (int u = 0; u < Q_XR; u++) dma_piece(nxt_t, 1, u);
-    }
-#pragma unroll
-    for (int p = 0; p < 27; p++) asm volatile("" : "+a"(bw[p][0]), "+a"(bw[p][1]));
-    // tile 0's pieces are older than tile 1's ten: retire them (and everything before), then meet
-    if (more) asm volatile("s_waitcnt vmcnt(10)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    int cur = 0;
-    float pe[2][16];
-    unsigned short *pyo[2] = {nullptr, nullptr};
-    bool have_prev = false;
-    auto epilogue_piece = [&](int m, int kp) {
-        const int k = 2 * kp;
-        const uint4 q = pair_store_image(
-            pack_bf16x4(pe[m][k * 4 + 0], pe[m][k * 4 + 1], pe[m][k * 4 + 2], pe[m][k * 4 + 3]),
-            pack_bf16x4(pe[m][k * 4 + 4], pe[m][k * 4 + 5], pe[m][k * 4 + 6], pe[m][k * 4 + 7]));
-        if (pyo[m]) *reinterpret_cast<uint4 *>(pyo[m] + 8 * k) = q;
-    };
-    i32x4 af[3][2][2];
-    auto read_a = [&](const unsigned char *Xs, int p, int buf) {
-        const int dz = p / 9, dy = (p / 3) % 3, dx = p % 3;
-        const int to = ((dz * 10 + dy) * 10 + dx) * 64;
-#pragma unroll
-        for (int m = 0; m < 2; m++)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) {
-                const uint4 q = *reinterpret_cast<const uint4 *>(Xs + ra[m][dy][s2] + to);
-                af[buf][m][s2] = *reinterpret_cast<const i32x4 *>(&q);
-            }
-    };
-    read_a(lds8, 0, 0);
-    read_a(lds8, 1, 1);
-    while (true) {
-        if (more2) nx2_t = decode(it + 2 * nlocal);
-        const int b2 = cur >= 1 ? cur - 1 : 2;  // (cur + 2) % 3: read last during the PREVIOUS tile, free since its barrier
-        const int b1 = cur == 2 ? 0 : cur + 1;  // (cur + 1) % 3
-        const unsigned char *Xs = lds8 + (size_t)cur * R_BUF;
-        const unsigned char *Xn = lds8 + (size_t)b1 * R_BUF;
-        f32x16 acc[2] = {biasv, biasv};
-#pragma unroll
-        for (int p = 0; p < 27; p++) {
-            if (p + 2 < 27) read_a(Xs, p + 2, (p + 2) % 3);
-            else if (more) read_a(Xn, p + 2 - 27, (p + 2) % 3);  // next tile's taps 0, 1 (behind the barrier of tap 24)
-            if (p < 4 && have_prev) epilogue_piece(p >> 1, p & 1);                       // stores first ...
-            if (p >= 4 && p <= 22 && !(p & 1) && more2) dma_piece(nx2_t, b2, (p - 4) >> 1);  // ... then the ten pieces
-            if (p == 24 && more) {
-                // the ten newest vector-memory operations of this wave are its pieces of tile t+2 (none if there is no
-                // such tile): everything older, i.e. the next tile's halo and the previous tile's stores, has landed
-                if (more2) asm volatile("s_waitcnt vmcnt(10)\n\ts_barrier" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++)
-#pragma unroll
-                for (int m = 0; m < 2; m++) MVD_MFMA16_AB(acc[m], bw[p][s2], af[p % 3][m][s2]);
-        }
-        asm volatile("s_nop 7\n\ts_nop 4" : "+a"(acc[0]), "+a"(acc[1]));
-        {
-            const int od = cur_t.od0 + wave;
-#pragma unroll
-            for (int m = 0; m < 2; m++) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) pe[m][r] = acc[m][r];
-                const int oh = cur_t.oh0 + 4 * m + (i >> 3), ow = cur_t.ow0 + (i & 7);
-                pyo[m] = (od < g.Do && oh < g.Ho && ow < g.Wo)
-                             ? y1 + ((((size_t)cur_t.n * g.Dy + od) * g.Hy + oh) * g.Wy + ow) * 32 + 8 * h
-                             : nullptr;
-            }
-            have_prev = true;
-        }
-        if (!more) break;
-        cur = b1;
-        it += nlocal;
-        cur_t = nxt_t;
-        nxt_t = nx2_t;
-        more = more2;
-        more2 = valid(it + 2 * nlocal);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) epilogue_piece(j >> 1, j & 1);  // the last tile
-}
-
 // ------------------------------------------------------------------------------------------------ k_fwd16z (round 2)
-// z-marching form of the 32 -> 32 channel 3x3x3 stride-1 convolution (same shape class as k_fwd16q).  What k_fwd16q's
-// ablation left as the bound was the traffic a 4x8x8 tile pulls through the CU's vector-memory pipe (a 6x10x10 halo:
-// 2.34 bytes fetched per byte used) with one wave per SIMD to issue it.  Here a workgroup owns an 8 x 32 (y, x) column
-// and walks a chunk of z-planes:
+// z-marching form of the 32 -> 32 channel 3x3x3 stride-1 convolution at high resolution (enc0.conv1, dec5.conv1 and their
+// input gradients: 537 MB of activations, 232 GFLOP each).  Its persistent tile-walking predecessors (DESIGN.md 3.4, 9.5;
+// removed) were bound by the traffic a 4x8x8 tile pulls through the CU's vector-memory pipe (a 6x10x10 halo: 2.34 bytes
+// fetched per byte used) with one wave per SIMD to issue it.  Here a workgroup owns an 8 x 32 (y, x) column and walks a
+// chunk of z-planes:
 //   * input plane z' arrives once (10 x 34 voxels: 1.33 bytes fetched per byte used, rows of 2 KB contiguous in HBM),
 //     register-staged (two planes in flight: loaded three planes ahead of its MFMAs -- one plane ahead left the loaded
 //     HBM latency exposed) into a ring of four LDS plane images;
 //   * every A fragment read from LDS (input row r, x shift dx, k-step) feeds up to SIX MFMAs: the three dz taps -- they
 //     accumulate into three different OUTPUT planes z'+1, z', z'-1, held as a ring of four accumulator sets, so no
 //     partial sum ever moves -- times the one or two M tiles (output rows) of the wave that see row r at some dy:
-//     24 ds_read_b128 per 108 MFMAs (k_fwd16q: 108);
-//   * a wave = two M tiles (two output rows of 32 voxels), the 27 taps' B fragments resident in the accumulator half of
-//     the register file as in k_fwd16q; the plane loop is unrolled four times so that ring positions are register names
-//     and LDS offsets are immediates;
+//     24 ds_read_b128 per 108 MFMAs (one read per MFMA in the tile walk);
+//   * a wave = two M tiles (two output rows of 32 voxels); a workgroup is 4 waves (one per SIMD, 512 registers each) and
+//     every lane keeps ALL 27 taps' B fragments (54 16-byte weight fragments, 216 registers) in the accumulator half of
+//     the register file for the whole walk, where the MFMA reads them (inline asm: with the builtin hipcc copies each one
+//     to a VGPR before use); the plane loop is unrolled four times so that ring positions are register names and LDS
+//     offsets are immediates;
 //   * the output plane completed by plane z' is converted between the MFMAs of plane z'+1 (fourth set), transposed
 //     through a 4-KB per-wave LDS scratch and stored as four fully contiguous 1-KB wave stores; the drained set is then
 //     re-initialised with the bias from an LDS table (ds_read_b128 straight into the accumulator registers).
@@ -1263,6 +630,7 @@ struct Fwd16ZTile {
     int wsel[27];
 };
 
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) u32x4 lds_u4;
@@ -1289,17 +657,13 @@ struct ZIdx { static constexpr int value = R; };
 // bit 1 = input prologue -- the staged input is the RAW output of the producing conv and is normalised + activated
 // between the buffer load and the LDS write: a = bf16(lrelu(fma(x, scale[n][c], shift[n][c]))), zeros where the voxel
 // lies outside the volume (the zero padding applies to the activation).
-template <int DBG, int FUSE = 0>
+template <int FUSE = 0>
 __global__ __launch_bounds__(256, 1) void k_fwd16z(const FwdGeom g, const Fwd16ZTile tg, const unsigned short *__restrict__ a1,
                                                    const unsigned short *__restrict__ w, const float *__restrict__ bias,
                                                    unsigned short *__restrict__ y1, float *__restrict__ tile_stats,
                                                    const float *__restrict__ in_scale, const float *__restrict__ in_shift,
                                                    const float slope) {
-    constexpr int dbg = DBG;
-    constexpr bool PRO = (FUSE & 2) != 0;  // 1: no global loads / LDS writes after the prologue, 2: no MFMAs, 4: no stores, 8: no epilogue,
-                              // 16: no barrier, 32: no A-fragment reads after the prologue, 64: descriptors not updated,
-                              // 128: no buffer loads / stores issued, 256: no bias re-initialisation (ablation builds;
-                              // results wrong)
+    constexpr bool PRO = (FUSE & 2) != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds8[];
     const unsigned lbase = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)lds8;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1489,7 +853,7 @@ __global__ __launch_bounds__(256, 1) void k_fwd16z(const FwdGeom g, const Fwd16Z
     // ONE branch-free body for every plane: a plane that does not exist (z' = -1 or D at the volume faces, and the
     // drain-only plane after the chunk) is a plane of zeros -- its descriptor has zero records, so the staging loads
     // return zeros without touching memory -- and an output plane that is not the chunk's is a descriptor with zero
-    // records, so its stores are dropped.  Ablation (MVD_FWD16Z_DBG=61: MFMAs only) had shown 38.7 cycles per MFMA
+    // records, so its stores are dropped.  Ablation (MFMAs only) had shown 38.7 cycles per MFMA
     // against 32.4 for the bare loop: ~60 scalar instructions and five branches evaluating plane flags in one clump at
     // every plane boundary, and an in-order wave issues no MFMA behind them (a second, flag-free copy of the body for
     // the interior planes made the register allocator spill 160 registers).  The price: 3 of the Zc + 3 planes of a chunk
@@ -1501,12 +865,12 @@ __global__ __launch_bounds__(256, 1) void k_fwd16z(const FwdGeom g, const Fwd16Z
         const bool lvn = live(j + 1);     // PRO: the plane written to LDS during this plane exists
         auto set_out_plane = [&]() {  // the plane held by DRN
             const int zo = zin(j) - 2;
-            const bool st = zo >= zb && zo < ze && !(dbg & 4);
+            const bool st = zo >= zb && zo < ze;
             rout = __builtin_amdgcn_make_buffer_rsrc(ybase + (size_t)max(zo, 0) * oplane, 0, st ? (int)oplane32 : 0, 0x00020000);
         };
         auto set_next_in_plane = [&]() {  // input plane j + 3
             const int z2 = zin(j + 3);
-            const bool lv = j + 3 < nproc && z2 >= 0 && z2 < g.Di && !(dbg & 1);
+            const bool lv = j + 3 < nproc && z2 >= 0 && z2 < g.Di;
             rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(abase + (size_t)max(z2, 0) * iplane), 0,
                                                     lv ? (int)iplane32 : 0, 0x00020000);
         };
@@ -1530,8 +894,7 @@ __global__ __launch_bounds__(256, 1) void k_fwd16z(const FwdGeom g, const Fwd16Z
         //   f 17-20 barrier (plane j+1 visible), wave w in slot 17 + w;   f 22-23 first fragments of plane j+1
 #pragma unroll
         for (int f = 0; f < 24; f++) {
-            if (dbg & 32) {
-            } else if (f + 2 < 24) MVD_Z_READ_A(R, f + 2, (f + 2) % 3)
+            if (f + 2 < 24) MVD_Z_READ_A(R, f + 2, (f + 2) % 3)
             else MVD_Z_READ_A(RN, f + 2 - 24, (f + 2) % 3)  // behind the barrier below
             // The four waves run the same instruction stream, and one barrier per plane would keep them in lockstep: 24
             // staging loads (and 24 13-cycle LDS store transfers) in one window of the CU's single vector-memory pipe.
@@ -1539,24 +902,22 @@ __global__ __launch_bounds__(256, 1) void k_fwd16z(const FwdGeom g, const Fwd16Z
             // write, ahead of its first read of the next image) -- after the first plane the waves run w slots apart --
             // and the staging loads sit in slots = 3 mod 4, the writes in slots = 1, 2 mod 4: no two waves load in the
             // same slot time, and the compiler can still count vmcnt (conditional loads cost it the count).
-            if (!(dbg & 1)) {
-                constexpr int wslot[6] = {1, 2, 6, 9, 10, 14};
+            constexpr int wslot[6] = {1, 2, 6, 9, 10, 14};
 #pragma unroll
-                for (int u = 0; u < 6; u++)
-                    if (f == wslot[u]) stage_write(RN & 1, IMGN, u, lvn);
-            }
-            if (f == 4 && !(dbg & 64)) set_out_plane();
-            if (f == 0 && !(dbg & 64)) set_next_in_plane();
+            for (int u = 0; u < 6; u++)
+                if (f == wslot[u]) stage_write(RN & 1, IMGN, u, lvn);
+            if (f == 4) set_out_plane();
+            if (f == 0) set_next_in_plane();
             if (f == 1) asm volatile("" : "+v"(S[DRN][0]), "+v"(S[DRN][1]));  // keeps the conversions in their slots
-            if (f >= 1 && f <= 4 && !(dbg & 8)) {
+            if (f >= 1 && f <= 4) {
                 epi_pack((f - 1) >> 1, ((f - 1) & 1) * 2);
                 epi_pack((f - 1) >> 1, ((f - 1) & 1) * 2 + 1);
             }
-            if ((f & 3) == 3 && !(dbg & 128)) stage_load(RN & 1, f >> 2);
-            if (f >= 6 && f < 14 && !(f & 1) && !(dbg & 8)) epi_read((f - 6) >> 1);
-            if (f >= 6 && f < 14 && (f & 1) && !(dbg & (8 | 128))) epi_store((f - 7) >> 1);
-            if (f >= 14 && f < 22 && !(dbg & 256)) bias_init(S[DRN][(f - 14) >> 2], (f - 14) & 3);  // the next plane's NEW set
-            if (f >= 17 && f <= 20 && !(dbg & 16)) {
+            if ((f & 3) == 3) stage_load(RN & 1, f >> 2);
+            if (f >= 6 && f < 14 && !(f & 1)) epi_read((f - 6) >> 1);
+            if (f >= 6 && f < 14 && (f & 1)) epi_store((f - 7) >> 1);
+            if (f >= 14 && f < 22) bias_init(S[DRN][(f - 14) >> 2], (f - 14) & 3);  // the next plane's NEW set
+            if (f >= 17 && f <= 20) {
                 // (this wave's plane writes retired in order before the fragment reads already consumed above)
                 if (wave == f - 17) asm volatile("s_barrier" ::: "memory");
             }
@@ -1565,7 +926,6 @@ __global__ __launch_bounds__(256, 1) void k_fwd16z(const FwdGeom g, const Fwd16Z
             for (int m = 0; m < 2; m++) {
                 const int dy = r - m;  // input row r is output row m shifted by dy - 1
                 if (dy < 0 || dy > 2) continue;
-                if (dbg & 2) continue;
                 MVD_MFMA16_ZV(S[NEW][m], bw[0 * 9 + dy * 3 + dx][ks], af[f % 3]);
                 MVD_MFMA16_ZV(S[MID][m], bw[1 * 9 + dy * 3 + dx][ks], af[f % 3]);
                 MVD_MFMA16_ZV(S[OLD][m], bw[2 * 9 + dy * 3 + dx][ks], af[f % 3]);
@@ -1575,7 +935,7 @@ __global__ __launch_bounds__(256, 1) void k_fwd16z(const FwdGeom g, const Fwd16Z
         // an MFMA result needs 12 wait states before anything but an accumulating MFMA reads it
         asm volatile("s_nop 7\n\ts_nop 4" : "+v"(S[OLD][0]), "+v"(S[OLD][1]));
     };
-    for (int j = 0; j <= ((dbg & 512) ? -1 : nproc); j += 4) {
+    for (int j = 0; j <= nproc; j += 4) {
         plane(ZIdx<0>(), j);
         if (j + 1 > nproc) break;
         plane(ZIdx<1>(), j + 1);
@@ -1598,182 +958,78 @@ static int num_cus16() {
     return n;
 }
 
-// -1: not this kernel's shape
-static int launch_fwd16p(const FwdGeom &g, const unsigned short *a1, const unsigned short *w, const float *bias,
+// k_fwd16z for its shape class; -1: not this kernel's shape
+static int launch_fwd16z(const FwdGeom &g, const unsigned short *a1, const unsigned short *w, const float *bias,
                          unsigned short *y1, unsigned short *y2, hipStream_t s, const Fwd16Fuse *fuse = nullptr,
                          int *stats_tiles_only = nullptr) {
-    static const int off = getenv("MVD_FWD16P") ? (atoi(getenv("MVD_FWD16P")) == 0) : 0;
-    if (off) return -1;
     // 32 reduce channels; 32 produce channels, or 32 + 32 into two tensors (the input gradient of a conv that read two
-    // concatenated 32-channel tensors: two independent 32 -> 32 problems on the same dy; k_fwd16z only)
+    // concatenated 32-channel tensors: two independent 32 -> 32 problems on the same dy)
     const bool two_out = g.K1 == 32 && g.K2 == 32 && y2 != nullptr;
     if (g.C1 != 32 || g.C2 != 0 || g.K1 != 32 || (g.K2 != 0 && !two_out) || g.ntaps != 27 || g.T != 27 || g.acc) return -1;
     for (int a = 0; a < 3; a++)
         if (g.sa[a] != 1 || g.so[a] != 1 || g.oo[a] != 0) return -1;
     if (g.Dy != g.Do || g.Hy != g.Ho || g.Wy != g.Wo) return -1;
-    int mn[3] = {127, 127, 127}, mx[3] = {-127, -127, -127};
-    for (int t = 0; t < 27; t++)
-        for (int a = 0; a < 3; a++) {
-            if (g.off[t][a] < mn[a]) mn[a] = g.off[t][a];
-            if (g.off[t][a] > mx[a]) mx[a] = g.off[t][a];
-        }
-    for (int a = 0; a < 3; a++)
-        if (mn[a] != -1 || mx[a] != 1) return -1;
-    Fwd16Tile tg;
-    memset(&tg, 0, sizeof(tg));
-    tg.EH = 10; tg.EW = 10; tg.nslots = 600;
-    for (int t = 0; t < 27; t++)
-        tg.toff[t] = ((g.off[t][0] + 1) * tg.EH + (g.off[t][1] + 1)) * tg.EW + (g.off[t][2] + 1);
-    tg.ntd = (g.Do + 3) / 4;
-    tg.nth = (g.Ho + 7) / 8;
-    tg.ntw = (g.Wo + 7) / 8;
-    const long nitems = (long)g.N * tg.ntd * tg.nth * tg.ntw;
+    // at least four 4x8x8 tiles per CU (the threshold of the tile-walking kernels this one replaced) or it does not pay
+    const long nitems = (long)g.N * ((g.Do + 3) / 4) * ((g.Ho + 7) / 8) * ((g.Wo + 7) / 8);
     const long ncu = ((long)num_cus16() / 8) * 8;
-    if (nitems < 4 * ncu || nitems > (1L << 30)) return -1;  // a walk of >= 4 tiles per workgroup or it does not pay
+    if (nitems < 4 * ncu || nitems > (1L << 30)) return -1;
     if ((long)g.N * g.Di * g.Hi * g.Wi * 32 >= (1L << 31)) return -1;  // 32-bit element offsets inside a tile
-    tg.nitems = (int)nitems;
-    static const int use_q = getenv("MVD_FWD16Q") ? atoi(getenv("MVD_FWD16Q")) : 1;
-    if (use_q) {
-        Fwd16QTile tq;
-        memset(&tq, 0, sizeof(tq));
-        tq.ntd = tg.ntd; tq.nth = tg.nth; tq.ntw = tg.ntw; tq.nitems = tg.nitems;
-        bool ok = true;
-        for (int p = 0; p < 27 && ok; p++) {
-            const int dz = p / 9 - 1, dy = (p / 3) % 3 - 1, dx = p % 3 - 1;
-            int hit = -1;
-            for (int t = 0; t < 27; t++)
-                if (g.off[t][0] == dz && g.off[t][1] == dy && g.off[t][2] == dx) hit = t;
-            if (hit < 0) ok = false;
-            else tq.wsel[p] = g.wt[hit];
-        }
-        // measured (round 2, enc0.conv1 dgrad, bench_conv --iters 40): k_fwd16r 0.282 ms, k_fwd16q 0.258 ms -- the DMA
-        // pieces cost the wave more issue time than ten register loads + ten ds_write_b128.  Selectable, off by default.
-        static const int use_z = getenv("MVD_FWD16Z") ? atoi(getenv("MVD_FWD16Z")) : 1;  // default (round 2): k_fwd16z
-        if (ok && use_z) {
-            Fwd16ZTile tz;
-            memset(&tz, 0, sizeof(tz));
-            memcpy(tz.wsel, tq.wsel, sizeof(tz.wsel));
-            tz.nty = (g.Ho + 7) / 8;
-            tz.ntx = (g.Wo + 31) / 32;
-            // z chunks: enough workgroups to fill the chip in whole rounds, chunks of >= 8 planes (2 extra input planes
-            // and two partly useful MFMA planes per chunk)
-            const long cols = (long)g.N * tz.nty * tz.ntx;
-            int best = 1;
-            double best_cost = 1e30;
-            for (int nz = 1; nz <= (g.Do + 7) / 8; nz++) {
-                const int zc = (g.Do + nz - 1) / nz;
-                const long wgs = cols * ((g.Do + zc - 1) / zc);
-                const double cost = (double)((wgs + ncu - 1) / ncu) * (zc + 2.5);
-                if (cost < best_cost - 1e-9) { best_cost = cost; best = nz; }
-            }
-            tz.zc = (g.Do + best - 1) / best;
-            tz.nzc = (g.Do + tz.zc - 1) / tz.zc;
-            tz.nitems = (int)(cols * tz.nzc);
-            if (stats_tiles_only) {  // query: tiles per sample of the statistics epilogue (none here); 0 = this kernel runs
-                *stats_tiles_only = 0;
-                return 0;
-            }
-            static const int dbgz = getenv("MVD_FWD16Z_DBG") ? atoi(getenv("MVD_FWD16Z_DBG")) & 1023 : 0;
-            typedef void (*kz_t)(const FwdGeom, const Fwd16ZTile, const unsigned short *, const unsigned short *, const float *,
-                                 unsigned short *, float *, const float *, const float *, const float);
-            kz_t kfn = k_fwd16z<0>;
-            switch (dbgz) {
-                case 1: kfn = k_fwd16z<1>; break;
-                case 2: kfn = k_fwd16z<2>; break;
-                case 4: kfn = k_fwd16z<4>; break;
-                case 5: kfn = k_fwd16z<5>; break;
-                case 13: kfn = k_fwd16z<13>; break;
-                case 29: kfn = k_fwd16z<29>; break;
-                case 61: kfn = k_fwd16z<61>; break;
-                case 125: kfn = k_fwd16z<125>; break;
-                case 189: kfn = k_fwd16z<189>; break;
-                case 317: kfn = k_fwd16z<317>; break;
-                case 509: kfn = k_fwd16z<509>; break;
-                case 1021: kfn = k_fwd16z<1021>; break;
-                default: break;
-            }
-            const bool want_stats = false;  // (k_fwd16y has the statistics epilogue)
-            const bool want_pro = fuse && fuse->in_scale && fuse->in_shift;
-            if (want_pro && two_out) return -1;
-            const int fz = (want_stats ? 1 : 0) | (want_pro ? 2 : 0);
-            if (fz == 2) kfn = k_fwd16z<0, 2>;
-            if (fuse && fuse->ntiles) *fuse->ntiles = want_stats ? tz.nzc * tz.nty * tz.ntx : 0;
-            static PerDeviceFlag configured_z[4];
-            if (!configured_z[fz]()) {
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)Z_LDS);
-                if (e != hipSuccess) {
-                    set_error("conv fwd16z: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-                    return 1;
-                }
-                configured_z[fz]() = true;
-            }
-            const int per_xcd = (tz.nitems + 7) / 8;
-            tz.kp = g.K1 + g.K2;
-            for (int q = 0; q < (two_out ? 2 : 1); q++) {
-                tz.koff = 32 * q;
-                hipLaunchKernelGGL(kfn, dim3((unsigned)(per_xcd * 8)), dim3(256), (size_t)Z_LDS, s, g,
-                                   tz, a1, w, bias, q ? y2 : y1, want_stats ? fuse->tile_stats : nullptr, want_pro ? fuse->in_scale : nullptr,
-                                   want_pro ? fuse->in_shift : nullptr, fuse ? fuse->slope : 0.f);
-                if (check_launch("conv fwd16z (z-marching bf16 mfma, weights in registers)")) return 1;
-            }
-            return 0;
-        }
-        if (stats_tiles_only) { *stats_tiles_only = 0; return 1; }
-        if (fuse && fuse->in_scale) return -1;   // only the z-marching kernel has the input prologue
-        if (fuse && fuse->ntiles) *fuse->ntiles = 0;
-        if (two_out) return -1;
-        static const int use_r = getenv("MVD_FWD16R") ? atoi(getenv("MVD_FWD16R")) : 0;
-        if (ok && use_r) {
-            static PerDeviceFlag configured_r;
-            if (!configured_r()) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_fwd16r), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)LDS_LIMIT16) != hipSuccess) {
-                    set_error("conv fwd16r: cannot raise the dynamic LDS limit");
-                    return 1;
-                }
-                configured_r() = true;
-            }
-            hipLaunchKernelGGL(k_fwd16r, dim3((unsigned)ncu), dim3(Q_TPB), 3 * (size_t)R_BUF, s, g, tq, a1, w, bias, y1);
-            return check_launch("conv fwd16r (persistent bf16 mfma, LDS-DMA halo)");
-        }
-        if (ok) {
-            static const int dbgq = getenv("MVD_FWD16Q_DBG") ? atoi(getenv("MVD_FWD16Q_DBG")) & 15 : 0;
-            typedef void (*kq_t)(const FwdGeom, const Fwd16QTile, const unsigned short *, const unsigned short *, const float *,
-                                 unsigned short *);
-            static const kq_t kq[16] = {k_fwd16q<0>, k_fwd16q<1>, k_fwd16q<2>, k_fwd16q<3>, k_fwd16q<4>, k_fwd16q<5>,
-                                        k_fwd16q<6>, k_fwd16q<7>, k_fwd16q<8>, k_fwd16q<9>, k_fwd16q<10>, k_fwd16q<11>,
-                                        k_fwd16q<12>, k_fwd16q<13>, k_fwd16q<14>, k_fwd16q<15>};
-            static PerDeviceFlag configured_q;
-            if (!configured_q()) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(kq[dbgq]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)LDS_LIMIT16) != hipSuccess) {
-                    set_error("conv fwd16q: cannot raise the dynamic LDS limit");
-                    return 1;
-                }
-                configured_q() = true;
-            }
-            hipLaunchKernelGGL(kq[dbgq], dim3((unsigned)ncu), dim3(Q_TPB), 2 * (size_t)Q_HALO, s, g, tq, a1, w, bias, y1);
-            return check_launch("conv fwd16q (persistent bf16 mfma, weights in registers)");
-        }
+    // weight index of the raster tap (dz, dy, dx), offsets -1..1.  The geometry builders (conv.hip) never emit the same
+    // offset twice, so 27 taps inside [-1, 1]^3 are the full 3x3x3 set; anything else is left to the generic kernels.
+    Fwd16ZTile tz;
+    memset(&tz, 0, sizeof(tz));
+    for (int p = 0; p < 27; p++) {
+        const int dz = p / 9 - 1, dy = (p / 3) % 3 - 1, dx = p % 3 - 1;
+        int hit = -1;
+        for (int t = 0; t < 27; t++)
+            if (g.off[t][0] == dz && g.off[t][1] == dy && g.off[t][2] == dx) hit = t;
+        if (hit < 0) return -1;
+        tz.wsel[p] = g.wt[hit];
     }
-    if (two_out) return -1;
-    if (stats_tiles_only) { *stats_tiles_only = 0; return 1; }
-    if (fuse && fuse->in_scale) return -1;
-    if (fuse && fuse->ntiles) *fuse->ntiles = 0;
-    const size_t lds = (size_t)P_WB + 2 * (size_t)P_HALO;
-    static PerDeviceFlag configured;
-    if (!configured()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_fwd16p), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)LDS_LIMIT16) != hipSuccess) {
-            set_error("conv fwd16p: cannot raise the dynamic LDS limit");
+    tz.nty = (g.Ho + 7) / 8;
+    tz.ntx = (g.Wo + 31) / 32;
+    // z chunks: enough workgroups to fill the chip in whole rounds, chunks of >= 8 planes (2 extra input planes
+    // and two partly useful MFMA planes per chunk)
+    const long cols = (long)g.N * tz.nty * tz.ntx;
+    int best = 1;
+    double best_cost = 1e30;
+    for (int nz = 1; nz <= (g.Do + 7) / 8; nz++) {
+        const int zc = (g.Do + nz - 1) / nz;
+        const long wgs = cols * ((g.Do + zc - 1) / zc);
+        const double cost = (double)((wgs + ncu - 1) / ncu) * (zc + 2.5);
+        if (cost < best_cost - 1e-9) { best_cost = cost; best = nz; }
+    }
+    tz.zc = (g.Do + best - 1) / best;
+    tz.nzc = (g.Do + tz.zc - 1) / tz.zc;
+    tz.nitems = (int)(cols * tz.nzc);
+    if (stats_tiles_only) {  // query: tiles per sample of the statistics epilogue (none here); 0 = this kernel runs
+        *stats_tiles_only = 0;
+        return 0;
+    }
+    const bool want_pro = fuse && fuse->in_scale && fuse->in_shift;
+    if (want_pro && two_out) return -1;
+    auto kfn = want_pro ? k_fwd16z<2> : k_fwd16z<0>;
+    if (fuse && fuse->ntiles) *fuse->ntiles = 0;  // (k_fwd16y has the statistics epilogue)
+    static PerDeviceFlag configured_z[2];
+    if (!configured_z[want_pro]()) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)Z_LDS);
+        if (e != hipSuccess) {
+            set_error("conv fwd16z: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
             return 1;
         }
-        configured() = true;
+        configured_z[want_pro]() = true;
     }
-    static const int dbg = getenv("MVD_FWD16P_DBG") ? atoi(getenv("MVD_FWD16P_DBG")) : 0;
-    hipLaunchKernelGGL(k_fwd16p, dim3((unsigned)ncu), dim3(P_TPB), lds, s, g, tg, a1, w, bias, y1, dbg);
-    return check_launch("conv fwd16p (persistent bf16 mfma)");
+    const int per_xcd = (tz.nitems + 7) / 8;
+    tz.kp = g.K1 + g.K2;
+    for (int q = 0; q < (two_out ? 2 : 1); q++) {
+        tz.koff = 32 * q;
+        hipLaunchKernelGGL(kfn, dim3((unsigned)(per_xcd * 8)), dim3(256), (size_t)Z_LDS, s, g, tz, a1, w, bias, q ? y2 : y1,
+                           (float *)nullptr, want_pro ? fuse->in_scale : nullptr, want_pro ? fuse->in_shift : nullptr,
+                           fuse ? fuse->slope : 0.f);
+        if (check_launch("conv fwd16z (z-marching bf16 mfma, weights in registers)")) return 1;
+    }
+    return 0;
 }
 
 // returns 0 ok, >0 error, -1 unsupported shape
@@ -1782,7 +1038,7 @@ int fwd_bf16_stats_tiles(const FwdGeom &g) {
     if ((g.C1 + g.C2) % 32 || (g.K1 + g.K2) % 32) return 0;
     if (launch_fwd16y(g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (num_cus16() / 8) * 8, &nt) == 0)
         return nt;
-    const int r = launch_fwd16p(g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nt);
+    const int r = launch_fwd16z(g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nt);
     return r == 0 ? nt : 0;
 }
 
@@ -1793,7 +1049,7 @@ int fwd_bf16_prologue_ok(const FwdGeom &g) {  // 1: the shape runs on a kernel w
         launch_fwd16y(g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (num_cus16() / 8) * 8, &nt) == 0)
         return 1;
     if (g.C1 != 32 || g.C2 != 0) return 0;
-    return launch_fwd16p(g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nt) == 0 ? 1 : 0;
+    return launch_fwd16z(g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nt) == 0 ? 1 : 0;
 }
 
 int fwd_bf16(const FwdGeom &g, const unsigned short *a1, const unsigned short *a2, const unsigned short *w,
@@ -1814,7 +1070,7 @@ int fwd_bf16(const FwdGeom &g, const unsigned short *a1, const unsigned short *a
     {
         int r = launch_fwd16y(g, a1, a2, w, bias, y1, y2, s, fuse, (num_cus16() / 8) * 8, nullptr);
         if (r >= 0) return r;
-        r = launch_fwd16p(g, a1, w, bias, y1, y2, s, fuse);
+        r = launch_fwd16z(g, a1, w, bias, y1, y2, s, fuse);
         if (r >= 0) return r;
         if (!fuse || (!fuse->in_scale && !fuse->tile_stats)) {
             r = launch_fwd16ys(g, a1, a2, w, bias, y1, y2, s, (num_cus16() / 8) * 8);
@@ -1843,10 +1099,8 @@ int fwd_bf16(const FwdGeom &g, const unsigned short *a1, const unsigned short *a
         for (int a = 0; a < 3; a++) tg.min_off[a] = mn[a];
         tg.magHW = magic(100, 1024);
         tg.magW = magic(10, 100);
-        for (int t = 0; t < g.ntaps; t++) {
+        for (int t = 0; t < g.ntaps; t++)
             tg.toff[t] = ((g.off[t][0] - mn[0]) * tg.EH + (g.off[t][1] - mn[1])) * tg.EW + (g.off[t][2] - mn[2]);
-            tg.tdy[t] = (signed char)(g.off[t][1] - mn[1]);
-        }
         tg.ntd = (g.Do + 7) / 8;
         tg.nth = (g.Ho + 7) / 8;
         tg.ntw = (g.Wo + 7) / 8;
@@ -1859,9 +1113,7 @@ int fwd_bf16(const FwdGeom &g, const unsigned short *a1, const unsigned short *a
             // (round 3: eight instead of four taps per weight group -- on the idea that a group's 16 KB of weights arrive from
             // L2 later than its 32 MFMAs per wave retire -- measured no different: 0.070 vs 0.069 ms on 128 -> 128 @32^3, 37 %
             // MFMA-busy either way)
-            static const int w8swz = getenv("MVD_FWD16_W8SWZ") ? atoi(getenv("MVD_FWD16_W8SWZ")) : 0;
-            int r = w8swz ? launch_fwd16<2, 2, 4, 8, true, 8>(g, tg, a1, a2, w, bias, y1, y2, ws, ws_bytes, s)
-                          : launch_fwd16<2, 2, 4, 8, false, 8>(g, tg, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
+            int r = launch_fwd16<2, 2, 4, 8, 8>(g, tg, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
             if (r >= 0) return r;
         }
     }
@@ -1896,16 +1148,8 @@ int fwd_bf16(const FwdGeom &g, const unsigned short *a1, const unsigned short *a
         tg.nth = (g.Ho + 4 * MT - 1) / (4 * MT);
         tg.ntw = (g.Wo + 7) / 8;
         tg.K = K;
-        for (int t = 0; t < g.ntaps; t++) tg.tdy[t] = (signed char)(g.off[t][1] - mn[1]);
-        // measured (round 2, tools/bench_conv.py --dtype bf16): conflict-free reads do NOT pay in this kernel -- with two
-        // workgroups per CU it is bound by instruction issue, and the per-read swizzle arithmetic costs 12-15 %
-        // (64->64 @64^3: 0.151 -> 0.174 ms).  Kept selectable (MVD_FWD16_SWZ=1) as the measured alternative.
-        static const int swz_on = getenv("MVD_FWD16_SWZ") ? atoi(getenv("MVD_FWD16_SWZ")) : 0;
-        const bool swz = swz_on && g.sa[0] == 1 && g.sa[1] == 1 && g.sa[2] == 1;
         int r = -1;
-#define MVD_L16(NT_, MT_, TG_, XR_)                                                                              \
-    (swz ? launch_fwd16<NT_, MT_, TG_, XR_, true>(g, tg, a1, a2, w, bias, y1, y2, ws, ws_bytes, s)             \
-         : launch_fwd16<NT_, MT_, TG_, XR_, false>(g, tg, a1, a2, w, bias, y1, y2, ws, ws_bytes, s))
+#define MVD_L16(NT_, MT_, TG_, XR_) launch_fwd16<NT_, MT_, TG_, XR_>(g, tg, a1, a2, w, bias, y1, y2, ws, ws_bytes, s)
         if (MT == 2) {
             r = NT == 2 ? MVD_L16(2, 2, 3, 10) : MVD_L16(1, 2, 4, 10);
         } else if (XR == 6) {

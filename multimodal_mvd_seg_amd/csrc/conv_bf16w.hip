@@ -96,35 +96,35 @@ __device__ inline void wz_wait(u32x4z (&r)[CNT]) {  // s_waitcnt vmcnt(N); the s
                      : "n"(N));
 }
 
-// NG = wave groups of the workgroup (4 waves each).  NG = 2: eight waves, two per SIMD -- group g takes the output rows
-// 4 g .. 4 g + 3 of every plane (8 of its 16 steps) with its own accumulators, which are added through LDS at the end.
 // Ablation (round 3, 32 -> 32 @128^3, kernel time under rocprofv3 with GRBM_GUI_ACTIVE): full kernel 193 us = 340 k cycles per
 // XCD at 1.76 GHz; without the staging loads / LDS writes 146 us = 295 k at 2.02 GHz; MFMAs + shifts only 135 us = 291 k at
 // 2.16 GHz; everything but the MFMAs 97 us at 2.51 GHz -- MFMA stream plus HBM stream run into the power limit, so the
-// parts "add up" in time although they overlap in cycles.  NG = 2 hides the operand reads (plane loop without staging
-// 0.142 vs 0.161 ms) but not that.
+// parts "add up" in time although they overlap in cycles.  (An eight-wave form, two wave groups per workgroup that split
+// the output rows of a plane, hid the operand reads -- plane loop without staging 0.142 vs 0.161 ms -- but not that:
+// measured equal inside the step, 11.27-11.41 vs 11.39-11.48 ms, and removed.)
 // PRO: loader prologue (ops.NormActConv3dFn backward): x is the RAW bf16 output of the producing conv; the operand of the
 // product is a = bf16(lrelu(fma(x, scale[n][c], shift[n][c]))) -- the arithmetic of k_in_apply_ss16 / the forward loader
 // prologue of k_fwd16y, applied to the staged 16-byte parts in registers (a thread's parts are always the channel octet
 // tid & 3: eight scale / shift registers), one part per step ten steps ahead of its LDS write; voxels outside the volume
 // stay zero (the zero padding applies to the activation).  The activated tensor is never read: it need not exist.
-template <int DBG, int NG, bool PRO>
-__global__ __launch_bounds__(256 * NG, 1) void k_wgrad16z(const WgradGeom g, const WgZTile tg, const unsigned short *__restrict__ a1,
+template <bool PRO>
+__global__ __launch_bounds__(256, 1) void k_wgrad16z(const WgradGeom g, const WgZTile tg, const unsigned short *__restrict__ a1,
                                                           const unsigned short *__restrict__ a2,
                                                           const unsigned short *__restrict__ b, float *__restrict__ partial,
                                                           float *__restrict__ pbias, const float *__restrict__ in_scale,
                                                           const float *__restrict__ in_shift, const float slope) {
-    static_assert(!PRO || NG == 1, "the loader prologue is scheduled for the four-wave form");
-    constexpr int NT = 256 * NG;                     // threads
-    constexpr int NA = (WZ_APARTS + NT - 1) / NT;    // staging loads per thread: x plane (6 / 3)
-    constexpr int NB = WZ_TH * WZ_TW * 4 / NT;       // dy plane (4 / 2)
-    constexpr int SP = 16 / NG;                      // steps per plane and wave
-    constexpr int ST_BAR1 = NG == 1 ? 3 : 0, ST_WA = ST_BAR1 + 1, ST_WB = ST_BAR1 + 2, ST_BAR2 = NG == 1 ? 7 : 3;
-    constexpr int ST_LD0 = NG == 1 ? 6 : 3;          // one staging load per step from here
-    static_assert(ST_LD0 + NA + NB <= SP && ST_WB < ST_LD0 + (NG == 1 ? 1 : 1), "staging schedule");
+    constexpr int NT = 256;                          // threads
+    constexpr int NA = (WZ_APARTS + NT - 1) / NT;    // staging loads per thread: x plane (6)
+    constexpr int NB = WZ_TH * WZ_TW * 4 / NT;       // dy plane (4)
+    constexpr int SP = 16;                           // steps per plane and wave
+    constexpr int ST_BAR1 = 3, ST_WA = ST_BAR1 + 1, ST_WB = ST_BAR1 + 2, ST_BAR2 = 7;
+    constexpr int ST_LD0 = 6;                        // one staging load per step from here
+    static_assert(ST_LD0 + NA + NB <= SP && ST_WB < ST_LD0 + 1, "staging schedule");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds8[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // grp (the wave group of the removed eight-wave form) is always 0, which the compiler cannot see: the row offsets derived
+    // from it stay until a change that re-measures this kernel -- its code is kept byte-identical to the measured one
     const int wave = wave8 & 3, grp = wave8 >> 2;
     const int i = lane & 31, h = lane >> 5;
     const int cb = blockIdx.y / tg.nkb, kb = blockIdx.y % tg.nkb;
@@ -154,8 +154,7 @@ __global__ __launch_bounds__(256 * NG, 1) void k_wgrad16z(const WgradGeom g, con
     const int q4 = (lane & 15) >> 2;
     const int colb = ((lane >> 4) & 1) * 32 + (lane & 3) * 8;
     const unsigned lane_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)lds8 + (unsigned)((8 * h + q4) * 64 + colb);
-    // the wave group's first output row
-    const unsigned growA = (unsigned)(grp * (WZ_TH / NG) * WZ_ROWB), growB = (unsigned)(grp * (WZ_TH / NG) * WZ_TW * 64);
+    const unsigned growA = (unsigned)(grp * WZ_TH * WZ_ROWB), growB = (unsigned)(grp * WZ_TH * WZ_TW * 64);
     // triples 2 w, 2 w + 1 (dz = T / 3, dy = T % 3), single tap 24 + w of the ninth triple (dz = dy = 2, dx = w)
     const int T0 = 2 * wave, T1 = 2 * wave + 1;
     const int dzq0 = T0 / 3, dzq1 = T1 / 3;
@@ -353,16 +352,14 @@ __global__ __launch_bounds__(256 * NG, 1) void k_wgrad16z(const WgradGeom g, con
             const unsigned nab = bB + (unsigned)(((p + 1) & 1) * WZ_BPLANE);
 #pragma unroll
             for (int st = 0; st < SP; st++) {
-                if (DBG & 1) {
-                } else if (st < SP - 1) {
+                if (st < SP - 1) {
                     const int imm = ((st + 1) >> 1) * WZ_ROWB + ((st + 1) & 1) * 16 * 64;
                     const int immB = (((st + 1) >> 1) * WZ_TW + ((st + 1) & 1) * 16) * 64;
                     fetch(aq0, aq1, as, ab, imm, immB, (st + 1) & 1);
                 } else {
                     fetch(naq0, naq1, nas, nab, 0, 0, 0);  // step 0 of the next plane (behind this plane's second barrier)
                 }
-                if (DBG & (2 | 32)) {
-                } else if (st >= ST_LD0 && st < ST_LD0 + NA) wz_bload(ra[SET][st - ST_LD0], voA[st - ST_LD0], rA);
+                if (st >= ST_LD0 && st < ST_LD0 + NA) wz_bload(ra[SET][st - ST_LD0], voA[st - ST_LD0], rA);
                 else if (st >= ST_LD0 + NA && st < ST_LD0 + NA + NB) wz_bload(rb[SET][st - ST_LD0 - NA], voB[st - ST_LD0 - NA], rB);
                 constexpr int ST_X0 = ST_LD0 + NB;  // PRO: part u of the OTHER set (x plane z + 3, loaded one plane ago) at step
                 if (PRO && st >= ST_X0 && st < ST_X0 + NA) {  // ST_X0 + u: every younger load is one of this plane's
@@ -377,57 +374,37 @@ __global__ __launch_bounds__(256 * NG, 1) void k_wgrad16z(const WgradGeom g, con
                     else wz_wait<Y0 + 5>(ra[1 - SET]);
                     xform(ra[1 - SET][st - ST_X0], voA[st - ST_X0] != 0x80000000u && p + 3 <= nz && plane_ok(z + 3));
                 }
-                if (!(DBG & 8)) mfmas(st & 1);
-                if (st == ST_WA && !(DBG & (2 | 64))) {
+                mfmas(st & 1);
+                if (st == ST_WA) {
                     wz_wait<2 * (NA + NB) - NA>(ra[SET]);  // (this set's loads are the older half of those outstanding)
                     write_A((p + 3) & 3, ra[SET]);
                 }
-                if (st == ST_WB && !(DBG & (2 | 64))) {
+                if (st == ST_WB) {
                     wz_wait<NA + NB>(rb[SET]);
                     write_B((p + 1) & 1, rb[SET]);
                 }
                 // the step as one pipeline: per MFMA gap two transposing reads of the next step's operands and two of this
-                // step's v_alignbit (NG = 1: what is not placed inside a gap is paid in full)
-                if (!(DBG & 16)) {
+                // step's v_alignbit (one wave per SIMD: what is not placed inside a gap is paid in full)
 #pragma unroll
-                    for (int j = 0; j < 7; j++) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        if (j < 6) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                        if (j >= 1 && j < 5) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                        if (PRO && st >= ST_X0 && st < ST_X0 + NA) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
-                        if ((st == ST_WA && j < NA) || (st == ST_WB && j < NB)) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                    }
+                for (int j = 0; j < 7; j++) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    if (j < 6) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                    if (j >= 1 && j < 5) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+                    if (PRO && st >= ST_X0 && st < ST_X0 + NA) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+                    if ((st == ST_WA && j < NA) || (st == ST_WB && j < NB)) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if (st == ST_BAR1 && !(DBG & 4)) asm volatile("s_barrier" ::: "memory");  // every wave has finished the previous plane's reads
-                if (st == ST_BAR2 && !(DBG & 4)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if (st == ST_BAR1) asm volatile("s_barrier" ::: "memory");  // every wave has finished the previous plane's reads
+                if (st == ST_BAR2) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
             }
             aq0 = naq0; aq1 = naq1; as = nas; ab = nab;
         };
-        for (int rep = 0; rep < ((DBG & 128) ? 2 : 1); rep++)  // (timing ablation: the plane loop twice = fixed cost + 2 x loop)
         for (int p = 0; p < nz; p += 2) {
             plane(p, std::integral_constant<int, 0>());
             if (p + 1 < nz) plane(p + 1, std::integral_constant<int, 1>());
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the last planes' zero-record loads)
-    }
-    if constexpr (NG == 2) {  // group 1's sums join group 0's through LDS ([register][thread]: conflict-free)
-        __syncthreads();
-        float *lf = reinterpret_cast<float *>(lds8);
-        static_assert(7 * 16 * 256 * 4 <= WZ_LDS, "accumulator exchange fits the LDS allocation");
-        if (grp == 1) {
-#pragma unroll
-            for (int j = 0; j < 7; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) lf[(j * 16 + r) * 256 + (tid & 255)] = acc[j][r];
-        }
-        __syncthreads();
-        if (grp == 1) return;
-#pragma unroll
-        for (int j = 0; j < 7; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[j][r] += lf[(j * 16 + r) * 256 + tid];
     }
 #pragma unroll
     for (int j = 0; j < 7; j++) {
@@ -748,18 +725,7 @@ int wgrad16z(const WgradGeom &g, const unsigned short *a1, const unsigned short 
     float *pbias = want_bias ? partial + need / sizeof(float) : nullptr;
     typedef void (*kfn_t)(const WgradGeom, const WgZTile, const unsigned short *, const unsigned short *, const unsigned short *,
                           float *, float *, const float *, const float *, float);
-    // wave groups: 1 (default) = four waves, 2 = eight.  Measured equal inside the step (11.27-11.41 vs 11.39-11.48 ms): with
-    // the staging traffic on, the kernel runs against the power limit (1.76 GHz; 2.16 GHz for the MFMA stream alone), where
-    // the cycles the second wave per SIMD saves (340 k -> 300 k per XCD without staging) do not turn into time
-    static const int ng_env = getenv("MVD_WGRAD16Z_NG") ? (atoi(getenv("MVD_WGRAD16Z_NG")) == 2 ? 2 : 1) : 1;
-    const int ng = pro ? 1 : ng_env;
-    kfn_t kfn = pro ? k_wgrad16z<0, 1, true> : ng == 2 ? k_wgrad16z<0, 2, false> : k_wgrad16z<0, 1, false>;
-#ifdef MVD_WG16Z_ABLATE
-    static const int dbg = getenv("MVD_WG16Z_DBG") ? atoi(getenv("MVD_WG16Z_DBG")) : 0;  // timing ablation only: results are wrong
-#define WZ_DBG(V) if (dbg == V && !pro) kfn = ng == 2 ? k_wgrad16z<V, 2, false> : k_wgrad16z<V, 1, false>;
-    WZ_DBG(1) WZ_DBG(2) WZ_DBG(3) WZ_DBG(4) WZ_DBG(8) WZ_DBG(16) WZ_DBG(32) WZ_DBG(64) WZ_DBG(128) WZ_DBG(129) WZ_DBG(130) WZ_DBG(131) WZ_DBG(160) WZ_DBG(192) WZ_DBG(136) WZ_DBG(132)
-#undef WZ_DBG
-#endif
+    kfn_t kfn = pro ? k_wgrad16z<true> : k_wgrad16z<false>;
     static PerDeviceFlag cfgd, cfgd_pro;
     PerDeviceFlag &cf = pro ? cfgd_pro : cfgd;
     if (!cf()) {
@@ -769,7 +735,7 @@ int wgrad16z(const WgradGeom &g, const unsigned short *a1, const unsigned short 
         }
         cf() = true;
     }
-    hipLaunchKernelGGL(kfn, dim3(tg.nsplit, (unsigned)blocks), dim3(256 * ng), WZ_LDS, s, g, tg, a1, a2, b, partial, pbias, in_scale, in_shift,
+    hipLaunchKernelGGL(kfn, dim3(tg.nsplit, (unsigned)blocks), dim3(256), WZ_LDS, s, g, tg, a1, a2, b, partial, pbias, in_scale, in_shift,
                        slope);
     if (check_launch("conv wgrad (bf16 z-marching)")) return 1;
     *nsplit_out = tg.nsplit;

@@ -286,7 +286,8 @@ size_t fwd_mfma_ws(int N, long out_vox, int K) {
 
 // ------------------------------------------------------------------------------------------------ CK = 32 kernel
 // Stride-1 gathers with C % 32 == 0 (every 3x3x3 conv fwd / dgrad of the net but the strided ones).
-//   * workgroup = 4 waves = a 4 x (4*MT) x 8 voxel tile x 32*NT output channels;
+//   * workgroup = 4 waves = a 4 x 4 x 8 voxel tile x 32*NT output channels, two workgroups per CU (the 4 x 8 x 8 tile,
+//     one per CU, was removed: DESIGN.md 9.5);
 //   * per 32-channel chunk the whole halo tile [slots][32 ch] -- each voxel one full 128-byte line, padded to 36
 //     floats against LDS bank conflicts -- is staged ONCE (the 8-channel chunks of k_fwd_mfma re-fetch every line four
 //     times and go HBM-bound);
@@ -305,7 +306,7 @@ struct Fwd32Tile {
     int dbg;
 };
 
-template <int NT, int MT, int TG>
+template <int NT, int TG>
 __global__ __launch_bounds__(256, 2) void k_fwd32(const FwdGeom g, const Fwd32Tile tg, const float *__restrict__ a1,
                                                   const float *__restrict__ a2, const float *__restrict__ w,
                                                   const float *__restrict__ bias, float *__restrict__ y1,
@@ -314,8 +315,9 @@ __global__ __launch_bounds__(256, 2) void k_fwd32(const FwdGeom g, const Fwd32Ti
     constexpr int KT = 32 * NT;
     constexpr int XS = 36;                       // floats per halo slot (32 + 4 pad)
     constexpr int WS = 20;                       // floats per (tap, h, k) weight row (16 + 4 pad)
-    constexpr int XR = MT == 2 ? 19 : 12;        // float4 per thread: 608 / 384 slots x 8
-    constexpr int XB = MT == 2 ? 10 : 12;        // staging batch (loads in flight per thread)
+    constexpr int MT = 1;                        // M tiles (4 rows of 8 voxels) per wave
+    constexpr int XR = 12;                       // float4 per thread: 384 slots x 8
+    constexpr int XB = 12;                       // staging batch (loads in flight per thread)
     constexpr int WR = TG * 2 * KT * 4 / 256;    // float4 per thread per weight group
     constexpr int WBUF = TG * 2 * KT * WS;       // floats per weight buffer
     static_assert(TG * 2 * KT * 4 % 256 == 0, "weight group must be a multiple of 256 float4");
@@ -926,11 +928,11 @@ static int run_split_reduce(const FwdGeom &g, const float *part, const float *bi
     return check_launch("conv fwd split reduce");
 }
 
-template <int NT, int MT, int TG>
+template <int NT, int TG>
 static int launch_fwd32(const FwdGeom &g, Fwd32Tile &tg, const float *a1, const float *a2, const float *w,
                         const float *bias, float *y1, float *y2, void *ws, size_t ws_bytes, hipStream_t s) {
-    auto kern = k_fwd32<NT, MT, TG>;
-    constexpr int XR = MT == 2 ? 19 : 12;
+    auto kern = k_fwd32<NT, TG>;
+    constexpr int XR = 12;
     const size_t lds = ((size_t)XR * 32 * 36 + 2 * (size_t)TG * 2 * (32 * NT) * 20) * 4;
     static PerDeviceFlag configured;
     if (!configured()) {
@@ -1003,7 +1005,7 @@ int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w,
         }
     const bool unit_stride = g.sa[0] == 1 && g.sa[1] == 1 && g.sa[2] == 1;
     if (LCK == 32 && unit_stride && !(dbg & 4)) {
-        // ---- CK = 32 kernel: 4x8x8 tile (one workgroup per CU) or 4x4x8 tile (two per CU)
+        // ---- CK = 32 kernel: 4x4x8 tile (two workgroups per CU)
         // a 64-wide N tile may span the two output pointers: each 32-wide half lies in one of them (K1 % 32 == 0)
         static int nt_rule = -1;  // MVD_CONV_NT: 0 = 64-wide N tile whenever K % 64 == 0, 1 (default) = narrow tile for skinny problems
         if (nt_rule < 0) nt_rule = getenv("MVD_CONV_NT") ? atoi(getenv("MVD_CONV_NT")) : 1;
@@ -1011,15 +1013,10 @@ int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w,
         // tile doubles the workgroup count and halves the serial MFMA chain of each
         const long wg64 = (long)g.N * ((g.Do + 3) / 4) * ((g.Ho + 3) / 4) * ((g.Wo + 7) / 8) * (K / 64);
         const int NT = (K % 64 == 0 && !(nt_rule == 1 && wg64 < 128)) ? 2 : 1;
-        static int force_mt = -1;
-        if (force_mt < 0) force_mt = getenv("MVD_CONV_MT") ? atoi(getenv("MVD_CONV_MT")) : 0;
-        static int force_tg = -1;
-        if (force_tg < 0) force_tg = getenv("MVD_CONV_TG") ? atoi(getenv("MVD_CONV_TG")) : 0;
-        const int MT = force_mt ? force_mt : 1;
         Fwd32Tile t32;
         memset(&t32, 0, sizeof(t32));
         t32.dbg = dbg;
-        const int T3[3] = {4, 4 * MT, 8};
+        const int T3[3] = {4, 4, 8};
         int E[3];
         for (int a = 0; a < 3; a++) {
             E[a] = (T3[a] - 1) + (mx[a] - mn[a]) + 1;
@@ -1035,21 +1032,15 @@ int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w,
         };
         t32.magHW = magic(t32.EH * t32.EW, t32.nslots);
         t32.magW = magic(t32.EW, t32.EH * t32.EW);
-        if (t32.nslots <= (MT == 2 ? 19 : 12) * 32 && t32.magHW > 0 && t32.magW > 0) {
+        if (t32.nslots <= 12 * 32 && t32.magHW > 0 && t32.magW > 0) {
             for (int t = 0; t < g.ntaps; t++)
                 t32.toff[t] = ((g.off[t][0] - mn[0]) * t32.EH + (g.off[t][1] - mn[1])) * t32.EW + (g.off[t][2] - mn[2]);
             t32.ntd = (g.Do + 3) / 4;
-            t32.nth = (g.Ho + 4 * MT - 1) / (4 * MT);
+            t32.nth = (g.Ho + 3) / 4;
             t32.ntw = (g.Wo + 7) / 8;
             t32.K = K;
-            if (MT == 2) {
-                if (NT == 2) return launch_fwd32<2, 2, 3>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
-                return launch_fwd32<1, 2, 3>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
-            }
-            if (NT == 2) return launch_fwd32<2, 1, 1>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
-            if (force_tg == 3) return launch_fwd32<1, 1, 3>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
-            if (force_tg == 1) return launch_fwd32<1, 1, 1>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
-            return launch_fwd32<1, 1, 2>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
+            if (NT == 2) return launch_fwd32<2, 1>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
+            return launch_fwd32<1, 2>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
         }
     }
     if (LCK == 32 && g.sa[0] == 2 && g.sa[1] == 2 && g.sa[2] == 2 && g.ntaps == 27 && g.T == 27 && K % 64 == 0 &&
@@ -1612,28 +1603,14 @@ __global__ __launch_bounds__(256, 1) void k_wgrad_wino(const WgradGeom g, const 
 // buffered so no MFMA operand register is rewritten behind the MFMA that reads it.  The position row a is a
 // template parameter (the kernel switches on the wave index once): every sign is an add/sub and the two patch rows of
 // a column come from one ds_read2st64_b32.  Tile fixed to 2x8x8 voxels (halo 4 x 10 x 10 slots).
-// B0 / NBW: the wave owns position columns b = B0 .. B0+NBW-1 (NBW = 4: four waves per workgroup, one per position row;
-// NBW = 2: eight waves, two per row -- half the accumulators per wave, so two waves share a SIMD and cover each
-// other's barrier / LDS waits).  TPB = threads per workgroup (staging loops).
-// GZ0 / NGZ: the wave owns filter planes GZ0 .. GZ0+NGZ-1 (3 planes by default; the twelve-wave variant gives each wave
-// one plane and all four columns: 64 accumulator registers, three waves per SIMD).
-typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
-#ifndef MVD_WG16_DBG
-#define MVD_WG16_DBG 0
-#endif
-#if (MVD_WG16_DBG & 64)  // diagnostic build only (tools/stamps_wgrad16.py): s_memtime stamps of one wave per tile
-__device__ long long g_wg16_stamps[64 * 8];
-extern "C" int mvd_debug_wg16_stamps(long long *host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_wg16_stamps), sizeof(long long) * 64 * 8) == hipSuccess ? 0 : 1;
-}
-#define MVD_WGS(K) { if (stamp_on && nst < 60) g_wg16_stamps[nst * 8 + (K)] = __builtin_amdgcn_s_memtime(); }
-#else
-#define MVD_WGS(K)
-#endif
-// DB: two LDS images (A 4 x 10 x 10 slots + B 2 x 8 x 8 slots, 67 584 bytes each, allocated exactly): a wave writes the
+// Twelve waves per workgroup: the wave owns position row A of filter plane GZ with all four position columns (64
+// accumulator registers, three waves per SIMD that cover each other's barrier / LDS waits).  The four- and eight-wave
+// forms (three planes, or two columns, per wave) and the single-image tile loop were removed: DESIGN.md 9.5.
+// Two LDS images (A 4 x 10 x 10 slots + B 2 x 8 x 8 slots, 67 584 bytes each, allocated exactly): a wave writes the
 // next tile into the other image as soon as its own steps are done -- under the MFMAs of the SIMD's younger waves -- and
 // the tile loop has ONE barrier per tile instead of barrier / write / barrier with the MFMA pipe idle.
-template <int A, int B0, int NBW, int TPB, int NA, int NB, int GZ0 = 0, int NGZ = 3, bool DB = false>
+typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
+template <int A, int GZ, int NA, int NB>
 __device__ __forceinline__ void wgrad_wino2_body(const WgradGeom &g, const WgTile &tg, const float *__restrict__ a1,
                                                  const float *__restrict__ a2, const float *__restrict__ b,
                                                  float *__restrict__ partial, float *__restrict__ pbias, float *As,
@@ -1641,16 +1618,16 @@ __device__ __forceinline__ void wgrad_wino2_body(const WgradGeom &g, const WgTil
     constexpr int RA = A == 0 ? 0 : (A == 2 ? 2 : 1);
     constexpr int RB = A == 0 ? 2 : (A == 1 ? 2 : (A == 2 ? 1 : 3));
     constexpr int EAW = 10, EAH = 10, EBW = 8, EBH = 8;
+    constexpr int TPB = 768;  // threads per workgroup (staging loops)
     const int tid = threadIdx.x, lane = tid & 63;
     const int i = lane & 31, h = lane >> 5;
     const int cb = blockIdx.y / tg.nkb, kb = blockIdx.y % tg.nkb;
     const int split = blockIdx.x;
     const int C = g.C1 + g.C2, K = g.K;
 
-    constexpr int NTL = NGZ * NBW;
-    f32x16 acc[NTL];  // [gz - GZ0][b - B0]
+    f32x16 acc[4];  // [position column b]
 #pragma unroll
-    for (int j = 0; j < NTL; j++)
+    for (int j = 0; j < 4; j++)
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[j][r] = 0.f;
 
@@ -1734,25 +1711,25 @@ __device__ __forceinline__ void wgrad_wino2_body(const WgradGeom &g, const WgTil
             }
         }
     };
-    constexpr int DBUF = (4 * EAH * EAW + 2 * EBH * EBW) * 128;  // bytes of one image pair (DB)
+    constexpr int DBUF = (4 * EAH * EAW + 2 * EBH * EBW) * 128;  // bytes of one image pair
     auto store_tile = [&](int par) {
-        float *Ad = As + (DB ? par * (DBUF / 4) : 0), *Bd = Bs + (DB ? par * (DBUF / 4) : 0);
+        float *Ad = As + par * (DBUF / 4), *Bd = Bs + par * (DBUF / 4);
 #pragma unroll
         for (int u = 0; u < NA; u++)
-            if (!DB || (u + 1) * TPB <= 4 * EAH * EAW * 8 || u * TPB + tid < na)  // (exact allocation: no slack to write into)
+            if ((u + 1) * TPB <= 4 * EAH * EAW * 8 || u * TPB + tid < na)  // (exact allocation: no slack to write into)
                 *reinterpret_cast<float4 *>(Ad + (size_t)(u * TPB + tid) * 4) = ra[u];
 #pragma unroll
         for (int u = 0; u < NB; u++)
-            if (!DB || (u + 1) * TPB <= 2 * EBH * EBW * 8 || u * TPB + tid < nb)
+            if ((u + 1) * TPB <= 2 * EBH * EBW * 8 || u * TPB + tid < nb)
                 *reinterpret_cast<float4 *>(Bd + (size_t)(u * TPB + tid) * 4) = rb[u];
     };
 
     const char *Ab = reinterpret_cast<const char *>(As), *Bb = reinterpret_cast<const char *>(Bs);
     const int abase = h * (EAH * EAW * 128) + i * 4;  // lane half's d-plane, lane column
     const int bbase = h * (EBH * EBW * 128) + i * 4;
-    // R of patch column `col` (halo x index) of quad row hq, plane gz
-    auto fetch_col = [&](int gz, int hq, int col, float &pa, float &pb) {
-        const int ad = abase + ((gz * EAH + 2 * hq) * EAW + col) * 128;
+    // R of patch column `col` (halo x index) of quad row hq
+    auto fetch_col = [&](int hq, int col, float &pa, float &pb) {
+        const int ad = abase + ((GZ * EAH + 2 * hq) * EAW + col) * 128;
         pa = *reinterpret_cast<const float *>(Ab + ad + RA * EAW * 128);
         pb = *reinterpret_cast<const float *>(Ab + ad + RB * EAW * 128);
     };
@@ -1771,45 +1748,29 @@ __device__ __forceinline__ void wgrad_wino2_body(const WgradGeom &g, const WgTil
         E[0] = f0; E[1] = f0 + f1; E[2] = f0 - f1; E[3] = -f1;
     };
 
-    float R[NGZ][4];      // [gz - GZ0][column ring: halo column x lives in slot x & 3]
-    float V[2][NGZ][4];   // MFMA A operands, double buffered over the step parity
-    float E[2][4];      // MFMA B operands
+    float R[4];      // column ring: halo column x lives in slot x & 3
+    float V[2][4];   // MFMA A operands, double buffered over the step parity
+    float E[2][4];   // MFMA B operands
     // bias gradient: wave 0 of the c-block-0 workgroups sees every dy value of its k-block exactly once (the 2x2
     // quads it fetches for E): per-lane partial sums, reduced over lanes halves / splits by k_dbias_reduce
-    const float bflag = (A == 0 && B0 == 0 && GZ0 == 0 && pbias != nullptr && cb == 0) ? 1.f : 0.f;
+    constexpr bool BIAS = A == 0 && GZ == 0;
+    const float bflag = (BIAS && pbias != nullptr && cb == 0) ? 1.f : 0.f;
     float bsum = 0.f;
-#if (MVD_WG16_DBG & 64)
-    const bool stamp_on = (MVD_WG16_DBG & 128) && blockIdx.x == 100 && blockIdx.y == 0 && A == 0 && GZ0 == 0 && B0 == 0 && lane == 0;
-    int nst = 0;
-#endif
     int tile = split;
     if (tile < tg.ntiles) load_tile(tile);
     int par = 0;
-    if (DB) {
-        if (tile < tg.ntiles) store_tile(0);
-        __syncthreads();
-    }
+    if (tile < tg.ntiles) store_tile(0);
+    __syncthreads();
     while (tile < tg.ntiles) {
-        MVD_WGS(0)
-        if (!DB) {
-            __syncthreads();
-            MVD_WGS(1)
-            store_tile(0);
-            MVD_WGS(2)
-            __syncthreads();
-        }
-        MVD_WGS(3)
         const int next = tile + tg.nsplit;
-        // Single image: the next tile's loads are issued here, every wave of the workgroup at the same time with the MFMA
-        // pipe idle (2 k of a 20 k ticks tile, tools/stamps_wgrad_wino.py); the same predicated loads one quad row into
-        // the steps measured 3-4 % SLOWER (the branches around them cost the pipelined LDS reads their counted waits).
-        // DB: unconditional BUFFER loads behind the MFMAs of the first quad row (issue_load): a lane whose halo voxel is
-        // outside the volume passes an out-of-range offset and gets zeros, after the last tile the descriptors have
-        // zero records.
+        // The next tile's loads are unconditional BUFFER loads behind the MFMAs of the first quad row (issue_load): a lane
+        // whose halo voxel is outside the volume passes an out-of-range offset and gets zeros, after the last tile the
+        // descriptors have zero records.  (Predicated loads inside the steps measured 3-4 % SLOWER than a burst with the
+        // MFMA pipe idle: the branches around them cost the pipelined LDS reads their counted waits.)
         bool nintA = true, nintB = true;
         int nz0 = 0, ny0 = 0, nx0 = 0;
         __amdgpu_buffer_rsrc_t rA, rB;
-        if (DB) {
+        {
             const bool more = next < tg.ntiles;
             unsigned r_ = (unsigned)(more ? next : 0);
             const int tw_ = (int)(r_ % (unsigned)tg.ntw); r_ /= (unsigned)tg.ntw;
@@ -1823,8 +1784,6 @@ __device__ __forceinline__ void wgrad_wino2_body(const WgradGeom &g, const WgTil
             const float *baseB = b + ((((long)n * g.Db + nz0) * g.Hb + ny0) * g.Wb + nx0) * (long)K;
             rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(baseA), 0, more ? 0x7fffffff : 0, 0x00020000);
             rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(baseB), 0, more ? 0x7fffffff : 0, 0x00020000);
-        } else if (next < tg.ntiles) {
-            load_tile(next);
         }
         auto issue_load = [&](int u) {
             if (u >= NA + NB) return;
@@ -1844,88 +1803,73 @@ __device__ __forceinline__ void wgrad_wino2_body(const WgradGeom &g, const WgTil
             if (isA) ra[ua] = f4;
             else rb[ub] = f4;
         };
-        MVD_WGS(4)
         // window of the first quad: columns 0..3 of quad row 0, and its dy quad
         {
             float e[4];
             fetch_e(0, 0, e);
 #pragma unroll
-            for (int gz = 0; gz < NGZ; gz++)
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    float pa, pb;
-                    fetch_col(GZ0 + gz, 0, c, pa, pb);
-                    R[gz][c] = rcomb(pa, pb);
-                }
-            make_E(e, E[0]);
-            if (A == 0 && B0 == 0 && GZ0 == 0) bsum += bflag * ((e[0] + e[1]) + (e[2] + e[3]));
-#pragma unroll
-            for (int gz = 0; gz < NGZ; gz++) {
-                V[0][gz][0] = R[gz][0] - R[gz][2];
-                V[0][gz][1] = R[gz][1] + R[gz][2];
-                V[0][gz][2] = R[gz][2] - R[gz][1];
-                V[0][gz][3] = R[gz][1] - R[gz][3];
+            for (int c = 0; c < 4; c++) {
+                float pa, pb;
+                fetch_col(0, c, pa, pb);
+                R[c] = rcomb(pa, pb);
             }
+            make_E(e, E[0]);
+            if (BIAS) bsum += bflag * ((e[0] + e[1]) + (e[2] + e[3]));
+            V[0][0] = R[0] - R[2];
+            V[0][1] = R[1] + R[2];
+            V[0][2] = R[2] - R[1];
+            V[0][3] = R[1] - R[3];
         }
         __builtin_amdgcn_sched_barrier(0);
-        // one quad row = four steps; WL: the next tile's loads ride behind the steps' MFMAs, two per step (DB, row 0)
+        // one quad row = four steps; WL: the next tile's loads ride behind the steps' MFMAs, two per step (row 0)
         auto quad_row = [&](int hq, auto WL) {
 #pragma unroll
             for (int wq = 0; wq < 4; wq++) {
-                constexpr int dummy = 0;
-                (void)dummy;
                 const int cur = wq & 1, nxt = cur ^ 1;
                 // the next step: (hq, wq + 1) needs columns 2wq+4, 2wq+5; after the row's last quad the whole window
                 // (columns 0..3) of quad row hq + 1 (the tile's very last step re-reads row hq: unused)
                 const int nhq = wq == 3 ? (hq < 3 ? hq + 1 : hq) : hq;
-                constexpr int NC = 4;  // columns fetched at a row end; 2 otherwise
-                float pa[NGZ][NC], pb[NGZ][NC], e[4];
+                float pa[4], pb[4], e[4];  // (four columns fetched at a row end; two otherwise)
 #pragma unroll
-                for (int j = 0; j < NTL; j++) {
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[cur][j / NBW][B0 + j % NBW], E[cur][B0 + j % NBW], acc[j], 0, 0,
-                                                                  0);
+                for (int j = 0; j < 4; j++) {
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[cur][j], E[cur][j], acc[j], 0, 0, 0);
                     if (j == 0) fetch_e(nhq, wq == 3 ? 0 : wq + 1, e);
-                    // fetch group of this MFMA slot: 3 groups (one plane each) in a row's interior, 6 (half a plane
-                    // each) at a row end; with 6 MFMAs per step the row-end groups start at slot 0
-                    const int fg = (NTL >= 7 || wq != 3) ? j - 1 : j;
+                    // fetches behind this MFMA slot: the two new columns in slot 1 in a row's interior, the four of the
+                    // next row's window over slots 0 and 1 at a row end
                     if (wq != 3) {
-                        if (fg >= 0 && fg < NGZ) {  // plane fg: two new columns
-                            fetch_col(GZ0 + fg, nhq, 2 * wq + 4, pa[fg][0], pb[fg][0]);
-                            fetch_col(GZ0 + fg, nhq, 2 * wq + 5, pa[fg][1], pb[fg][1]);
+                        if (j == 1) {
+                            fetch_col(nhq, 2 * wq + 4, pa[0], pb[0]);
+                            fetch_col(nhq, 2 * wq + 5, pa[1], pb[1]);
                         }
-                    } else {
-                        if (fg >= 0 && fg < 2 * NGZ) {  // plane fg/2: four columns, two per slot
-                            const int gz = fg >> 1, c2 = (fg & 1) * 2;
-                            fetch_col(GZ0 + gz, nhq, c2, pa[gz][c2], pb[gz][c2]);
-                            fetch_col(GZ0 + gz, nhq, c2 + 1, pa[gz][c2 + 1], pb[gz][c2 + 1]);
-                        }
+                    } else if (j < 2) {
+                        fetch_col(nhq, 2 * j, pa[2 * j], pb[2 * j]);
+                        fetch_col(nhq, 2 * j + 1, pa[2 * j + 1], pb[2 * j + 1]);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 // window update + operands of the next step (VALU only; the MFMAs above read V[cur] / E[cur])
                 make_E(e, E[nxt]);
-                if (A == 0 && B0 == 0 && GZ0 == 0) {  // the tile's very last fetch is a re-read: not counted
+                if (BIAS) {  // the tile's very last fetch is a re-read: not counted
                     const float fl = (wq == 3 && hq == 3) ? 0.f : bflag;
                     bsum += fl * ((e[0] + e[1]) + (e[2] + e[3]));
                 }
-#pragma unroll
-                for (int gz = 0; gz < NGZ; gz++) {
+                // (a one-trip loop, left from the form with several filter planes per wave: without it the compiler orders
+                // the adds below differently, and this kernel's code is kept byte-identical to its measured form)
+                for (int gz = 0; gz < 1; gz++) {
                     if (wq != 3) {
-                        R[gz][(2 * wq + 4) & 3] = rcomb(pa[gz][0], pb[gz][0]);
-                        R[gz][(2 * wq + 5) & 3] = rcomb(pa[gz][1], pb[gz][1]);
+                        R[(2 * wq + 4) & 3] = rcomb(pa[0], pb[0]);
+                        R[(2 * wq + 5) & 3] = rcomb(pa[1], pb[1]);
                     } else {
 #pragma unroll
-                        for (int c = 0; c < 4; c++) R[gz][c] = rcomb(pa[gz][c], pb[gz][c]);
+                        for (int c = 0; c < 4; c++) R[c] = rcomb(pa[c], pb[c]);
                     }
                     // next quad's patch columns are x = 2*nwq .. 2*nwq+3 with nwq = wq + 1 (or 0)
-                    constexpr int dummy2 = 0;
-                    (void)dummy2;
                     const int x0 = wq == 3 ? 0 : 2 * wq + 2;
-                    const float r0 = R[gz][x0 & 3], r1 = R[gz][(x0 + 1) & 3], r2 = R[gz][(x0 + 2) & 3], r3 = R[gz][(x0 + 3) & 3];
-                    V[nxt][gz][0] = r0 - r2;
-                    V[nxt][gz][1] = r1 + r2;
-                    V[nxt][gz][2] = r2 - r1;
-                    V[nxt][gz][3] = r1 - r3;
+                    const float r0 = R[x0 & 3], r1 = R[(x0 + 1) & 3], r2 = R[(x0 + 2) & 3], r3 = R[(x0 + 3) & 3];
+                    V[nxt][0] = r0 - r2;
+                    V[nxt][1] = r1 + r2;
+                    V[nxt][2] = r2 - r1;
+                    V[nxt][3] = r1 - r3;
                 }
                 if constexpr (decltype(WL)::value) {
                     issue_load(2 * wq);
@@ -1934,40 +1878,27 @@ __device__ __forceinline__ void wgrad_wino2_body(const WgradGeom &g, const WgTil
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
-        if constexpr (DB) {
-            quad_row(0, std::true_type{});
+        quad_row(0, std::true_type{});
 #pragma unroll 1
-            for (int hq = 1; hq < 4; hq++) quad_row(hq, std::false_type{});
-        } else {
-#pragma unroll 1
-            for (int hq = 0; hq < 4; hq++) quad_row(hq, std::false_type{});
-        }
-        MVD_WGS(5)
-        if (DB) {
-            if (next < tg.ntiles) store_tile(par ^ 1);
-            MVD_WGS(6)
-            __syncthreads();
-            MVD_WGS(7)
-            par ^= 1;
-            Ab = reinterpret_cast<const char *>(As) + par * DBUF;
-            Bb = reinterpret_cast<const char *>(Bs) + par * DBUF;
-        }
-#if (MVD_WG16_DBG & 64)
-        nst++;
-#endif
+        for (int hq = 1; hq < 4; hq++) quad_row(hq, std::false_type{});
+        if (next < tg.ntiles) store_tile(par ^ 1);
+        __syncthreads();
+        par ^= 1;
+        Ab = reinterpret_cast<const char *>(As) + par * DBUF;
+        Bb = reinterpret_cast<const char *>(Bs) + par * DBUF;
         tile = next;
     }
     // partial[split][gz][a][b][c][k]; D layout: col = lane&31 -> k, row -> c
 #pragma unroll
-    for (int j = 0; j < NTL; j++) {
-        float *po = partial + ((((size_t)split * 3 + GZ0 + j / NBW) * 4 + A) * 4 + B0 + j % NBW) * C * K;
+    for (int j = 0; j < 4; j++) {
+        float *po = partial + ((((size_t)split * 3 + GZ) * 4 + A) * 4 + j) * C * K;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
             po[(size_t)(c0 + row) * K + k0 + i] = acc[j][r];
         }
     }
-    if (A == 0 && B0 == 0 && GZ0 == 0 && pbias != nullptr && cb == 0) pbias[((size_t)split * 2 + h) * K + k0 + i] = bsum;
+    if (BIAS && pbias != nullptr && cb == 0) pbias[((size_t)split * 2 + h) * K + k0 + i] = bsum;
 }
 
 // dbias[k] = sum over splits and lane halves of pbias[row][k]   (fp64, fixed order).  Block = 64 channels x 16 row
@@ -2004,57 +1935,18 @@ int dbias_reduce(const float *pbias, float *dbias, int K, int nrows, hipStream_t
     return check_launch("conv wgrad dbias reduce");
 }
 
-template <int NA, int NB>
-__global__ __launch_bounds__(256, 1) void k_wgrad_wino2(const WgradGeom g, const WgTile tg, const float *__restrict__ a1,
-                                                        const float *__restrict__ a2, const float *__restrict__ b,
-                                                        float *__restrict__ partial, float *__restrict__ pbias) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *As = lds;
-    float *Bs = lds + (size_t)NA * 1024;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // one code copy per position row: every wave of the workgroup runs the same trip counts, so the barriers inside
-    // the copies pair up
-    if (wave == 0) wgrad_wino2_body<0, 0, 4, 256, NA, NB>(g, tg, a1, a2, b, partial, pbias, As, Bs);
-    else if (wave == 1) wgrad_wino2_body<1, 0, 4, 256, NA, NB>(g, tg, a1, a2, b, partial, pbias, As, Bs);
-    else if (wave == 2) wgrad_wino2_body<2, 0, 4, 256, NA, NB>(g, tg, a1, a2, b, partial, pbias, As, Bs);
-    else wgrad_wino2_body<3, 0, 4, 256, NA, NB>(g, tg, a1, a2, b, partial, pbias, As, Bs);
-}
-
-// eight-wave variant: wave w owns position row w >> 1 and the columns {0,1} or {2,3}; NA8 / NB8 = float4 per thread of the
-// same LDS tiles staged by 512 threads
-template <int NA8, int NB8>
-__global__ __launch_bounds__(512, 2) void k_wgrad_wino2w8(const WgradGeom g, const WgTile tg, const float *__restrict__ a1,
-                                                          const float *__restrict__ a2, const float *__restrict__ b,
-                                                          float *__restrict__ partial, float *__restrict__ pbias) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *As = lds;
-    float *Bs = lds + (size_t)NA8 * 2048;  // A region: NA8 float4 per thread x 512 threads
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#define MVD_W8(AA, BB) wgrad_wino2_body<AA, BB, 2, 512, NA8, NB8>(g, tg, a1, a2, b, partial, pbias, As, Bs)
-    switch (wave) {
-        case 0: MVD_W8(0, 0); break;
-        case 1: MVD_W8(0, 2); break;
-        case 2: MVD_W8(1, 0); break;
-        case 3: MVD_W8(1, 2); break;
-        case 4: MVD_W8(2, 0); break;
-        case 5: MVD_W8(2, 2); break;
-        case 6: MVD_W8(3, 0); break;
-        default: MVD_W8(3, 2); break;
-    }
-#undef MVD_W8
-}
-
-// twelve-wave variant: wave w owns position row w & 3 and filter plane w >> 2 with all four columns (4 accumulator tiles):
-// three waves per SIMD; NA12 / NB12 = float4 per thread of the same LDS tiles staged by 768 threads
-template <int NA12, int NB12, bool DB12 = false>
+// wave w owns position row w & 3 and filter plane w >> 2 (one code copy each: every wave of the workgroup runs the same
+// trip counts, so the barriers inside the copies pair up); NA12 / NB12 = float4 per thread of the LDS tiles staged by
+// 768 threads
+template <int NA12, int NB12>
 __global__ __launch_bounds__(768, 1) void k_wgrad_wino2w12(const WgradGeom g, const WgTile tg, const float *__restrict__ a1,
                                                            const float *__restrict__ a2, const float *__restrict__ b,
                                                            float *__restrict__ partial, float *__restrict__ pbias) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *As = lds;
-    float *Bs = lds + (DB12 ? (size_t)4 * 10 * 10 * 32 : (size_t)NA12 * 3072);  // A: exact (DB) / NA12 float4 x 768 threads
+    float *Bs = lds + (size_t)4 * 10 * 10 * 32;  // the A image is allocated exactly
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#define MVD_W12(AA, GZ) wgrad_wino2_body<AA, 0, 4, 768, NA12, NB12, GZ, 1, DB12>(g, tg, a1, a2, b, partial, pbias, As, Bs)
+#define MVD_W12(AA, GZ) wgrad_wino2_body<AA, GZ, NA12, NB12>(g, tg, a1, a2, b, partial, pbias, As, Bs)
     switch (wave) {
         case 0: MVD_W12(0, 0); break;
         case 1: MVD_W12(1, 0); break;
@@ -2514,20 +2406,12 @@ __global__ __launch_bounds__(256, 2) void k_wgrad16(const WgradGeom g, const WgT
 #pragma unroll
     for (int e = 0; e < 8; e++) ones[e] = (__bf16)1.0f;
 
-#if (MVD_WG16_DBG & 64)
-    const bool stamp_on = !(MVD_WG16_DBG & 128) && blockIdx.x == 100 && blockIdx.y == 0 && wave == 0 && lane == 0;
-    int nst = 0;
-#endif
     int tile = split;
     if (tile < tg.ntiles) load_tile(tile);
     while (tile < tg.ntiles) {
-        MVD_WGS(0)
         __syncthreads();
-        MVD_WGS(1)
         store_tile();
-        MVD_WGS(2)
         __syncthreads();
-        MVD_WGS(3)
         const int next = tile + tg.nsplit;
         // TRI: the next tile's global loads are issued one or two per MFMA step inside the step loop.  Issued in one
         // burst they cost the burst's time at the L1's 64 B/clk -- 57 KB per tile and workgroup, 2-3 kilocycles of the
@@ -2547,7 +2431,6 @@ __global__ __launch_bounds__(256, 2) void k_wgrad16(const WgradGeom g, const WgT
         } else if (next < tg.ntiles) {
             load_tile(next);
         }
-        MVD_WGS(4)
         // operands of step s+1 are fetched (step-table read, address adds, transposing reads) before the MFMAs of step s
         // are issued, into the other half of a double buffer: un-pipelined, every step exposed two LDS round trips
         // (table, then operands: s_waitcnt lgkmcnt(0) twice) and 16 address adds in front of its 7 MFMAs
@@ -2569,7 +2452,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad16(const WgradGeom g, const WgT
             // compiler places are then exact counts, i.e. the MFMAs of step s wait for the reads of step s and not
             // for the reads of step s + 1 issued just before them.  (With the run-time loop and the ones-slot branch
             // around the single-tap reads every second step sat behind s_waitcnt lgkmcnt(0): 75 instead of 32 pipe
-            // cycles per MFMA and wave in the s_memtime stamps of tools/stamps_wgrad16.py.)
+            // cycles per MFMA and wave in in-kernel s_memtime stamps.)
             // raw[buf]: the union reads of the two triples (3 x 4 voxels each), the single tap (2 x 4) and dy (2 x 4)
             constexpr int NSTEP = (NA == 10 ? 256 : 128) / 16;  // == TV / 16 (host-checked)
             s16x4 rt[2][2][3], rs[2][2], rbv[2][2];
@@ -2661,10 +2544,6 @@ __global__ __launch_bounds__(256, 2) void k_wgrad16(const WgradGeom g, const WgT
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[0][SH == 2 ? 0 : j], bv[0][SH == 1 ? 0 : j], acc[j], 0, 0, 0);
             }
         }
-        MVD_WGS(5)
-#if (MVD_WG16_DBG & 64)
-        nst++;
-#endif
         tile = next;
     }
 #pragma unroll
@@ -3046,12 +2925,7 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
             if (wino_mode() == 2 && tg.TH == 8 && tg.TW == 8 && tg.EAh == 10 && tg.EAw == 10 && tg.EBh == 8 && tg.EBw == 8 &&
                 need_w2 <= ws_bytes) {
                 float *pbias = (dbias && dbias_done) ? partial + need_m2 / sizeof(float) : nullptr;
-                // MVD_WGRAD_W8: 12 (default) = twelve waves (one plane per wave, 3 per SIMD), 1 = eight waves, 0 = four waves
-                static const int w8 = getenv("MVD_WGRAD_W8") ? atoi(getenv("MVD_WGRAD_W8")) : 12;
-                // MVD_WGRAD_DB=0: single LDS image (barrier / write / barrier per tile)
-                static const int db12 = getenv("MVD_WGRAD_DB") ? atoi(getenv("MVD_WGRAD_DB")) : 1;
-                auto kern2 = w8 == 12 ? (db12 ? k_wgrad_wino2w12<5, 2, true> : k_wgrad_wino2w12<5, 2, false>)
-                                      : (w8 ? k_wgrad_wino2w8<7, 2> : k_wgrad_wino2<13, 4>);
+                auto kern2 = k_wgrad_wino2w12<5, 2>;  // twelve waves (one plane per wave, 3 per SIMD), two LDS images
                 static PerDeviceFlag cfgd_w2;
                 if (!cfgd_w2()) {
                     if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern2), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3061,10 +2935,8 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
                     }
                     cfgd_w2() = true;
                 }
-                hipLaunchKernelGGL(kern2, grid, dim3(w8 == 12 ? 768 : (w8 ? 512 : 256)),
-                                   w8 == 12 ? (db12 ? (size_t)2 * (4 * 100 + 2 * 64) * 128 : (size_t)(5 + 2) * 12288)
-                                            : (w8 ? (size_t)(7 + 2) * 8192 : (size_t)(13 + 4) * 4096), s, g,
-                                   tg, a1, a2, b, partial, pbias);
+                hipLaunchKernelGGL(kern2, grid, dim3(768), (size_t)2 * (4 * 100 + 2 * 64) * 128, s, g, tg, a1, a2, b, partial,
+                                   pbias);
                 if (check_launch("conv wgrad (winograd 2-D)")) return 1;
                 if (pbias) {
                     hipLaunchKernelGGL(k_dbias_reduce, dim3(cdiv(g.K, 64)), dim3(1024), 0, s, pbias, dbias, g.K, tg.nsplit * 2);

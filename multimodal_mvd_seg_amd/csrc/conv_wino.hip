@@ -32,7 +32,7 @@ struct WinoTile {
     int ntd, nth, ntw, nkb;
     int nitems;
     int K;
-    int dbg;  // MVD_WINO_DBG ablation bits: 1 no activation loads, 2 no MFMAs, 4 no weight prefetch loads
+    int dbg;  // unused (read only by the removed ablation build); kept so the argument layout stays
 };
 
 // U layout: [cc][g = (oz+1)*3 + (oy+1)][p][e4][h][k][4], reduce channel c = cc*32 + h*16 + e (e = e4*4 + c4): the
@@ -89,11 +89,6 @@ int pack_weight_wino(const float *w, float *uf, float *ub, int K, int C, hipStre
 
 constexpr int WXS = 36;   // floats per halo slot (32 + 4 pad)
 constexpr int WXR = 12;   // float4 per thread: 360 slots x 8 / 256 threads = 11.25
-#ifdef MVD_WINO_ABLATE            // ablation build: MVD_WINO_DBG bit 0 skips the halo loads, bit 2 the weight loads
-constexpr bool kAblate = true;
-#else
-constexpr bool kAblate = false;
-#endif
 constexpr int WXB = 6;    // staging batch (loads in flight per thread)
 
 // Workgroup = 4 waves on one 4 x 4 x 8 voxel tile (64 pairs) x 32 output channels.  Wave w: M half = w & 1 (d-planes
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino(const FwdGeom g, const Wino
             for (int q = 0; q < WXB; q++) {
                 const int idx = (base + q) * 256 + tid_;
                 v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (idx < nx && !(kAblate && (tg.dbg & 1))) {
+                if (idx < nx) {
                     const int slot = idx >> 3;
                     const int ez = (slot * tg.magHW) >> 16, rem = slot - ez * EHW;
                     const int ey = (rem * tg.magW) >> 16, ex = rem - ey * tg.EW;
@@ -200,11 +195,9 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino(const FwdGeom g, const Wino
                 // next position's weights: (gi, 1) after (gi, 0), (gi + 1, 0) after (gi, 1); the chunk's last step
                 // re-reads its own block (harmless)
                 const int nxt = pp == 0 ? gi * 4 + 1 : (gi < 8 ? gi * 4 + 4 : gi * 4 + 1);
-                if (!(kAblate && (tg.dbg & 4))) {
 #pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        wb[pp ^ 1][e] = *reinterpret_cast<const float4 *>(uc + (size_t)nxt * ustep + e * uq);
-                }
+                for (int e = 0; e < 4; e++)
+                    wb[pp ^ 1][e] = *reinterpret_cast<const float4 *>(uc + (size_t)nxt * ustep + e * uq);
                 // (vv is double-buffered over pp: rewriting an operand register right behind the MFMA that reads it stalls)
                 if (ph == 0) {  // wave-uniform: p0 = d0 - d2, p1 = d1 + d2
 #pragma unroll
@@ -217,15 +210,13 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino(const FwdGeom g, const Wino
                         vv[pp][e] = pp == 0 ? make_float4(s1[e].x - s0[e].x, s1[e].y - s0[e].y, s1[e].z - s0[e].z, s1[e].w - s0[e].w)
                                         : make_float4(s0[e].x - s2[e].x, s0[e].y - s2[e].y, s0[e].z - s2[e].z, s0[e].w - s2[e].w);
                 }
-                if (!(kAblate && (tg.dbg & 2))) {
 #pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const float4 bq = wb[pp][e];
-                        acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[pp][e].x, bq.x, acc[pp], 0, 0, 0);
-                        acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[pp][e].y, bq.y, acc[pp], 0, 0, 0);
-                        acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[pp][e].z, bq.z, acc[pp], 0, 0, 0);
-                        acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[pp][e].w, bq.w, acc[pp], 0, 0, 0);
-                    }
+                for (int e = 0; e < 4; e++) {
+                    const float4 bq = wb[pp][e];
+                    acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[pp][e].x, bq.x, acc[pp], 0, 0, 0);
+                    acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[pp][e].y, bq.y, acc[pp], 0, 0, 0);
+                    acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[pp][e].z, bq.z, acc[pp], 0, 0, 0);
+                    acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[pp][e].w, bq.w, acc[pp], 0, 0, 0);
                 }
             }
         }
@@ -435,24 +426,9 @@ __device__ inline float4 f4_axpy(float s, const float4 b, const float4 a) {  // 
 __device__ inline float4 f4_sub(const float4 a, const float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ inline float4 f4_add(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
-#ifndef MVD_W2B
-#define MVD_W2B 12
-#endif
-constexpr int W2B = MVD_W2B;  // staging loads in flight per thread before the LDS stores
+constexpr int W2B = 12;  // staging loads in flight per thread before the LDS stores
 constexpr int W2EH = 6, W2EW = 10, W2EHW = 60;  // halo of the 4 x 4 x 8 tile: 6 x 6 x 10 slots
 
-#ifndef MVD_WINO_DBG
-#define MVD_WINO_DBG 0
-#endif
-#if (MVD_WINO_DBG & 64)  // diagnostic build only (tools/stamps_wino.py): s_memtime stamps of one wave per chunk
-__device__ long long g_wino_stamps[64 * 8];
-extern "C" int mvd_debug_wino_stamps(long long *host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_wino_stamps), sizeof(long long) * 64 * 8) == hipSuccess ? 0 : 1;
-}
-#define MVD_WS(K) { if (stamp_on && nst < 60) g_wino_stamps[nst * 8 + (K)] = __builtin_amdgcn_s_memtime(); }
-#else
-#define MVD_WS(K)
-#endif
 __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const WinoTile tg, const float *__restrict__ a1,
                                                       const float *__restrict__ a2, const float *__restrict__ u,
                                                       const float *__restrict__ bias, float *__restrict__ y1,
@@ -515,12 +491,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[b][r] = 0.f;
 
-#if (MVD_WINO_DBG & 64)
-    const bool stamp_on = item == 300 && wave == 0 && lane == 0;
-    int nst = 0;
-#endif
     for (int cc = 0; cc < nch; cc++) {
-        MVD_WS(0)
         const int c0 = cc * 32;
         const float *src;
         int Cs, cofs;
@@ -534,9 +505,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
 #pragma unroll
         for (int b = 0; b < 4; b++)
             wb[0][b] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(uc + b * uq) + ulane);
-        MVD_WS(1)
         __syncthreads();  // every wave is done with the previous chunk's halo
-        MVD_WS(2)
         {
             // byte offsets inside a (n, z) plane; only used when okA / okB (host checks Hi * Wi * Cs * 4 < 2^31)
             const unsigned offA = (unsigned)((ihA * g.Wi + iw) * Cs + cofs + part * 4) << 2;
@@ -548,7 +517,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
                 for (int q = 0; q < W2B; q++) {
                     const int pq = base + q, id = iz0 + (pq >> 1);  // plane: wave-uniform
                     const float *plane = src + ((size_t)n * g.Di + id) * g.Hi * g.Wi * Cs;
-                    const bool ok = ((pq & 1) ? okB : okA) && id >= 0 && id < g.Di && !(kAblate && (tg.dbg & 1));
+                    const bool ok = ((pq & 1) ? okB : okA) && id >= 0 && id < g.Di;
                     v[q] = v4f{0.f, 0.f, 0.f, 0.f};
                     if (ok) {
                         unsigned o = (pq & 1) ? offB : offA;
@@ -563,9 +532,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
                 }
             }
         }
-        MVD_WS(3)
         __syncthreads();
-        MVD_WS(4)
         // 12 steps (plane gz, channel quarter e).  The patch of step s + 1 is read from LDS before the MFMAs of step s
         // are issued, so its latency hides behind them: the P[ra] rows go to a second register set (parity e & 1), the
         // P[rb] rows back into the registers the transform of step s has just released.
@@ -582,17 +549,15 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
             for (int e = 0; e < 4; e++) {
                 {   // next step's weights: (gz, e + 1), (gz + 1, 0); the chunk's last step re-reads its own
                     const int nxt = (gz == 2 && e == 3) ? gz * 16 + e : (e == 3 ? (gz + 1) * 16 : gz * 16 + e + 1);
-                    if (!(kAblate && (tg.dbg & 4))) {
-                        const float *un = uc + (size_t)nxt * ustep;  // wave-uniform
-                        // opaque 32-bit copy: the zero-extension stays in this block, so the loads select the
-                        // scalar-base + 32-bit-offset form (no 64-bit VALU add per load)
-                        unsigned ul = ulane;
-                        asm("" : "+v"(ul));
+                    const float *un = uc + (size_t)nxt * ustep;  // wave-uniform
+                    // opaque 32-bit copy: the zero-extension stays in this block, so the loads select the
+                    // scalar-base + 32-bit-offset form (no 64-bit VALU add per load)
+                    unsigned ul = ulane;
+                    asm("" : "+v"(ul));
 #pragma unroll
-                        for (int b = 0; b < 4; b++)
-                            wb[(e + 1) & 1][b] =
-                                *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(un + b * uq) + ul);
-                    }
+                    for (int b = 0; b < 4; b++)
+                        wb[(e + 1) & 1][b] =
+                            *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(un + b * uq) + ul);
                 }
                 // next step's patch (the last step of the chunk reads plane 3 = a valid, unused halo plane)
                 const int pn = (e == 3) ? po + W2EHW * (WXS / 4) : po + e + 1;
@@ -621,10 +586,6 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
                 for (int b = 0; b < 4; b++) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vh[b].y, wb[e & 1][b].w, acc[b], 0, 0, 0);
             }
         }
-        MVD_WS(5)
-#if (MVD_WINO_DBG & 64)
-        nst++;
-#endif
     }
     // the bias, settled before the first store (common.h): the stores of the tile then pipeline instead of running as
     // sixteen serialised write round trips
@@ -636,9 +597,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
         t0[r] = (acc[0][r] + acc[1][r]) + acc[2][r];
         t1[r] = (acc[1][r] - acc[2][r]) - acc[3][r];
     }
-    MVD_WS(0)
     __syncthreads();  // all MFMA operand reads of the halo are done
-    MVD_WS(1)
     {
         float *xo = Xs + (size_t)wave * 2048 + lane;
 #pragma unroll
@@ -647,9 +606,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
             xo[1024 + r * 64] = t1[r];
         }
     }
-    MVD_WS(2)
     __syncthreads();
-    MVD_WS(3)
     // wave (yr, yc) = (wave >> 1, wave & 1) finishes output voxel (yr, yc) of each quad from column tile t_yc of
     // position rows {0,1,2} (yr = 0: sum) or {1,2,3} (yr = 1: t[1] - t[2] - t[3]).  Accumulator row r of lane half h is
     // quad q = (r & 3) + 8 * (r >> 2) + 4 * h = (plane r & 3, column 2 * ((r >> 2) & 1) + h, quad row r >> 3): plane,
@@ -678,7 +635,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
             const int od = od0 + (r & 3), oh = oh0 + 2 * (r >> 3) + yr;   // wave-uniform
             const int owu = ow0 + yc + 4 * ((r >> 2) & 1);                // wave-uniform part of ow
             const size_t uo = ((((size_t)n * g.Dy + od) * g.Hy + oh) * g.Wy + owu) * Ks;
-            if (od < g.Do && oh < g.Ho && (((r >> 2) & 1) ? okw1 : okw0) && !(kAblate && (tg.dbg & 8) && val != 12345.f)) {
+            if (od < g.Do && oh < g.Ho && (((r >> 2) & 1) ? okw1 : okw0)) {
                 ylane[uo] = val;
                 ssum += val;
                 ssq += val * val;
@@ -699,7 +656,6 @@ __global__ __launch_bounds__(256, 3) void k_fwd_wino2(const FwdGeom g, const Win
             }
         }
     }
-    MVD_WS(6)
     if (stats != nullptr) {  // block-uniform
         // sum x, sum x^2 over the tile's (up to 128) voxels per output channel, in a fixed order: lane halves, then waves
         ssum += __shfl_xor(ssum, 32, 64);
@@ -745,9 +701,6 @@ int fwd_wino(const FwdGeom &g, const float *a1, const float *a2, const float *u,
     if (!plain && !mirrored) return -1;
     WinoTile tg;
     memset(&tg, 0, sizeof(tg));
-    static int dbg = -1;
-    if (dbg < 0) dbg = getenv("MVD_WINO_DBG") ? atoi(getenv("MVD_WINO_DBG")) : 0;
-    tg.dbg = dbg;
     tg.EH = 6; tg.EW = 10; tg.nslots = 360;
     auto magic = [](int d, int nmax) -> int {
         int m = (1 << 16) / d + 1;

@@ -166,7 +166,7 @@ def test_cfg2_conv_bf16_exact_integer_data(name):
     """The bf16 engines (configs[3], [4]) at the real cfg-2 layer shapes, batch 2, on small-integer data: the operands are
     exact in bf16, every product and fp32 partial sum is an exact integer, so y / dX must equal torch's exact fp32 result
     rounded once to bf16 (round-to-nearest-even), and the fp32 weight / bias gradients must be exact -- bit for bit.
-    Covers k_fwd16q (32 -> 32 at 128^3), k_fwd16 in all its tile variants incl. the split-reduce path, k_wgrad16."""
+    Covers k_fwd16y / k_fwd16z (32 -> 32 at 128^3), k_fwd16 in all its tile variants incl. the split-reduce path, k_wgrad16."""
     from multimodal_mvd_seg_amd import ops
     C1, C2, K, sp, st = CONVS[name]
     g = torch.Generator().manual_seed(sum(name.encode()) + 1)

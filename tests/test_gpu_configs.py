@@ -3,7 +3,7 @@
 * configs[0] -- nnUNetTrainer 3d_fullres, ONE modality, 64^3 patch, batch 2, five stages (the reference's own CPU-runnable
   case): C_in = 1 takes the narrow-input engines that the 4-modality tests never reach.
 * configs[3] -- mutual-distillation dual branch + soft-clDice topology term in bf16 mixed precision at real channel
-  widths (32 ... 256), so the step runs on the bf16 MFMA engines (k_fwd16 / k_fwd16p / k_wgrad16), not on the tiny
+  widths (32 ... 256), so the step runs on the bf16 MFMA engines (k_fwd16 / k_fwd16y / k_wgrad16), not on the tiny
   8/16/32-channel fp32 fixture of round 1.
 """
 import copy

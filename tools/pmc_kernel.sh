@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes (each in its own rocprofv3 run, --kernel-trace only) over one layer / pass of tools/bench_conv.py.
-#   LAYER=dec5.conv1 WHAT=fwd DTYPE=bf16 TAG=fwd16q tools/pmc_kernel.sh      (run through gpurun from the repo root)
+#   LAYER=dec5.conv1 WHAT=fwd DTYPE=bf16 TAG=fwd16z tools/pmc_kernel.sh      (run from the repo root)
 # Output: gpurun_out/pmc_$TAG/p*/ ... counter_collection.csv + kernel_trace.csv; summarise with tools/pmc_summary.py
 set -e
 export TMPDIR=/tmp PYTHONPATH=$PWD
