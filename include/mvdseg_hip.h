@@ -119,6 +119,15 @@ int mvd_conv3d_fwd_wino3(const float *x1, int C1, const float *x2, int C2, const
 int mvd_conv3d_fwd_wino3_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *vf,
                                const float *bias, float *y, float *stats, int *stats_done, int N, int D, int H, int W,
                                int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream);
+/* The same epilogue in the direct fp32 engines (the narrow-input / chunked kernel k_fwd_mfma and the stride-2 kernel
+ * k_fwd32s; a tile is one wave's plane of the workgroup tile, at most 64 values).  mvd_conv3d_fwd_stats_tiles: tiles per
+ * sample of the kernel that would run for this conv, 0 when it has no epilogue; mvd_conv3d_fwd_stats: mvd_conv3d_fwd with
+ * stats [N][stats_tiles][K][2]; *stats_done = 1 when they were written (a conv that would split its reduce channels over
+ * workgroups runs unsplit then: ask only where a statistics pass would run otherwise). */
+long mvd_conv3d_fwd_stats_tiles(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]);
+int mvd_conv3d_fwd_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *bias, float *y,
+                         float *stats, long stats_tiles, int *stats_done, int N, int D, int H, int W, int K,
+                         const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream);
 int mvd_conv3d_dgrad_wino3(const float *dy, const float *wb, const float *vb, float *dx1, int C1, float *dx2, int C2,
                            int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
                            size_t ws_bytes, void *stream);
@@ -131,6 +140,12 @@ int mvd_set_wgrad_wino3_min_items(long n);
 int mvd_conv_wgrad_wino3_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3],
                                     const int stride[3]);
 long mvd_wgrad_wino3_launches(void);
+/* The fp32 weight gradients of the narrow-input layer (k_wgrad_smallc: an idle GEMM row with a ones operand) and of the
+ * transposed convs (k_wgrad_mfma: plain adds on the dy fragments each wave stages) also produce the bias gradient, so no
+ * column-sum pass over dy runs for them (the workspace must hold the extra rows, mvd_conv*_wgrad_workspace_bytes; the
+ * column-sum pass runs otherwise).  MVD_WGRAD_BIAS_FOLD=0 / mvd_set_wgrad_bias_fold(0) restore the separate pass (< 0:
+ * back to the environment); dw does not depend on it. */
+int mvd_set_wgrad_bias_fold(int on);
 size_t mvd_conv3d_wgrad_workspace_bytes(int C, int K, int T, int N, int Do, int Ho, int Wo);
 int mvd_conv3d_wgrad(const float *x1, int C1, const float *x2, int C2, const float *dy, float *dw, float *dbias,
                      int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
@@ -300,6 +315,26 @@ int mvd_instnorm_lrelu_fwd_prestats(const float *x, const float *tile_stats, lon
 int mvd_instnorm_lrelu_bwd(const float *x, const float *dy, const float *gamma, const float *beta,
                            const float *mean, const float *rstd, float *dx, float *dgamma, float *dbeta, int N,
                            long V, int C, float slope, void *ws, size_t ws_bytes, void *stream);
+/* Small volumes run ONE launch per direction (a workgroup keeps 16 channels of a sample in registers: x is read once,
+ * fp64 sums in a fixed order, the arithmetic of the three-launch form) when C % 4 == 0, V <= 1024 and voxels x channels
+ * per sample is at most MVD_IN_SMALL_MAX (default 327680: measured at batch 2, profiles/r11_instnorm_small.txt; the backward
+ * kernel walks the batch serially, so for N > 2 its limit is 2 / N of that); MVD_IN_SMALL=0 keeps three launches.  mvd_instnorm_single_launch: 1 when the fp32 entry points above would take it -- a producing conv then
+ * need not emit tile statistics; mvd_instnorm_single_launches: such launches since the library was loaded. */
+int mvd_instnorm_single_launch(long V, int C);
+/* launches of the stand-alone forward statistics pass over x (k_in_stats) since the library was loaded */
+long mvd_instnorm_stats_pass_launches(void);
+long mvd_instnorm_single_launches(void);
+/* A/B and test aid: the limit in voxels x channels per sample (0: never; < 0: back to MVD_IN_SMALL_MAX / the default) */
+int mvd_set_instnorm_small_max(long max_elems);
+/* The same backward for the block whose only consumer is the fused seg head (mvd_seghead_*_fused), from the head's planar
+ * logit gradient dlogits [N,K,V] and weight w [K,C]: dy[v][c] = sum_k dlogits[k][v] * w[k][c] is formed inside the two
+ * passes (the value mvd_seghead_bwd_fused stores as dx, bit for bit), so that tensor is neither written nor read back --
+ * call mvd_seghead_bwd_fused with dx = NULL for dw / dbias.  fp32, C % 4 == 0, K <= 8.  Always the three-launch kernels:
+ * results bit-identical to mvd_seghead_bwd_fused + mvd_instnorm_lrelu_bwd in its three-launch form (a volume small enough
+ * for that entry's single launch differs from it in the order of the fp64 sums). */
+int mvd_instnorm_lrelu_bwd_head(const float *x, const float *dlogits, const float *w, int K, const float *gamma,
+                                const float *beta, const float *mean, const float *rstd, float *dx, float *dgamma,
+                                float *dbeta, int N, long V, int C, float slope, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1x1x1 segmentation head (K5): x NDHWC [N,V,C] -> logits planar [N,K,V].  Replaces decoder.seg_layers[s]

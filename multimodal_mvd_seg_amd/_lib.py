@@ -41,6 +41,9 @@ SIGNATURES = {
     "mvd_conv3d_fwd_wino": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
                                     c_size_t, _P]),
     "mvd_conv_stats_tiles": (c_size_t, [c_int, c_int, c_int]),
+    "mvd_conv3d_fwd_stats_tiles": (c_long, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
+    "mvd_conv3d_fwd_stats": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_long, _P, c_int, c_int, c_int, c_int, c_int, _I3,
+                                     _I3, _P, c_size_t, _P]),
     "mvd_conv3d_fwd_wino_stats": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
                                           _I3, _I3, _P, c_size_t, _P]),
     "mvd_conv3d_dgrad_wino": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
@@ -59,6 +62,7 @@ SIGNATURES = {
     "mvd_set_wgrad_wino3_min_items": (c_int, [c_long]),
     "mvd_conv_wgrad_wino3_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
     "mvd_wgrad_wino3_launches": (c_long, []),
+    "mvd_set_wgrad_bias_fold": (c_int, [c_int]),
     "mvd_conv3d_wgrad_bf16": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
                                       c_size_t, _P]),
     "mvd_convT3d_wgrad_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _P, c_size_t,
@@ -110,6 +114,12 @@ SIGNATURES = {
     "mvd_instnorm_lrelu_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_float, c_float, _P, c_size_t, _P]),
     "mvd_instnorm_lrelu_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_float, _P, c_size_t,
                                        _P]),
+    "mvd_instnorm_single_launch": (c_int, [c_long, c_int]),
+    "mvd_instnorm_single_launches": (c_long, []),
+    "mvd_instnorm_stats_pass_launches": (c_long, []),
+    "mvd_set_instnorm_small_max": (c_int, [c_long]),
+    "mvd_instnorm_lrelu_bwd_head": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_float, _P,
+                                            c_size_t, _P]),
     "mvd_seghead_fwd": (c_int, [_P, _P, _P, _P, c_int, c_long, c_int, c_int, _P]),
     "mvd_seghead_bwd_workspace_bytes": (c_size_t, [c_int, c_long, c_int, c_int]),
     "mvd_seghead_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_int, c_int, _P, c_size_t, _P]),

@@ -315,8 +315,16 @@ static void conv_fwd_geom(FwdGeom &g, int N, int D, int H, int W, int C1, int C2
 // the direct engines otherwise)
 static int run_fwd(const FwdGeom &g, const float *a1, const float *a2, const float *w, const float *bias, float *y1,
                    float *y2, void *ws, size_t ws_bytes, hipStream_t s, const float *u = nullptr, float *stats = nullptr,
-                   int *stats_done = nullptr, bool u3d = false) {
+                   int *stats_done = nullptr, bool u3d = false, long direct_tiles = 0) {
     if (stats_done) *stats_done = 0;
+    if (direct_tiles > 0) {  // statistics from the direct engine's epilogue ([N][direct_tiles][K][2], fwd_mfma)
+        if (g_engine_mode == 0) {
+            int r = fwd_mfma(g, a1, a2, w, bias, y1, y2, ws, ws_bytes, s, stats, direct_tiles, stats_done);
+            if (r >= 0) return r;
+            if (stats_done) *stats_done = 0;
+        }
+        return fwd_scalar(g, a1, a2, w, bias, y1, y2, s);
+    }
     if (u3d) {
         if (g_engine_mode == 0 && u && !g_wino_off && wino3_enabled() &&
             wino3_items(g.Do, g.Ho, g.Wo, g.K1 + g.K2) >= g_wino3_min_items) {
@@ -402,13 +410,13 @@ size_t mvd_conv_fwd_workspace_bytes(int N, long out_voxels, int K) { return fwd_
 static int conv3d_fwd_impl(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *uf,
                            const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
                            const int stride[3], void *ws, size_t ws_bytes, void *stream, float *stats = nullptr,
-                           int *stats_done = nullptr, bool u3d = false) {
+                           int *stats_done = nullptr, bool u3d = false, long direct_tiles = 0) {
     MVD_REQUIRE(x1 && wf && y && C1 > 0 && C2 >= 0 && (C2 == 0 || x2), "conv3d_fwd: null pointer / bad channels");
     MVD_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && K > 0, "conv3d_fwd: bad shape");
     if (check_ks(ksize, stride, "conv3d_fwd")) return 2;
     FwdGeom g;
     conv_fwd_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
-    return run_fwd(g, x1, x2, wf, bias, y, nullptr, ws, ws_bytes, as_stream(stream), uf, stats, stats_done, u3d);
+    return run_fwd(g, x1, x2, wf, bias, y, nullptr, ws, ws_bytes, as_stream(stream), uf, stats, stats_done, u3d, direct_tiles);
 }
 
 int mvd_conv3d_fwd(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *bias, float *y, int N,
@@ -447,6 +455,30 @@ int mvd_conv3d_fwd_wino_stats(const float *x1, int C1, const float *x2, int C2, 
     MVD_REQUIRE(stats_done, "conv3d_fwd_wino_stats: stats_done is required");
     return conv3d_fwd_impl(x1, C1, x2, C2, wf, uf, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, stats,
                            stats_done);
+}
+
+/* The direct fp32 engines' statistics epilogue (the narrow-input / chunked kernel and the stride-2 kernel): tiles per sample
+ * of the kernel that would run for this conv, 0 when it has none (Winograd layers use mvd_conv3d_fwd_wino*_stats) */
+long mvd_conv3d_fwd_stats_tiles(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
+    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || K <= 0 || !ksize || !stride || g_engine_mode != 0) return 0;
+    for (int a = 0; a < 3; a++)
+        if (!(ksize[a] == 1 || ksize[a] == 3) || !(stride[a] == 1 || stride[a] == 2)) return 0;
+    FwdGeom g;
+    conv_fwd_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
+    long tiles = 0;
+    // (alignment of the tensors is checked at the call; the pointers here only have to be non-null and aligned)
+    const float *al = reinterpret_cast<const float *>(uintptr_t(64));
+    if (fwd_mfma(g, al, C2 ? al : nullptr, al, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, &tiles) != 0)
+        return 0;
+    return tiles;
+}
+
+int mvd_conv3d_fwd_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *bias, float *y,
+                         float *stats, long stats_tiles, int *stats_done, int N, int D, int H, int W, int K,
+                         const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {
+    MVD_REQUIRE(stats && stats_done && stats_tiles > 0, "conv3d_fwd_stats: stats, stats_tiles and stats_done are required");
+    return conv3d_fwd_impl(x1, C1, x2, C2, wf, nullptr, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, stats,
+                           stats_done, false, stats_tiles);
 }
 
 int mvd_pack_weights_batch(int n, const float *const *w, float *const *wf, float *const *wb, float *const *uf,
@@ -665,6 +697,11 @@ int mvd_conv_wgrad_wino3_applicable(int N, int D, int H, int W, int C1, int C2, 
 
 long mvd_wgrad_wino3_launches(void) { return wgrad_wino3_launches(); }
 
+int mvd_set_wgrad_bias_fold(int on) {
+    set_wgrad_bias_fold(on);
+    return 0;
+}
+
 int mvd_conv3d_wgrad(const float *x1, int C1, const float *x2, int C2, const float *dy, float *dw, float *dbias, int N,
                      int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes,
                      void *stream) {
@@ -785,11 +822,11 @@ int mvd_convT3d_wgrad(const float *x, const float *dy, float *dw, float *dbias, 
     convT_wgrad_geom(g, N, D, H, W, C, K, stride);
     MVD_REQUIRE(ws_bytes >= mvd_convT3d_wgrad_workspace_bytes(C, K, g.T, N, D, H, W), "convT3d_wgrad: workspace too small");
     hipStream_t s = as_stream(stream);
-    if (dbias) {
-        int r = colsum(dy, dbias, (long)N * g.Db * g.Hb * g.Wb, K, ws, s);
-        if (r) return r;
-    }
-    return run_wgrad(g, x, nullptr, dy, dw, ws, ws_bytes, s);
+    int dbias_done = 0;  // the MFMA kernel sums the dy fragments it stages where it can (wgrad_mfma)
+    int r = run_wgrad(g, x, nullptr, dy, dw, ws, ws_bytes, s, dbias, &dbias_done);
+    if (r) return r;
+    if (dbias && !dbias_done) return colsum(dy, dbias, (long)N * g.Db * g.Hb * g.Wb, K, ws, s);  // ws is free again
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ bf16 twins

@@ -64,8 +64,12 @@ int fwd_scalar(const FwdGeom &g, const float *a1, const float *a2, const float *
                float *y2, hipStream_t s);
 // ws/ws_bytes: optional scratch for the split-reduce path of skinny problems (few tiles, many reduce channels)
 size_t fwd_mfma_ws(int N, long out_vox, int K);
+// stats (optional, [N][stats_tiles][K][2]) / stats_done: the InstanceNorm statistics epilogue of the chunked and the stride-2
+// kernels (per-wave tiles of at most 64 values; plain forward convs); it runs when stats_tiles is the kernel's own count.
+// plan (optional): nothing is launched, *plan = that count for the kernel that would run (0: no epilogue)
 int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w, const float *bias, float *y1, float *y2,
-             void *ws, size_t ws_bytes, hipStream_t s);
+             void *ws, size_t ws_bytes, hipStream_t s, float *stats = nullptr, long stats_tiles = 0, int *stats_done = nullptr,
+             long *plan = nullptr);
 size_t wgrad_scalar_ws(const WgradGeom &g);
 int wgrad_scalar(const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws,
                  size_t ws_bytes, hipStream_t s);
@@ -122,6 +126,7 @@ bool wgrad_wino3_selected(const WgradGeom &g);
 size_t wgrad_wino3_ws(int nsplit, int C, int K);
 int wgrad_wino3_enabled();  // MVD_WGRAD_WINO3: 0 off, 1 (default) on
 void set_wgrad_wino3_min_items(long n);
+void set_wgrad_bias_fold(int on);  // bias gradient inside the narrow-input / transposed-conv weight gradients (< 0: environment)
 long wgrad_wino3_launches();  // launches of k_wgrad_wino3 since the library was loaded
 // dbias[k] = fp64 sum of the rows pbias[0..nrows)[k] in a fixed order (k_dbias_reduce, conv_mfma.hip)
 int dbias_reduce(const float *pbias, float *dbias, int K, int nrows, hipStream_t s);

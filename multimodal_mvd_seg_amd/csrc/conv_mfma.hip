@@ -81,7 +81,8 @@ template <int CK, int NT, int MT, bool L32>
 __global__ __launch_bounds__(256, 2) void k_fwd_mfma(const FwdGeom g, const FwdTile tg, const float *__restrict__ a1,
                                                      const float *__restrict__ a2, const float *__restrict__ w,
                                                      const float *__restrict__ bias, float *__restrict__ y1,
-                                                     float *__restrict__ y2, const int S, float *__restrict__ part) {
+                                                     float *__restrict__ y2, const int S, float *__restrict__ part,
+                                                     float *__restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int HH = CK / 2;
     constexpr int KT = 32 * NT;
@@ -230,6 +231,35 @@ __global__ __launch_bounds__(256, 2) void k_fwd_mfma(const FwdGeom g, const FwdT
 
     // epilogue: C/D layout col = lane&31 (channel), row = (r&3) + 8*(r>>2) + 4*(lane>>5) (voxel of the 32-row M tile)
     const int od = od0 + wave;
+    // InstanceNorm statistics epilogue (stats, optional; host: S == 1): a "tile" is one wave's part of the workgroup tile, the
+    // 4 MT x 8 voxels of plane od -- (sum, sum of squares) of the values stored below, per lane over its rows in a fixed
+    // order, then the two lane halves; planes past the volume write zeros.  Layout [n][tile][K][2] (k_in_tiles_reduce).
+    if (stats) {
+        const size_t tl = ((size_t)(td_ * 4 + wave) * tg.nth + th_) * tg.ntw + tw_;
+        float *so = stats + (((size_t)n * tg.ntd * 4 * tg.nth * tg.ntw + tl) * tg.K) * 2;
+#pragma unroll
+        for (int q_ = 0; q_ < NT; q_++) {
+            const int k = kb * KT + q_ * 32 + i;
+            const float bv = settled(bias ? bias[k] : 0.f);
+            float sa = 0.f, sq = 0.f;
+            if (od < g.Do) {
+#pragma unroll
+                for (int m = 0; m < MT; m++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        const int oh = oh0 + 4 * m + (r >> 2), ow = ow0 + 4 * h + (r & 3);
+                        if (oh < g.Ho && ow < g.Wo) {
+                            const float val = acc[m][q_][r] + bv;
+                            sa += val;
+                            sq += val * val;
+                        }
+                    }
+            }
+            sa += __shfl_xor(sa, 32);
+            sq += __shfl_xor(sq, 32);
+            if (h == 0) *reinterpret_cast<float2 *>(so + (size_t)k * 2) = make_float2(sa, sq);
+        }
+    }
     if (od >= g.Do) return;
 #pragma unroll
     for (int m = 0; m < MT; m++)
@@ -502,7 +532,7 @@ constexpr int SXB = 6;   // staging batch of the generic path (loads in flight p
 __global__ __launch_bounds__(512, 1) void k_fwd32s(const FwdGeom g, const Fwd32Tile tg, const float *__restrict__ a1,
                                                    const float *__restrict__ a2, const float *__restrict__ w,
                                                    const float *__restrict__ bias, float *__restrict__ y1,
-                                                   float *__restrict__ y2) {
+                                                   float *__restrict__ y2, float *__restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) float Xs[];
     constexpr int XS = 36;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -674,8 +704,30 @@ __global__ __launch_bounds__(512, 1) void k_fwd32s(const FwdGeom g, const Fwd32T
         for (int r = 0; r < 16; r++) acc[r] += xi[r * 64];
     }
     const int od = od0 + dl;
-    if (od >= g.Do) return;
     const float bv = settled(bias ? bias[kcol] : 0.f);
+    // InstanceNorm statistics epilogue (stats, optional), after the two tap halves are added: a "tile" is one wave's plane of
+    // the workgroup tile (4 x 8 voxels of plane od), see k_fwd_mfma
+    if (stats) {
+        const size_t tl = ((size_t)(td_ * 2 + dl) * tg.nth + th_) * tg.ntw + tw_;
+        float *so = stats + (((size_t)n * tg.ntd * 2 * tg.nth * tg.ntw + tl) * tg.K) * 2;
+        float sa = 0.f, sq = 0.f;
+        if (od < g.Do) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int oh = oh0 + (row >> 3), ow = ow0 + (row & 7);
+                if (oh < g.Ho && ow < g.Wo) {
+                    const float val = acc[r] + bv;
+                    sa += val;
+                    sq += val * val;
+                }
+            }
+        }
+        sa += __shfl_xor(sa, 32);
+        sq += __shfl_xor(sq, 32);
+        if (h == 0) *reinterpret_cast<float2 *>(so + (size_t)kcol * 2) = make_float2(sa, sq);
+    }
+    if (od >= g.Do) return;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -848,8 +900,10 @@ int dgrad32s(int N, int D, int H, int W, int C, int K, int Do, int Ho, int Wo, c
 }
 
 static int num_cus();
+// plan (optional): no launch, *plan = statistics tiles per sample of the epilogue; stats (optional, [N][tiles][K][2]) with
+// stats_tiles = the caller's tile count: the epilogue runs when the counts agree, *stats_done = 1 then
 static int launch_fwd32s(const FwdGeom &g, const float *a1, const float *a2, const float *w, const float *bias, float *y1,
-                         float *y2, hipStream_t s) {
+                         float *y2, hipStream_t s, float *stats, long stats_tiles, int *stats_done, long *plan) {
     const int K = g.K1 + g.K2;
     Fwd32Tile tg;
     memset(&tg, 0, sizeof(tg));
@@ -882,6 +936,12 @@ static int launch_fwd32s(const FwdGeom &g, const float *a1, const float *a2, con
     const long nitems = (long)g.N * tg.ntd * tg.nth * tg.ntw * tg.nkb;
     if (nitems > (1L << 30)) return -1;
     tg.nitems = (int)nitems;
+    const long my_tiles = (long)tg.ntd * 2 * tg.nth * tg.ntw;
+    if (plan) {
+        *plan = my_tiles;
+        return 0;
+    }
+    float *st = (stats && stats_done && stats_tiles == my_tiles) ? stats : nullptr;
     const size_t lds = (size_t)tg.nslots * 36 * sizeof(float);
     static PerDeviceFlag cfgd;
     if (!cfgd()) {
@@ -893,8 +953,10 @@ static int launch_fwd32s(const FwdGeom &g, const float *a1, const float *a2, con
         cfgd() = true;
     }
     const unsigned grid = (unsigned)(((nitems + 7) / 8) * 8);
-    hipLaunchKernelGGL(k_fwd32s, dim3(grid), dim3(512), lds, s, g, tg, a1, a2, w, bias, y1, y2);
-    return check_launch("conv fwd (stride 2, CK=32)");
+    hipLaunchKernelGGL(k_fwd32s, dim3(grid), dim3(512), lds, s, g, tg, a1, a2, w, bias, y1, y2, st);
+    if (check_launch("conv fwd (stride 2, CK=32)")) return 1;
+    if (st) *stats_done = 1;
+    return 0;
 }
 
 static int num_cus() {
@@ -961,7 +1023,14 @@ static int launch_fwd32(const FwdGeom &g, Fwd32Tile &tg, const float *a1, const 
 
 template <int CK, int NT, int MT, bool L32>
 static int launch_fwd(const FwdGeom &g, FwdTile &tg, size_t lds, const float *a1, const float *a2, const float *w,
-                      const float *bias, float *y1, float *y2, void *ws, size_t ws_bytes, hipStream_t s) {
+                      const float *bias, float *y1, float *y2, void *ws, size_t ws_bytes, hipStream_t s, float *stats,
+                      long stats_tiles, int *stats_done, long *plan) {
+    const long my_tiles = (long)tg.ntd * 4 * tg.nth * tg.ntw;  // (plan / stats: see launch_fwd32s)
+    if (plan) {
+        *plan = my_tiles;
+        return 0;
+    }
+    float *st = (stats && stats_done && stats_tiles == my_tiles) ? stats : nullptr;
     auto kern = k_fwd_mfma<CK, NT, MT, L32>;
     static size_t configured = 0;
     if (lds > configured) {
@@ -977,17 +1046,27 @@ static int launch_fwd(const FwdGeom &g, FwdTile &tg, size_t lds, const float *a1
     const long tiles = (long)tg.ntd * tg.nth * tg.ntw;
     const size_t out_elems = (size_t)g.N * g.Do * g.Ho * g.Wo * K;
     // split the reduce chunks when the launch cannot fill the chip (8^3 / 4^3 stages with 320-640 channels)
-    const int S = split_for(ws, ws_bytes, tiles * nkb * g.N, (g.C1 + g.C2) / CK, out_elems, nkb);
+    // (the statistics epilogue needs the finished sums in one workgroup: a caller that asks for it gets no channel split --
+    // ops asks only where a statistics pass over the output would run otherwise)
+    const int S = st ? 1 : split_for(ws, ws_bytes, tiles * nkb * g.N, (g.C1 + g.C2) / CK, out_elems, nkb);
     dim3 grid((unsigned)tiles, nkb * S, g.N);
     float *part = reinterpret_cast<float *>(ws);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, g, tg, a1, a2, w, bias, y1, y2, S, part);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, g, tg, a1, a2, w, bias, y1, y2, S, part, st);
     if (check_launch("conv fwd (mfma)")) return 1;
     if (S > 1) return run_split_reduce(g, part, bias, y1, y2, S, out_elems, s);
+    if (st) *stats_done = 1;
     return 0;
 }
 
 int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w, const float *bias, float *y1, float *y2,
-             void *ws, size_t ws_bytes, hipStream_t s) {
+             void *ws, size_t ws_bytes, hipStream_t s, float *stats, long stats_tiles, int *stats_done, long *plan) {
+    if (plan) *plan = 0;
+    if (stats_done) *stats_done = 0;
+    // the epilogue sums what is stored at the iteration voxel: plain (non-transposed, one output tensor) forward convs only
+    if (g.K2 != 0 || g.so[0] != 1 || g.so[1] != 1 || g.so[2] != 1 || g.oo[0] || g.oo[1] || g.oo[2]) {
+        stats = nullptr;
+        if (plan) return 0;
+    }
     const int C = g.C1 + g.C2, K = g.K1 + g.K2;
     const int LCK = wl_ck(C);  // chunk size of the packed weight layout
     if (LCK == 0 || g.ntaps < 1 || g.ntaps > 27) return -1;
@@ -1039,6 +1118,7 @@ int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w,
             t32.nth = (g.Ho + 3) / 4;
             t32.ntw = (g.Wo + 7) / 8;
             t32.K = K;
+            if (plan) return 0;  // (k_fwd32 has no statistics epilogue: the Winograd kernels serve these layers)
             if (NT == 2) return launch_fwd32<2, 1>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
             return launch_fwd32<1, 2>(g, t32, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
         }
@@ -1048,7 +1128,7 @@ int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w,
         !(dbg & 8)) {
         const long items = (long)g.N * ((g.Do + 1) / 2) * ((g.Ho + 3) / 4) * ((g.Wo + 7) / 8) * (K / 64);
         if (items >= 256) {  // enough workgroups for the chip; the small stages stay on the chunked kernel
-            int r = launch_fwd32s(g, a1, a2, w, bias, y1, y2, s);
+            int r = launch_fwd32s(g, a1, a2, w, bias, y1, y2, s, stats, stats_tiles, stats_done, plan);
             if (r >= 0) return r;
         }
     }
@@ -1086,9 +1166,9 @@ int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w,
         tg.ntw = (g.Wo + 7) / 8;
 #define MVD_FWD_DISPATCH(CKV, L32V)                                                                                      \
     {                                                                                                                    \
-        if (MT == 2 && NT == 2) return launch_fwd<CKV, 2, 2, L32V>(g, tg, lds, a1, a2, w, bias, y1, y2, ws, ws_bytes, s); \
-        if (MT == 2 && NT == 1) return launch_fwd<CKV, 1, 2, L32V>(g, tg, lds, a1, a2, w, bias, y1, y2, ws, ws_bytes, s); \
-        return launch_fwd<CKV, 1, 1, L32V>(g, tg, lds, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);                         \
+        if (MT == 2 && NT == 2) return launch_fwd<CKV, 2, 2, L32V>(g, tg, lds, a1, a2, w, bias, y1, y2, ws, ws_bytes, s, stats, stats_tiles, stats_done, plan); \
+        if (MT == 2 && NT == 1) return launch_fwd<CKV, 1, 2, L32V>(g, tg, lds, a1, a2, w, bias, y1, y2, ws, ws_bytes, s, stats, stats_tiles, stats_done, plan); \
+        return launch_fwd<CKV, 1, 1, L32V>(g, tg, lds, a1, a2, w, bias, y1, y2, ws, ws_bytes, s, stats, stats_tiles, stats_done, plan); \
     }
         if (LCK == 32) MVD_FWD_DISPATCH(8, true)
         else if (CK == 8) MVD_FWD_DISPATCH(8, false)
@@ -1298,13 +1378,19 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_mfma(const WgradGeom g, const 
     };
     // bias gradient (SH == 1: every tap reads the same dy slot): the tap-group-0 wave of the c-block-0 workgroups sees
     // every dy value of its k-block exactly once per (split, group) -- per-lane sums, reduced by k_dbias_reduce
-    const bool dob = SH == 1 && pbias != nullptr && cb == 0 && wave == 0;
+    // SH == 2 (transposed conv, kernel == stride, every tap slot of the four waves in use -- host-checked): the taps read
+    // disjoint dy slots that together cover the dy tile once, so every wave of the c-block-0 workgroups adds its own
+    // fragments; rows [(split, group, lane half, wave)]
+    const bool dob = pbias != nullptr && cb == 0 && (SH == 1 ? wave == 0 : SH == 2);
     float bsum = 0.f;
     auto mfmas = [&](const float (&av)[NAV], const float (&bv)[NBV]) {
 #pragma unroll
         for (int j = 0; j < TPW; j++)
             acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[SH == 2 ? 0 : j], bv[SH == 1 ? 0 : j], acc[j], 0, 0, 0);
         if (SH == 1 && dob) bsum += bv[0];
+        if (SH == 2 && dob)
+#pragma unroll
+            for (int j = 0; j < NBV; j++) bsum += bv[j];
     };
     // scheduling hint for one (reads of the next step | MFMAs of this step) block: one MFMA, then a few of the
     // next step's LDS reads / address VALU ops under its shadow
@@ -1360,6 +1446,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_mfma(const WgradGeom g, const 
         tile = next;
     }
     if (SH == 1 && dob && i < kvalid) pbias[((size_t)(split * 2 + grp) * 2 + h) * K + k0 + i] = bsum;
+    if (SH == 2 && dob && i < kvalid) pbias[(((size_t)(split * 2 + grp) * 2 + h) * 4 + wave) * K + k0 + i] = bsum;
     // partial[split][t][c][k]; D layout: col = lane&31 -> k, row -> c
 #pragma unroll
     for (int j = 0; j < TPW; j++) {
@@ -2063,7 +2150,8 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_wino(const float *__restri
 // 32w..32w+31, one MFMA per voxel pair.  A tile in LDS is [slots][C] (16 B per voxel at C = 4), B tile [128][32 k].
 template <int NAS, int NB>
 __global__ __launch_bounds__(256, 2) void k_wgrad_smallc(const WgradGeom g, const WgTile tg, const float *__restrict__ a1,
-                                                         const float *__restrict__ b, float *__restrict__ partial) {
+                                                         const float *__restrict__ b, float *__restrict__ partial,
+                                                         float *__restrict__ pbias) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *As = lds;                               // NAS*256 float4
     float *Bs = lds + (size_t)NAS * 1024;          // NB*256 float4
@@ -2084,6 +2172,10 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_smallc(const WgradGeom g, cons
     // byte offset added to slot*C*4; the lane half h is the second voxel of the pair (s2 even, TW a power of two >= 2: it
     // only moves wx by one), so it is a per-lane constant here and the step's slot offsets stay wave-uniform
     const int arow = (toffs[rtap] * C + rc) * 4 + h * g.sa[2] * C * 4;
+    // bias gradient (pbias, optional; ntaps * C < 128, host-checked): the first GEMM row past the (tap, channel) pairs is idle
+    // -- its A operand is the constant 1, so that accumulator row collects the column sums of the dy tile (every dy voxel is
+    // in exactly one tile and one k-step; voxels outside the volume are staged as zeros)
+    const bool ones = pbias != nullptr && row == g.ntaps * C;
     const int k0 = kb * 32;
     const int kvalid = (K - k0) < 32 ? (K - k0) : 32;
     const int EAhw = tg.EAh * tg.EAw, EBhw = tg.EBh * tg.EBw;
@@ -2140,6 +2232,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_smallc(const WgradGeom g, cons
         const int sa_ = ((dz * g.sa[0]) * tg.EAh + hy * g.sa[1]) * tg.EAw + wx * g.sa[2];
         const int sb_ = ((dz * g.sb[0]) * tg.EBh + hy * g.sb[1]) * tg.EBw + wx * g.sb[2];
         av = *reinterpret_cast<const float *>(Ab + sa_ * C * 4 + arow);
+        av = ones ? 1.f : av;
         bv = *reinterpret_cast<const float *>(Bb + sb_ * 128 + tb0);
     };
     int tile = split;
@@ -2175,6 +2268,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_smallc(const WgradGeom g, cons
             const int t = rr / C, c = rr - t * C;
             partial[(((size_t)split * g.ntaps + t) * C + c) * K + k0 + i] = acc[r];
         }
+        if (pbias && rr == g.ntaps * C && i < kvalid) pbias[(size_t)split * K + k0 + i] = acc[r];
     }
 }
 
@@ -2645,6 +2739,14 @@ static int wgrad_max_split(const WgradGeom &g, int per_cu = 2) {
     return (int)ns;
 }
 
+// MVD_WGRAD_BIAS_FOLD=0: the narrow-input and transposed-conv weight gradients leave the bias gradient to the column-sum pass
+static int g_wgrad_bias_fold = -1;  // < 0: from the environment at first use
+static bool wgrad_bias_fold() {
+    if (g_wgrad_bias_fold < 0) g_wgrad_bias_fold = getenv("MVD_WGRAD_BIAS_FOLD") ? (atoi(getenv("MVD_WGRAD_BIAS_FOLD")) != 0) : 1;
+    return g_wgrad_bias_fold != 0;
+}
+void set_wgrad_bias_fold(int on) { g_wgrad_bias_fold = on < 0 ? -1 : (on != 0); }
+
 static bool wgrad_mfma_ok(const WgradGeom &g) {
     const int C = g.C1 + g.C2;
     if (g.ntaps < 1 || g.ntaps > 27) return false;
@@ -2656,8 +2758,9 @@ static bool wgrad_mfma_ok(const WgradGeom &g) {
 
 size_t wgrad_mfma_ws(const WgradGeom &g) {
     if (!wgrad_mfma_ok(g)) return 0;
-    // split-K partials + the bias-gradient rows (two lane halves per partial)
-    size_t ws = (size_t)wgrad_max_split(g) * (g.ntaps * (size_t)(g.C1 + g.C2) + 2) * g.K * sizeof(float) + 256;
+    // split-K partials + the bias-gradient rows (two lane halves per partial; per wave as well for transposed convs: 16 rows
+    // per fp32 split = 8 per split counted here)
+    size_t ws = (size_t)wgrad_max_split(g) * (g.ntaps * (size_t)(g.C1 + g.C2) + 8) * g.K * sizeof(float) + 256;
     // the F(2x2x2,3x3x3) kernel: 64 positions at the fp32 split count (one workgroup per CU)
     const int C = g.C1 + g.C2;
     if (g.ntaps == 27 && C % 32 == 0 && g.K % 32 == 0) {
@@ -2820,7 +2923,8 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
             }                                                                                                      \
             cfgd() = true;                                                                                           \
         }                                                                                                          \
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, g, tg, a1, a2, b, partial, (SH) == 1 ? pbias_g : nullptr); \
+        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, g, tg, a1, a2, b, partial,                               \
+                           (SH) == 1 ? pbias_g : (SH) == 2 ? pbias_t : nullptr);                                    \
     }
     bool sameA = true, sameB = true;
     for (int t = 1; t < g.ntaps; t++) {
@@ -2973,11 +3077,24 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
         if ((size_t)ns2 * g.ntaps * C * g.K * sizeof(float) <= ws_bytes) tg.nsplit = (int)ns2;
         auto kern = k_wgrad_smallc<2, 4>;
         const size_t lds2 = (size_t)(2 + 4) * 4096 + 32 * 4;
-        hipLaunchKernelGGL(kern, dim3(tg.nsplit, tg.nkb), dim3(256), lds2, s, g, tg, a1, b, partial);
+        // bias gradient from the idle GEMM row behind the (tap, channel) pairs, one row of K sums per split
+        const size_t need_s = (size_t)tg.nsplit * g.ntaps * C * g.K * sizeof(float);
+        float *pbias_s = nullptr;
+        if (wgrad_bias_fold() && dbias && dbias_done && g.ntaps * C < 128 && g.sb[0] == 1 && g.sb[1] == 1 && g.sb[2] == 1 &&
+            need_s + (size_t)tg.nsplit * g.K * sizeof(float) <= ws_bytes)
+            pbias_s = partial + need_s / sizeof(float);
+        hipLaunchKernelGGL(kern, dim3(tg.nsplit, tg.nkb), dim3(256), lds2, s, g, tg, a1, b, partial, pbias_s);
         if (check_launch("conv wgrad (mfma, narrow input)")) return 1;
         const long per2 = (long)g.ntaps * C * g.K;
-        launch_wgrad_reduce_f((unsigned)(cdiv(per2, 64)), s, g, partial, dw, tg.nsplit, (const float *)nullptr,
-                           (float *)nullptr, 0, 0);
+        const int wblocks2 = (int)cdiv(per2, 64);
+        if (pbias_s) {  // the bias rows ride in the same reduce launch
+            launch_wgrad_reduce_f((unsigned)(wblocks2 + cdiv(g.K, 64)), s, g, partial, dw, tg.nsplit, (const float *)pbias_s,
+                               dbias, tg.nsplit, wblocks2);
+            *dbias_done = 1;
+        } else {
+            launch_wgrad_reduce_f((unsigned)wblocks2, s, g, partial, dw, tg.nsplit, (const float *)nullptr, (float *)nullptr, 0,
+                               0);
+        }
         return check_launch("conv wgrad reduce (mfma)");
     }
 #define WG_TPW(NA, NB, SH)                     \
@@ -2997,6 +3114,17 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
     float *pbias_g = nullptr;
     if (dbias && dbias_done && cfg == 0 && sameB && need_g + (size_t)4 * tg.nsplit * g.K * sizeof(float) <= ws_bytes)
         pbias_g = partial + need_g / sizeof(float);
+    // transposed conv with kernel == stride: the taps' dy slots are disjoint and tile dy (ob = every offset of the stride
+    // box once), and with ntaps a multiple of 4 no wave carries an alias tap -- each wave sums the fragments it stages
+    float *pbias_t = nullptr;
+    if (wgrad_bias_fold() && dbias && dbias_done && cfg == 1 && sameA && g.ntaps == 4 * tpw &&
+        g.ntaps == g.sb[0] * g.sb[1] * g.sb[2] && need_g + (size_t)16 * tg.nsplit * g.K * sizeof(float) <= ws_bytes) {
+        bool box = true;  // tap t <-> offset (pd, ph, pw) of the stride box, each once (convT_wgrad_geom's order)
+        for (int t = 0; t < g.ntaps; t++)
+            box = box && g.ob[t][0] == t / (g.sb[1] * g.sb[2]) && g.ob[t][1] == (t / g.sb[2]) % g.sb[1] &&
+                  g.ob[t][2] == t % g.sb[2];
+        if (box) pbias_t = partial + need_g / sizeof(float);
+    }
     if (cfg == 0) {
         if (sameB) WG_TPW(7, 2, 1)
         else WG_TPW(7, 2, 0)
@@ -3012,6 +3140,10 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
     if (pbias_g) {  // the bias rows ride in the same reduce launch
         launch_wgrad_reduce_f((unsigned)(wblocks + cdiv(g.K, 64)), s, g, partial, dw, 2 * tg.nsplit,
                            (const float *)pbias_g, dbias, tg.nsplit * 4, wblocks);
+        *dbias_done = 1;
+    } else if (pbias_t && cfg == 1) {
+        launch_wgrad_reduce_f((unsigned)(wblocks + cdiv(g.K, 64)), s, g, partial, dw, 2 * tg.nsplit,
+                           (const float *)pbias_t, dbias, tg.nsplit * 16, wblocks);
         *dbias_done = 1;
     } else {
         launch_wgrad_reduce_f((unsigned)(wblocks), s, g, partial, dw, 2 * tg.nsplit, (const float *)nullptr,

@@ -270,16 +270,47 @@ __global__ void k_in_apply_rows(const float *__restrict__ x, const float *__rest
     }
 }
 
+// ---- the backward of the LAST decoder block straight from the logit gradient (ops.NormActSegHeadFn, fp32): the fused seg
+// head is the only consumer of the activated tensor a, so its gradient d a[v][c] = sum_k dl[n][k][v] * w[k][c] is formed in
+// the two backward passes from the planar logit gradient (K floats per voxel) instead of being written and read back
+// twice (C floats per voxel).  The expression and the k order are those of k_seghead_dx4 (loss.hip) on a zeroed
+// accumulator, so d a is the value that kernel stores, bit for bit.
+constexpr int HKMAX = 8;  // classes (KMAX of loss.hip); the class count is a template parameter here (registers)
+template <int HK>
+__device__ __forceinline__ void head_w_load(float4 (&wk)[HK], const float *__restrict__ w, int C, int g) {
+#pragma unroll
+    for (int k = 0; k < HK; k++) wk[k] = *reinterpret_cast<const float4 *>(w + (size_t)k * C + g * 4);
+}
+template <int HK>  // all class gradients of voxel v in flight at once
+__device__ __forceinline__ void head_dl_load(float (&dq)[HK], const float *__restrict__ dl, int n, long V, long v) {
+#pragma unroll
+    for (int k = 0; k < HK; k++) dq[k] = dl[((size_t)n * HK + k) * V + v];
+}
+template <int HK>
+__device__ __forceinline__ float4 head_da(const float (&dq)[HK], const float4 (&wk)[HK]) {
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < HK; k++) {
+        a.x = fmaf(dq[k], wk[k].x, a.x);  // (explicit: k_seghead_dx4's a += d * w compiles to one fma per class, the first
+        a.y = fmaf(dq[k], wk[k].y, a.y);  // on +0; left to contraction, some of these came out as a multiply and an add)
+        a.z = fmaf(dq[k], wk[k].z, a.z);
+        a.w = fmaf(dq[k], wk[k].w, a.w);
+    }
+    return a;
+}
+
 #ifndef MVD_IN_NRB
 #define MVD_IN_NRB 4
 #endif
 constexpr int NRB = MVD_IN_NRB;  // rows in flight per thread in the backward apply pass
-template <bool XB, bool YB>
-__global__ void k_in_bwd_apply_rows(const float *__restrict__ x, const float *__restrict__ dy,
+// HK > 0: dy is the planar logit gradient dl [N][HK][V] of the fused seg head and hw its weight [HK][C] (see head_da); the
+// grid of in_bwd has at most 256 threads per block for C % 4 == 0
+template <bool XB, bool YB, int HK = 0>
+__global__ __launch_bounds__(HK > 0 ? 256 : 1024) void k_in_bwd_apply_rows(const float *__restrict__ x, const float *__restrict__ dy,
                                     const float *__restrict__ gamma, const float *__restrict__ beta,
                                     const float *__restrict__ mean, const float *__restrict__ rstd,
                                     const float *__restrict__ sums, float *__restrict__ dx, int C, int CG, int R, long V,
-                                    long chunk, float slope) {
+                                    long chunk, float slope, const float *__restrict__ hw = nullptr) {
     const int n = blockIdx.y, t = threadIdx.x;
     const int g = t % CG, r = t / CG;
     if (r >= R) return;
@@ -300,13 +331,26 @@ __global__ void k_in_bwd_apply_rows(const float *__restrict__ x, const float *__
         m2[i] = sums[nc * 2 + 1] * invV;
     }
     const size_t base = ((size_t)n * V) * C + (size_t)g * 4;
+    float4 wk[HK > 0 ? HK : 1];
+    if constexpr (HK > 0) head_w_load(wk, hw, C, g);
     long v = v0 + r;
     for (; v + (NRB - 1L) * R < v1; v += (long)NRB * R) {  // NRB rows (2 NRB loads) in flight
         float4 q[NRB], e[NRB];
+        if constexpr (HK > 0) {
+            float dq[NRB][HK];
 #pragma unroll
-        for (int u = 0; u < NRB; u++) {
-            q[u] = ld4<XB>(x, base + (size_t)(v + (long)u * R) * C);
-            e[u] = ld4<YB>(dy, base + (size_t)(v + (long)u * R) * C);
+            for (int u = 0; u < NRB; u++) {
+                q[u] = ld4<XB>(x, base + (size_t)(v + (long)u * R) * C);
+                head_dl_load(dq[u], dy, n, V, v + (long)u * R);
+            }
+#pragma unroll
+            for (int u = 0; u < NRB; u++) e[u] = head_da(dq[u], wk);
+        } else {
+#pragma unroll
+            for (int u = 0; u < NRB; u++) {
+                q[u] = ld4<XB>(x, base + (size_t)(v + (long)u * R) * C);
+                e[u] = ld4<YB>(dy, base + (size_t)(v + (long)u * R) * C);
+            }
         }
 #pragma unroll
         for (int u = 0; u < NRB; u++) {
@@ -323,7 +367,13 @@ __global__ void k_in_bwd_apply_rows(const float *__restrict__ x, const float *__
     }
     for (; v < v1; v += R) {
         float4 q = ld4<XB>(x, base + (size_t)v * C);
-        float4 e = ld4<YB>(dy, base + (size_t)v * C);
+        float4 e;
+        if constexpr (HK > 0) {
+            float dq[HK];
+            head_dl_load(dq, dy, n, V, v);
+            e = head_da(dq, wk);
+        } else
+            e = ld4<YB>(dy, base + (size_t)v * C);
         float f[4] = {q.x, q.y, q.z, q.w}, d[4] = {e.x, e.y, e.z, e.w};
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -337,11 +387,14 @@ __global__ void k_in_bwd_apply_rows(const float *__restrict__ x, const float *__
 }
 
 // ---- bwd pass 1: partial[n][b][c][2] = (sum dz, sum dz*xhat)
-template <int VEC, bool XB, bool YB>
-__global__ void k_in_bwd_stats(const float *__restrict__ x, const float *__restrict__ dy,
+// HK > 0 (VEC == 4): dy is the planar logit gradient dl [N][HK][V] of the fused seg head and hw its weight [HK][C] (see head_da)
+template <int VEC, bool XB, bool YB, int HK = 0>
+__global__ __launch_bounds__(HK > 0 ? 256 : 1024) void k_in_bwd_stats(const float *__restrict__ x, const float *__restrict__ dy,
                                const float *__restrict__ gamma, const float *__restrict__ beta,
                                const float *__restrict__ mean, const float *__restrict__ rstd,
-                               double *__restrict__ partial, int C, int CG, int R, long V, long chunk, float slope) {
+                               double *__restrict__ partial, int C, int CG, int R, long V, long chunk, float slope,
+                               const float *__restrict__ hw = nullptr) {
+    static_assert(HK == 0 || VEC == 4, "the head form works on 4-channel groups");
     extern __shared__ double sm[];
     const int n = blockIdx.y, b = blockIdx.x, nblk = gridDim.x;
     const int t = threadIdx.x;
@@ -363,11 +416,23 @@ __global__ void k_in_bwd_stats(const float *__restrict__ x, const float *__restr
             be[i] = beta[c];
         }
         const size_t base = ((size_t)n * V) * C + (size_t)g * VEC;
+        float4 wk[HK > 0 ? HK : 1];
+        if constexpr (HK > 0) head_w_load(wk, hw, C, g);
         long v = v0 + r;
         if (VEC == 4) {
             for (; v + R < v1; v += 2L * R) {  // two rows (four loads) in flight per thread, accumulated in row order
-                const float4 q0 = ld4<XB>(x, base + (size_t)v * C), e0 = ld4<YB>(dy, base + (size_t)v * C);
-                const float4 q1 = ld4<XB>(x, base + (size_t)(v + R) * C), e1 = ld4<YB>(dy, base + (size_t)(v + R) * C);
+                const float4 q0 = ld4<XB>(x, base + (size_t)v * C), q1 = ld4<XB>(x, base + (size_t)(v + R) * C);
+                float4 e0, e1;
+                if constexpr (HK > 0) {
+                    float d0[HK], d1[HK];
+                    head_dl_load(d0, dy, n, V, v);
+                    head_dl_load(d1, dy, n, V, v + R);
+                    e0 = head_da(d0, wk);
+                    e1 = head_da(d1, wk);
+                } else {
+                    e0 = ld4<YB>(dy, base + (size_t)v * C);
+                    e1 = ld4<YB>(dy, base + (size_t)(v + R) * C);
+                }
                 const float fx[2][4] = {{q0.x, q0.y, q0.z, q0.w}, {q1.x, q1.y, q1.z, q1.w}};
                 const float dd[2][4] = {{e0.x, e0.y, e0.z, e0.w}, {e1.x, e1.y, e1.z, e1.w}};
 #pragma unroll
@@ -384,9 +449,15 @@ __global__ void k_in_bwd_stats(const float *__restrict__ x, const float *__restr
         }
         for (; v < v1; v += R) {
             float f[VEC], d[VEC];
-            if (VEC == 4) {
+            if constexpr (VEC == 4) {
                 float4 q = ld4<XB>(x, base + (size_t)v * C);
-                float4 e = ld4<YB>(dy, base + (size_t)v * C);
+                float4 e;
+                if constexpr (HK > 0) {
+                    float dq[HK];
+                    head_dl_load(dq, dy, n, V, v);
+                    e = head_da(dq, wk);
+                } else
+                    e = ld4<YB>(dy, base + (size_t)v * C);
                 f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
                 d[0] = e.x; d[1] = e.y; d[2] = e.z; d[3] = e.w;
             } else {
@@ -580,11 +651,223 @@ __global__ void k_in_bwd_apply(const float *__restrict__ x, const float *__restr
     }
 }
 
+// ---- small volumes (the 16^3 and deeper stages): ONE launch per direction instead of three.  A workgroup owns SMW float4
+// lanes (16 channels, 64 contiguous bytes of every voxel row) of one sample; thread (lane gl, row r) keeps rows r, r + RP,
+// ... (at most MAXR) in registers, so x (and dy) are read once.  Sums: per thread in fp64 in row order, a fixed xor
+// tree over the 16 rows of a wave, then the waves in ascending order -- every thread ends with the same totals, no
+// atomics.  mean / rstd with the arithmetic of k_in_finalize, y with that of k_in_apply_rows, dx with that of
+// k_in_bwd_apply_rows on the float-rounded sums, dgamma / dbeta over n in ascending order as k_in_bwd_finalize.
+constexpr int SMW = 4;
+constexpr int SM_MAXR = 16;  // rows per thread: V <= 1024 on 256 threads (a 1024-thread form for V <= 4096 lost to the three
+                             // launches at every size it added, profiles/r11_instnorm_small.txt)
+__device__ __forceinline__ void small_reduce(double (&s)[4], double (&ss)[4], double (*sm)[SMW][8], int gl) {  // sm[4 waves]
+#pragma unroll
+    for (int off = SMW; off < 64; off <<= 1)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            s[i] += __shfl_xor(s[i], off);
+            ss[i] += __shfl_xor(ss[i], off);
+        }
+    const int wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if (nw == 1) return;
+    if ((threadIdx.x & 63) < SMW)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            sm[wv][gl][2 * i] = s[i];
+            sm[wv][gl][2 * i + 1] = ss[i];
+        }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; i++) s[i] = ss[i] = 0.0;
+    for (int w = 0; w < nw; w++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            s[i] += sm[w][gl][2 * i];
+            ss[i] += sm[w][gl][2 * i + 1];
+        }
+}
+
+template <int MAXR>
+__global__ __launch_bounds__(256) void k_in_small_fwd(const float *__restrict__ x, const float *__restrict__ gamma,
+                                                       const float *__restrict__ beta, float *__restrict__ y,
+                                                       float *__restrict__ mean, float *__restrict__ rstd, int C, long V,
+                                                       float eps, float slope) {
+    __shared__ double sm[4][SMW][8];
+    const int n = blockIdx.y, gl = threadIdx.x % SMW, r = threadIdx.x / SMW, RP = blockDim.x / SMW;
+    const int g = blockIdx.x * SMW + gl;
+    const bool act = g < (C >> 2);  // (the last workgroup of a C that is no multiple of 16)
+    const size_t base = ((size_t)n * V) * C + (size_t)g * 4;
+    float4 q[MAXR];
+#pragma unroll
+    for (int j = 0; j < MAXR; j++) {
+        const long v = r + (long)j * RP;
+        q[j] = (act && v < V) ? ld4<false>(x, base + (size_t)v * C) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < MAXR; j++) {  // (rows past V hold zeros: they add nothing)
+        const float f[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            s[i] += (double)f[i];
+            ss[i] += (double)f[i] * (double)f[i];
+        }
+    }
+    small_reduce(s, ss, sm, gl);
+    if (!act) return;
+    float mu[4], rs[4], ga[4], be[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const double m = s[i] / (double)V;
+        double var = ss[i] / (double)V - m * m;
+        if (var < 0) var = 0;
+        mu[i] = (float)m;
+        rs[i] = (float)(1.0 / sqrt(var + (double)eps));
+        ga[i] = gamma[g * 4 + i];
+        be[i] = beta[g * 4 + i];
+    }
+    if (r == 0)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            mean[(size_t)n * C + g * 4 + i] = mu[i];
+            rstd[(size_t)n * C + g * 4 + i] = rs[i];
+        }
+#pragma unroll
+    for (int j = 0; j < MAXR; j++) {
+        const long v = r + (long)j * RP;
+        if (v < V) {
+            float f[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const float xh = (f[i] - mu[i]) * rs[i];
+                const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
+                f[i] = z > 0.f ? z : z * slope;
+            }
+            st4<false>(y, base + (size_t)v * C, f[0], f[1], f[2], f[3]);
+        }
+    }
+}
+
+template <int MAXR>
+__global__ __launch_bounds__(256) void k_in_small_bwd(const float *__restrict__ x, const float *__restrict__ dy,
+                                                       const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                       const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                       float *__restrict__ dx, float *__restrict__ dgamma,
+                                                       float *__restrict__ dbeta, int N, int C, long V, float slope) {
+    __shared__ double sm[4][SMW][8];
+    const int gl = threadIdx.x % SMW, r = threadIdx.x / SMW, RP = blockDim.x / SMW;
+    const int g = blockIdx.x * SMW + gl;
+    const bool act = g < (C >> 2);
+    const int gc = act ? g : 0;  // (idle lanes read channel group 0's parameters and store nothing)
+    const float invV = 1.0f / (float)V;
+    float ga[4], be[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        ga[i] = gamma[gc * 4 + i];
+        be[i] = beta[gc * 4 + i];
+    }
+    double tg[4] = {0, 0, 0, 0}, tb[4] = {0, 0, 0, 0};
+    for (int n = 0; n < N; n++) {
+        const size_t base = ((size_t)n * V) * C + (size_t)gc * 4;
+        float mu[4], rs[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            mu[i] = mean[(size_t)n * C + gc * 4 + i];
+            rs[i] = rstd[(size_t)n * C + gc * 4 + i];
+        }
+        float4 q[MAXR], e[MAXR];
+#pragma unroll
+        for (int j = 0; j < MAXR; j++) {
+            const long v = r + (long)j * RP;
+            const bool in = act && v < V;
+            q[j] = in ? ld4<false>(x, base + (size_t)v * C) : make_float4(0.f, 0.f, 0.f, 0.f);
+            e[j] = in ? ld4<false>(dy, base + (size_t)v * C) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < MAXR; j++) {  // q <- xhat, e <- dz (rows past V: dz = 0, they add nothing)
+            float f[4] = {q[j].x, q[j].y, q[j].z, q[j].w}, d[4] = {e[j].x, e[j].y, e[j].z, e[j].w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const float xh = (f[i] - mu[i]) * rs[i];
+                const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
+                const float dz = z > 0.f ? d[i] : d[i] * slope;
+                s[i] += (double)dz;
+                ss[i] += (double)dz * (double)xh;
+                f[i] = xh;
+                d[i] = dz;
+            }
+            q[j] = make_float4(f[0], f[1], f[2], f[3]);
+            e[j] = make_float4(d[0], d[1], d[2], d[3]);
+        }
+        if (n > 0) __syncthreads();  // the totals of sample n - 1 have been read
+        small_reduce(s, ss, sm, gl);
+        float m1[4], m2[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            m1[i] = (float)s[i] * invV;
+            m2[i] = (float)ss[i] * invV;
+            tb[i] += s[i];
+            tg[i] += ss[i];
+        }
+#pragma unroll
+        for (int j = 0; j < MAXR; j++) {
+            const long v = r + (long)j * RP;
+            if (act && v < V) {
+                const float xh[4] = {q[j].x, q[j].y, q[j].z, q[j].w}, dz[4] = {e[j].x, e[j].y, e[j].z, e[j].w};
+                float f[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) f[i] = ga[i] * rs[i] * (dz[i] - m1[i] - xh[i] * m2[i]);
+                st4<false>(dx, base + (size_t)v * C, f[0], f[1], f[2], f[3]);
+            }
+        }
+    }
+    if (act && r == 0)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {  // (scalar stores: the gradients may be slices of a flat buffer)
+            dgamma[g * 4 + i] = (float)tg[i];
+            dbeta[g * 4 + i] = (float)tb[i];
+        }
+}
+
 }  // namespace mvd
 
 using namespace mvd;
 
+// ---- single-launch selection (MVD_IN_SMALL=0: always the three-launch form).  The default limit is where the single launch
+// stopped winning on MI355X (tools/bench_instnorm_small.py, profiles/r11_instnorm_small.txt); MVD_IN_SMALL_MAX moves it.
+constexpr long kInSmallMaxDefault = 327680;  // voxels x channels per sample (8x8x16 x 320 still won, 8x16x16 x 256 lost)
+static long g_in_small_launches = 0;
+static int in_small_threads(long V) {  // block size whose threads hold a sample's rows, 0: too many voxels
+    for (int t = 64; t <= 256; t *= 4)
+        if ((long)(t / SMW) * SM_MAXR >= V) return t;
+    return 0;
+}
+static long g_in_small_max = -1;  // < 0: from the environment at first use
+// nb: batch size of a BACKWARD launch, 0 for the forward.  The limit was measured at batch 2.  The forward grid has a
+// workgroup per (16 channels, sample) and scales with the batch as the three launches do; the backward grid has C / 16
+// workgroups that walk the samples one after the other (the order of dgamma / dbeta), so its time grows with N where the
+// three launches spread over the chip: past two samples the backward limit shrinks with 2 / N (reasoned, not measured).
+static int in_small_ok(long V, int C, int nb = 0) {
+    static const int on = getenv("MVD_IN_SMALL") ? atoi(getenv("MVD_IN_SMALL")) : 1;
+    if (g_in_small_max < 0)
+        g_in_small_max = getenv("MVD_IN_SMALL_MAX") ? atol(getenv("MVD_IN_SMALL_MAX")) : kInSmallMaxDefault;
+    if (!on || C % 4 != 0 || V <= 0) return 0;
+    const long elems = V * C;
+    if (nb > 2 ? elems * nb > 2 * g_in_small_max : elems > g_in_small_max) return 0;
+    return in_small_threads(V);
+}
+
 extern "C" {
+
+int mvd_instnorm_single_launch(long V, int C) { return in_small_ok(V, C) > 0 ? 1 : 0; }
+long mvd_instnorm_single_launches(void) { return g_in_small_launches; }
+static long g_in_stats_pass_launches = 0;
+long mvd_instnorm_stats_pass_launches(void) { return g_in_stats_pass_launches; }
+int mvd_set_instnorm_small_max(long max_elems) {  // < 0: back to MVD_IN_SMALL_MAX / the default; 0: never
+    g_in_small_max = max_elems < 0 ? -1 : max_elems;
+    return 0;
+}
 
 int mvd_instnorm_nblk(int N, long V, int C) { return norm_geom(N, V, C).nblk; }
 
@@ -602,6 +885,14 @@ static int in_fwd(const float *x, bool xb, const float *gamma, const float *beta
     MVD_REQUIRE(ws_bytes >= mvd_instnorm_workspace_bytes(N, V, C), "instnorm_fwd: workspace too small");
     NormGeom g = norm_geom(N, V, C);
     hipStream_t s = as_stream(stream);
+    if (!xb && !yb) {
+        if (const int th = in_small_ok(V, C)) {  // (tile statistics, if any, are not needed)
+            hipLaunchKernelGGL(k_in_small_fwd<SM_MAXR>, dim3(cdiv(C / 4, SMW), N), dim3(th), 0, s, x, gamma, beta, y, mean, rstd,
+                               C, V, eps, slope);
+            g_in_small_launches++;
+            return check_launch("instnorm forward (single launch)");
+        }
+    }
     double *partial = reinterpret_cast<double *>(ws);
     size_t sm = (size_t)g.R * C * 2 * sizeof(double);
     MVD_REQUIRE(sm <= 64 * 1024, "instnorm_fwd: C too large for the LDS reduce");
@@ -628,6 +919,7 @@ static int in_fwd(const float *x, bool xb, const float *gamma, const float *beta
             hipLaunchKernelGGL((k_in_stats<4, false>), grid, dim3(g.threads), sm, s, x, partial, C, g.CG, g.R, V, g.chunk);
         else
             hipLaunchKernelGGL((k_in_stats<1, false>), grid, dim3(g.threads), sm, s, x, partial, C, g.CG, g.R, V, g.chunk);
+        g_in_stats_pass_launches++;
         if (check_launch("instnorm stats")) return 1;
         // bf16 in and out: the apply pass takes the scale / shift form -- ONE arithmetic for the stand-alone pass, the apply after
         // a conv's statistics epilogue and the loader prologues (conv, weight gradient, seg head), so fused and un-fused
@@ -672,12 +964,20 @@ static int in_fwd(const float *x, bool xb, const float *gamma, const float *beta
 
 static int in_bwd(const float *x, bool xb, const float *dy, bool yb, const float *gamma, const float *beta,
                   const float *mean, const float *rstd, float *dx, float *dgamma, float *dbeta, int N, long V, int C,
-                  float slope, void *ws, size_t ws_bytes, void *stream) {
+                  float slope, void *ws, size_t ws_bytes, void *stream, const float *head_w = nullptr, int K = 0) {
     MVD_REQUIRE(x && dy && gamma && beta && mean && rstd && dx && dgamma && dbeta && ws, "instnorm_bwd: null pointer");
     MVD_REQUIRE(N > 0 && N <= 65535 && V > 0 && C > 0 && C <= 1024, "instnorm_bwd: bad shape");
     MVD_REQUIRE(ws_bytes >= mvd_instnorm_workspace_bytes(N, V, C), "instnorm_bwd: workspace too small");
     NormGeom g = norm_geom(N, V, C);
     hipStream_t s = as_stream(stream);
+    if (!xb && !yb && !head_w) {
+        if (const int th = in_small_ok(V, C, N)) {
+            hipLaunchKernelGGL(k_in_small_bwd<SM_MAXR>, dim3(cdiv(C / 4, SMW)), dim3(th), 0, s, x, dy, gamma, beta, mean, rstd, dx,
+                               dgamma, dbeta, N, C, V, slope);
+            g_in_small_launches++;
+            return check_launch("instnorm backward (single launch)");
+        }
+    }
     double *partial = reinterpret_cast<double *>(ws);
     float *sums = reinterpret_cast<float *>(partial + (size_t)N * g.nblk * C * 2);
     size_t sm = (size_t)g.R * C * 2 * sizeof(double);
@@ -685,11 +985,25 @@ static int in_bwd(const float *x, bool xb, const float *dy, bool yb, const float
     const bool v4 = (C % 4 == 0) && (g.CG * 4 == C);
     dim3 grid(g.nblk, N);
     MVD_REQUIRE(v4 || !(xb || yb), "instnorm_bwd: bf16 I/O needs C %% 4 == 0");
-    if (v4) {
+    MVD_REQUIRE(!head_w || (v4 && !xb && !yb && K > 0 && K <= HKMAX),
+                "instnorm_bwd: the logit-gradient form needs fp32, C %% 4 == 0 and K <= 8");
+    if (head_w) {
+        MVD_REQUIRE(g.threads <= 256, "instnorm_bwd: block size of the logit-gradient form");
+#define MVD_HEAD_STATS(KK)                                                                                                      \
+    case KK:                                                                                                                    \
+        hipLaunchKernelGGL((k_in_bwd_stats<4, false, false, KK>), grid, dim3(g.threads), sm, s, x, dy, gamma, beta, mean, rstd, \
+                           partial, C, g.CG, g.R, V, g.chunk, slope, head_w);                                                   \
+        break;
+        switch (K) {
+            MVD_HEAD_STATS(1) MVD_HEAD_STATS(2) MVD_HEAD_STATS(3) MVD_HEAD_STATS(4)
+            MVD_HEAD_STATS(5) MVD_HEAD_STATS(6) MVD_HEAD_STATS(7) MVD_HEAD_STATS(8)
+        }
+#undef MVD_HEAD_STATS
+    } else if (v4) {
         auto kern = xb ? (yb ? k_in_bwd_stats<4, true, true> : k_in_bwd_stats<4, true, false>)
                        : (yb ? k_in_bwd_stats<4, false, true> : k_in_bwd_stats<4, false, false>);
         hipLaunchKernelGGL(kern, grid, dim3(g.threads), sm, s, x, dy, gamma, beta, mean, rstd, partial, C, g.CG, g.R, V,
-                           g.chunk, slope);
+                           g.chunk, slope, (const float *)nullptr);
     } else
         hipLaunchKernelGGL((k_in_bwd_stats<1, false, false>), grid, dim3(g.threads), sm, s, x, dy, gamma, beta, mean, rstd,
                            partial, C, g.CG, g.R, V, g.chunk, slope);
@@ -709,8 +1023,20 @@ static int in_bwd(const float *x, bool xb, const float *dy, bool yb, const float
         const long chunk2 = cdiv(V, nb2);
         auto kern = xb ? (yb ? k_in_bwd_apply_rows<true, true> : k_in_bwd_apply_rows<true, false>)
                        : (yb ? k_in_bwd_apply_rows<false, true> : k_in_bwd_apply_rows<false, false>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, s, x, dy, gamma, beta, mean, rstd,
-                           sums, dx, C, g.CG, g.R, V, chunk2, slope);
+        if (head_w) {
+#define MVD_HEAD_APPLY(KK)                                                                                                        \
+    case KK:                                                                                                                      \
+        hipLaunchKernelGGL((k_in_bwd_apply_rows<false, false, KK>), dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, s, x, \
+                           dy, gamma, beta, mean, rstd, sums, dx, C, g.CG, g.R, V, chunk2, slope, head_w);                        \
+        break;
+            switch (K) {
+                MVD_HEAD_APPLY(1) MVD_HEAD_APPLY(2) MVD_HEAD_APPLY(3) MVD_HEAD_APPLY(4)
+                MVD_HEAD_APPLY(5) MVD_HEAD_APPLY(6) MVD_HEAD_APPLY(7) MVD_HEAD_APPLY(8)
+            }
+#undef MVD_HEAD_APPLY
+        } else
+            hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, s, x, dy, gamma, beta, mean, rstd,
+                               sums, dx, C, g.CG, g.R, V, chunk2, slope, (const float *)nullptr);
     }
     else
         hipLaunchKernelGGL(k_in_bwd_apply<1>, dim3(bx, N), dim3(256), 0, s, x, dy, gamma, beta, mean, rstd, sums, dx, C,
@@ -727,6 +1053,17 @@ int mvd_instnorm_lrelu_bwd(const float *x, const float *dy, const float *gamma, 
                            const float *rstd, float *dx, float *dgamma, float *dbeta, int N, long V, int C,
                            float slope, void *ws, size_t ws_bytes, void *stream) {
     return in_bwd(x, false, dy, false, gamma, beta, mean, rstd, dx, dgamma, dbeta, N, V, C, slope, ws, ws_bytes, stream);
+}
+
+// InstanceNorm backward of the block whose only consumer is the fused seg head, from the head's logit gradient: dy of
+// mvd_instnorm_lrelu_bwd is formed on the fly as dlogits^T w (what mvd_seghead_bwd_fused would store as dx); same grids,
+// chunks and orders, so dx / dgamma / dbeta are bit-identical to the two-call form.  fp32, C % 4 == 0, K <= 8.
+int mvd_instnorm_lrelu_bwd_head(const float *x, const float *dlogits, const float *w, int K, const float *gamma,
+                                const float *beta, const float *mean, const float *rstd, float *dx, float *dgamma,
+                                float *dbeta, int N, long V, int C, float slope, void *ws, size_t ws_bytes, void *stream) {
+    MVD_REQUIRE(w && (((uintptr_t)w) & 15) == 0, "instnorm_bwd_head: head weight (16-byte aligned) required");
+    return in_bwd(x, false, dlogits, false, gamma, beta, mean, rstd, dx, dgamma, dbeta, N, V, C, slope, ws, ws_bytes, stream, w,
+                  K);
 }
 
 int mvd_instnorm_lrelu_fwd_prestats(const float *x, const float *tile_stats, long ntiles, const float *gamma,

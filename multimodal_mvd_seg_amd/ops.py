@@ -522,6 +522,9 @@ LAUNCH_TIMER = None
 
 
 BF16_CONV_STATS = [os.environ.get("MVD_BF16_CONV_STATS", "1") != "0"]
+# fp32: InstanceNorm statistics from the epilogue of the direct conv kernels too (the first layer and the stride-2 layers; the
+# Winograd layers always had it) -- MVD_DIRECT_CONV_STATS=0: the statistics pass over their outputs
+DIRECT_CONV_STATS = [os.environ.get("MVD_DIRECT_CONV_STATS", "1") != "0"]
 
 
 def conv3d_fwd_bf16(x1, C1, x2, C2, wf, bias, y, N, D, H, W, K, ks, stride, ws, in_scale=None, in_shift=None, slope=0.01):
@@ -601,8 +604,26 @@ class Conv3dFn(Function):
                 if done.value:
                     y._mvd_tile_stats = (stats, ntiles)
             else:
-                call("mvd_conv3d_fwd_wino", _p(x1), C1, _p(x2), C2, _p(wf), _p(uf), _p(bias), _p(y), N, D, H, W, K, i3(ks),
-                     i3(stride), _p(ws), ws.numel(), _stream())
+                # the direct engines of the narrow-input and the stride-2 layers have the same epilogue; asked for only where
+                # the norm behind the conv would otherwise run a statistics pass (a small volume takes its own, in one launch).
+                # The trade: a chunked conv that is asked for statistics does not split its reduce channels over workgroups
+                # (launch_fwd), which skinny problems -- few tiles, >= 32 reduce channels -- use to fill the chip.  In the
+                # benchmark network no layer is both split and asked (the skinny stride-2 layers feed small norms); at other
+                # patch sizes a chunked stride-2 layer with more than 1024 output voxels gives up its split for a statistics
+                # pass of a few microseconds (MVD_DIRECT_CONV_STATS=0 keeps the split).
+                ntiles = 0
+                if DIRECT_CONV_STATS[0] and len(ks) == 3 and not query("mvd_instnorm_single_launch", od[0] * od[1] * od[2], K):
+                    ntiles = query("mvd_conv3d_fwd_stats_tiles", N, D, H, W, C1, C2, K, i3(ks), i3(stride))
+                if ntiles > 0:
+                    stats = torch.empty((N, ntiles, K, 2), dtype=torch.float32, device=x1.device)
+                    done = ctypes.c_int(0)
+                    call("mvd_conv3d_fwd_stats", _p(x1), C1, _p(x2), C2, _p(wf), _p(bias), _p(y), _p(stats), ntiles,
+                         ctypes.byref(done), N, D, H, W, K, i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
+                    if done.value:
+                        y._mvd_tile_stats = (stats, ntiles)
+                else:
+                    call("mvd_conv3d_fwd_wino", _p(x1), C1, _p(x2), C2, _p(wf), _p(uf), _p(bias), _p(y), N, D, H, W, K, i3(ks),
+                         i3(stride), _p(ws), ws.numel(), _stream())
         if timed:
             ev1 = torch.cuda.Event(enable_timing=True)
             ev1.record()
@@ -1077,13 +1098,19 @@ class SegHeadFn(Function):
         return (None if joined is not None else dx), dw.view(ctx.wshape), db
 
 
+# fp32 NormActSegHeadFn.backward: the InstanceNorm backward forms d a from the logit gradient in its own two passes
+# (mvd_instnorm_lrelu_bwd_head) instead of reading a stored d a (MVD_NORM_BWD_FROM_DL=0: the two-call form; same bits)
+NORM_BWD_FROM_DL = [os.environ.get("MVD_NORM_BWD_FROM_DL", "1") != "0"]
+
+
 class NormActSegHeadFn(Function):
     """The LAST decoder block's InstanceNorm3d + LeakyReLU folded into the seg head that is its only consumer (UNetDecoder.py:110
     after get_network_from_plans.py:41-44): `y0` is the RAW output of the block's conv (with the statistics its epilogue
     emitted attached), the head kernels apply the normalisation + activation in their loaders (mvd_seghead_*_fused: bf16 in the
     scale / shift form of the bf16 apply pass, fp32 in the mean / rstd form of the fp32 one) -- the activated tensor of the
     top decoder stage is never written.  Backward: d a from the head's input-gradient kernel, the InstanceNorm backward on
-    (y0, d a), dW / db over the re-computed a.  Bit-identical to the two separate nodes."""
+    (y0, d a), dW / db over the re-computed a.  Bit-identical to the two separate nodes.  In fp32 d a is not stored either: the
+    InstanceNorm backward forms it from the logit gradient and the head weight (NORM_BWD_FROM_DL), same bits again."""
 
     @staticmethod
     def forward(ctx, y0, gamma, beta, eps, slope, weight, bias):
@@ -1136,7 +1163,8 @@ class NormActSegHeadFn(Function):
         dev = y0.device
         dl = dl.contiguous()
         need_x = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        da = empty_cl3d(y0.shape, dev, y0.dtype) if need_x else None
+        from_dl = need_x and not bf and NORM_BWD_FROM_DL[0]
+        da = empty_cl3d(y0.shape, dev, y0.dtype) if need_x and not from_dl else None
         dw = torch.empty((K, C), dtype=torch.float32, device=dev)
         db = torch.empty((K,), dtype=torch.float32, device=dev)
         ws = _Workspace.get(query("mvd_seghead_bwd_workspace_bytes", N, V, C, K), dev)
@@ -1153,7 +1181,10 @@ class NormActSegHeadFn(Function):
             dg = sink_g if sink_g is not None else torch.empty((C,), dtype=torch.float32, device=dev)
             db_ = sink_b if sink_b is not None else torch.empty((C,), dtype=torch.float32, device=dev)
             ws = _Workspace.get(query("mvd_instnorm_workspace_bytes", N, V, C), dev)
-            if bf:
+            if from_dl:
+                call("mvd_instnorm_lrelu_bwd_head", _p(y0), _p(dl), _p(w), K, _p(g), _p(b), _p(mean), _p(rstd), _p(dy0), _p(dg),
+                     _p(db_), N, V, C, ctx.slope, _p(ws), ws.numel(), _stream())
+            elif bf:
                 call("mvd_instnorm_lrelu_bwd_bf16", _p(y0), 1, _p(da), _p(g), _p(b), _p(mean), _p(rstd), _p(dy0), _p(dg),
                      _p(db_), N, V, C, ctx.slope, _p(ws), ws.numel(), _stream())
             else:
