@@ -561,6 +561,20 @@ int mvd_feed_warp_seg(const float *seg, float *out, int C, int D, int H, int W, 
                       const double *affine12, int flip_mask, int replace, int replace_from, int replace_to,
                       void *stream);
 
+/* The in-plane ("dummy 2-D") form of the same transform for anisotropic plans (nnUNetTrainer.py:695-717,
+ * Convert3DTo2DTransform / Convert2DTo3DTransform around the SpatialTransform): [C][D][H][W] is resampled as
+ * C*D independent slices under ONE in-plane map p(oy, ox) = A (o - (f-1)/2) + off, o = (oy, ox), f = (fh, fw); axis 0
+ * keeps its size D.  affine6 is a HOST array {A row-major 2x2 (4), off (2)} copied into the kernel arguments.  Pinned
+ * to scipy.ndimage per slice.  coef is prefiltered in-plane only (mvd_feed_bspline_prefilter_f32 with axis_mask 6).
+ * H*W < 2^31, C*D < 8*65535.
+ * mvd_feed_warp2d_data_f32: out[C][D][fh][fw] = 2-D map_coordinates(coef[c][z], p, order=3, mode='constant', cval), 16
+ *   taps.  flip_mask is still the 3-bit OUTPUT mirror: bit 0 flips the slice index z, bits 1 / 2 the in-plane axes.
+ * mvd_feed_warp2d_seg: the same p with 4 linear taps and the winner rule and replacement of mvd_feed_warp_seg. */
+int mvd_feed_warp2d_data_f32(const float *coef, float *out, int C, int D, int H, int W, int fh, int fw,
+                             const double *affine6, int flip_mask, float cval, void *stream);
+int mvd_feed_warp2d_seg(const float *seg, float *out, int C, int D, int H, int W, int fh, int fw, const double *affine6,
+                        int flip_mask, int replace, int replace_from, int replace_to, void *stream);
+
 /* Intensity augmentations of the feed (nnUNetTrainer.py:719-736: GaussianNoise, GaussianBlur, BrightnessMultiplicative,
  * ContrastAugmentation, SimulateLowResolution, Gamma (inverted), Gamma) and MaskTransform, on the batch patch
  * [C][D][H][W] (V = D*H*W voxels per channel, C <= 16, bit c of chmask selects channel c).  Per-channel parameters are
@@ -580,6 +594,9 @@ int mvd_feed_warp_seg(const float *seg, float *out, int C, int D, int H, int W, 
  * mvd_feed_lowres_gather_f32: dpad [td+2pad][th+2pad][tw+2pad] = zoom(x', (td,th,tw)/(D,H,W), order=0, mode='nearest',
  *   grid_mode=True) edge-padded by pad, with x' the single channel x un-mirrored on flip_mask (SimulateLowResolution's
  *   downsample; the upsample is mvd_feed_bspline_prefilter_f32 + mvd_feed_warp_data_f32 with a diagonal affine).
+ * mvd_feed_lowres_gather2d_f32: the in-plane form (ignore_axes=(0,), the dummy 2-D mode): dpad [D][th+2pad][tw+2pad],
+ *   axis 0 is neither resized nor padded (bit 0 of flip_mask still un-mirrors its index); the upsample is
+ *   mvd_feed_bspline_prefilter_f32 with axis_mask 6 + mvd_feed_warp2d_data_f32 with a diagonal affine.
  * mvd_feed_mask_remove_label: data[c] = 0 where seg[0] < 0 for the channels of chmask (MaskTransform), then
  *   replace_from -> replace_to in all Cs seg channels when `replace` != 0 (RemoveLabelTransform). */
 size_t mvd_feed_stats_workspace_bytes(int C);
@@ -592,6 +609,8 @@ int mvd_feed_gaussian_noise_f32(float *x, int C, long V, int chmask, uint64_t ke
                                 void *stream);
 int mvd_feed_lowres_gather_f32(const float *x, float *dpad, int D, int H, int W, int td, int th, int tw, int pad,
                                int flip_mask, void *stream);
+int mvd_feed_lowres_gather2d_f32(const float *x, float *dpad, int D, int H, int W, int th, int tw, int pad,
+                                 int flip_mask, void *stream);
 int mvd_feed_mask_remove_label(float *data, float *seg, int C, int Cs, long V, int chmask, int replace,
                                int replace_from, int replace_to, void *stream);
 

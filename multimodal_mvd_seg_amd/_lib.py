@@ -180,12 +180,15 @@ SIGNATURES = {
     "mvd_feed_bspline_prefilter_f32": (c_int, [_P] + [c_int] * 5 + [_P]),
     "mvd_feed_warp_data_f32": (c_int, [_P, _P] + [c_int] * 7 + [_P, c_int, c_float, _P]),
     "mvd_feed_warp_seg": (c_int, [_P, _P] + [c_int] * 7 + [_P] + [c_int] * 4 + [_P]),
+    "mvd_feed_warp2d_data_f32": (c_int, [_P, _P] + [c_int] * 6 + [_P, c_int, c_float, _P]),
+    "mvd_feed_warp2d_seg": (c_int, [_P, _P] + [c_int] * 6 + [_P] + [c_int] * 4 + [_P]),
     "mvd_feed_stats_workspace_bytes": (c_size_t, [c_int]),
     "mvd_feed_channel_stats_f32": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_int, _P, _P, _P]),
     "mvd_feed_intensity_apply_f32": (c_int, [_P, c_int, c_long, c_int, c_int, _P, _P, _P, _P]),
     "mvd_feed_gaussian_blur_f32": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P]),
     "mvd_feed_gaussian_noise_f32": (c_int, [_P, c_int, c_long, c_int, c_uint64, c_uint64, c_float, _P]),
     "mvd_feed_lowres_gather_f32": (c_int, [_P, _P] + [c_int] * 8 + [_P]),
+    "mvd_feed_lowres_gather2d_f32": (c_int, [_P, _P] + [c_int] * 7 + [_P]),
     "mvd_feed_mask_remove_label": (c_int, [_P, _P, c_int, c_int, c_long] + [c_int] * 4 + [_P]),
     "mvd_export_resize_argmax_u8": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P]),
     "mvd_export_resize_softmax_f32": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, c_int, _P]),

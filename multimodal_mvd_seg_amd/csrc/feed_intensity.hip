@@ -298,6 +298,23 @@ __global__ void __launch_bounds__(256) k_lowres_gather(const float *__restrict__
     }
 }
 
+// The in-plane form (SimulateLowResolutionTransform with ignore_axes=(0,), the dummy 2-D mode): axis 0 keeps its size and
+// its index, dpad [D][th+2pad][tw+2pad] is padded on H and W only.
+__global__ void __launch_bounds__(256) k_lowres_gather2d(const float *__restrict__ x, float *__restrict__ dpad, int D,
+                                                         int H, int W, int th, int tw, int pad, int flip_mask) {
+    const int ph = th + 2 * pad, pw = tw + 2 * pad;
+    const long total = (long)D * ph * pw;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+        const int qx = (int)(q % pw), qy = (int)((q / pw) % ph), qz = (int)(q / ((long)pw * ph));
+        const int uy = min(max(qy - pad, 0), th - 1), ux = min(max(qx - pad, 0), tw - 1);
+        int sz = qz, sy = zoom0_index(uy, H, th), sx = zoom0_index(ux, W, tw);
+        if (flip_mask & 1) sz = D - 1 - sz;
+        if (flip_mask & 2) sy = H - 1 - sy;
+        if (flip_mask & 4) sx = W - 1 - sx;
+        dpad[q] = x[((long)sz * H + sy) * W + sx];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ mask + RemoveLabel
 __global__ void __launch_bounds__(256) k_mask_remove_label(float *__restrict__ data, float *__restrict__ seg, int C,
                                                            int Cs, long V, int chmask, int do_rep, float rep_from,
@@ -416,6 +433,19 @@ int mvd_feed_lowres_gather_f32(const float *x, float *dpad, int D, int H, int W,
     hipLaunchKernelGGL(k_lowres_gather, dim3(stride_grid(total, 4096)), dim3(256), 0, as_stream(stream), x, dpad, D, H,
                        W, td, th, tw, pad, flip_mask);
     return check_launch("feed_lowres_gather_f32");
+}
+
+int mvd_feed_lowres_gather2d_f32(const float *x, float *dpad, int D, int H, int W, int th, int tw, int pad,
+                                 int flip_mask, void *stream) {
+    MVD_REQUIRE(x && dpad, "feed_lowres_gather2d_f32: null pointer");
+    MVD_REQUIRE(D > 0 && H > 0 && W > 0 && th > 0 && tw > 0 && pad >= 0, "feed_lowres_gather2d_f32: bad shape");
+    MVD_REQUIRE(flip_mask >= 0 && flip_mask < 8, "feed_lowres_gather2d_f32: flip_mask is a 3-bit axis mask");
+    MVD_REQUIRE(D < (1 << 20) && H < (1 << 20) && W < (1 << 20) && th < (1 << 20) && tw < (1 << 20) && pad <= 64,
+                "feed_lowres_gather2d_f32: bad shape");
+    const long total = (long)D * (th + 2 * pad) * (tw + 2 * pad);
+    hipLaunchKernelGGL(k_lowres_gather2d, dim3(stride_grid(total, 4096)), dim3(256), 0, as_stream(stream), x, dpad, D, H,
+                       W, th, tw, pad, flip_mask);
+    return check_launch("feed_lowres_gather2d_f32");
 }
 
 int mvd_feed_mask_remove_label(float *data, float *seg, int C, int Cs, long V, int chmask, int replace,

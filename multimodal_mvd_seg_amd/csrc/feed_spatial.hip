@@ -7,6 +7,8 @@
 //                             B-spline taps at floor(p)-1 .. floor(p)+2, tap indices mirrored, cval outside [0, n-1]
 //   k_spatial_warp_seg     == batchgenerators interpolate_img(order=1, cval=-1, is_seg=True): per-label linear
 //                             indicator, the largest label reaching 0.5 wins, 0 elsewhere
+//   k_spatial_warp2d_*     == the same two resamplers per slice (c, z) under one in-plane map: the dummy 2-D mode of
+//                             anisotropic plans (Convert3DTo2DTransform); 4x4 cubic / 4 linear taps
 // Planar fp32 [C][D][H][W].  The per-sample coordinate map is p = A (o - (f-1)/2) + off, A and off by value.
 #include "common.h"
 
@@ -229,6 +231,159 @@ __global__ void __launch_bounds__(256) k_spatial_warp_seg(const float *__restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------ in-plane (dummy 2-D)
+// Convert3DTo2DTransform around the SpatialTransform (nnUNetTrainer.py:695-717): [C][D][H][W] is [C*D][H][W] and one
+// in-plane map p(oy, ox) = A (o - (f-1)/2) + off moves every slice of every channel.  A lane owns one (oy, ox) of a
+// 16 x 16 tile and walks kPlanesPerBlock consecutive planes (c, z); grid.z deals the planes.
+struct Affine6 {
+    double a[6];  // A row-major (2x2), then the offset (2)
+};
+
+constexpr int kPlanesPerBlock = 8;
+
+__device__ __forceinline__ bool warp2d_pixel(int fh, int fw, int &oy, int &ox) {
+    ox = blockIdx.x * 16 + (threadIdx.x & 15);
+    oy = blockIdx.y * 16 + (threadIdx.x >> 4);
+    return ox < fw && oy < fh;
+}
+
+__device__ __forceinline__ bool warp2d_coord(const Affine6 &T, int oy, int ox, int fh, int fw, int H, int W,
+                                             double (&p)[2]) {
+    const double q0 = oy - 0.5 * (fh - 1), q1 = ox - 0.5 * (fw - 1);
+    p[0] = T.a[0] * q0 + T.a[1] * q1 + T.a[4];
+    p[1] = T.a[2] * q0 + T.a[3] * q1 + T.a[5];
+    return p[0] >= 0.0 && p[0] <= (double)(H - 1) && p[1] >= 0.0 && p[1] <= (double)(W - 1);
+}
+
+// Walk of the planes [p0, p1) of one block: `in` is the plane read, `out` the plane stored.  Bit 0 of flip_mask mirrors
+// the slice index inside its channel (MirrorTransform runs after Convert2DTo3DTransform).  Wave-uniform.
+struct PlaneWalk {
+    long c, p1;
+    int z, D, flip;
+    __device__ __forceinline__ PlaneWalk(long planes, int D_, int flip_mask) : D(D_), flip(flip_mask & 1) {
+        const long p0 = (long)blockIdx.z * kPlanesPerBlock;
+        p1 = p0 + kPlanesPerBlock < planes ? p0 + kPlanesPerBlock : planes;
+        c = p0 / D;
+        z = (int)(p0 - c * D);
+    }
+    __device__ __forceinline__ bool more() const { return c * D + z < p1; }
+    __device__ __forceinline__ long in() const { return c * D + z; }
+    __device__ __forceinline__ long out() const { return c * D + (flip ? D - 1 - z : z); }
+    __device__ __forceinline__ void next() {
+        if (++z == D) {
+            z = 0;
+            ++c;
+        }
+    }
+};
+
+// One tap: a wave-uniform plane base plus a 32-bit byte offset (H*W < 2^30, checked at the entry).
+__device__ __forceinline__ float tap(const float *plane, unsigned boff) {
+    return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(plane) + boff);
+}
+
+// out[c][flip(z, oy, ox)] = sum of the 4x4 taps of slice (c, z) of coef at p(oy, ox) (cval outside the domain).
+// Coordinate, domain test, weights and the 16 tap offsets once per lane; the plane walk reuses them.
+__global__ void __launch_bounds__(256) k_spatial_warp2d_data(const float *__restrict__ coef, float *__restrict__ out,
+                                                             long planes, int D, int H, int W, int fh, int fw,
+                                                             Affine6 T, int flip_mask, float cval) {
+    int oy, ox;
+    if (!warp2d_pixel(fh, fw, oy, ox)) return;
+    const long oarea = (long)fh * fw, iarea = (long)H * W;
+    const int sy = (flip_mask & 2) ? fh - 1 - oy : oy, sx = (flip_mask & 4) ? fw - 1 - ox : ox;
+    const long o = (long)sy * fw + sx;
+    PlaneWalk pw(planes, D, flip_mask);
+    double p[2];
+    if (!warp2d_coord(T, oy, ox, fh, fw, H, W, p)) {
+        for (; pw.more(); pw.next()) out[pw.out() * oarea + o] = cval;
+        return;
+    }
+    const int n[2] = {H, W};
+    float w[2][4];
+    int idx[2][4];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+        const double f = floor(p[d]);
+        cubic_weights((float)(p[d] - f), w[d]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) idx[d][k] = mirror_index((int)f - 1 + k, n[d]);
+    }
+    unsigned off[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) off[k] = 4u * (unsigned)(idx[0][k >> 2] * W + idx[1][k & 3]);
+#pragma clang loop vectorize(disable) unroll(disable)
+    for (; pw.more(); pw.next()) {
+        const float *src = coef + pw.in() * iarea;
+        float acc = 0.f;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const float v = w[1][0] * tap(src, off[4 * a]) + w[1][1] * tap(src, off[4 * a + 1]) +
+                            w[1][2] * tap(src, off[4 * a + 2]) + w[1][3] * tap(src, off[4 * a + 3]);
+            acc += w[0][a] * v;
+        }
+        out[pw.out() * oarea + o] = acc;
+    }
+}
+
+// The same walk with the 4 bilinear taps and k_spatial_warp_seg's winner rule: the largest label whose indicator sum
+// reaches 0.5, 0 otherwise and outside; then L == rep_from becomes rep_to when do_rep.
+__global__ void __launch_bounds__(256) k_spatial_warp2d_seg(const float *__restrict__ seg, float *__restrict__ out,
+                                                            long planes, int D, int H, int W, int fh, int fw, Affine6 T,
+                                                            int flip_mask, int do_rep, float rep_from, float rep_to) {
+    int oy, ox;
+    if (!warp2d_pixel(fh, fw, oy, ox)) return;
+    const long oarea = (long)fh * fw, iarea = (long)H * W;
+    const int sy = (flip_mask & 2) ? fh - 1 - oy : oy, sx = (flip_mask & 4) ? fw - 1 - ox : ox;
+    const long o = (long)sy * fw + sx;
+    PlaneWalk pw(planes, D, flip_mask);
+    double p[2];
+    if (!warp2d_coord(T, oy, ox, fh, fw, H, W, p)) {
+        const float res = (do_rep && 0.f == rep_from) ? rep_to : 0.f;
+        for (; pw.more(); pw.next()) out[pw.out() * oarea + o] = res;
+        return;
+    }
+    const int n[2] = {H, W};
+    float w[2][2];
+    int idx[2][2];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+        const double f = floor(p[d]);
+        const float t = (float)(p[d] - f);
+        w[d][0] = 1.f - t;
+        w[d][1] = t;
+        idx[d][0] = (int)f;
+        idx[d][1] = mirror_index((int)f + 1, n[d]);
+    }
+    float wt[4];
+    unsigned off[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        wt[k] = w[0][k >> 1] * w[1][k & 1];
+        off[k] = 4u * (unsigned)(idx[0][k >> 1] * W + idx[1][k & 1]);
+    }
+#pragma clang loop vectorize(disable)
+    for (; pw.more(); pw.next()) {
+        const float *src = seg + pw.in() * iarea;
+        float lab[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lab[k] = tap(src, off[k]);
+        float res = 0.f;
+        bool found = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float ind = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ind += lab[j] == lab[k] ? wt[j] : 0.f;
+            if (ind >= 0.5f && (!found || lab[k] > res)) {
+                res = lab[k];
+                found = true;
+            }
+        }
+        if (do_rep && res == rep_from) res = rep_to;
+        out[pw.out() * oarea + o] = res;
+    }
+}
+
 }  // namespace mvd
 
 using namespace mvd;
@@ -255,6 +410,31 @@ static Affine12 load_affine(const double *a) {
 }
 
 static dim3 warp_grid(int fd, int fh, int fw) { return dim3((fw + 7) / 8, (fh + 7) / 8, (fd + 3) / 4); }
+
+static bool spatial2d_shape_ok(int C, int D, int H, int W, int fh, int fw) {
+    const int lim = 1 << 30;
+    if (C <= 0 || D <= 0 || H <= 0 || W <= 0 || fh <= 0 || fw <= 0) return false;
+    if (D >= lim || H >= lim || W >= lim || fh >= lim || fw >= lim) return false;
+    if ((long)H * W >= (1L << 30)) return false;  // 32-bit tap byte offsets within one plane
+    if ((long)C * D >= (long)kPlanesPerBlock * 65535) return false;  // grid.z
+    return (fh + 15) / 16 < 65536;                                   // grid.y
+}
+
+static bool affine6_ok(const double *a) {
+    for (int i = 0; i < 6; ++i)
+        if (!(a[i] == a[i]) || a[i] > 1e9 || a[i] < -1e9) return false;
+    return true;
+}
+
+static Affine6 load_affine6(const double *a) {
+    Affine6 t;
+    for (int i = 0; i < 6; ++i) t.a[i] = a[i];
+    return t;
+}
+
+static dim3 warp2d_grid(long planes, int fh, int fw) {
+    return dim3((fw + 15) / 16, (fh + 15) / 16, (unsigned)cdiv(planes, (long)kPlanesPerBlock));
+}
 
 extern "C" {
 
@@ -307,5 +487,30 @@ int mvd_feed_warp_seg(const float *seg, float *out, int C, int D, int H, int W, 
                        fd, fh, fw, load_affine(affine12), flip_mask, replace ? 1 : 0, (float)replace_from,
                        (float)replace_to);
     return check_launch("feed_warp_seg");
+}
+
+int mvd_feed_warp2d_data_f32(const float *coef, float *out, int C, int D, int H, int W, int fh, int fw,
+                             const double *affine6, int flip_mask, float cval, void *stream) {
+    MVD_REQUIRE(coef && out && affine6, "feed_warp2d_data_f32: null pointer");
+    MVD_REQUIRE(spatial2d_shape_ok(C, D, H, W, fh, fw), "feed_warp2d_data_f32: bad shape");
+    MVD_REQUIRE(flip_mask >= 0 && flip_mask < 8, "feed_warp2d_data_f32: flip_mask is a 3-bit axis mask");
+    MVD_REQUIRE(affine6_ok(affine6), "feed_warp2d_data_f32: affine6 must be finite");
+    const long planes = (long)C * D;
+    hipLaunchKernelGGL(k_spatial_warp2d_data, warp2d_grid(planes, fh, fw), dim3(256), 0, as_stream(stream), coef, out,
+                       planes, D, H, W, fh, fw, load_affine6(affine6), flip_mask, cval);
+    return check_launch("feed_warp2d_data_f32");
+}
+
+int mvd_feed_warp2d_seg(const float *seg, float *out, int C, int D, int H, int W, int fh, int fw, const double *affine6,
+                        int flip_mask, int replace, int replace_from, int replace_to, void *stream) {
+    MVD_REQUIRE(seg && out && affine6, "feed_warp2d_seg: null pointer");
+    MVD_REQUIRE(spatial2d_shape_ok(C, D, H, W, fh, fw), "feed_warp2d_seg: bad shape");
+    MVD_REQUIRE(flip_mask >= 0 && flip_mask < 8, "feed_warp2d_seg: flip_mask is a 3-bit axis mask");
+    MVD_REQUIRE(affine6_ok(affine6), "feed_warp2d_seg: affine6 must be finite");
+    const long planes = (long)C * D;
+    hipLaunchKernelGGL(k_spatial_warp2d_seg, warp2d_grid(planes, fh, fw), dim3(256), 0, as_stream(stream), seg, out,
+                       planes, D, H, W, fh, fw, load_affine6(affine6), flip_mask, replace ? 1 : 0, (float)replace_from,
+                       (float)replace_to);
+    return check_launch("feed_warp2d_seg");
 }
 }

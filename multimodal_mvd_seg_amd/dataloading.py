@@ -13,7 +13,9 @@ coordinate mesh, rotation matrices) is restated.  The intensity augmentations (:
 contrast, low-resolution simulation, the two gammas) and MaskTransform run on the device when the loader is given
 `intensity_augmentation=True` / `mask_channels` (csrc/feed_intensity.hip): their numeric cores are pinned to
 numpy / scipy.ndimage, their batchgenerators glue (which values are drawn, in which order) is restated in
-`draw_intensity`.
+`draw_intensity`.  Anisotropic plans (`do_dummy_2d_data_aug=True`, nnUNetTrainer.py:695-717) take the in-plane form of both
+stages: one 2-D map per sample moves every slice of every channel, and the low-resolution simulation leaves axis 0 alone
+(DESIGN 19).
 """
 import ctypes
 
@@ -107,11 +109,30 @@ def spatial_affine(spatial, patch_size):
     return [float(v) for v in a.reshape(-1)] + [float(v) for v in off]
 
 
-def _affine_arg(affine):
+def rotation_matrix_2d(a):
+    """batchgenerators create_matrix_rotation_2d; rotate_coords_2d multiplies a coordinate ROW vector (y, x) by it."""
+    return np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+
+
+def spatial_affine_2d(spatial, patch_size_2d):
+    """The 6 doubles of the in-plane map p = A (o - (f-1)/2) + off of the dummy 2-D mode for spatial = (a_x, 0, 0, sc)
+    (augment_spatial, dim == 2: rotate_coords_2d, scale_coords, + ctr): A = sc R^T, off = n/2 - 0.5 over (H, W).  The
+    lower-right 2x2 block of spatial_affine((a_x, 0, 0, sc)): axis 0 stays the identity."""
+    ax, ay, az, sc = spatial
+    if ay != 0 or az != 0:
+        raise ValueError("spatial_affine_2d: the in-plane map only rotates about axis 0 (a_y = a_z = 0)")
+    if len(patch_size_2d) != 2:
+        raise ValueError("spatial_affine_2d: patch_size_2d is (H, W)")
+    a = sc * rotation_matrix_2d(ax).T
+    off = np.asarray(patch_size_2d, dtype=np.float64) / 2. - 0.5
+    return [float(v) for v in a.reshape(-1)] + [float(v) for v in off]
+
+
+def _affine_arg(affine, n=12):
     vals = [float(v) for v in affine]
-    if len(vals) != 12:
-        raise ValueError("affine: 12 values (A row-major, then the offset)")
-    return (ctypes.c_double * 12)(*vals)
+    if len(vals) != n:
+        raise ValueError(f"affine: {n} values (A row-major, then the offset)")
+    return (ctypes.c_double * n)(*vals)
 
 
 def bspline_prefilter(patch, axis_mask=7):
@@ -143,6 +164,31 @@ def spatial_transform_seg(seg, out, affine, flip_mask=0, replace=None):
     rf, rt = (replace if replace is not None else (0, 0))
     call("mvd_feed_warp_seg", _p(seg), _p(out), *[int(v) for v in seg.shape], *[int(v) for v in out.shape[1:]],
          _affine_arg(affine), int(flip_mask), int(replace is not None), int(rf), int(rt), _stream())
+
+
+def _check_2d_pair(src, out, name):
+    if not (src.is_cuda and out.is_cuda and src.dtype == torch.float32 and out.dtype == torch.float32
+            and src.is_contiguous() and out.is_contiguous() and src.dim() == 4 and out.dim() == 4
+            and out.shape[0] == src.shape[0] and out.shape[1] == src.shape[1]):
+        raise RuntimeError(f"{name}: contiguous float32 device tensors [C,D,H,W] -> [C,D,fh,fw] (axis 0 keeps its size)")
+
+
+def spatial_transform_data_2d(coef, out, affine, flip_mask=0, cval=0.0):
+    """out[C,D,fh,fw] <- per slice (c, z) the 2-D map_coordinates(order=3, mode='constant', cval) of the IN-PLANE
+    prefiltered patch coef[C,D,H,W] (bspline_prefilter(..., 6)) at p = A (o - (f-1)/2) + off (affine: 6 values, A 2x2
+    row-major, then off), mirrored on the axes of the 3-bit flip_mask (bit 0 flips the slice index)."""
+    _check_2d_pair(coef, out, "spatial_transform_data_2d")
+    call("mvd_feed_warp2d_data_f32", _p(coef), _p(out), *[int(v) for v in coef.shape], *[int(v) for v in out.shape[2:]],
+         _affine_arg(affine, 6), int(flip_mask), float(cval), _stream())
+
+
+def spatial_transform_seg_2d(seg, out, affine, flip_mask=0, replace=None):
+    """out[C,D,fh,fw] <- per slice the 2-D interpolate_img(order=1, mode='constant', cval=-1, is_seg=True) of the float32
+    label patch seg[C,D,H,W] at the same coordinates; replace=(from, to) applies RemoveLabelTransform after the vote."""
+    _check_2d_pair(seg, out, "spatial_transform_seg_2d")
+    rf, rt = (replace if replace is not None else (0, 0))
+    call("mvd_feed_warp2d_seg", _p(seg), _p(out), *[int(v) for v in seg.shape], *[int(v) for v in out.shape[2:]],
+         _affine_arg(affine, 6), int(flip_mask), int(replace is not None), int(rf), int(rt), _stream())
 
 
 def _dev_f32(t, name, dim=4):
@@ -247,6 +293,19 @@ def lowres_gather(x, dpad, target_shape, flip_mask=0, pad=LOWRES_PAD):
          _stream())
 
 
+def lowres_gather_2d(x, dpad, target_shape_2d, flip_mask=0, pad=LOWRES_PAD):
+    """dpad [D, th+2pad, tw+2pad] <- per slice zoom(x'[z], (th, tw)/(H, W), order=0, mode='nearest', grid_mode=True)
+    edge-padded by pad in-plane, with x' the single channel x [D,H,W] un-mirrored on flip_mask: the downsample of
+    SimulateLowResolutionTransform(ignore_axes=(0,))."""
+    _dev_f32(x, "lowres_gather_2d", 3)
+    _dev_f32(dpad, "lowres_gather_2d", 3)
+    t = [int(v) for v in target_shape_2d]
+    if len(t) != 2 or list(dpad.shape) != [int(x.shape[0]), t[0] + 2 * pad, t[1] + 2 * pad]:
+        raise RuntimeError("lowres_gather_2d: dpad must be [D, th + 2 pad, tw + 2 pad]")
+    call("mvd_feed_lowres_gather2d_f32", _p(x), _p(dpad), *[int(v) for v in x.shape], *t, int(pad), int(flip_mask),
+         _stream())
+
+
 def mask_remove_label(data, seg, channels, replace=(-1, 0)):
     """MaskTransform (data[c] = 0 where seg[0] < 0, c in channels) then RemoveLabelTransform(replace) on seg, in place;
     data [C,D,H,W], seg [Cs,D,H,W] float32."""
@@ -271,6 +330,12 @@ def lowres_affine(shape, target):
     s = [t / n for n, t in zip(shape, target)]
     a = [s[0], 0., 0., 0., s[1], 0., 0., 0., s[2]]
     return a + [si * n / 2. - 0.5 + LOWRES_PAD for si, n in zip(s, shape)]
+
+
+def lowres_affine_2d(shape_2d, target_2d):
+    """lowres_affine over (H, W) only: 6 values for spatial_transform_data_2d."""
+    s = [t / n for n, t in zip(shape_2d, target_2d)]
+    return [s[0], 0., 0., s[1]] + [si * n / 2. - 0.5 + LOWRES_PAD for si, n in zip(s, shape_2d)]
 
 
 INTENSITY_KEYS = ('noise', 'blur', 'brightness', 'contrast', 'lowres', 'gamma_inverted', 'gamma')
@@ -305,9 +370,13 @@ class DeviceDataLoader3D:
         if self.rotation_for_DA is None and self.patch_size != self.final_patch_size:
             # the larger initial patch only exists to feed the rotation / scaling transform
             raise NotImplementedError("DeviceDataLoader3D: patch_size must equal final_patch_size (no SpatialTransform)")
-        if do_dummy_2d_data_aug:
-            raise NotImplementedError("DeviceDataLoader3D: do_dummy_2d_data_aug (the in-plane 2-D SpatialTransform of "
-                                      "Convert3DTo2DTransform) is not implemented")
+        # anisotropic plans (nnUNetTrainer.py:695-717): the SpatialTransform runs in-plane on [C*D, H, W] and the
+        # low-resolution simulation ignores axis 0
+        self.do_dummy_2d_data_aug = bool(do_dummy_2d_data_aug)
+        if self.do_dummy_2d_data_aug and self.patch_size[0] != self.final_patch_size[0]:
+            raise NotImplementedError("DeviceDataLoader3D: do_dummy_2d_data_aug needs patch_size[0] == "
+                                      "final_patch_size[0]: the in-plane 2-D SpatialTransform of Convert3DTo2DTransform "
+                                      "leaves axis 0 alone, so it cannot crop or resample it")
         if self.rotation_for_DA is not None and any(p < f for p, f in zip(self.patch_size, self.final_patch_size)):
             raise ValueError("DeviceDataLoader3D: patch_size must not be smaller than final_patch_size")
         # the intensity stage (nnUNetTrainer.py:719-736) with its per-sample / per-channel probabilities, and
@@ -438,10 +507,12 @@ class DeviceDataLoader3D:
         nnUNetTrainer.py:703-714; absent from the reference tree -- restated from its published source).  No elastic
         draw (do_elastic_deform=False short-circuits); a rotation draw, then per axis x, y, z an axis draw and an angle;
         a scaling draw, then the down/up choice and the factor (independent_scale_for_each_axis=False short-circuits).
+        In the dummy 2-D mode (augment_spatial's dim == 2) only the x axis draw and angle exist: the y / z draws sit
+        inside `if dim == 3`, so a rotation costs 2 draws, not 6, and a_y = a_z = 0.
         Returns None for an unmodified sample, else (a_x, a_y, a_z, sc)."""
         rot, sc, modified = [0., 0., 0.], 1., False
         if np.random.uniform() < self.p_rot_per_sample:
-            for i, ax in enumerate(('x', 'y', 'z')):
+            for i, ax in enumerate(('x',) if self.do_dummy_2d_data_aug else ('x', 'y', 'z')):
                 if np.random.uniform() <= self.p_rot_per_axis:
                     rot[i] = np.random.uniform(*self.rotation_for_DA[ax])
             modified = True
@@ -572,6 +643,16 @@ class DeviceDataLoader3D:
                 if z is None:
                     continue
                 t = lowres_target_shape(shape, z)
+                if self.do_dummy_2d_data_aug:  # ignore_axes=(0,): target_shape[0] = shape[0], everything in-plane
+                    dpad = st['dpad'][:shape[0] * int(np.prod([v + 2 * LOWRES_PAD for v in t[1:]]))].view(
+                        shape[0], *[v + 2 * LOWRES_PAD for v in t[1:]])
+                    lowres_gather_2d(x[c], dpad, t[1:], flip_mask)
+                    d4 = dpad.unsqueeze(0)
+                    channel_stats(d4, st['stats1'][0], st['ws'])
+                    bspline_prefilter(d4, 6)
+                    spatial_transform_data_2d(d4, x[c:c + 1], lowres_affine_2d(shape[1:], t[1:]), flip_mask, 0.0)
+                    intensity_apply(x[c:c + 1], OP_CLIP, None, st['stats1'][0])
+                    continue
                 dpad = st['dpad'][:int(np.prod([v + 2 * LOWRES_PAD for v in t]))].view(
                     *[v + 2 * LOWRES_PAD for v in t])
                 lowres_gather(x[c], dpad, t, flip_mask)
@@ -614,10 +695,16 @@ class DeviceDataLoader3D:
                 pdata, pseg = self._scratch_for(data, seg)
                 crop_pad_data(data, pdata, boxes[j], 0, 0.0)
                 crop_pad_seg(seg, pseg, boxes[j], 0, -1)
-                bspline_prefilter(pdata, 7)
-                affine = spatial_affine(spatial[j], self.patch_size)
-                spatial_transform_data(pdata, data_all[j], affine, flips[j], 0.0)
-                spatial_transform_seg(pseg, target[j], affine, flips[j], replace=remove)
+                if self.do_dummy_2d_data_aug:
+                    bspline_prefilter(pdata, 6)
+                    affine = spatial_affine_2d(spatial[j], self.patch_size[1:])
+                    spatial_transform_data_2d(pdata, data_all[j], affine, flips[j], 0.0)
+                    spatial_transform_seg_2d(pseg, target[j], affine, flips[j], replace=remove)
+                else:
+                    bspline_prefilter(pdata, 7)
+                    affine = spatial_affine(spatial[j], self.patch_size)
+                    spatial_transform_data(pdata, data_all[j], affine, flips[j], 0.0)
+                    spatial_transform_seg(pseg, target[j], affine, flips[j], replace=remove)
             if intensity is not None:
                 self.apply_intensity(data_all[j], intensity[j], flips[j])
             if self.mask_channels is not None:

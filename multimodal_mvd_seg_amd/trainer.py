@@ -493,7 +493,10 @@ class nnUNetTrainerMI355(object):
 
     # -- training feed (nnUNetTrainer.py:377-434 and :600-630, fed from HBM by dataloading.DeviceDataLoader3D) ----
     def configure_rotation_dummyDA_mirroring_and_inital_patch_size(self):
-        """The 3-D branch of nnUNetTrainer.py:377-434 (ANISO_THRESHOLD = 3, configuration.py:7)."""
+        """nnUNetTrainer.py:377-434 for 3-D plans (ANISO_THRESHOLD = 3, configuration.py:7), both branches: an isotropic
+        patch rotates about every axis by +-30 degrees; an anisotropic one (max / patch[0] > 3) takes the dummy 2-D
+        mode -- in-plane rotation by +-180 degrees, axis 0 of the initial patch kept -- which the device feed runs with
+        its in-plane kernels.  True 2-D plans stay refused."""
         patch_size = self.configuration_manager.patch_size
         dim = len(patch_size)
         if dim != 3:
