@@ -1600,6 +1600,9 @@ class MseFn(Function):
             if a.stride() != b.stride():
                 a = a.contiguous()
                 b = b.contiguous()
+        # k_mse_fwd reads float4: a dense operand that does not start on a 16-byte boundary (a view into a larger buffer)
+        # moves to an allocation of its own, strides kept
+        a, b = (t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.preserve_format) for t in (a, b))
         n = a.numel()
         out = torch.empty((1,), dtype=torch.float32, device=a.device)
         ws = _Workspace.get(query("mvd_mse_workspace_bytes", n), a.device)
