@@ -275,7 +275,9 @@ int mvd_seghead_bwd_bf16(const uint16_t *x, const float *w, const float *dlogits
 /* The seg head of the LAST decoder stage reading the RAW bf16 output of that stage's last conv (UNetDecoder.py:110 after
  * get_network_from_plans.py:41-44): a = bf16(lrelu(x * scale[n][c] + shift[n][c])) is applied in the loaders, the activated
  * tensor is not materialised.  _bwd: dx = d a (the caller runs the InstanceNorm backward on it), dw / dbias over the
- * re-computed a.  Bit-identical to mvd_seghead_*_bf16 over the tensor mvd_instnorm_lrelu_apply_bf16 would write. */
+ * re-computed a.  Bit-identical to mvd_seghead_*_bf16 over the tensor mvd_instnorm_lrelu_apply_bf16 would write: the
+ * forward runs the kernel mvd_seghead_fwd_path names for the shape (one thread or 2 / 4 / 8 lanes per voxel), with the
+ * loader prologue. */
 int mvd_seghead_bf16_fused_ok(int N, long V, int C, int K);
 /* fp32 twins (mean / rstd / gamma / beta: the arithmetic of the fp32 apply pass); same eligibility query */
 int mvd_seghead_fwd_fused(const float *x, const float *mean, const float *rstd, const float *gamma, const float *beta, float slope,
@@ -345,6 +347,14 @@ int mvd_seghead_fwd(const float *x, const float *w, const float *bias, float *lo
 size_t mvd_seghead_bwd_workspace_bytes(int N, long V, int C, int K);
 int mvd_seghead_bwd(const float *x, const float *w, const float *dlogits, float *dx, float *dw, float *dbias, int N,
                     long V, int C, int K, int accumulate, void *ws, size_t ws_bytes, void *stream);
+/* Which kernel the entry points above (fp32 and bf16 alike) run for a shape; no device call.  `aligned`: bit 0 x, bit 1 w,
+ * bit 2 dlogits, bit 3 dx lies on a 16-byte boundary.  -1: a shape the entry points refuse (K > 8, ...).
+ * fwd: 0 k_seghead_fwd, 1 k_seghead_fwd_vox (C % 4 == 0), 2 / 4 / 8 k_seghead_fwd_voxp<P> (C % 32 == 0, C >= 64, fewer than
+ * 2^20 voxels in the batch).  dx: 0 k_seghead_dx, 1 k_seghead_dx4 (C % 4 == 0, C <= 1024, V % 4 == 0).
+ * dw: 0 k_seghead_dw, 1 k_seghead_dw4 (C % 4 == 0, C <= 1024), 2 k_seghead_dw4v (V % 4 == 0 as well). */
+int mvd_seghead_fwd_path(int N, long V, int C, int K, int aligned);
+int mvd_seghead_dx_path(int N, long V, int C, int K, int aligned);
+int mvd_seghead_dw_path(int N, long V, int C, int K, int aligned);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Fused softmax + cross-entropy + soft-Dice statistics (K7).  Replaces DC_and_CE_loss

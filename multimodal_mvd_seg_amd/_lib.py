@@ -123,6 +123,9 @@ SIGNATURES = {
     "mvd_seghead_fwd": (c_int, [_P, _P, _P, _P, c_int, c_long, c_int, c_int, _P]),
     "mvd_seghead_bwd_workspace_bytes": (c_size_t, [c_int, c_long, c_int, c_int]),
     "mvd_seghead_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mvd_seghead_fwd_path": (c_int, [c_int, c_long, c_int, c_int, c_int]),
+    "mvd_seghead_dx_path": (c_int, [c_int, c_long, c_int, c_int, c_int]),
+    "mvd_seghead_dw_path": (c_int, [c_int, c_long, c_int, c_int, c_int]),
     "mvd_dcce_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
     "mvd_dcce_fwd": (c_int, [_P, _P, _P, c_int, c_long, c_int, _P, c_size_t, _P]),
     "mvd_dcce_finalize": (c_int, [_P, c_int, _P, c_int, _P, _P, c_long, c_int, c_int, c_int, c_float, c_float, c_float,

@@ -164,10 +164,14 @@ __global__ __launch_bounds__(256) void k_seghead_fwd_vox(const float *__restrict
 // Deep levels (many channels, few voxels: 320 channels at 8^3 is 1024 threads looping over 320 channels each): P adjacent
 // lanes share a voxel, lane p takes the 32-channel chunks p, p + P, ...; the K partial sums meet by xor-shuffles (fixed
 // tree: deterministic).  A lane reads 128 (64) contiguous bytes per chunk, the P lanes of a voxel consecutive chunks.
-template <bool XB, int P>
+// PRO as in k_seghead_fwd_vox (a lane's chunk of scale / shift is not wave-uniform here: vector loads).
+template <bool XB, int P, int PRO = 0>
 __global__ __launch_bounds__(256) void k_seghead_fwd_voxp(const float *__restrict__ x, const float *__restrict__ w,
                                                           const float *__restrict__ bias, float *__restrict__ logits, long V,
-                                                          int C, int K) {
+                                                          int C, int K, const float *__restrict__ scale = nullptr,
+                                                          const float *__restrict__ shift = nullptr, float slope = 0.f,
+                                                          const float *__restrict__ gamma = nullptr,
+                                                          const float *__restrict__ beta = nullptr) {
     const int n = blockIdx.y;
     const long gt = (long)blockIdx.x * 256 + threadIdx.x;
     const long v = gt / P;
@@ -183,6 +187,17 @@ __global__ __launch_bounds__(256) void k_seghead_fwd_voxp(const float *__restric
         float4 q[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) q[j] = ld4<XB>(x, xo + c0 + 4 * j);
+        if (PRO == 1) {
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                q[j] = seg_pro4(q[j], scale + (size_t)n * C + c0 + 4 * j, shift + (size_t)n * C + c0 + 4 * j, slope);
+        }
+        if (PRO == 2) {   // fp32: scale = mean, shift = rstd of sample n
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                q[j] = seg_pro4f(q[j], scale + (size_t)n * C + c0 + 4 * j, shift + (size_t)n * C + c0 + 4 * j, gamma + c0 + 4 * j,
+                                 beta + c0 + 4 * j, slope);
+        }
 #pragma unroll
         for (int k = 0; k < KMAX; k++)
             if (k < K) {  // uniform
@@ -191,6 +206,10 @@ __global__ __launch_bounds__(256) void k_seghead_fwd_voxp(const float *__restric
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
                     const float4 w4 = *reinterpret_cast<const float4 *>(wk + 4 * j);
+                    // Left to the compiler's contraction ON PURPOSE: it fuses part of this chain and keeps part as packed
+                    // multiplies + adds, so an explicit fmaf chain would change the bits of the plain kernel (PRO = 0: every
+                    // deep-supervision head with C >= 64).  The PRO = 1 / 2 instantiations must round like PRO = 0 (the fused
+                    // node is bit-identical to the two-node chain); tests/test_gpu_seghead.py pins that at every K and width.
                     a += q[j].x * w4.x;
                     a += q[j].y * w4.y;
                     a += q[j].z * w4.z;
@@ -883,26 +902,70 @@ static inline long cap_per_n(long total_blocks, int N) {
     return c > 0 ? c : 1;
 }
 
+// P lanes per voxel (seghead_fwd_path), plain (PRO = 0) or with the loader prologue of the fused entry points
+template <bool XB, int PRO>
+static void launch_seghead_voxp(int P, hipStream_t s, const float *x, const float *w, const float *bias, float *logits, int N,
+                                long V, int C, int K, const float *scale, const float *shift, float slope, const float *gamma,
+                                const float *beta) {
+    const dim3 grid(cdiv(V * P, 256), N);
+#define MVD_SH_LAUNCH(PP)                                                                                                    \
+    hipLaunchKernelGGL((k_seghead_fwd_voxp<XB, PP, PRO>), grid, dim3(256), 0, s, x, w, bias, logits, V, C, K, scale, shift, slope, \
+                       gamma, beta)
+    if (P == 8) MVD_SH_LAUNCH(8);
+    else if (P == 4) MVD_SH_LAUNCH(4);
+    else MVD_SH_LAUNCH(2);
+#undef MVD_SH_LAUNCH
+}
+
 extern "C" {
+
+// ---- which kernel a shape runs: ONE copy of the conditions, used by the launch code below and by the host-only queries
+// mvd_seghead_{fwd,dx,dw}_path (tests ask the library instead of restating the thresholds).  `aligned`: bit 0 x, bit 1 w,
+// bit 2 dlogits, bit 3 dx on a 16-byte boundary.  -1: a shape the entry points refuse.
+enum { SH_AL_X = 1, SH_AL_W = 2, SH_AL_DL = 4, SH_AL_DX = 8 };
+static inline bool seghead_shape_ok(int N, long V, int C, int K) {
+    return N > 0 && N <= 65535 && V > 0 && C > 0 && K > 0 && K <= KMAX;
+}
+static inline int seghead_align_mask(const void *x, const void *w, const void *dl, const void *dx) {
+    return ((((uintptr_t)x) & 15) == 0 ? SH_AL_X : 0) | ((((uintptr_t)w) & 15) == 0 ? SH_AL_W : 0) |
+           ((((uintptr_t)dl) & 15) == 0 ? SH_AL_DL : 0) | ((((uintptr_t)dx) & 15) == 0 ? SH_AL_DX : 0);
+}
+// 0 k_seghead_fwd, 1 k_seghead_fwd_vox, 2 / 4 / 8 k_seghead_fwd_voxp<P>
+static int seghead_fwd_path(int N, long V, int C, int K, int aligned) {
+    if (!seghead_shape_ok(N, V, C, K)) return -1;
+    // few voxels, many channels: 2 / 4 / 8 lanes per voxel (>= 2 chunks of 32 channels per lane where C allows)
+    if (C % 32 == 0 && C >= 64 && (aligned & (SH_AL_X | SH_AL_W)) == (SH_AL_X | SH_AL_W) && (long)N * V < (1L << 20))
+        return C >= 256 ? 8 : (C >= 128 ? 4 : 2);
+    if (C % 4 == 0 && (aligned & SH_AL_X)) return 1;
+    return 0;
+}
+// 0 k_seghead_dx, 1 k_seghead_dx4
+static int seghead_dx_path(int N, long V, int C, int K, int aligned) {
+    if (!seghead_shape_ok(N, V, C, K)) return -1;
+    const int need = SH_AL_DX | SH_AL_W | SH_AL_DL;
+    return (C % 4 == 0 && C / 4 <= 256 && V % 4 == 0 && (aligned & need) == need) ? 1 : 0;
+}
+// rows of 4-channel groups per 256-thread block of k_seghead_dw4 / dw4v (0: C is not served by them) and their LDS bytes
+static inline int seghead_dw_rows(int C) { return (C % 4 == 0 && C / 4 <= 256) ? 256 / (C / 4) : 0; }
+static inline size_t seghead_dw_lds(int C, int K) { return (size_t)seghead_dw_rows(C) * (K * C + K) * sizeof(float); }
+// 0 k_seghead_dw, 1 k_seghead_dw4, 2 k_seghead_dw4v
+static int seghead_dw_path(int N, long V, int C, int K, int aligned) {
+    if (!seghead_shape_ok(N, V, C, K)) return -1;
+    if (!(seghead_dw_rows(C) >= 1 && seghead_dw_lds(C, K) <= 60 * 1024 && (aligned & SH_AL_X))) return 0;
+    return (V % 4 == 0 && (aligned & SH_AL_DL)) ? 2 : 1;
+}
 
 static int seghead_fwd_impl(const float *x, bool xb, const float *w, const float *bias, float *logits, int N, long V,
                             int C, int K, void *stream) {
     MVD_REQUIRE(x && w && bias && logits, "seghead_fwd: null pointer");
-    MVD_REQUIRE(N > 0 && N <= 65535 && V > 0 && C > 0 && K > 0 && K <= KMAX, "seghead_fwd: bad shape (K<=8)");
-    if (C % 32 == 0 && C >= 64 && (((uintptr_t)x | (uintptr_t)w) & 15) == 0 && (long)N * V < (1L << 20)) {
-        // few voxels, many channels: 2 / 4 / 8 lanes per voxel (>= 2 chunks of 32 channels per lane where C allows)
-        const int P = C >= 256 ? 8 : (C >= 128 ? 4 : 2);
-        const dim3 grid(cdiv(V * P, 256), N);
-#define MVD_SH_LAUNCH(PP)                                                                                                  \
-    hipLaunchKernelGGL((xb ? k_seghead_fwd_voxp<true, PP> : k_seghead_fwd_voxp<false, PP>), grid, dim3(256), 0, as_stream(stream), x, \
-                       w, bias, logits, V, C, K)
-        if (P == 8) MVD_SH_LAUNCH(8);
-        else if (P == 4) MVD_SH_LAUNCH(4);
-        else MVD_SH_LAUNCH(2);
-#undef MVD_SH_LAUNCH
+    MVD_REQUIRE(seghead_shape_ok(N, V, C, K), "seghead_fwd: bad shape (K<=8)");
+    const int P = seghead_fwd_path(N, V, C, K, seghead_align_mask(x, w, nullptr, nullptr));
+    if (P >= 2) {
+        if (xb) launch_seghead_voxp<true, 0>(P, as_stream(stream), x, w, bias, logits, N, V, C, K, nullptr, nullptr, 0.f, nullptr, nullptr);
+        else launch_seghead_voxp<false, 0>(P, as_stream(stream), x, w, bias, logits, N, V, C, K, nullptr, nullptr, 0.f, nullptr, nullptr);
         return check_launch("seghead_fwd (lanes per voxel)");
     }
-    if (C % 4 == 0 && (((uintptr_t)x) & 15) == 0) {
+    if (P == 1) {
         auto kv = xb ? k_seghead_fwd_vox<true> : k_seghead_fwd_vox<false>;
         hipLaunchKernelGGL(kv, dim3(cdiv(V, 256), N), dim3(256), 0, as_stream(stream), x, w, bias, logits, V, C, K,
                            (const float *)nullptr, (const float *)nullptr, 0.f, (const float *)nullptr, (const float *)nullptr);
@@ -912,6 +975,9 @@ static int seghead_fwd_impl(const float *x, bool xb, const float *w, const float
     hipLaunchKernelGGL(kern, dim3(cdiv(V, 64), N), dim3(256), 0, as_stream(stream), x, w, bias, logits, V, C, K);
     return check_launch("seghead_fwd");
 }
+int mvd_seghead_fwd_path(int N, long V, int C, int K, int aligned) { return seghead_fwd_path(N, V, C, K, aligned); }
+int mvd_seghead_dx_path(int N, long V, int C, int K, int aligned) { return seghead_dx_path(N, V, C, K, aligned); }
+int mvd_seghead_dw_path(int N, long V, int C, int K, int aligned) { return seghead_dw_path(N, V, C, K, aligned); }
 int mvd_seghead_fwd(const float *x, const float *w, const float *bias, float *logits, int N, long V, int C, int K,
                     void *stream) {
     return seghead_fwd_impl(x, false, w, bias, logits, N, V, C, K, stream);
@@ -946,11 +1012,12 @@ static int seghead_bwd_impl(const float *x, bool xb, const float *w, const float
                             float *dbias, int N, long V, int C, int K, int accumulate, void *ws, size_t ws_bytes,
                             void *stream) {
     MVD_REQUIRE(x && w && dlogits && ws, "seghead_bwd: null pointer");
-    MVD_REQUIRE(N > 0 && N <= 65535 && V > 0 && C > 0 && K > 0 && K <= KMAX, "seghead_bwd: bad shape (K<=8)");
+    MVD_REQUIRE(seghead_shape_ok(N, V, C, K), "seghead_bwd: bad shape (K<=8)");
     MVD_REQUIRE(ws_bytes >= mvd_seghead_bwd_workspace_bytes(N, V, C, K), "seghead_bwd: workspace too small");
     hipStream_t s = as_stream(stream);
+    const int aligned = seghead_align_mask(x, w, dlogits, dx);
     if (dx) {
-        if (C % 4 == 0 && C / 4 <= 256 && V % 4 == 0 && (((uintptr_t)dx | (uintptr_t)w | (uintptr_t)dlogits) & 15) == 0) {
+        if (seghead_dx_path(N, V, C, K, aligned) == 1) {
             const long R = 256 / (C / 4);
             long nb = cdiv(V / 4, R);
             if (nb > 8192) nb = 8192;
@@ -958,6 +1025,7 @@ static int seghead_bwd_impl(const float *x, bool xb, const float *w, const float
                                dx, V, C, K, accumulate);
         } else {
             size_t sm = ((size_t)K * C + (size_t)K * 64) * sizeof(float);
+            MVD_REQUIRE(sm <= 64 * 1024, "seghead_bwd: K x C too large for the LDS weight tile of the generic dx kernel");
             hipLaunchKernelGGL(xb ? k_seghead_dx<true> : k_seghead_dx<false>, dim3(cdiv(V, 64), N), dim3(256), sm, s, dlogits, w,
                                dx, V, C, K, accumulate);
         }
@@ -968,13 +1036,14 @@ static int seghead_bwd_impl(const float *x, bool xb, const float *w, const float
         int nblk;
         long chunk = seghead_chunk((long)N * V, &nblk);
         double *partial = reinterpret_cast<double *>(ws);
-        const int CG = C / 4, R = (C % 4 == 0 && CG <= 256) ? 256 / CG : 0;
-        const size_t smb = (size_t)R * (K * C + K) * sizeof(float);
-        if (R >= 1 && smb <= 60 * 1024 && (((uintptr_t)x) & 15) == 0 && V % 4 == 0 && (((uintptr_t)dlogits) & 15) == 0)
+        const int path = seghead_dw_path(N, V, C, K, aligned);
+        const int CG = C / 4, R = seghead_dw_rows(C);
+        const size_t smb = seghead_dw_lds(C, K);
+        if (path == 2)
             hipLaunchKernelGGL(xb ? k_seghead_dw4v<true> : k_seghead_dw4v<false>, dim3(nblk), dim3((R * CG + 63) / 64 * 64),
                                smb, s, x, dlogits, partial, N, V, C, K, chunk, (const float *)nullptr, (const float *)nullptr, 0.f,
                                (const float *)nullptr, (const float *)nullptr);
-        else if (R >= 1 && smb <= 60 * 1024 && (((uintptr_t)x) & 15) == 0)
+        else if (path == 1)
             hipLaunchKernelGGL(xb ? k_seghead_dw4<true> : k_seghead_dw4<false>, dim3(nblk), dim3((R * CG + 63) / 64 * 64), smb, s, x, dlogits, partial, N, V,
                                C, K, chunk);
         else
@@ -1009,6 +1078,13 @@ int mvd_seghead_fwd_bf16_fused(const uint16_t *x, const float *scale, const floa
     MVD_REQUIRE(x && scale && shift && w && bias && logits, "seghead_fwd_bf16_fused: null pointer");
     MVD_REQUIRE(mvd_seghead_bf16_fused_ok(N, V, C, K) && (((uintptr_t)x) & 15) == 0,
                 "seghead_fwd_bf16_fused: shape not served (query mvd_seghead_bf16_fused_ok)");
+    // the kernel the plain entry point runs for this shape (its accumulation order: the results are bit-identical to it)
+    const int P = seghead_fwd_path(N, V, C, K, seghead_align_mask(x, w, nullptr, nullptr));
+    if (P >= 2) {
+        launch_seghead_voxp<true, 1>(P, as_stream(stream), reinterpret_cast<const float *>(x), w, bias, logits, N, V, C, K, scale,
+                                     shift, slope, nullptr, nullptr);
+        return check_launch("seghead_fwd (fused InstanceNorm + LeakyReLU loader, lanes per voxel)");
+    }
     hipLaunchKernelGGL((k_seghead_fwd_vox<true, 1>), dim3(cdiv(V, 256), N), dim3(256), 0, as_stream(stream),
                        reinterpret_cast<const float *>(x), w, bias, logits, V, C, K, scale, shift, slope, (const float *)nullptr,
                        (const float *)nullptr);
@@ -1056,6 +1132,11 @@ int mvd_seghead_fwd_fused(const float *x, const float *mean, const float *rstd, 
     MVD_REQUIRE(x && mean && rstd && gamma && beta && w && bias && logits, "seghead_fwd_fused: null pointer");
     MVD_REQUIRE(mvd_seghead_bf16_fused_ok(N, V, C, K) && (((uintptr_t)x) & 15) == 0,
                 "seghead_fwd_fused: shape not served (query mvd_seghead_bf16_fused_ok)");
+    const int P = seghead_fwd_path(N, V, C, K, seghead_align_mask(x, w, nullptr, nullptr));
+    if (P >= 2) {
+        launch_seghead_voxp<false, 2>(P, as_stream(stream), x, w, bias, logits, N, V, C, K, mean, rstd, slope, gamma, beta);
+        return check_launch("seghead_fwd (fused InstanceNorm + LeakyReLU loader, fp32, lanes per voxel)");
+    }
     hipLaunchKernelGGL((k_seghead_fwd_vox<false, 2>), dim3(cdiv(V, 256), N), dim3(256), 0, as_stream(stream), x, w, bias, logits, V, C,
                        K, mean, rstd, slope, gamma, beta);
     return check_launch("seghead_fwd (fused InstanceNorm + LeakyReLU loader, fp32)");

@@ -187,6 +187,23 @@ class ConvT3dF64(Function):
         return dx, dw, (db if ctx.has_b else None), None
 
 
+# ----------------------------------------------------------------------------------------- 1x1x1 segmentation head
+def seghead_fwd(x, w, b):
+    """logits [N,K,D,H,W] = w [K,C] (or [K,C,1,1,1]) over the channels of x [N,C,D,H,W], plus b [K]; everything in fp64."""
+    K = w.shape[0]
+    w2 = w.to(torch.float64).reshape(K, -1)
+    return torch.einsum('kc,ncdhw->nkdhw', w2, x.to(torch.float64)) + b.to(torch.float64).view(1, K, 1, 1, 1)
+
+
+def seghead_bwd(x, w, dl):
+    """(dx, dw in the shape of w, db) of seghead_fwd for the logit gradient dl [N,K,D,H,W]; everything in fp64."""
+    K = w.shape[0]
+    w2, x64, dl64 = w.to(torch.float64).reshape(K, -1), x.to(torch.float64), dl.to(torch.float64)
+    dx = torch.einsum('kc,nkdhw->ncdhw', w2, dl64)
+    dw = torch.einsum('nkdhw,ncdhw->kc', dl64, x64).reshape(w.shape)
+    return dx, dw, dl64.sum((0, 2, 3, 4))
+
+
 # ----------------------------------------------------------------------------------------- InstanceNorm + LeakyReLU
 def instnorm_lrelu_fwd(x, gamma, beta, eps=1e-5, slope=0.01):
     """(y, z, xhat, rstd): InstanceNorm3d(eps, affine, biased variance) then LeakyReLU(slope)."""

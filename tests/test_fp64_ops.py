@@ -67,6 +67,29 @@ def test_convT3d_restatement_equals_torch_fp64(stride):
         assert float((a.detach() - r.detach()).abs().max()) <= 1e-12 * max(1.0, float(r.abs().max()))
 
 
+@pytest.mark.parametrize("N,C,K,sp", [(1, 1, 1, (1, 1, 1)), (3, 7, 8, (3, 5, 4)), (2, 33, 5, (2, 2, 2)), (1, 4, 2, (5, 7, 9))])
+def test_seghead_restatement_equals_torch_fp64(N, C, K, sp):
+    """oracle seghead_fwd / seghead_bwd (the fp64 truth of tests/test_gpu_seghead.py) against F.conv3d with autograd"""
+    g = torch.Generator().manual_seed(N * 100 + C * 10 + K)
+    x = torch.randn(N, C, *sp, generator=g, dtype=D64)
+    w = torch.randn(K, C, 1, 1, 1, generator=g, dtype=D64)
+    b = torch.randn(K, generator=g, dtype=D64)
+    xr, wr, br = x.clone().requires_grad_(), w.clone().requires_grad_(), b.clone().requires_grad_()
+    ref = F.conv3d(xr, wr, br)
+    gy = torch.randn(ref.shape, generator=g, dtype=D64)
+    ref.backward(gy)
+    y = O.seghead_fwd(x, w, b)
+    dx, dw, db = O.seghead_bwd(x, w, gy)
+    assert y.dtype == D64 and dx.dtype == D64 and dw.dtype == D64 and db.dtype == D64
+    for a, r in ((y, ref), (dx, xr.grad), (dw, wr.grad), (db, br.grad)):
+        assert a.shape == r.shape
+        assert float((a - r.detach()).abs().max()) <= 1e-12 * max(1.0, float(r.abs().max()))
+    # fp32 operands are widened, not computed in fp32; a [K,C] weight gives a [K,C] gradient
+    y32 = O.seghead_fwd(x.float(), w.float().view(K, C), b.float())
+    assert y32.dtype == D64 and torch.equal(y32, O.seghead_fwd(x.float().double(), w.float().double(), b.float().double()))
+    assert O.seghead_bwd(x, w.view(K, C), gy)[1].shape == (K, C)
+
+
 def test_instnorm_lrelu_restatement_equals_torch_fp64():
     g = torch.Generator().manual_seed(2)
     x = torch.randn(2, 5, 4, 6, 3, generator=g, dtype=D64) * 1.3 + 0.4
