@@ -339,6 +339,34 @@ int mvd_instnorm_lrelu_bwd_head(const float *x, const float *dlogits, const floa
                                 float *dbeta, int N, long V, int C, float slope, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * BatchNorm3d(eps, affine, momentum, track_running_stats) + LeakyReLU(slope), fused.  Replaces the nn.BatchNorm3d +
+ * nn.LeakyReLU of every ConvDropoutNormReLU of the BN trainer variant
+ * (variants/network_architecture/nnUNetTrainerBN.py:31-32: norm_op = get_matching_batchnorm(conv_op), norm_op_kwargs =
+ * {'eps': 1e-5, 'affine': True}).  x, y, dy, dx: [N,V,C] NDHWC, fp32 or bf16 storage (x_is_bf16 / y_is_bf16; dy has y's
+ * type, dx has x's); gamma, beta, mean, rstd, the running buffers and dgamma / dbeta are fp32 [C].  Statistics over the
+ * M = N*V values of a channel: fp64 partial sums per block, one wave per channel sums them in a fixed order (no atomics:
+ * bit-identical from run to run).  The library allocates nothing: ws of mvd_batchnorm_workspace_bytes (partials
+ * [N][nblk][C][2] doubles, nblk from mvd_batchnorm_nblk, + [C][2] floats).
+ *   _fwd (training): mean / rstd (biased variance, eps inside the root) are outputs saved for _bwd; running_mean =
+ *     (1-m) running_mean + m mean and running_var = (1-m) running_var + m var M/(M-1) are updated in place and
+ *     num_batches_tracked (ONE int64 on the device) is incremented by the finalize kernel, so a replayed graph advances
+ *     all three.  M == 1 is refused, as torch refuses it.
+ *   _eval: one pass with the running statistics, which it only reads.
+ *   _bwd (of _fwd only): dx = gamma rstd (dz - sum dz / M - xhat sum(dz xhat) / M); dgamma / dbeta are overwritten. */
+int mvd_batchnorm_nblk(int N, long V, int C);
+size_t mvd_batchnorm_workspace_bytes(int N, long V, int C);
+int mvd_batchnorm_lrelu_fwd(const void *x, int x_is_bf16, const float *gamma, const float *beta, void *y, int y_is_bf16,
+                            float *mean, float *rstd, float *running_mean, float *running_var,
+                            int64_t *num_batches_tracked, int N, long V, int C, float eps, double momentum, float slope,
+                            void *ws, size_t ws_bytes, void *stream);
+int mvd_batchnorm_lrelu_eval(const void *x, int x_is_bf16, const float *gamma, const float *beta, void *y, int y_is_bf16,
+                             const float *running_mean, const float *running_var, int N, long V, int C, float eps,
+                             float slope, void *stream);
+int mvd_batchnorm_lrelu_bwd(const void *x, int x_is_bf16, const void *dy, int y_is_bf16, const float *gamma,
+                            const float *beta, const float *mean, const float *rstd, void *dx, float *dgamma, float *dbeta,
+                            int N, long V, int C, float slope, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * 1x1x1 segmentation head (K5): x NDHWC [N,V,C] -> logits planar [N,K,V].  Replaces decoder.seg_layers[s]
  * (UNetDecoder.py:70,110).  w: torch layout [K][C], bias [K]. */
 int mvd_seghead_fwd(const float *x, const float *w, const float *bias, float *logits, int N, long V, int C, int K,

@@ -9,3 +9,14 @@ not need a GPU; running any op does, and fails loudly when libmvdseg_hip.so is m
 from . import _lib  # noqa: F401
 
 __version__ = "0.1.0"
+
+__all__ = ["nnUNetTrainerBNMI355"]
+
+
+def __getattr__(name):
+    # the trainer variant a user names on the command line (nnUNetTrainerBN); resolved on first use so that importing the
+    # package stays as light as before
+    if name == "nnUNetTrainerBNMI355":
+        from .trainer import nnUNetTrainerBNMI355
+        return nnUNetTrainerBNMI355
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

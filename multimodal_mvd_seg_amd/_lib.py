@@ -5,7 +5,7 @@ The product path has NO fallback: if the shared library is missing or a call fai
 """
 import ctypes
 import os
-from ctypes import c_float, c_int, c_long, c_size_t, c_uint64, c_void_p
+from ctypes import c_double, c_float, c_int, c_long, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmvdseg_hip.so")
@@ -120,6 +120,13 @@ SIGNATURES = {
     "mvd_set_instnorm_small_max": (c_int, [c_long]),
     "mvd_instnorm_lrelu_bwd_head": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_float, _P,
                                             c_size_t, _P]),
+    "mvd_batchnorm_nblk": (c_int, [c_int, c_long, c_int]),
+    "mvd_batchnorm_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
+    "mvd_batchnorm_lrelu_fwd": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_float,
+                                        c_double, c_float, _P, c_size_t, _P]),
+    "mvd_batchnorm_lrelu_eval": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_long, c_int, c_float, c_float, _P]),
+    "mvd_batchnorm_lrelu_bwd": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_float, _P,
+                                        c_size_t, _P]),
     "mvd_seghead_fwd": (c_int, [_P, _P, _P, _P, c_int, c_long, c_int, c_int, _P]),
     "mvd_seghead_bwd_workspace_bytes": (c_size_t, [c_int, c_long, c_int, c_int]),
     "mvd_seghead_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_int, c_int, _P, c_size_t, _P]),

@@ -57,6 +57,30 @@ class HipInstanceNorm3d(nn.InstanceNorm3d):
         return ops.InstanceNormLeakyReLUFn.apply(x, self.weight, self.bias, self.eps, 1.0)
 
 
+class HipBatchNorm3d(nn.BatchNorm3d):
+    """nn.BatchNorm3d of the BN trainer variant (nnUNetTrainerBN.py:31-32); torch registers weight, bias, running_mean,
+    running_var and num_batches_tracked, so the state_dict keys are the reference's.  Inside ConvDropoutNormReLU it is
+    fused with the LeakyReLU (mvd_batchnorm_lrelu_fwd / _eval); calling it alone applies slope 1 (identity activation)."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, **kwargs):
+        if not affine:
+            raise NotImplementedError("BatchNorm3d(affine=False) is not on the reference's path (nnUNetTrainerBN.py:32)")
+        if not track_running_stats:
+            raise NotImplementedError("BatchNorm3d(track_running_stats=False) is not built: the kernels keep running "
+                                      "statistics")
+        if momentum is None:
+            raise NotImplementedError("BatchNorm3d(momentum=None), the cumulative moving average, is not built")
+        super().__init__(num_features, eps=eps, momentum=momentum, affine=True, track_running_stats=True, **kwargs)
+
+    def norm_act(self, x, slope, out_bf16=False):
+        return ops.BatchNormLeakyReLUFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var,
+                                              self.num_batches_tracked, self.eps, self.momentum, slope, self.training,
+                                              out_bf16)
+
+    def forward(self, x):
+        return self.norm_act(x, 1.0)
+
+
 class HipSegLayer(nn.Conv3d):
     """1x1x1 Conv3d producing planar logits (decoder.seg_layers[s])."""
 
@@ -65,7 +89,10 @@ class HipSegLayer(nn.Conv3d):
 
 
 class ConvDropoutNormReLU(nn.Module):
-    """conv -> (no dropout) -> InstanceNorm3d -> LeakyReLU; kwargs as in get_network_from_plans.py:39-45."""
+    """conv -> (no dropout) -> InstanceNorm3d -> LeakyReLU; kwargs as in get_network_from_plans.py:39-45.  The block of a
+    BatchNorm3d network is the subclass ConvDropoutBatchNormReLU below: this class keeps refusing every other norm_op."""
+    batch_norm = False                                     # (True in ConvDropoutBatchNormReLU)
+    _norm_ops = (nn.InstanceNorm3d, HipInstanceNorm3d)     # what norm_op must subclass, what the block builds
 
     def __init__(self, conv_op, input_channels, output_channels, kernel_size, stride, conv_bias=False, norm_op=None,
                  norm_op_kwargs=None, dropout_op=None, dropout_op_kwargs=None, nonlin=None, nonlin_kwargs=None,
@@ -77,8 +104,8 @@ class ConvDropoutNormReLU(nn.Module):
             raise NotImplementedError("nonlin_first=False on the reference's path")
         # the fused kernel IS InstanceNorm3d(affine) + LeakyReLU (get_network_from_plans.py:41-44): anything else in the
         # plans would silently compute something different, so refuse it
-        if norm_op is not None and not (isinstance(norm_op, type) and issubclass(norm_op, nn.InstanceNorm3d)):
-            raise NotImplementedError(f"norm_op {norm_op!r}: only nn.InstanceNorm3d is on the reference's path")
+        if norm_op is not None and not (isinstance(norm_op, type) and issubclass(norm_op, self._norm_ops[0])):
+            raise NotImplementedError(f"norm_op {norm_op!r}: only nn.{self._norm_ops[0].__name__} is on the reference's path")
         if norm_op is None:
             raise NotImplementedError("norm_op=None: the fused conv block always normalises (InstanceNorm3d)")
         if nonlin is not None and not (isinstance(nonlin, type) and issubclass(nonlin, nn.LeakyReLU)):
@@ -86,14 +113,14 @@ class ConvDropoutNormReLU(nn.Module):
         if nonlin is None:
             raise NotImplementedError("nonlin=None: the fused conv block always applies LeakyReLU")
         if not dict(norm_op_kwargs or {'affine': True}).get('affine', False):
-            raise NotImplementedError("InstanceNorm3d(affine=False) is not on the reference's path")
+            raise NotImplementedError(f"{self._norm_ops[0].__name__}(affine=False) is not on the reference's path")
         self.input_channels, self.output_channels = input_channels, output_channels
         self.stride = _tup3(stride)
         k = _tup3(kernel_size)
         self.conv = HipConv3d(input_channels, output_channels, k, self.stride, padding=[(i - 1) // 2 for i in k],
                               dilation=1, bias=conv_bias)
         norm_op_kwargs = norm_op_kwargs or {'eps': 1e-5, 'affine': True}
-        self.norm = HipInstanceNorm3d(output_channels, **norm_op_kwargs)
+        self.norm = self._norm_ops[1](output_channels, **norm_op_kwargs)
         nonlin_kwargs = dict(nonlin_kwargs or {'inplace': True})
         self.nonlin = nonlin(**nonlin_kwargs)
         self.all_modules = nn.Sequential(self.conv, self.norm, self.nonlin)
@@ -127,6 +154,16 @@ class ConvDropoutNormReLU(nn.Module):
         return np.prod([self.output_channels, *output_size], dtype=np.int64)
 
 
+class ConvDropoutBatchNormReLU(ConvDropoutNormReLU):
+    """conv -> BatchNorm3d -> LeakyReLU, the block of the BN trainer variant (nnUNetTrainerBN.py:31-32): its own kernels
+    (mvd_batchnorm_lrelu_*), batch statistics in train(), running statistics in eval(); never an InstanceNorm fusion."""
+    batch_norm = True
+    _norm_ops = (nn.BatchNorm3d, HipBatchNorm3d)
+
+    def norm_act(self, y):
+        return self.norm.norm_act(y, self.nonlin.negative_slope, self.precision == "bf16")
+
+
 class StackedConvBlocks(nn.Module):
     def __init__(self, num_convs, conv_op, input_channels, output_channels, kernel_size, initial_stride,
                  conv_bias=False, norm_op=None, norm_op_kwargs=None, dropout_op=None, dropout_op_kwargs=None,
@@ -134,13 +171,16 @@ class StackedConvBlocks(nn.Module):
         super().__init__()
         if not isinstance(output_channels, (tuple, list)):
             output_channels = [output_channels] * num_convs
+        # a norm_op that subclasses nn.BatchNorm3d selects the BN block; everything else goes to (and is judged by) the
+        # InstanceNorm block
+        block = ConvDropoutBatchNormReLU if isinstance(norm_op, type) and issubclass(norm_op, nn.BatchNorm3d) \
+            else ConvDropoutNormReLU
         self.convs = nn.Sequential(
-            ConvDropoutNormReLU(conv_op, input_channels, output_channels[0], kernel_size, initial_stride, conv_bias,
-                                norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs,
-                                nonlin_first),
-            *[ConvDropoutNormReLU(conv_op, output_channels[i - 1], output_channels[i], kernel_size, 1, conv_bias,
-                                  norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs,
-                                  nonlin_first) for i in range(1, num_convs)])
+            block(conv_op, input_channels, output_channels[0], kernel_size, initial_stride, conv_bias,
+                  norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs, nonlin_first),
+            *[block(conv_op, output_channels[i - 1], output_channels[i], kernel_size, 1, conv_bias,
+                    norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs, nonlin_first)
+              for i in range(1, num_convs)])
         self.output_channels = output_channels[-1]
         self.initial_stride = _tup3(initial_stride)
 
@@ -156,7 +196,7 @@ class StackedConvBlocks(nn.Module):
         for i, blk in enumerate(blocks):
             nxt = blocks[i + 1] if i + 1 < len(blocks) else None
             fuse_next = nxt is not None and self._can_fuse(blk, nxt, x if raw is None else raw)
-            tail = raw_tail and nxt is None and FUSE_PROLOGUE[0]
+            tail = raw_tail and nxt is None and FUSE_PROLOGUE[0] and not blk.batch_norm
             if raw is None and not fuse_next and not tail:
                 x = blk(x, x2) if i == 0 else blk(x)      # the plain module call (forward hooks fire)
                 continue
@@ -174,6 +214,8 @@ class StackedConvBlocks(nn.Module):
     @staticmethod
     def _can_fuse(blk, nxt, inp):
         """Shape-only test (before anything runs) whether blk's InstanceNorm + LeakyReLU can ride in nxt's conv loader."""
+        if blk.batch_norm:   # batch statistics: the loader prologues carry per-sample scale / shift
+            return False
         train = torch.is_grad_enabled()
         mode = str(FUSE_PROLOGUE_TRAIN[0]).lower()
         if not (blk.precision == "bf16" and FUSE_PROLOGUE[0]) or (train and mode in ("0", "false")):

@@ -932,6 +932,81 @@ class InstanceNormLeakyReLUFn(Function):
         return dx, dg, db, None, None, None
 
 
+class BatchNormLeakyReLUFn(Function):
+    """BatchNorm3d(eps, affine, momentum, track_running_stats=True) + LeakyReLU(slope) fused (nnUNetTrainerBN.py:31-32).
+    training: batch statistics over (N, D, H, W); the kernel updates running_mean / running_var / num_batches_tracked in
+    place on the device (so a graph replay does too).  Otherwise one pass with the running statistics, which are only
+    read.  Per-sample statistics a producing conv may have attached to x (_mvd_tile_stats / _mvd_tile_stats16) are not
+    used: they are InstanceNorm's."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, slope, training,
+                out_bf16=False):
+        if gamma is None or beta is None:
+            raise NotImplementedError("BatchNorm3d(affine=False) is not on the reference's path (nnUNetTrainerBN.py:32)")
+        if running_mean is None or running_var is None or num_batches_tracked is None:
+            raise NotImplementedError("BatchNorm3d(track_running_stats=False) is not built: the kernels keep running "
+                                      "statistics")
+        if momentum is None:
+            raise NotImplementedError("BatchNorm3d(momentum=None), the cumulative moving average, is not built")
+        N, C = x.shape[:2]
+        V = x[0, 0].numel()
+        if training and N * V == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        _require_cuda(x, gamma, beta, running_mean, running_var, num_batches_tracked)
+        if not (running_mean.dtype == running_var.dtype == torch.float32 and num_batches_tracked.dtype == torch.int64 and
+                running_mean.is_contiguous() and running_var.is_contiguous()):
+            raise RuntimeError("batchnorm: running_mean / running_var must be contiguous fp32, num_batches_tracked int64")
+        x = to_ndhwc(x)
+        xb = _is_bf16(x)
+        yb = bool(out_bf16) or xb  # a bf16 input never widens again inside the network
+        y = empty_cl3d(x.shape, x.device, BF16 if yb else torch.float32)
+        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        ctx.training = bool(training)
+        if not training:
+            call("mvd_batchnorm_lrelu_eval", _p(x), int(xb), _p(g), _p(b), _p(y), int(yb), _p(running_mean), _p(running_var),
+                 N, V, C, float(eps), float(slope), _stream())
+            return y
+        mean = torch.empty((C,), dtype=torch.float32, device=x.device)
+        rstd = torch.empty((C,), dtype=torch.float32, device=x.device)
+        ws = _Workspace.get(query("mvd_batchnorm_workspace_bytes", N, V, C), x.device)
+        call("mvd_batchnorm_lrelu_fwd", _p(x), int(xb), _p(g), _p(b), _p(y), int(yb), _p(mean), _p(rstd), _p(running_mean),
+             _p(running_var), _p(num_batches_tracked), N, V, C, float(eps), float(momentum), float(slope), _p(ws), ws.numel(),
+             _stream())
+        ctx.save_for_backward(x, g, b, mean, rstd)
+        ctx.slope = float(slope)
+        ctx.yb = yb
+        ctx.params = (gamma, beta)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        if not ctx.training:
+            raise RuntimeError("batchnorm: backward through an eval-mode forward (running statistics) is not built; "
+                               "call .train() before a step that differentiates")
+        x, g, b, mean, rstd = ctx.saved_tensors
+        dy = to_ndhwc(dy)
+        N, C = x.shape[:2]
+        V = x[0, 0].numel()
+        dx = empty_cl3d(x.shape, x.device, x.dtype)
+        gamma, beta = ctx.params
+        sink_g = _take_grad(gamma) if ctx.needs_input_grad[1] else None
+        sink_b = _take_grad(beta) if ctx.needs_input_grad[2] else None
+        dg = sink_g if sink_g is not None else torch.empty((C,), dtype=torch.float32, device=x.device)
+        db = sink_b if sink_b is not None else torch.empty((C,), dtype=torch.float32, device=x.device)
+        ws = _Workspace.get(query("mvd_batchnorm_workspace_bytes", N, V, C), x.device)
+        call("mvd_batchnorm_lrelu_bwd", _p(x), int(_is_bf16(x)), _p(dy), int(ctx.yb), _p(g), _p(b), _p(mean), _p(rstd),
+             _p(dx), _p(dg), _p(db), N, V, C, ctx.slope, _p(ws), ws.numel(), _stream())
+        if sink_g is not None:
+            dg = None
+            _grad_done(gamma)
+        if sink_b is not None:
+            db = None
+            _grad_done(beta)
+        return (dx, dg, db) + (None,) * 8
+
+
 # NormActConv3dFn.backward: take the weight gradient through the loader prologue of k_wgrad16z (0: re-materialise the
 # activated tensor with one apply pass first -- the A/B and cross-check switch)
 WGRAD_PROLOGUE = os.environ.get("MVD_WGRAD_PROLOGUE", "1") != "0"

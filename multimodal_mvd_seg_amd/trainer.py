@@ -215,8 +215,9 @@ def make_plans(patch_size, strides, batch_size=2, base_features=32, max_features
 
 
 def get_network_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
-                           deep_supervision=True):
-    """get_network_from_plans.py:15-92 for UNet_class_name == 'PlainConvUNet'."""
+                           deep_supervision=True, norm_op=nn.InstanceNorm3d, norm_op_kwargs=None):
+    """get_network_from_plans.py:15-92 for UNet_class_name == 'PlainConvUNet'.  norm_op / norm_op_kwargs: what the
+    network_architecture trainer variants replace (nnUNetTrainerBN.py:31-32); the default is the builder's own."""
     num_stages = len(configuration_manager.conv_kernel_sizes)
     dim = len(configuration_manager.conv_kernel_sizes[0])
     if dim != 3:
@@ -232,7 +233,7 @@ def get_network_from_plans(plans_manager, dataset_json, configuration_manager, n
         strides=configuration_manager.pool_op_kernel_sizes, num_classes=label_manager.num_segmentation_heads,
         deep_supervision=deep_supervision, n_conv_per_stage=configuration_manager.n_conv_per_stage_encoder,
         n_conv_per_stage_decoder=configuration_manager.n_conv_per_stage_decoder, conv_bias=True,
-        norm_op=nn.InstanceNorm3d, norm_op_kwargs={'eps': 1e-5, 'affine': True}, dropout_op=None,
+        norm_op=norm_op, norm_op_kwargs=dict(norm_op_kwargs or {'eps': 1e-5, 'affine': True}), dropout_op=None,
         dropout_op_kwargs=None, nonlin=nn.LeakyReLU, nonlin_kwargs={'inplace': True})
     model.apply(InitWeights_He(1e-2))
     return model
@@ -550,8 +551,16 @@ class nnUNetTrainerMI355(object):
         data = data.to(self.device, non_blocking=True)
         target = [i.to(self.device, non_blocking=True) for i in target] if isinstance(target, list) \
             else target.to(self.device, non_blocking=True)
+        # on_validation_epoch_start (:939-940) puts the network in eval(); a caller that validates between train steps gets
+        # the same here, and its mode back afterwards.  Only BatchNorm reads the flag: running statistics, left untouched.
+        was_training = self.network.training
+        self.network.eval()
+        try:
+            with torch.no_grad():
+                l, output = self._forward_loss(data, target)
+        finally:
+            self.network.train(was_training)
         with torch.no_grad():
-            l, output = self._forward_loss(data, target)
             if self.enable_deep_supervision:
                 output, target = output[0], target[0]
             lm = self.label_manager
@@ -655,6 +664,22 @@ class nnUNetTrainerMI355Benchmark_noDataLoading(nnUNetTrainerMI355):
     def initialize(self):
         super().initialize()
         self.dummy_batch = self.make_dummy_batch()
+
+
+class nnUNetTrainerBNMI355(nnUNetTrainerMI355):
+    """variants/network_architecture/nnUNetTrainerBN.py:10-42: the same trainer with BatchNorm3d in place of
+    InstanceNorm3d -- only the static network builder differs.  The running statistics are module buffers (not in
+    FlatParams): the training kernels update them on the device, so the eager and the graphed step move them alike, and
+    eval() (validation_step, perform_actual_validation, the sliding-window predictor) reads them without writing.  Under
+    data parallelism every rank keeps its own buffers and rank 0's are the ones to save, which is the checkpoint torch
+    DDP (broadcast_buffers=True) writes."""
+
+    @staticmethod
+    def build_network_architecture(plans_manager, dataset_json, configuration_manager, num_input_channels,
+                                   enable_deep_supervision: bool = True) -> nn.Module:
+        return get_network_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
+                                      deep_supervision=enable_deep_supervision, norm_op=nn.BatchNorm3d,
+                                      norm_op_kwargs={'eps': 1e-5, 'affine': True})
 
 
 # ------------------------------------------------------------------------------------------------ MVD dual branch
