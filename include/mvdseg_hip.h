@@ -542,6 +542,23 @@ int mvd_sgd_nesterov_step(float *p, const float *g, float *buf, const float *sum
 int mvd_sgd_nesterov_step_dev(float *p, const float *g, float *buf, const float *sumsq, long n, const float *hyper,
                               void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Adam / AdamW (optionally amsgrad) with global-norm clipping.  Replaces torch.nn.utils.clip_grad_norm_(params, 12) +
+ * torch.optim.Adam(W).step (variants/optimizer/nnUNetTrainerAdam.py:10-13, :22-24) on flat parameter / gradient /
+ * exp_avg / exp_avg_sq [/ max_exp_avg_sq] buffers of n floats; sumsq comes from mvd_grad_sumsq.  vmax == NULL: amsgrad
+ * off.  decoupled != 0: AdamW (p *= 1 - lr*wd), else Adam (g += wd*p).
+ *   hyper: DEVICE buffer of 128 bytes, 8-byte aligned: 8 doubles written by the caller {lr, beta1, beta2, eps,
+ *     weight_decay, max_norm (<= 0: no clipping), grad_scale, unused}, then 16 floats the library writes.
+ *   step:  DEVICE int64, the number of steps taken so far (0 before the first).
+ * Two launches on `stream`: one thread sets step += 1 and forms the fp32 scalars of the update (lr / (1 - beta1^step),
+ * sqrt(1 - beta2^step), 1 - lr*wd, ...) in fp64 behind hyper's doubles; the streaming kernel reads only those, so a
+ * hipGraph-captured step follows the schedule and the bias correction without re-capture.
+ *   g *= grad_scale; g *= min(1, max_norm / (grad_scale*sqrt(sumsq)+1e-6)); weight decay; m += (1-beta1)*(g-m);
+ *   v = v*beta2 + (1-beta2)*g*g; vhat = amsgrad ? (vmax = max(vmax, v)) : v;
+ *   p -= step_size*m / (sqrt(vhat)/bc2sqrt + eps) */
+int mvd_adam_step(float *p, const float *g, float *m, float *v, float *vmax, const float *sumsq, long n, double *hyper,
+                  long long *step, int decoupled, void *stream);
+
 /* misc elementwise helpers used by the host glue (all fixed-order / exact) */
 int mvd_nchw_to_ndhwc(const float *src, float *dst, int N, int C, long V, void *stream);
 int mvd_ndhwc_to_nchw(const float *src, float *dst, int N, int C, long V, void *stream);

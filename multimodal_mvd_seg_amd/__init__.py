@@ -10,13 +10,15 @@ from . import _lib  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["nnUNetTrainerBNMI355"]
+__all__ = ["nnUNetTrainerBNMI355", "nnUNetTrainerAdamMI355", "nnUNetTrainerVanillaAdamMI355",
+           "nnUNetTrainerAdam1en3MI355", "nnUNetTrainerAdam3en4MI355", "nnUNetTrainerVanillaAdam1en3MI355",
+           "nnUNetTrainerVanillaAdam3en4MI355", "nnUNetTrainerCosAnnealMI355"]
 
 
 def __getattr__(name):
-    # the trainer variant a user names on the command line (nnUNetTrainerBN); resolved on first use so that importing the
-    # package stays as light as before
-    if name == "nnUNetTrainerBNMI355":
-        from .trainer import nnUNetTrainerBNMI355
-        return nnUNetTrainerBNMI355
+    # the trainer variants a user names on the command line (nnUNetTrainerBN, nnUNetTrainerAdam, ...); resolved on first use
+    # so that importing the package stays as light as before
+    if name in __all__:
+        from . import trainer
+        return getattr(trainer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -24,7 +24,7 @@ from torch import nn
 from . import losses, ops
 from .dataloading import DeviceDataLoader3D, get_patch_size
 from .network import InitWeights_He, MI355PlainConvUNet, MVDDualBranchNet, set_precision
-from .optim import FlatParams, FusedSGDNesterov, PolyLRScheduler
+from .optim import CosineAnnealingLR, FlatParams, FusedAdam, FusedSGDNesterov, PolyLRScheduler
 from .parallel import BucketedGradReducer, broadcast_parameters, ddp_batch_split
 
 
@@ -310,13 +310,16 @@ class nnUNetTrainerMI355(object):
         self._set_batch_size_and_oversample()
         self.was_initialized = True
 
-    def configure_optimizers(self):
+    def _flat_params(self):
         # flat buffers in forward-execution order (network.parameters_in_execution_order): the gradient all-reduce buckets --
         # contiguous slices cut from the end -- then complete in backward order (parallel.BucketedGradReducer)
         order = getattr(self.network, "parameters_in_execution_order", None)
         params = order() if order is not None else list(self.network.parameters())
         name_of = {id(p): n for n, p in self.network.named_parameters()}   # (the layout signature of the optimizer state)
-        optimizer = FusedSGDNesterov(FlatParams([(name_of.get(id(p)), p) for p in params]), self.initial_lr,
+        return FlatParams([(name_of.get(id(p)), p) for p in params])
+
+    def configure_optimizers(self):
+        optimizer = FusedSGDNesterov(self._flat_params(), self.initial_lr,
                                      weight_decay=self.weight_decay, momentum=0.99, nesterov=True, max_grad_norm=12)
         lr_scheduler = PolyLRScheduler(optimizer, self.initial_lr, self.num_epochs)
         return optimizer, lr_scheduler
@@ -680,6 +683,66 @@ class nnUNetTrainerBNMI355(nnUNetTrainerMI355):
         return get_network_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
                                       deep_supervision=enable_deep_supervision, norm_op=nn.BatchNorm3d,
                                       norm_op_kwargs={'eps': 1e-5, 'affine': True})
+
+
+# ------------------------------------------------------------------------------------------------ optimizer / schedule variants
+class nnUNetTrainerAdamMI355(nnUNetTrainerMI355):
+    """variants/optimizer/nnUNetTrainerAdam.py:8-17: AdamW(lr, weight_decay, amsgrad=True) with PolyLR.  Like the
+    reference's class it overrides configure_optimizers alone; clip_grad_norm_(12) belongs to train_step (:918) and
+    stays fused into the update (optim.FusedAdam)."""
+
+    def configure_optimizers(self):
+        optimizer = FusedAdam(self._flat_params(), lr=self.initial_lr, weight_decay=self.weight_decay, amsgrad=True,
+                              decoupled_weight_decay=True, max_grad_norm=12)
+        lr_scheduler = PolyLRScheduler(optimizer, self.initial_lr, self.num_epochs)
+        return optimizer, lr_scheduler
+
+
+class nnUNetTrainerVanillaAdamMI355(nnUNetTrainerMI355):
+    """nnUNetTrainerAdam.py:20-28: Adam(lr, weight_decay) (L2 weight decay, no amsgrad) with PolyLR."""
+
+    def configure_optimizers(self):
+        optimizer = FusedAdam(self._flat_params(), lr=self.initial_lr, weight_decay=self.weight_decay, max_grad_norm=12)
+        lr_scheduler = PolyLRScheduler(optimizer, self.initial_lr, self.num_epochs)
+        return optimizer, lr_scheduler
+
+
+class nnUNetTrainerVanillaAdam1en3MI355(nnUNetTrainerVanillaAdamMI355):
+    def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=torch.device('cuda'),
+                 specified_cfg=''):
+        super().__init__(plans, configuration, fold, dataset_json, unpack_dataset, device, specified_cfg)
+        self.initial_lr = 1e-3   # nnUNetTrainerAdam.py:35
+
+
+class nnUNetTrainerVanillaAdam3en4MI355(nnUNetTrainerVanillaAdamMI355):
+    def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=torch.device('cuda'),
+                 specified_cfg=''):
+        super().__init__(plans, configuration, fold, dataset_json, unpack_dataset, device, specified_cfg)
+        self.initial_lr = 3e-4   # :43
+
+
+class nnUNetTrainerAdam1en3MI355(nnUNetTrainerAdamMI355):
+    def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=torch.device('cuda'),
+                 specified_cfg=''):
+        super().__init__(plans, configuration, fold, dataset_json, unpack_dataset, device, specified_cfg)
+        self.initial_lr = 1e-3   # :50
+
+
+class nnUNetTrainerAdam3en4MI355(nnUNetTrainerAdamMI355):
+    def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=torch.device('cuda'),
+                 specified_cfg=''):
+        super().__init__(plans, configuration, fold, dataset_json, unpack_dataset, device, specified_cfg)
+        self.initial_lr = 3e-4   # :58
+
+
+class nnUNetTrainerCosAnnealMI355(nnUNetTrainerMI355):
+    """variants/lr_schedule/nnUNetTrainerCosAnneal.py:7-12: the base trainer's SGD with CosineAnnealingLR(T_max=num_epochs)."""
+
+    def configure_optimizers(self):
+        optimizer = FusedSGDNesterov(self._flat_params(), self.initial_lr, weight_decay=self.weight_decay, momentum=0.99,
+                                     nesterov=True, max_grad_norm=12)
+        lr_scheduler = CosineAnnealingLR(optimizer, T_max=self.num_epochs)
+        return optimizer, lr_scheduler
 
 
 # ------------------------------------------------------------------------------------------------ MVD dual branch
