@@ -17,7 +17,8 @@
 //   * U is fetched straight from L2 one step ahead of the MFMAs that use it (scalar base + 32-bit lane offset); every
 //     U fragment serves the 32 octets of the workgroup: 16 B/clk/CU, the U traffic of k_fwd_wino2;
 //   * output transform: W stage in registers, D stage across the wave pairs (w, w + 4) and H stage across the four
-//     position rows through the freed halo buffer; bias and the optional InstanceNorm statistics in the epilogue.
+//     position rows through the freed halo buffer, 16 bytes per lane and LDS instruction; stores through one scalar
+//     base per output column + a 32-bit lane offset; bias and the optional InstanceNorm statistics in the epilogue.
 // Octet i of the M tile: layer j = popcount(i >> 2) & 1, quad row qr = (i >> 2) & 3, quad column qc = i & 3.  With the
 // 80-byte slot stride and the even-x-first halo rows (k_fwd_wino2) every ds_read_b128 lane group of 16 lanes then has
 // one j and all 16 (qr, qc), i.e. 16 distinct 16-byte bank groups: all operand reads are bank-conflict free.
@@ -58,7 +59,14 @@ struct Wino3Tile {
     int nth4;                // 4-row tiles along H of the statistics layout (mvd_conv_stats_tiles)
     int nitems;
     int K;
+    unsigned rkb, rtw, rth, rtd;  // w3_recip of nkb, ntw, nth, ntd: the item decomposition stays on the scalar unit
 };
+
+// n / d for n * d < 2^31 as a multiply by m = ceil(2^31 / d) and a shift: with e = m d - 2^31 < d the quotient is exact
+// while n e < 2^31.  On wave-uniform operands this is s_mul_hi_u32 / s_mul_i32 / s_lshr_b64; a 32-bit udiv goes through
+// v_rcp_iflag_f32 and about ten vector instructions.
+inline unsigned w3_recip(int d) { return (unsigned)(((1ul << 31) + (unsigned long)d - 1) / (unsigned long)d); }
+__device__ __forceinline__ unsigned w3_div(unsigned n, unsigned m) { return (unsigned)(((unsigned long long)n * m) >> 31); }
 
 constexpr int W3S = 20;                    // floats per slot (16 channels + 4 pad: 80-byte stride)
 constexpr int W3E = 10;                    // halo extent along H and W
@@ -79,12 +87,13 @@ __global__ __launch_bounds__(512, 1) void k_fwd_wino3(const FwdGeom g, const Win
     const int per_xcd = (tg.nitems + 7) >> 3;
     const int item = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
     if (item >= tg.nitems) return;  // whole workgroup
-    unsigned r_ = (unsigned)item;
-    const int kb = __builtin_amdgcn_readfirstlane((int)(r_ % (unsigned)tg.nkb)); r_ /= (unsigned)tg.nkb;
-    const int tw_ = __builtin_amdgcn_readfirstlane((int)(r_ % (unsigned)tg.ntw)); r_ /= (unsigned)tg.ntw;
-    const int th_ = __builtin_amdgcn_readfirstlane((int)(r_ % (unsigned)tg.nth)); r_ /= (unsigned)tg.nth;
-    const int td_ = __builtin_amdgcn_readfirstlane((int)(r_ % (unsigned)tg.ntd));
-    const int n = __builtin_amdgcn_readfirstlane((int)(r_ / (unsigned)tg.ntd));
+    // item -> (kb, tw, th, td, n), kb fastest: scalar arithmetic only (host reciprocals, w3_div)
+    unsigned r_ = (unsigned)item, q_;
+    q_ = w3_div(r_, tg.rkb); const int kb = (int)(r_ - q_ * (unsigned)tg.nkb); r_ = q_;
+    q_ = w3_div(r_, tg.rtw); const int tw_ = (int)(r_ - q_ * (unsigned)tg.ntw); r_ = q_;
+    q_ = w3_div(r_, tg.rth); const int th_ = (int)(r_ - q_ * (unsigned)tg.nth); r_ = q_;
+    q_ = w3_div(r_, tg.rtd); const int td_ = (int)(r_ - q_ * (unsigned)tg.ntd);
+    const int n = (int)q_;
 
     const int C = g.C1 + g.C2;
     const int nch = C >> 4;
@@ -232,16 +241,25 @@ __global__ __launch_bounds__(512, 1) void k_fwd_wino3(const FwdGeom g, const Win
             t[p][0][r] = (acc[p][0][r] + acc[p][1][r]) + acc[p][2][r];
             t[p][1][r] = (acc[p][1][r] - acc[p][2][r]) - acc[p][3][r];
         }
-    // D stage across the wave pair (a, a + 4): z0 = (M0 + M1) + M2, z1 = M1 - (M2 + M3) over pz
+    // D stage across the wave pair (a, a + 4): z0 = (M0 + M1) + M2, z1 = M1 - (M2 + M3) over pz.  Exchange layout: a
+    // tile of 16 accumulator rows x 64 lanes is [r >> 2][lane][r & 3], so every access is one ds_write_b128 /
+    // ds_read_b128 of 16 contiguous bytes per lane (conflict free), and every reader reads the lane index it or its
+    // partner wrote.
     __syncthreads();  // all MFMA operand reads of the image are done
-    float *xr = Xs + (size_t)a * 4096 + lane;  // exchange region of position row a: 4 tiles [oz][ox]
+    v4f *xr = reinterpret_cast<v4f *>(Xs + (size_t)a * 4096) + lane;  // region of position row a: 4 tiles [oz][ox]
     if (pzh == 1) {
 #pragma unroll
         for (int ox = 0; ox < 2; ox++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                xr[(0 * 2 + ox) * 1024 + r * 64] = t[0][ox][r];                 // M2
-                xr[(1 * 2 + ox) * 1024 + r * 64] = t[0][ox][r] + t[1][ox][r];  // M2 + M3
+            for (int rq = 0; rq < 4; rq++) {
+                v4f m2, m23;
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    m2[e] = t[0][ox][rq * 4 + e];                           // M2
+                    m23[e] = t[0][ox][rq * 4 + e] + t[1][ox][rq * 4 + e];  // M2 + M3
+                }
+                xr[(0 * 2 + ox) * 256 + rq * 64] = m2;
+                xr[(1 * 2 + ox) * 256 + rq * 64] = m23;
             }
     }
     __syncthreads();
@@ -250,42 +268,57 @@ __global__ __launch_bounds__(512, 1) void k_fwd_wino3(const FwdGeom g, const Win
 #pragma unroll
         for (int ox = 0; ox < 2; ox++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const float m2 = xr[(0 * 2 + ox) * 1024 + r * 64], m23 = xr[(1 * 2 + ox) * 1024 + r * 64];
-                xr[(0 * 2 + ox) * 1024 + r * 64] = (t[0][ox][r] + t[1][ox][r]) + m2;
-                xr[(1 * 2 + ox) * 1024 + r * 64] = t[1][ox][r] - m23;
+            for (int rq = 0; rq < 4; rq++) {
+                const v4f m2 = xr[(0 * 2 + ox) * 256 + rq * 64], m23 = xr[(1 * 2 + ox) * 256 + rq * 64];
+                v4f z0, z1;
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    z0[e] = (t[0][ox][rq * 4 + e] + t[1][ox][rq * 4 + e]) + m2[e];
+                    z1[e] = t[1][ox][rq * 4 + e] - m23[e];
+                }
+                xr[(0 * 2 + ox) * 256 + rq * 64] = z0;
+                xr[(1 * 2 + ox) * 256 + rq * 64] = z1;
             }
     }
     __syncthreads();
     // H stage: wave (oz, oy, ox) = (w >> 2, (w >> 1) & 1, w & 1) finishes output (oz, oy, ox) of every octet from tile
     // [oz][ox] of position rows {0,1,2} (oy = 0: sum) or {1,2,3} (oy = 1: T1 - T2 - T3)
     const int oz = wave >> 2, oy = (wave >> 1) & 1, ox = wave & 1;
-    const float *xt = Xs + (size_t)(oz * 2 + ox) * 1024 + lane;
+    const v4f *xt = reinterpret_cast<const v4f *>(Xs + (size_t)(oz * 2 + ox) * 1024) + lane;
     float vals[16];
 #pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const float ta = xt[(size_t)(oy + 0) * 4096 + r * 64], tb = xt[(size_t)(oy + 1) * 4096 + r * 64],
-                    tc = xt[(size_t)(oy + 2) * 4096 + r * 64];
-        vals[r] = (oy == 0 ? (ta + tb) + tc : (ta - tb) - tc) + bv;
+    for (int rq = 0; rq < 4; rq++) {
+        const v4f ta = xt[(oy + 0) * 1024 + rq * 64], tb = xt[(oy + 1) * 1024 + rq * 64], tc = xt[(oy + 2) * 1024 + rq * 64];
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            vals[rq * 4 + e] = (oy == 0 ? (ta[e] + tb[e]) + tc[e] : (ta[e] - tb[e]) - tc[e]) + bv;
     }
     __builtin_amdgcn_sched_barrier(0);
-    // accumulator row r of lane half h is octet m = (r & 3) + 8 (r >> 2) + 4 h: qc = r & 3, m >> 2 = 2 (r >> 2) + h
-    float *ylane;
-    int Ks;
-    if (k < g.K1) {
-        ylane = y1 + k; Ks = g.K1;
-    } else {
-        ylane = y2 + (k - g.K1); Ks = g.K2;
+    // accumulator row r of lane half h is octet m = (r & 3) + 8 (r >> 2) + 4 h: qc = r & 3, m >> 2 = 2 (r >> 2) + h.
+    // Addresses: one scalar base per output column (r & 3) + a 32-bit lane offset per row group (r >> 2), as load_halo
+    // (the host checks that the offsets fit).  K1 is a multiple of 32, so the whole block writes one of the two tensors.
+    const bool two = kb * 32 >= g.K1;  // block-uniform
+    const int Ks = two ? g.K2 : g.K1;
+    float *ywave = (two ? y2 + (kb * 32 - g.K1) : y1 + kb * 32) +
+                   ((((size_t)n * g.Dy + (od0 + oz)) * g.Hy + (oh0 + oy)) * g.Wy + (ow0 + ox)) * Ks;
+    unsigned yoff[4];  // BYTES from ywave of column 0, row group r >> 2
+    bool yok[4];
+#pragma unroll
+    for (int rg = 0; rg < 4; rg++) {
+        const int m2 = 2 * rg + h;
+        const int j = __builtin_popcount(m2) & 1, q = m2 & 3;
+        yoff[rg] = (unsigned)(((2 * j * g.Hy + 2 * q) * g.Wy) * Ks + i) << 2;
+        yok[rg] = od0 + 2 * j + oz < g.Do && oh0 + 2 * q + oy < g.Ho;
     }
     float ssum[2] = {0.f, 0.f}, ssq[2] = {0.f, 0.f};  // per 4-row half of the tile (the 4x4x8 statistics tiles)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int m2 = 2 * (r >> 2) + h;
-        const int j = __builtin_popcount(m2) & 1, q = m2 & 3;
-        const int od = od0 + 2 * j + oz, oh = oh0 + 2 * q + oy, ow = ow0 + 2 * (r & 3) + ox;
-        if (od < g.Do && oh < g.Ho && ow < g.Wo) {
+        const int ow = ow0 + 2 * (r & 3) + ox;  // wave-uniform
+        if (yok[r >> 2] && ow < g.Wo) {
             const float val = vals[r];
-            ylane[((((size_t)n * g.Dy + od) * g.Hy + oh) * g.Wy + ow) * Ks] = val;
+            unsigned o = yoff[r >> 2];
+            asm("" : "+v"(o));  // scalar column base + 32-bit lane offset
+            *reinterpret_cast<float *>(reinterpret_cast<char *>(ywave + (size_t)(2 * (r & 3)) * Ks) + o) = val;
             ssum[(r >> 2) & 1] += val;  // (oh - oh0) >> 2 = q >> 1 = (r >> 2) & 1
             ssq[(r >> 2) & 1] += val * val;
         }
@@ -333,6 +366,8 @@ int fwd_wino3(const FwdGeom &g, const float *a1, const float *a2, const float *u
     if (g.Dy != g.Do || g.Hy != g.Ho || g.Wy != g.Wo) return -1;
     if (((uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)u) & 15) return -1;
     if ((long)g.Hi * g.Wi * (C > 0 ? (g.C1 > g.C2 ? g.C1 : g.C2) : 0) * 4 >= (1L << 31)) return -1;
+    // the kernel's 32-bit store offsets span two output planes and the tile's rows inside them
+    if ((long)(2 * g.Hy + 8) * g.Wy * (g.K1 > g.K2 ? g.K1 : g.K2) * 4 >= (1L << 31)) return -1;
     bool plain = true, mirrored = true;
     for (int t = 0; t < 27; t++) {
         const int oz = g.off[t][0], oy = g.off[t][1], ox = g.off[t][2];
@@ -353,6 +388,14 @@ int fwd_wino3(const FwdGeom &g, const float *a1, const float *a2, const float *u
     const long nitems = (long)g.N * tg.ntd * tg.nth * tg.ntw * tg.nkb;
     if (nitems > (1L << 30)) return -1;
     tg.nitems = (int)nitems;
+    // w3_div is exact while item * divisor < 2^31
+    int dmax = tg.nkb;
+    for (int d : {tg.ntw, tg.nth, tg.ntd}) dmax = d > dmax ? d : dmax;
+    if (nitems * dmax >= (1L << 31)) return -1;
+    tg.rkb = w3_recip(tg.nkb);
+    tg.rtw = w3_recip(tg.ntw);
+    tg.rth = w3_recip(tg.nth);
+    tg.rtd = w3_recip(tg.ntd);
     static PerDeviceFlag cfgd;
     if (!cfgd()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_fwd_wino3), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--what", default="fwd,dgrad,wgrad")
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
-    ap.add_argument("--wino", type=int, default=1, help="fp32: 1 = Winograd entries (default, what ops.py calls), 0 = direct")
+    ap.add_argument("--wino", type=int, default=1, help="fp32: 1 = F(2x2,3x3) Winograd entries (default), 3 = F(2x2x2,3x3x3) entries (k_fwd_wino3), 0 = direct")
     args = ap.parse_args()
     bf = args.dtype == "bf16"
     dt = torch.bfloat16 if bf else torch.float32
@@ -61,16 +61,22 @@ def main():
         ks, sd = i3((3, 3, 3)), i3((st, st, st))
         flops = 2.0 * 27 * (C1 + C2) * K * N * So ** 3
         uf = ub = None
-        if not bf and args.wino and query("mvd_conv_wino_applicable", N, S, S, S, C1, C2, K, i3((3, 3, 3)), i3((st, st, st))):
+        e3 = ""  # "3": the *_wino3 entries with the 3-D tables in place of uf / ub
+        if not bf and args.wino == 3 and query("mvd_conv_wino3_applicable", N, S, S, S, C1, C2, K, i3((3, 3, 3)), i3((st, st, st))):
+            uf = torch.empty(query("mvd_wino3_weight_elems", C1 + C2, K), device=dev)
+            ub = torch.empty(query("mvd_wino3_weight_elems", C1 + C2, K), device=dev)
+            call("mvd_pack_weight_wino3", P(w), P(uf), P(ub), K, C1 + C2, s)
+            e3 = "3"
+        elif not bf and args.wino and query("mvd_conv_wino_applicable", N, S, S, S, C1, C2, K, i3((3, 3, 3)), i3((st, st, st))):
             uf = torch.empty(query("mvd_wino_weight_elems", C1 + C2, K), device=dev)
             ub = torch.empty(query("mvd_wino_weight_elems", C1 + C2, K), device=dev)
             call("mvd_pack_weight_wino", P(w), P(uf), P(ub), K, C1 + C2, s)
         fns = {
-            "fwd": (lambda: call("mvd_conv3d_fwd_wino", P(x1), C1, P(x2), C2, P(wf), P(uf), P(bias), P(y), N, S, S, S, K, ks,
+            "fwd": (lambda: call("mvd_conv3d_fwd_wino" + e3, P(x1), C1, P(x2), C2, P(wf), P(uf), P(bias), P(y), N, S, S, S, K, ks,
                                  sd, P(ws), ws.numel(), s)) if not bf else
                    (lambda: call("mvd_conv3d_fwd_bf16", P(x1), C1, P(x2), C2, P(wf), P(bias), P(y), N, S, S, S, K, ks, sd,
                                  P(ws), ws.numel(), s)),
-            "dgrad": (lambda: call("mvd_conv3d_dgrad_wino", P(dy), P(wb), P(ub), P(dx1), C1, P(dx2), C2, N, S, S, S, K, ks,
+            "dgrad": (lambda: call("mvd_conv3d_dgrad_wino" + e3, P(dy), P(wb), P(ub), P(dx1), C1, P(dx2), C2, N, S, S, S, K, ks,
                                    sd, P(ws), ws.numel(), s)) if not bf else
                      (lambda: call("mvd_conv3d_dgrad_bf16", P(dy), P(wb), P(dx1), C1, P(dx2), C2, N, S, S, S, K, ks, sd,
                                    P(ws), ws.numel(), s)),
