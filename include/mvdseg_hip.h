@@ -131,6 +131,27 @@ int mvd_conv3d_fwd_stats(const float *x1, int C1, const float *x2, int C2, const
 int mvd_conv3d_dgrad_wino3(const float *dy, const float *wb, const float *vb, float *dx1, int C1, float *dx2, int C2,
                            int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
                            size_t ws_bytes, void *stream);
+/* F(2x2,3x3) engine of the 9-tap in-plane layers: kernel size (1,3,3), stride 1, 32-multiple channels -- the convs of a 2-D
+ * network seen as [N,C,1,H,W] and the in-plane layers of anisotropic 3-D plans (4 multiply-adds per output and channel
+ * pair instead of 9).  Other 9-tap kernels, e.g. (3,3,1), keep the direct engine.  mvd_conv_wino2p_applicable: forward (1)
+ * | input gradient (2) bits for which the kernel has its minimum of work items (4 planes x 4 x 8 outputs x 32 produced
+ * channels over all N*D planes; mvd_set_wino2p_min_items, < 0 restores the default, a huge value turns the kernel off; env
+ * MVD_WINO2P_MIN, MVD_WINO=0).  mvd_pack_weight_wino2p: torch weight [K][C][1][3][3] -> pf (forward) / pb (input gradient),
+ * mvd_wino2p_weight_elems(C, K) = 16*C*K floats each; in mvd_pack_weights_batch3 a job with T = 9 takes them as uf / ub.
+ * The *_wino2p conv entries take the table in place of uf / ub and fall back to the direct engines where the kernel does
+ * not run.  No statistics epilogue.  mvd_conv_wino2p_applicable judges the shape alone: a call whose pointers are not
+ * 16-byte aligned, or with more than 2^30 work items or K*32 >= 2^27, also falls back to the direct engines (same
+ * results) although the bits were set. */
+int mvd_set_wino2p_min_items(long n);
+int mvd_conv_wino2p_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]);
+size_t mvd_wino2p_weight_elems(int C, int K);
+int mvd_pack_weight_wino2p(const float *w, float *pf, float *pb, int K, int C, void *stream);
+int mvd_conv3d_fwd_wino2p(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *pf,
+                          const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
+                          const int stride[3], void *ws, size_t ws_bytes, void *stream);
+int mvd_conv3d_dgrad_wino2p(const float *dy, const float *wb, const float *pb, float *dx1, int C1, float *dx2, int C2,
+                            int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
+                            size_t ws_bytes, void *stream);
 /* F(2x2x2,3x3x3) weight gradient: mvd_conv3d_wgrad runs it for fp32 3x3x3 stride-1 convs with 32-multiple channels
  * (two inputs included) that have at least the minimum of work items PER SAMPLE (2x8x8 dy voxels x 32 input x 32
  * output channels; mvd_set_wgrad_wino3_min_items, < 0 restores the default) unless MVD_WGRAD_WINO3=0 or MVD_WINO=0.

@@ -59,6 +59,14 @@ SIGNATURES = {
                                            _I3, _I3, _P, c_size_t, _P]),
     "mvd_conv3d_dgrad_wino3": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
                                        c_size_t, _P]),
+    "mvd_set_wino2p_min_items": (c_int, [c_long]),
+    "mvd_conv_wino2p_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
+    "mvd_wino2p_weight_elems": (c_size_t, [c_int, c_int]),
+    "mvd_pack_weight_wino2p": (c_int, [_P, _P, _P, c_int, c_int, _P]),
+    "mvd_conv3d_fwd_wino2p": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
+                                      c_size_t, _P]),
+    "mvd_conv3d_dgrad_wino2p": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
+                                        c_size_t, _P]),
     "mvd_set_wgrad_wino3_min_items": (c_int, [c_long]),
     "mvd_conv_wgrad_wino3_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
     "mvd_wgrad_wino3_launches": (c_long, []),

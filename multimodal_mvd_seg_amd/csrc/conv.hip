@@ -19,6 +19,10 @@ static long g_wino_min_items = getenv("MVD_WINO_MIN") ? atol(getenv("MVD_WINO_MI
 // sample
 static const long kWino3MinItemsDefault = 128;
 static long g_wino3_min_items = getenv("MVD_WINO3_MIN") ? atol(getenv("MVD_WINO3_MIN")) : kWino3MinItemsDefault;
+// the F(2x2,3x3) engine of the 9-tap 1x3x3 layers (conv_wino2p.hip) takes a layer with at least this many work items (4 planes
+// x 4 x 8 outputs x 32 channels, over all N * D planes: its tile spans samples when D = 1); MVD_WINO2P_MIN overrides
+static const long kWino2pMinItemsDefault = 256;
+static long g_wino2p_min_items = getenv("MVD_WINO2P_MIN") ? atol(getenv("MVD_WINO2P_MIN")) : kWino2pMinItemsDefault;
 static long wino3_items(int D, int H, int W, int K) { return (long)((D + 3) / 4) * ((H + 7) / 8) * ((W + 7) / 8) * (K / 32); }
 
 // =============================================================================================== scalar forward-type
@@ -325,6 +329,14 @@ static int run_fwd(const FwdGeom &g, const float *a1, const float *a2, const flo
         }
         return fwd_scalar(g, a1, a2, w, bias, y1, y2, s);
     }
+    if (u && g.T == 9) {  // the table of a 1x3x3 layer (mvd_pack_weight_wino2p); 27-tap problems never come here
+        if (g_engine_mode == 0 && !g_wino_off && !u3d &&
+            wino2p_items(g.N, g.Do, g.Ho, g.Wo, g.K1 + g.K2) >= g_wino2p_min_items) {
+            int r = fwd_wino2p(g, a1, a2, u, bias, y1, y2, s);
+            if (r >= 0) return r;
+        }
+        u = nullptr;
+    }
     if (u3d) {
         if (g_engine_mode == 0 && u && !g_wino_off && wino3_enabled() &&
             wino3_items(g.Do, g.Ho, g.Wo, g.K1 + g.K2) >= g_wino3_min_items) {
@@ -534,9 +546,11 @@ int mvd_pack_weights_batch3(int n, const float *const *w, float *const *wf, floa
                     "pack_weights_batch3: job without source or destination");
         MVD_REQUIRE(K[q] > 0 && C[q] > 0 && T[q] > 0 && T[q] <= MVD_MAX_TAPS, "pack_weights_batch3: bad K / C / T");
         if (uf[q] || ub[q]) MVD_REQUIRE(wino_mode() == 2, "pack_weights_batch3: Winograd tables need MVD_WINO=2");
+        // T = 9: uf / ub are the F(2x2,3x3) tables of a 1x3x3 layer (mvd_pack_weight_wino2p); the caller passes them for
+        // that kernel shape only
         if (uf[q] || ub[q] || vf[q] || vb[q])
-            MVD_REQUIRE(T[q] == 27 && !transposed[q] && K[q] % 32 == 0 && C[q] % 32 == 0,
-                        "pack_weights_batch3: Winograd tables need a 3x3x3 conv with C %% 32 == 0 and K %% 32 == 0");
+            MVD_REQUIRE((T[q] == 27 || (T[q] == 9 && !vf[q] && !vb[q])) && !transposed[q] && K[q] % 32 == 0 && C[q] % 32 == 0,
+                        "pack_weights_batch3: Winograd tables need a 3x3x3 (or, uf / ub, 1x3x3) conv with C %% 32 == 0 and K %% 32 == 0");
     }
     return pack_weights_batch(n, w, wf, wb, uf, ub, K, C, T, transposed, as_stream(stream), vf, vb);
 }
@@ -559,6 +573,47 @@ int mvd_conv3d_fwd_wino3_stats(const float *x1, int C1, const float *x2, int C2,
 static int conv3d_dgrad_impl(const float *dy, const float *wb, const float *ub, float *dx1, int C1, float *dx2, int C2,
                              int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
                              size_t ws_bytes, void *stream, bool u3d = false);
+
+// ------------------------------------------------------------------------------------- F(2x2,3x3) engine of 1x3x3 layers
+int mvd_set_wino2p_min_items(long n) {
+    g_wino2p_min_items = n < 0 ? kWino2pMinItemsDefault : n;
+    return 0;
+}
+
+/* forward (1) | input gradient (2) bits: mvd_conv3d_fwd_wino2p / mvd_conv3d_dgrad_wino2p would run k_fwd_wino2p */
+int mvd_conv_wino2p_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
+    if (g_engine_mode != 0 || g_wino_off || !ksize || !stride) return 0;
+    if (ksize[0] != 1 || ksize[1] != 3 || ksize[2] != 3) return 0;
+    for (int a = 0; a < 3; a++)
+        if (stride[a] != 1) return 0;
+    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 % 32 || C2 % 32 || K % 32 || C1 <= 0 || C2 < 0 || K <= 0) return 0;
+    const int cmax = C1 + C2 > K ? C1 + C2 : K;
+    if ((long)H * W * cmax * 4 >= (1L << 31) || (long)N * D > (1L << 30)) return 0;
+    return (wino2p_items(N, D, H, W, K) >= g_wino2p_min_items ? 1 : 0) |
+           (wino2p_items(N, D, H, W, C1 + C2) >= g_wino2p_min_items ? 2 : 0);
+}
+
+size_t mvd_wino2p_weight_elems(int C, int K) { return (size_t)16 * C * K; }
+
+int mvd_pack_weight_wino2p(const float *w, float *uf, float *ub, int K, int C, void *stream) {
+    MVD_REQUIRE(w && (uf || ub) && K > 0 && C > 0, "pack_weight_wino2p: bad arguments");
+    MVD_REQUIRE(K % 32 == 0 && C % 32 == 0, "pack_weight_wino2p: needs C %% 32 == 0 and K %% 32 == 0");
+    return pack_weight_wino2p(w, uf, ub, K, C, as_stream(stream));
+}
+
+int mvd_conv3d_fwd_wino2p(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *pf,
+                          const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
+                          const int stride[3], void *ws, size_t ws_bytes, void *stream) {
+    MVD_REQUIRE(ksize && ksize[0] == 1 && ksize[1] == 3 && ksize[2] == 3, "conv3d_fwd_wino2p: the table is that of a 1x3x3 kernel");
+    return conv3d_fwd_impl(x1, C1, x2, C2, wf, pf, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream);
+}
+
+int mvd_conv3d_dgrad_wino2p(const float *dy, const float *wb, const float *pb, float *dx1, int C1, float *dx2, int C2,
+                            int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
+                            size_t ws_bytes, void *stream) {
+    MVD_REQUIRE(ksize && ksize[0] == 1 && ksize[1] == 3 && ksize[2] == 3, "conv3d_dgrad_wino2p: the table is that of a 1x3x3 kernel");
+    return conv3d_dgrad_impl(dy, wb, pb, dx1, C1, dx2, C2, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream);
+}
 
 int mvd_conv3d_dgrad(const float *dy, const float *wb, float *dx1, int C1, float *dx2, int C2, int N, int D, int H, int W,
                      int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {

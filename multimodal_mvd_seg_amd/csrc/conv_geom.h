@@ -91,6 +91,13 @@ int fwd_wino3(const FwdGeom &g, const float *a1, const float *a2, const float *u
               hipStream_t s, float *stats = nullptr, int *stats_done = nullptr);
 int pack_weight_wino3(const float *w, float *uf, float *ub, int K, int C, hipStream_t s);
 int wino3_enabled();  // MVD_WINO3: 0 off, 1 (default) on
+// F(2x2,3x3) engine of the 9-tap in-plane (1x3x3, stride 1) problems (conv_wino2p.hip): the fwd_wino contract with the
+// table of pack_weight_wino2p (16*C*K floats); no statistics epilogue.  wino2p_items: its work items (4 planes x 4 x 8
+// outputs x 32 channels) for N*D planes
+int fwd_wino2p(const FwdGeom &g, const float *a1, const float *a2, const float *u, const float *bias, float *y1, float *y2,
+               hipStream_t s);
+int pack_weight_wino2p(const float *w, float *uf, float *ub, int K, int C, hipStream_t s);
+long wino2p_items(int N, int D, int H, int W, int K);
 int dgrad32s(int N, int D, int H, int W, int C, int K, int Do, int Ho, int Wo, const float *dy, const float *wb, float *dx,
              hipStream_t s, int accumulate = 0);
 // bf16 twin (conv_bf16.hip): all eight parity classes of a 3x3x3 stride-2 conv's input gradient from one staged dy tile

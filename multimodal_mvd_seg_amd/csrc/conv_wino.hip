@@ -333,6 +333,13 @@ __global__ __launch_bounds__(256) void k_pack_batch(const PackBatch pb) {
         const float v = J.transposed ? J.w[((size_t)c * J.K + k) * J.T + t] : J.w[((size_t)k * J.C + c) * J.T + t];
         if (J.wf) J.wf[widx(wl_ck(J.C), J.T, J.C, J.K, t, c, k)] = v;
         if (J.wb) J.wb[widx(wl_ck(J.K), J.T, J.K, J.C, t, k, c)] = v;
+        if (J.T == 9 && !J.transposed && (J.uf || J.ub)) {
+            // a 1x3x3 layer: uf / ub are the F(2x2,3x3) tables of conv_wino2p.hip (16 positions per (k, c) pair over the
+            // pair's 9 threads: t and, for t < 7, t + 9)
+            const float *wp = J.w + ((size_t)k * J.C + c) * 9;
+            pack_wino2p_entry(wp, J.uf, J.ub, J.K, J.C, k, c, t);
+            if (t + 9 < 16) pack_wino2p_entry(wp, J.uf, J.ub, J.K, J.C, k, c, t + 9);
+        }
         return;
     }
     const int K = J.K, C = J.C;

@@ -38,6 +38,37 @@ __device__ __forceinline__ v2f wino2_input_transform(v2f sg, v2f &a0, v2f a1, v2
 // (x -> (x >> 1) + 5 * (x & 1)): 0, 5, 1, 6
 __device__ __forceinline__ constexpr int w2_coff(int c) { return (c >> 1) + 5 * (c & 1); }
 
+// ---------------------------------------------------------------------------- F(2x2,3x3) tables of 1x3x3 layers (conv_wino2p.hip)
+// U layout: [cc][a][e4][b][h][k][4], reduce channel c = cc*32 + h*16 + e4*4 + c4 (u2idx of conv_wino.hip without gz)
+__host__ __device__ inline size_t u2pidx(int K, int cc, int a, int b, int h, int k, int e) {
+    return (((((((size_t)cc * 4 + a) * 4 + (e >> 2)) * 4 + b) * 2 + h) * K + k) << 2) + (e & 3);
+}
+
+// one (a, b, c, k) entry of uf (forward: reduce C, produce K) and ub (input gradient: reduce K, produce C, filter mirrored
+// in both axes) from the 9 taps wp[i*3 + j] of the (k, c) pair; pos = a*4 + b.  One summation order for the per-layer and
+// the batched pack: bit-identical tables.
+__device__ __forceinline__ void pack_wino2p_entry(const float *wp, float *__restrict__ uf, float *__restrict__ ub, int K,
+                                                  int C, int k, int c, int pos) {
+    const float G[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
+    const int b = pos & 3, a = (pos >> 2) & 3;
+    if (uf) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) s += G[a][i] * G[b][j] * wp[i * 3 + j];
+        uf[u2pidx(K, c >> 5, a, b, (c >> 4) & 1, k, c & 15)] = s;
+    }
+    if (ub) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) s += G[a][i] * G[b][j] * wp[(2 - i) * 3 + (2 - j)];
+        ub[u2pidx(C, k >> 5, a, b, (k >> 4) & 1, c, k & 15)] = s;
+    }
+}
+
 // ---------------------------------------------------------------------------- F(2x2x2,3x3x3) weight tables (conv_wino3.hip)
 // U3 layout: [cc][pz][a][e][b][h][k][4], reduce channel c = cc*16 + h*8 + e*4 + c4 (e: 4-channel step of the chunk)
 __host__ __device__ inline size_t u3idx(int K, int cc, int pz, int a, int b, int h, int k, int e8) {

@@ -719,3 +719,98 @@ class DeviceDataLoader3D:
 
     def __next__(self):
         return self.generate_train_batch()
+
+
+class DeviceDataLoader2D(DeviceDataLoader3D):
+    """nnUNetDataLoader2D (data_loader_2d.py:7-86) over the same HBM-resident [C,D,H,W] cases: per sample, in the
+    reference's numpy-RNG order, the oversample decision, the class draw when forced, the slice draw (from the class's z
+    column, or uniform over the slices), get_bbox on the 2-D shape with that slice's locations (columns 0, 2, 3) and
+    overwrite_class, then crop and pad (data 0, seg -1).  The device work is DeviceDataLoader3D's on the [C,1,H,W] slice:
+    a box is (slice, y, x) with a patch of depth 1, so the crop kernels cut the slice straight out of the resident volume;
+    the SpatialTransform is the in-plane one (augment_spatial with dim == 2 is what the dummy 2-D mode runs per slice,
+    DESIGN 19: rotation about x only); mirroring runs over the two axes (bits H and W); the deep-supervision targets are
+    the order-0 picks.  Batches are data [B,C,H,W] and target a list of [B,1,h,w] (one tensor without scales).
+    patch_size / final_patch_size / mirror_axes / deep_supervision_scales are 2-D, as the 2-D trainer passes them."""
+
+    def __init__(self, data, batch_size, patch_size, final_patch_size, label_manager, oversample_foreground_percent=0.0,
+                 sampling_probabilities=None, pad_sides=None, probabilistic_oversampling=False, mirror_axes=None,
+                 deep_supervision_scales=None, device="cuda:0", rotation_for_DA=None, scale_range=(0.7, 1.4),
+                 p_rot_per_sample=0.2, p_scale_per_sample=0.2, p_rot_per_axis=1.0, intensity_augmentation=False,
+                 mask_channels=None):
+        if len(patch_size) != 2 or len(final_patch_size) != 2:
+            raise ValueError("DeviceDataLoader2D: patch_size and final_patch_size have two axes")
+        if intensity_augmentation:
+            # the blur kernel filters all three axes of a volume; on an extent-1 axis that is a multiplication by the sum of
+            # the weights, which the 2-D transform does not do -- not routed around yet, so not offered
+            raise NotImplementedError("DeviceDataLoader2D: the intensity stage is not built for the 2d configuration")
+        if mask_channels is not None and any(mask_channels):
+            raise NotImplementedError("DeviceDataLoader2D: MaskTransform belongs to the intensity stage, which is not built "
+                                      "for the 2d configuration")
+        if mirror_axes and max(mirror_axes) > 1:
+            raise ValueError("DeviceDataLoader2D: mirror_axes are axes of the slice, (0, 1) at most")
+        super().__init__(data, batch_size, (1, *patch_size), (1, *final_patch_size), label_manager,
+                         oversample_foreground_percent=oversample_foreground_percent,
+                         sampling_probabilities=sampling_probabilities,
+                         pad_sides=None if pad_sides is None else (0, *pad_sides),
+                         probabilistic_oversampling=probabilistic_oversampling,
+                         mirror_axes=[a + 1 for a in mirror_axes] if mirror_axes else None,
+                         deep_supervision_scales=None if deep_supervision_scales is None
+                         else [(1, *s) for s in deep_supervision_scales],
+                         device=device, rotation_for_DA=rotation_for_DA, scale_range=scale_range,
+                         p_rot_per_sample=p_rot_per_sample, p_scale_per_sample=p_scale_per_sample,
+                         p_rot_per_axis=p_rot_per_axis, do_dummy_2d_data_aug=True)
+
+    def get_bbox_2d(self, data_shape, force_fg, class_locations, overwrite_class=None, verbose=False):
+        """get_bbox over the two axes of a slice (class_locations rows are (c, y, x))."""
+        full = (self.patch_size, self.need_to_pad)
+        self.patch_size, self.need_to_pad = self.patch_size[1:], self.need_to_pad[1:]
+        try:
+            return self.get_bbox(data_shape, force_fg, class_locations, overwrite_class, verbose)
+        finally:
+            self.patch_size, self.need_to_pad = full
+
+    def select_slice_and_bbox(self, j, shape, properties):
+        """data_loader_2d.py:17-62 for sample j of a case of shape [C,D,H,W]: (slice, lower corner (y, x))."""
+        force_fg = self.get_do_oversample(j)
+        locations = properties['class_locations']
+        if not force_fg:
+            selected = self.annotated_classes_key if self.has_ignore else None
+        else:
+            eligible = [k for k in locations.keys() if len(locations[k]) > 0]
+            if len(eligible) > 1:   # the all-annotated-classes key only serves cases that have nothing more specific
+                for i, k in enumerate(eligible):
+                    if isinstance(k, tuple) and k == self.annotated_classes_key:
+                        del eligible[i]
+                        break
+            selected = eligible[np.random.choice(len(eligible))] if len(eligible) > 0 else None
+        if selected is not None:
+            z = int(np.random.choice(locations[selected][:, 1]))
+            rows = locations[selected]
+            in_slice = {selected: rows[rows[:, 1] == z][:, (0, 2, 3)]}
+        else:
+            z = int(np.random.choice(shape[1]))
+            in_slice = None
+        lbs, _ = self.get_bbox_2d(tuple(shape[2:]), force_fg if selected is not None else None, in_slice,
+                                  overwrite_class=selected)
+        return z, [int(v) for v in lbs]
+
+    def plan_batch(self):
+        """keys, then per sample (oversample?, class, slice, bbox) -> boxes (slice, y, x); then per sample the
+        SpatialTransform draws (only with rotation_for_DA), then per sample the mirror draw."""
+        keys = self.get_indices()
+        boxes = []
+        for j, k in enumerate(keys):
+            data, _, properties = self._case(k)
+            z, lbs = self.select_slice_and_bbox(j, tuple(data.shape), properties)
+            boxes.append([z] + lbs)
+        if self.rotation_for_DA is None:
+            return list(keys), boxes, [self.draw_mirror() for _ in keys]
+        spatial = [self.draw_spatial() for _ in keys]
+        return list(keys), boxes, spatial, [self.draw_mirror() for _ in keys]
+
+    def generate_train_batch(self, plan=None):
+        out = super().generate_train_batch(plan)
+        out['data'] = out['data'].squeeze(2)
+        t = out['target']
+        out['target'] = [i.squeeze(2) for i in t] if isinstance(t, list) else t.squeeze(2)
+        return out

@@ -69,15 +69,24 @@ def compute_gaussian(tile_size: Sequence[int], sigma_scale: float = 1. / 8, valu
 
 class SlidingWindowPredictor:
     """`predict_sliding_window_return_logits(image [C,D,H,W]) -> logits [K,D,H,W]` as nnUNetPredictor's
-    (`tile_step_size`, `use_gaussian`, `use_mirroring`, `allowed_mirroring_axes` have the reference's meaning)."""
+    (`tile_step_size`, `use_gaussian`, `use_mirroring`, `allowed_mirroring_axes` have the reference's meaning).
+    A 2-tuple `patch_size` is the 2d configuration (predict_from_raw_data.py:530-547): the [C,D,H,W] image is predicted
+    slice by slice with a 2-D network, padding, Gaussian and mirroring over the last two axes only.  `slice_batch`: how
+    many slices' tiles of the same in-plane origin go through the network as one batch (one 2-D tile per forward is
+    launch-bound; InstanceNorm is per sample, so a slice's result does not depend on the batching; 1 = one tile per
+    forward)."""
 
     def __init__(self, network: torch.nn.Module, patch_size: Sequence[int], num_segmentation_heads: int,
                  tile_step_size: float = 0.5, use_gaussian: bool = True, use_mirroring: bool = True,
-                 allowed_mirroring_axes: Tuple[int, ...] = (0, 1, 2), device: torch.device = torch.device('cuda')):
+                 allowed_mirroring_axes: Tuple[int, ...] = (0, 1, 2), device: torch.device = torch.device('cuda'),
+                 slice_batch: int = 8):
         if torch.device(device).type != 'cuda':
             raise RuntimeError("SlidingWindowPredictor needs an MI355X (device type 'cuda'); there is no CPU path")
         self.network = network
         self.patch_size = tuple(int(i) for i in patch_size)
+        if len(self.patch_size) not in (2, 3):
+            raise ValueError(f"patch_size must have 2 or 3 axes, got {self.patch_size}")
+        self.slice_batch = max(1, int(slice_batch))
         self.num_heads = int(num_segmentation_heads)
         self.tile_step_size = tile_step_size
         self.use_gaussian = use_gaussian
@@ -86,8 +95,12 @@ class SlidingWindowPredictor:
         self.device = torch.device(device)
         self._gaussian = None
 
-    # predict_from_raw_data.py:528-560 (3-D branch)
+    # predict_from_raw_data.py:528-560: the 3-D branch, and the slice-wise 2-D branch (:530-547: for each slice d, for sx,
+    # for sy) whose entries are (d, sx, sy)
     def _internal_get_sliding_window_slicers(self, image_size):
+        if len(self.patch_size) < len(image_size):
+            steps = compute_steps_for_sliding_window(image_size[1:], self.patch_size, self.tile_step_size)
+            return [(d, sx, sy) for d in range(image_size[0]) for sx in steps[0] for sy in steps[1]]
         steps = compute_steps_for_sliding_window(image_size, self.patch_size, self.tile_step_size)
         return [(sx, sy, sz) for sx in steps[0] for sy in steps[1] for sz in steps[2]]
 
@@ -96,7 +109,9 @@ class SlidingWindowPredictor:
         if not self.use_mirroring or not self.allowed_mirroring_axes:
             return []
         ax = self.allowed_mirroring_axes
-        assert max(ax) <= 2, 'mirror_axes does not match the dimension of the input!'
+        assert max(ax) <= len(self.patch_size) - 1, 'mirror_axes does not match the dimension of the input!'
+        if len(self.patch_size) == 2:   # axes (0, 1) of the slice are H and W: bits 1 and 2 of mvd_flip_add
+            return [sum(2 << a for a in c) for c in [(0,), (1,), (0, 1)] if all(a in ax for a in c)]
         order = [(0,), (1,), (2,), (0, 1), (0, 2), (1, 2), (0, 1, 2)]
         return [sum(1 << a for a in c) for c in order if all(a in ax for a in c)]
 
@@ -120,13 +135,51 @@ class SlidingWindowPredictor:
         total = pred.clone()
         C = x.shape[1]
         K = pred.shape[1]
-        d, h, w = self.patch_size
+        if len(self.patch_size) == 2:
+            # a batch of B slices [B,C,h,w]: B*C (B*K) planes of depth 1, flipped in H / W alike
+            (h, w), d = self.patch_size, 1
+            C, K = C * x.shape[0], K * x.shape[0]
+        else:
+            d, h, w = self.patch_size
         xf = torch.empty_like(x)
         for m in masks:
             call("mvd_flip_add", P(x), P(xf), C, d, h, w, m, 0, self._s())
             pm = self._network_logits(xf)
             call("mvd_flip_add", P(pm), P(total), K, d, h, w, m, 1, self._s())
         return total, len(masks) + 1
+
+    def _predict_2d(self, img):
+        """The slice-wise branch: accumulation into the 3-D volume with mvd_sw_accumulate(pd = 1, sx = d).  Tiles are
+        grouped by in-plane origin and batched over slices; a voxel of slice d only ever receives tiles of slice d, in the
+        (sx, sy) order of the reference's loop, so the grouping does not change the order of its sums."""
+        P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        shape = tuple(img.shape[1:])
+        ph, pw = self.patch_size
+        new = [shape[0], max(shape[1], ph), max(shape[2], pw)]
+        below = [0, (new[1] - shape[1]) // 2, (new[2] - shape[2]) // 2]
+        data = torch.zeros((img.shape[0], *new), dtype=torch.float32, device=self.device)
+        data[:, :, below[1]:below[1] + shape[1], below[2]:below[2] + shape[2]] = img
+        D, H, W = new
+        K = self.num_heads
+        logits = torch.zeros((K, D, H, W), dtype=torch.float32, device=self.device)
+        npred = torch.zeros((D, H, W), dtype=torch.float32, device=self.device)
+        if self.use_gaussian and self._gaussian is None:
+            self._gaussian = torch.from_numpy(compute_gaussian(self.patch_size, 1. / 8, 1000.0)).to(self.device)
+        g = self._gaussian if self.use_gaussian else None
+        origins = []
+        for (_d, sx, sy) in self._internal_get_sliding_window_slicers((D, H, W)):
+            if (sx, sy) not in origins:
+                origins.append((sx, sy))
+        for d0 in range(0, D, self.slice_batch):
+            d1 = min(D, d0 + self.slice_batch)
+            for (sx, sy) in origins:
+                workon = data[:, d0:d1, sx:sx + ph, sy:sy + pw].permute(1, 0, 2, 3).contiguous()   # [B,C,ph,pw]
+                total, npasses = self._internal_maybe_mirror_and_predict(workon)
+                for b in range(d1 - d0):
+                    call("mvd_sw_accumulate", P(total[b]), P(g), 1.0 / npasses, P(logits), P(npred), K, 1, ph, pw, D, H, W,
+                         d0 + b, sx, sy, self._s())
+        call("mvd_sw_normalize", P(logits), P(npred), K, D * H * W, self._s())
+        return logits[:, :, below[1]:below[1] + shape[1], below[2]:below[2] + shape[2]]
 
     def predict_sliding_window_return_logits(self, input_image: torch.Tensor) -> torch.Tensor:
         assert isinstance(input_image, torch.Tensor)
@@ -140,6 +193,8 @@ class SlidingWindowPredictor:
         try:
             with torch.no_grad():
                 img = input_image.to(self.device, dtype=torch.float32)
+                if len(self.patch_size) == 2:
+                    return self._predict_2d(img)
                 # pad to at least the patch size, centred (pad_nd_image(..., 'constant', value 0), :665-667)
                 shape = tuple(img.shape[1:])
                 new = [max(s, p) for s, p in zip(shape, self.patch_size)]

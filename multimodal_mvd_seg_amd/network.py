@@ -30,10 +30,23 @@ FUSE_PROLOGUE_TRAIN = [os.environ.get("MVD_FUSE_PROLOGUE_TRAIN", "auto")]
 FUSE_SEGHEAD = [os.environ.get("MVD_FUSE_SEGHEAD", "1") != "0"]
 
 
-def _tup3(v):
+def _tup3(v, dim=3):
     if isinstance(v, (int, np.integer)):
-        return (int(v),) * 3
+        return (int(v),) * dim
     return tuple(int(i) for i in v)
+
+
+def _conv_dim(conv_op):
+    """3 for nn.Conv3d (3d_fullres), 2 for nn.Conv2d (the 2d configuration); everything else is refused."""
+    if conv_op is nn.Conv3d:
+        return 3
+    if conv_op is nn.Conv2d:
+        return 2
+    raise NotImplementedError(f"conv_op {conv_op!r}: nn.Conv3d (3d_fullres) and nn.Conv2d (2d) are built")
+
+
+def _as5(t):
+    return t.unsqueeze(2) if t is not None and t.dim() == 4 else t
 
 
 class HipConv3d(nn.Conv3d):
@@ -88,24 +101,88 @@ class HipSegLayer(nn.Conv3d):
         return ops.SegHeadFn.apply(x, self.weight, self.bias)
 
 
+# ------------------------------------------------------------------------------------------------ the 2d configuration
+# The 2-D layers are torch's 2-D modules (parameter shapes, state_dict keys, InitWeights_He dispatch) whose forward is the
+# 3-D autograd function on the [N,C,1,H,W] view of the activation: kernel (1,kh,kw), stride (1,s,s).  The PARAMETER itself
+# goes into the function ([K,C,kh,kw] is the memory of [K,C,1,kh,kw]: ops.ks3), so the packed-weight cache, the flat
+# gradient slices of optim.FlatParams and gradient sharing see the real parameter.  Called with [N,C,H,W] they return
+# [N,K,H,W]; inside the network the activations stay [N,C,1,H,W] (NDHWC), so the attributes the kernels hang on their
+# outputs (tile statistics, shared gradients) reach the consumer.
+class HipConv2d(nn.Conv2d):
+    """nn.Conv2d (kernel 3 or 1 per axis, stride 1 or 2) whose forward is ops.Conv3dFn on [N,C,1,H,W]; `x2`: a second
+    input concatenated along channels without materialising the cat."""
+
+    def forward(self, x, x2=None):
+        y = ops.Conv3dFn.apply(_as5(x), _as5(x2), self.weight, self.bias, (1,) + tuple(self.stride))
+        return y.squeeze(2) if x.dim() == 4 else y
+
+
+class HipConvTranspose2d(nn.ConvTranspose2d):
+    def forward(self, x):
+        y = ops.ConvTranspose3dFn.apply(_as5(x), self.weight, self.bias, (1,) + tuple(self.stride))
+        return y.squeeze(2) if x.dim() == 4 else y
+
+
+class HipInstanceNorm2d(nn.InstanceNorm2d):
+    """Inside ConvDropoutNormReLU it is fused with the LeakyReLU; calling it alone applies slope 1."""
+
+    def forward(self, x):
+        y = ops.InstanceNormLeakyReLUFn.apply(_as5(x), self.weight, self.bias, self.eps, 1.0)
+        return y.squeeze(2) if x.dim() == 4 else y
+
+
+class HipBatchNorm2d(nn.BatchNorm2d):
+    """nn.BatchNorm2d of the BN trainer variant on 2-D plans (get_matching_batchnorm); refusals as HipBatchNorm3d."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, **kwargs):
+        if not affine:
+            raise NotImplementedError("BatchNorm2d(affine=False) is not on the reference's path (nnUNetTrainerBN.py:32)")
+        if not track_running_stats:
+            raise NotImplementedError("BatchNorm2d(track_running_stats=False) is not built: the kernels keep running "
+                                      "statistics")
+        if momentum is None:
+            raise NotImplementedError("BatchNorm2d(momentum=None), the cumulative moving average, is not built")
+        super().__init__(num_features, eps=eps, momentum=momentum, affine=True, track_running_stats=True, **kwargs)
+
+    def norm_act(self, x, slope, out_bf16=False):
+        y = ops.BatchNormLeakyReLUFn.apply(_as5(x), self.weight, self.bias, self.running_mean, self.running_var,
+                                           self.num_batches_tracked, self.eps, self.momentum, slope, self.training,
+                                           out_bf16)
+        return y.squeeze(2) if x.dim() == 4 else y
+
+    def forward(self, x):
+        return self.norm_act(x, 1.0)
+
+
+class HipSegLayer2d(nn.Conv2d):
+    """1x1 Conv2d producing planar logits (decoder.seg_layers[s] of a 2-D network)."""
+
+    def forward(self, x):
+        y = ops.SegHeadFn.apply(_as5(x), self.weight, self.bias)
+        return y.squeeze(2) if x.dim() == 4 else y
+
+
 class ConvDropoutNormReLU(nn.Module):
     """conv -> (no dropout) -> InstanceNorm3d -> LeakyReLU; kwargs as in get_network_from_plans.py:39-45.  The block of a
     BatchNorm3d network is the subclass ConvDropoutBatchNormReLU below: this class keeps refusing every other norm_op."""
     batch_norm = False                                     # (True in ConvDropoutBatchNormReLU)
     _norm_ops = (nn.InstanceNorm3d, HipInstanceNorm3d)     # what norm_op must subclass, what the block builds
+    _norm_ops_2d = (nn.InstanceNorm2d, HipInstanceNorm2d)  # the same for conv_op = nn.Conv2d
 
     def __init__(self, conv_op, input_channels, output_channels, kernel_size, stride, conv_bias=False, norm_op=None,
                  norm_op_kwargs=None, dropout_op=None, dropout_op_kwargs=None, nonlin=None, nonlin_kwargs=None,
                  nonlin_first=False):
         super().__init__()
+        self.dim = dim = _conv_dim(conv_op) if conv_op is not None else 3
+        norm_ops = self._norm_ops if dim == 3 else self._norm_ops_2d
         if dropout_op is not None:
             raise NotImplementedError("dropout is not on the reference's path (get_network_from_plans.py:43)")
         if nonlin_first:
             raise NotImplementedError("nonlin_first=False on the reference's path")
         # the fused kernel IS InstanceNorm3d(affine) + LeakyReLU (get_network_from_plans.py:41-44): anything else in the
         # plans would silently compute something different, so refuse it
-        if norm_op is not None and not (isinstance(norm_op, type) and issubclass(norm_op, self._norm_ops[0])):
-            raise NotImplementedError(f"norm_op {norm_op!r}: only nn.{self._norm_ops[0].__name__} is on the reference's path")
+        if norm_op is not None and not (isinstance(norm_op, type) and issubclass(norm_op, norm_ops[0])):
+            raise NotImplementedError(f"norm_op {norm_op!r}: only nn.{norm_ops[0].__name__} is on the reference's path")
         if norm_op is None:
             raise NotImplementedError("norm_op=None: the fused conv block always normalises (InstanceNorm3d)")
         if nonlin is not None and not (isinstance(nonlin, type) and issubclass(nonlin, nn.LeakyReLU)):
@@ -113,14 +190,18 @@ class ConvDropoutNormReLU(nn.Module):
         if nonlin is None:
             raise NotImplementedError("nonlin=None: the fused conv block always applies LeakyReLU")
         if not dict(norm_op_kwargs or {'affine': True}).get('affine', False):
-            raise NotImplementedError(f"{self._norm_ops[0].__name__}(affine=False) is not on the reference's path")
+            raise NotImplementedError(f"{norm_ops[0].__name__}(affine=False) is not on the reference's path")
         self.input_channels, self.output_channels = input_channels, output_channels
-        self.stride = _tup3(stride)
-        k = _tup3(kernel_size)
-        self.conv = HipConv3d(input_channels, output_channels, k, self.stride, padding=[(i - 1) // 2 for i in k],
-                              dilation=1, bias=conv_bias)
+        self.stride = _tup3(stride, dim)
+        k = _tup3(kernel_size, dim)
+        if len(k) != dim or len(self.stride) != dim:
+            raise NotImplementedError(f"kernel size {k} / stride {self.stride} do not have the {dim} axes of {conv_op.__name__}")
+        if dim == 2 and not (all(i in (1, 3) for i in k) and all(i in (1, 2) for i in self.stride)):
+            raise NotImplementedError(f"2-D conv: kernel size 3 or 1 and stride 1 or 2 per axis are built (got {k}, {self.stride})")
+        self.conv = (HipConv3d if dim == 3 else HipConv2d)(input_channels, output_channels, k, self.stride,
+                                                           padding=[(i - 1) // 2 for i in k], dilation=1, bias=conv_bias)
         norm_op_kwargs = norm_op_kwargs or {'eps': 1e-5, 'affine': True}
-        self.norm = self._norm_ops[1](output_channels, **norm_op_kwargs)
+        self.norm = norm_ops[1](output_channels, **norm_op_kwargs)
         nonlin_kwargs = dict(nonlin_kwargs or {'inplace': True})
         self.nonlin = nonlin(**nonlin_kwargs)
         self.all_modules = nn.Sequential(self.conv, self.norm, self.nonlin)
@@ -159,6 +240,7 @@ class ConvDropoutBatchNormReLU(ConvDropoutNormReLU):
     (mvd_batchnorm_lrelu_*), batch statistics in train(), running statistics in eval(); never an InstanceNorm fusion."""
     batch_norm = True
     _norm_ops = (nn.BatchNorm3d, HipBatchNorm3d)
+    _norm_ops_2d = (nn.BatchNorm2d, HipBatchNorm2d)
 
     def norm_act(self, y):
         return self.norm.norm_act(y, self.nonlin.negative_slope, self.precision == "bf16")
@@ -173,8 +255,9 @@ class StackedConvBlocks(nn.Module):
             output_channels = [output_channels] * num_convs
         # a norm_op that subclasses nn.BatchNorm3d selects the BN block; everything else goes to (and is judged by) the
         # InstanceNorm block
-        block = ConvDropoutBatchNormReLU if isinstance(norm_op, type) and issubclass(norm_op, nn.BatchNorm3d) \
-            else ConvDropoutNormReLU
+        dim = _conv_dim(conv_op) if conv_op is not None else 3
+        block = ConvDropoutBatchNormReLU if isinstance(norm_op, type) and \
+            issubclass(norm_op, nn.BatchNorm3d if dim == 3 else nn.BatchNorm2d) else ConvDropoutNormReLU
         self.convs = nn.Sequential(
             block(conv_op, input_channels, output_channels[0], kernel_size, initial_stride, conv_bias,
                   norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs, nonlin_first),
@@ -182,7 +265,7 @@ class StackedConvBlocks(nn.Module):
                     norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs, nonlin_first)
               for i in range(1, num_convs)])
         self.output_channels = output_channels[-1]
-        self.initial_stride = _tup3(initial_stride)
+        self.initial_stride = _tup3(initial_stride, dim)
 
     def forward(self, x, x2=None, raw_tail=False):
         """conv -> norm -> act per block.  raw_tail (the last decoder stage in front of its seg head, bf16): the LAST block's
@@ -248,8 +331,7 @@ class PlainConvEncoder(nn.Module):
                  nonlin=None, nonlin_kwargs=None, return_skips: bool = False, nonlin_first: bool = False,
                  pool: str = 'conv'):
         super().__init__()
-        if conv_op is not nn.Conv3d:
-            raise NotImplementedError("3d_fullres path only (conv_op = nn.Conv3d)")
+        dim = _conv_dim(conv_op)
         if pool != 'conv':
             raise NotImplementedError("the reference's plans use strided convolutions (pool='conv')")
         if isinstance(kernel_sizes, int):
@@ -270,13 +352,13 @@ class PlainConvEncoder(nn.Module):
             input_channels = features_per_stage[s]
         self.stages = nn.Sequential(*stages)
         self.output_channels = list(features_per_stage)
-        self.strides = [_tup3(i) for i in strides]
+        self.strides = [_tup3(i, dim) for i in strides]
         self.return_skips = return_skips
         # read by the decoder (UNetDecoder.py:39-65)
         self.conv_op, self.norm_op, self.norm_op_kwargs = conv_op, norm_op, norm_op_kwargs
         self.nonlin, self.nonlin_kwargs = nonlin, nonlin_kwargs
         self.dropout_op, self.dropout_op_kwargs = dropout_op, dropout_op_kwargs
-        self.conv_bias, self.kernel_sizes = conv_bias, [_tup3(k) for k in kernel_sizes]
+        self.conv_bias, self.kernel_sizes = conv_bias, [_tup3(k, dim) for k in kernel_sizes]
 
     def forward(self, x):
         ret = []
@@ -312,16 +394,18 @@ class UNetDecoder(nn.Module):
             n_conv_per_stage = [n_conv_per_stage] * (n_stages_encoder - 1)
         assert len(n_conv_per_stage) == n_stages_encoder - 1
         stages, transpconvs, seg_layers = [], [], []
+        dim3 = _conv_dim(encoder.conv_op) == 3
+        HipConvTranspose, HipSeg = (HipConvTranspose3d, HipSegLayer) if dim3 else (HipConvTranspose2d, HipSegLayer2d)
         for s in range(1, n_stages_encoder):
             below = encoder.output_channels[-s]
             skip = encoder.output_channels[-(s + 1)]
             st = encoder.strides[-s]
-            transpconvs.append(HipConvTranspose3d(below, skip, st, st, bias=encoder.conv_bias))
+            transpconvs.append(HipConvTranspose(below, skip, st, st, bias=encoder.conv_bias))
             stages.append(StackedConvBlocks(
                 n_conv_per_stage[s - 1], encoder.conv_op, 2 * skip, skip, encoder.kernel_sizes[-(s + 1)], 1,
                 encoder.conv_bias, encoder.norm_op, encoder.norm_op_kwargs, encoder.dropout_op,
                 encoder.dropout_op_kwargs, encoder.nonlin, encoder.nonlin_kwargs, nonlin_first))
-            seg_layers.append(HipSegLayer(skip, num_classes, 1, 1, 0, bias=True))
+            seg_layers.append(HipSeg(skip, num_classes, 1, 1, 0, bias=True))
         self.stages = nn.ModuleList(stages)
         self.transpconvs = nn.ModuleList(transpconvs)
         self.seg_layers = nn.ModuleList(seg_layers)
@@ -399,6 +483,15 @@ class MI355PlainConvUNet(nn.Module):
     def forward(self, x, return_last_feature=False):
         if not x.is_cuda:
             raise RuntimeError("MI355PlainConvUNet runs on the MI355X only (no CPU path); move the input to cuda")
+        if _conv_dim(self.encoder.conv_op) == 2:
+            # the 2d configuration: [N,C,H,W] in, [N,K,h,w] logits out; inside, every tensor is the [N,C,1,H,W] view
+            if x.dim() != 4:
+                raise RuntimeError(f"2-D MI355PlainConvUNet: input must be [N,C,H,W], got {tuple(x.shape)}")
+            out = self.decoder(self.encoder(ops.to_ndhwc(x.unsqueeze(2))), return_last_feature)
+            sq = lambda o: [t.squeeze(2) for t in o] if isinstance(o, (list, tuple)) else o.squeeze(2)
+            if return_last_feature:
+                return sq(out[0]), (out[1].squeeze(2) if out[1] is not None else None)
+            return sq(out)
         skips = self.encoder(ops.to_ndhwc(x))
         return self.decoder(skips, return_last_feature)
 
@@ -432,6 +525,10 @@ def set_precision(module: nn.Module, precision: str):
     is no GradScaler (the reference needs one for fp16, nnUNetTrainer.py:916-920)."""
     if precision not in ("fp32", "bf16"):
         raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
+    if precision == "bf16" and any(isinstance(m, ConvDropoutNormReLU) and m.dim == 2 for m in module.modules()):
+        # the generic bf16 engines take the (1,3,3) / (1,2,2) / (1,1,1) layers, but the 2-D network's forward misses the
+        # project's bf16 bar against fp64 (DESIGN 25): refused until the layer behind that is found
+        raise NotImplementedError("bf16 mixed precision is not built for 2-D networks (the 2d configuration runs fp32)")
     for m in module.modules():
         if isinstance(m, ConvDropoutNormReLU):
             m.precision = precision

@@ -68,6 +68,14 @@ def _grad_done(param):
         done()
 
 
+def ks3(weight):
+    """Kernel size of a conv weight as three axes: a 2-D layer's [K,C,kh,kw] parameter is the [K,C,1,kh,kw] weight of the
+    same memory (the 2-D modules of network.py pass their real parameters, so that the packed-weight cache, the flat
+    gradient slices and the fused optimizer see the parameter itself)."""
+    sp = tuple(weight.shape[2:])
+    return (1,) + sp if len(sp) == 2 else sp
+
+
 def _is_cl3d(t):
     return t.dim() == 5 and t.is_contiguous(memory_format=CL3D)
 
@@ -177,8 +185,15 @@ def _pack_stamp(w, owner=None):
 
 
 def _packed(weight, transposed, want_uf=False, want_ub=False, want_vf=False, want_vb=False):
-    """uf / ub: the F(2x2,3x3) tables (mvd_pack_weight_wino), vf / vb: the F(2x2x2,3x3x3) tables (mvd_pack_weight_wino3)."""
+    """uf / ub: the F(2x2,3x3) tables (mvd_pack_weight_wino; of a 9-tap weight: those of the 1x3x3 engine,
+    mvd_pack_weight_wino2p -- the caller asks for them for kernel size (1,3,3) only), vf / vb: the F(2x2x2,3x3x3) tables
+    (mvd_pack_weight_wino3)."""
     w = weight.detach()
+    sfx2 = "2p" if w[0, 0].numel() == 9 else ""
+    if sfx2 and (want_uf or want_ub) and ks3(w) != (1, 3, 3):
+        # (3,3,1) and (3,1,3) weights have 9 taps too; the 9-tap tables -- here and as the T = 9 job of the batched
+        # repack, which packs whatever entry carries uf / ub -- are those of the in-plane kernel alone
+        raise RuntimeError(f"_packed: Winograd tables of a 9-tap weight exist for kernel size (1,3,3) only, got {ks3(w)}")
     if not w.is_contiguous():  # no cache for a strided view: pack a contiguous copy
         e = _PackEntry()
         e.gen = 0
@@ -187,10 +202,10 @@ def _packed(weight, transposed, want_uf=False, want_ub=False, want_vf=False, wan
         wc = w.contiguous()
         K, C = wc.shape[:2]
         if want_uf or want_ub:
-            n = query("mvd_wino_weight_elems", C, K)
+            n = query("mvd_wino%s_weight_elems" % sfx2, C, K)
             e.uf = torch.empty((n,), dtype=torch.float32, device=w.device) if want_uf else None
             e.ub = torch.empty((n,), dtype=torch.float32, device=w.device) if want_ub else None
-            call("mvd_pack_weight_wino", _p(wc), _p(e.uf), _p(e.ub), K, C, _stream())
+            call("mvd_pack_weight_wino" + sfx2, _p(wc), _p(e.uf), _p(e.ub), K, C, _stream())
         if want_vf or want_vb:
             n = query("mvd_wino3_weight_elems", C, K)
             e.vf = torch.empty((n,), dtype=torch.float32, device=w.device) if want_vf else None
@@ -219,7 +234,7 @@ def _packed(weight, transposed, want_uf=False, want_ub=False, want_vf=False, wan
         stale = True
     new_wino = False
     if (want_uf and e.uf is None) or (want_ub and e.ub is None):
-        n = query("mvd_wino_weight_elems", e.C, e.K)
+        n = query("mvd_wino%s_weight_elems" % sfx2, e.C, e.K)
         if want_uf and e.uf is None:
             e.uf = torch.empty((n,), dtype=torch.float32, device=w.device)
         if want_ub and e.ub is None:
@@ -240,7 +255,7 @@ def _packed(weight, transposed, want_uf=False, want_ub=False, want_vf=False, wan
         new_wino3 = e.vf is not None or e.vb is not None
         e.stamp = _pack_stamp(w, weight)
     if new_wino:
-        call("mvd_pack_weight_wino", _p(w), _p(e.uf), _p(e.ub), e.K, e.C, _stream())
+        call("mvd_pack_weight_wino" + sfx2, _p(w), _p(e.uf), _p(e.ub), e.K, e.C, _stream())
     if new_wino3:
         call("mvd_pack_weight_wino3", _p(w), _p(e.vf), _p(e.vb), e.K, e.C, _stream())
     return e
@@ -557,11 +572,13 @@ class Conv3dFn(Function):
         x1 = to_ndhwc(x1)
         x2 = to_ndhwc(x2) if x2 is not None else None
         K, C = weight.shape[:2]
-        ks = tuple(weight.shape[2:])
+        ks = ks3(weight)
         N, C1, D, H, W = x1.shape
         C2 = x2.shape[1] if x2 is not None else 0
         if C1 + C2 != C:
             raise RuntimeError(f"conv3d: weight expects {C} input channels, got {C1}+{C2}")
+        if weight.dim() == 4 and D != 1:
+            raise RuntimeError("conv3d: a 2-D weight [K,C,kh,kw] needs [N,C,1,H,W] activations")
         if x2 is not None and tuple(x2.shape[2:]) != (D, H, W):
             raise RuntimeError("conv3d: the two concatenated inputs differ in spatial size")
         bf = _is_bf16(x1)
@@ -587,13 +604,23 @@ class Conv3dFn(Function):
             wino = query("mvd_conv_wino_applicable", N, D, H, W, C1, C2, K, i3(ks), i3(stride)) if len(ks) == 3 else 0
             wino3 = query("mvd_conv_wino3_applicable", N, D, H, W, C1, C2, K, i3(ks), i3(stride)) if wino else 0
             wino2 = wino & ~wino3
-            pk = _packed(weight, False, bool(wino2 & 1), bool(wino2 & 2), bool(wino3 & 1), bool(wino3 & 2))
+            # the 9-tap in-plane layers (1x3x3: a 2-D network's convs, anisotropic 3-D plans): F(2x2,3x3) per plane where
+            # mvd_conv_wino2p_applicable has it (uf / ub of such a weight are that engine's tables), the direct engines else
+            wino2p = query("mvd_conv_wino2p_applicable", N, D, H, W, C1, C2, K, i3(ks), i3(stride)) \
+                if tuple(ks) == (1, 3, 3) else 0
+            pk = _packed(weight, False, bool((wino2 | wino2p) & 1), bool((wino2 | wino2p) & 2), bool(wino3 & 1),
+                         bool(wino3 & 2))
             wf, wb = pk.wf, pk.wb
             uf = pk.vf if wino3 & 1 else (pk.uf if wino2 & 1 else None)
-            ub = pk.vb if wino3 & 2 else (pk.ub if wino2 & 2 else None)
+            ub = pk.vb if wino3 & 2 else (pk.ub if (wino2 | wino2p) & 2 else None)
             sfx3 = "3" if wino3 & 1 else ""
             ctx.ub3 = bool(wino3 & 2)
-            if uf is not None:
+            ctx.ub2p = bool(wino2p & 2)
+            if wino2p & 1:
+                # (no statistics epilogue in this kernel: the InstanceNorm behind it runs its statistics pass)
+                call("mvd_conv3d_fwd_wino2p", _p(x1), C1, _p(x2), C2, _p(wf), _p(pk.uf), _p(bias), _p(y), N, D, H, W, K,
+                     i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
+            elif uf is not None:
                 # the Winograd kernel also emits the per-tile (sum, sum of squares) of its output: the InstanceNorm that
                 # follows (InstanceNormLeakyReLUFn picks them up from the tensor) skips its statistics pass
                 ntiles = query("mvd_conv_stats_tiles", od[0], od[1], od[2])
@@ -672,7 +699,8 @@ class Conv3dFn(Function):
                 call("mvd_conv3d_dgrad_bf16", _p(dy), _p(wb), _p(dx1), C1, _p(dx2), C2, N, D, H, W, K, i3(ks), i3(stride),
                      _p(ws), ws.numel(), _stream())
             else:
-                call("mvd_conv3d_dgrad_wino3" if ctx.ub3 else "mvd_conv3d_dgrad_wino", _p(dy), _p(wb), _p(ub), _p(dx1), C1,
+                call("mvd_conv3d_dgrad_wino3" if ctx.ub3 else ("mvd_conv3d_dgrad_wino2p" if ctx.ub2p else
+                                                               "mvd_conv3d_dgrad_wino"), _p(dy), _p(wb), _p(ub), _p(dx1), C1,
                      _p(dx2), C2, N, D, H, W, K, i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
             if need1:
                 _publish(ctx.share1, dx1)
@@ -682,7 +710,7 @@ class Conv3dFn(Function):
             T = ks[0] * ks[1] * ks[2]
             weight, bias = ctx.params
             sink_w, sink_b = _take_grad(weight), (_take_grad(bias) if has_bias else None)
-            dw = sink_w if sink_w is not None else torch.empty((K, C1 + C2, *ks), dtype=torch.float32, device=dev)
+            dw = sink_w if sink_w is not None else torch.empty(tuple(weight.shape), dtype=torch.float32, device=dev)
             db = (sink_b if sink_b is not None else torch.empty((K,), dtype=torch.float32, device=dev)) if has_bias else None
             nb = query("mvd_conv3d_wgrad_workspace_bytes", C1 + C2, K, T, N, *od)
             ws = _Workspace.get(nb, dev)
@@ -801,7 +829,7 @@ class ConvTranspose3dFn(Function):
         ctx.share = _share_of(x)
         x = to_ndhwc(x)
         C, K = weight.shape[:2]
-        if tuple(weight.shape[2:]) != tuple(stride):
+        if ks3(weight) != tuple(stride):
             raise RuntimeError("convT3d: only kernel_size == stride is on the hot path")
         N, Cx, D, H, W = x.shape
         if Cx != C:
@@ -845,7 +873,7 @@ class ConvTranspose3dFn(Function):
             T = stride[0] * stride[1] * stride[2]
             weight, bias = ctx.params
             sink_w, sink_b = _take_grad(weight), (_take_grad(bias) if has_bias else None)
-            dw = sink_w if sink_w is not None else torch.empty((C, K, *stride), dtype=torch.float32, device=dev)
+            dw = sink_w if sink_w is not None else torch.empty(tuple(weight.shape), dtype=torch.float32, device=dev)
             db = (sink_b if sink_b is not None else torch.empty((K,), dtype=torch.float32, device=dev)) if has_bias else None
             nb = query("mvd_convT3d_wgrad_workspace_bytes", C, K, T, N, D, H, W)
             ws = _Workspace.get(nb, dev)

@@ -22,7 +22,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import losses, ops
-from .dataloading import DeviceDataLoader3D, get_patch_size
+from .dataloading import DeviceDataLoader2D, DeviceDataLoader3D, get_patch_size
 from .network import InitWeights_He, MI355PlainConvUNet, MVDDualBranchNet, set_precision
 from .optim import CosineAnnealingLR, FlatParams, FusedAdam, FusedSGDNesterov, PolyLRScheduler
 from .parallel import BucketedGradReducer, broadcast_parameters, ddp_batch_split
@@ -203,25 +203,32 @@ def determine_num_input_channels(plans_manager, configuration_manager, dataset_j
 
 
 def make_plans(patch_size, strides, batch_size=2, base_features=32, max_features=320, n_conv=2, batch_dice=False,
-               conv_kernel_sizes=None):
-    """A minimal nnUNetPlans.json-shaped dict for the synthetic configurations of BASELINE.json."""
+               conv_kernel_sizes=None, configuration='3d_fullres'):
+    """A minimal nnUNetPlans.json-shaped dict for the synthetic configurations of BASELINE.json.  `configuration`: the name
+    of the entry ('2d' with a 2-tuple patch size and 2-tuple strides writes a 2-D plan)."""
     n = len(strides)
-    return {'plans_name': 'nnUNetPlans', 'configurations': {'3d_fullres': {
+    return {'plans_name': 'nnUNetPlans', 'configurations': {configuration: {
         'patch_size': list(patch_size), 'batch_size': batch_size, 'UNet_class_name': 'PlainConvUNet',
         'UNet_base_num_features': base_features, 'unet_max_num_features': max_features,
         'n_conv_per_stage_encoder': [n_conv] * n, 'n_conv_per_stage_decoder': [n_conv] * (n - 1),
-        'conv_kernel_sizes': conv_kernel_sizes or [[3, 3, 3]] * n, 'pool_op_kernel_sizes': [list(s) for s in strides],
+        'conv_kernel_sizes': conv_kernel_sizes or [[3] * len(patch_size)] * n,
+        'pool_op_kernel_sizes': [list(s) for s in strides],
         'batch_dice': batch_dice}}}
 
 
 def get_network_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
                            deep_supervision=True, norm_op=nn.InstanceNorm3d, norm_op_kwargs=None):
     """get_network_from_plans.py:15-92 for UNet_class_name == 'PlainConvUNet'.  norm_op / norm_op_kwargs: what the
-    network_architecture trainer variants replace (nnUNetTrainerBN.py:31-32); the default is the builder's own."""
+    network_architecture trainer variants replace (nnUNetTrainerBN.py:31-32); the default is the builder's own.
+    dim = len(conv_kernel_sizes[0]) picks the conv (:21-23): 3 -> nn.Conv3d, 2 -> nn.Conv2d (the 2d configuration) with the
+    norm of the same family in two dimensions (InstanceNorm2d; get_matching_batchnorm for the BN variant)."""
     num_stages = len(configuration_manager.conv_kernel_sizes)
     dim = len(configuration_manager.conv_kernel_sizes[0])
-    if dim != 3:
-        raise NotImplementedError("3d_fullres only")
+    if dim not in (2, 3):
+        raise NotImplementedError(f"{dim}-D plans: the 3d_fullres and 2d configurations are built")
+    conv_op = nn.Conv3d if dim == 3 else nn.Conv2d
+    if dim == 2:
+        norm_op = {nn.InstanceNorm3d: nn.InstanceNorm2d, nn.BatchNorm3d: nn.BatchNorm2d}.get(norm_op, norm_op)
     if configuration_manager.UNet_class_name != 'PlainConvUNet':
         raise NotImplementedError("north_star names PlainConvUNet; ResidualEncoderUNet is out of scope")
     label_manager = plans_manager.get_label_manager(dataset_json)
@@ -229,7 +236,7 @@ def get_network_from_plans(plans_manager, dataset_json, configuration_manager, n
         input_channels=num_input_channels, n_stages=num_stages,
         features_per_stage=[min(configuration_manager.UNet_base_num_features * 2 ** i,
                                 configuration_manager.unet_max_num_features) for i in range(num_stages)],
-        conv_op=nn.Conv3d, kernel_sizes=configuration_manager.conv_kernel_sizes,
+        conv_op=conv_op, kernel_sizes=configuration_manager.conv_kernel_sizes,
         strides=configuration_manager.pool_op_kernel_sizes, num_classes=label_manager.num_segmentation_heads,
         deep_supervision=deep_supervision, n_conv_per_stage=configuration_manager.n_conv_per_stage_encoder,
         n_conv_per_stage_decoder=configuration_manager.n_conv_per_stage_decoder, conv_bias=True,
@@ -497,20 +504,27 @@ class nnUNetTrainerMI355(object):
 
     # -- training feed (nnUNetTrainer.py:377-434 and :600-630, fed from HBM by dataloading.DeviceDataLoader3D) ----
     def configure_rotation_dummyDA_mirroring_and_inital_patch_size(self):
-        """nnUNetTrainer.py:377-434 for 3-D plans (ANISO_THRESHOLD = 3, configuration.py:7), both branches: an isotropic
+        """nnUNetTrainer.py:377-434 (ANISO_THRESHOLD = 3, configuration.py:7).  3-D plans, both branches: an isotropic
         patch rotates about every axis by +-30 degrees; an anisotropic one (max / patch[0] > 3) takes the dummy 2-D
         mode -- in-plane rotation by +-180 degrees, axis 0 of the initial patch kept -- which the device feed runs with
-        its in-plane kernels.  True 2-D plans stay refused."""
+        its in-plane kernels.  2-D plans (:386-401): no dummy mode, rotation about x by +-15 degrees when
+        max / min of the patch exceeds 1.5 and by +-180 degrees otherwise, mirroring over both axes."""
         patch_size = self.configuration_manager.patch_size
         dim = len(patch_size)
-        if dim != 3:
-            raise NotImplementedError("configure_rotation_dummyDA_mirroring_and_inital_patch_size: 3-D plans only")
-        do_dummy_2d_data_aug = (max(patch_size) / patch_size[0]) > ANISO_THRESHOLD
-        if do_dummy_2d_data_aug:
-            rotation_for_DA = {'x': (-180. / 360 * 2. * np.pi, 180. / 360 * 2. * np.pi), 'y': (0, 0), 'z': (0, 0)}
+        if dim not in (2, 3):
+            raise NotImplementedError("configure_rotation_dummyDA_mirroring_and_inital_patch_size: 2-D and 3-D plans only")
+        if dim == 2:
+            do_dummy_2d_data_aug = False
+            deg = 15. if max(patch_size) / min(patch_size) > 1.5 else 180.
+            rotation_for_DA = {'x': (-deg / 360 * 2. * np.pi, deg / 360 * 2. * np.pi), 'y': (0, 0), 'z': (0, 0)}
+            mirror_axes = (0, 1)
         else:
-            rotation_for_DA = {ax: (-30. / 360 * 2. * np.pi, 30. / 360 * 2. * np.pi) for ax in ('x', 'y', 'z')}
-        mirror_axes = (0, 1, 2)
+            do_dummy_2d_data_aug = (max(patch_size) / patch_size[0]) > ANISO_THRESHOLD
+            if do_dummy_2d_data_aug:
+                rotation_for_DA = {'x': (-180. / 360 * 2. * np.pi, 180. / 360 * 2. * np.pi), 'y': (0, 0), 'z': (0, 0)}
+            else:
+                rotation_for_DA = {ax: (-30. / 360 * 2. * np.pi, 30. / 360 * 2. * np.pi) for ax in ('x', 'y', 'z')}
+            mirror_axes = (0, 1, 2)
         # the reference sizes the initial patch with (0.85, 1.25), not the (0.7, 1.4) the transform draws from
         initial_patch_size = get_patch_size(patch_size[-dim:], *rotation_for_DA.values(), (0.85, 1.25))
         if do_dummy_2d_data_aug:
@@ -525,6 +539,16 @@ class nnUNetTrainerMI355(object):
         use_mask_for_norm, MaskTransform: the reference's whole training recipe."""
         rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, mirror_axes = \
             self.configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+        if len(self.configuration_manager.patch_size) == 2:
+            # nnUNetDataLoader2D (:612-617): slices of the resident cases, geometric transforms on the device
+            if intensity_augmentation:
+                raise NotImplementedError("the intensity stage of the device feed is not built for the 2d configuration")
+            return DeviceDataLoader2D(dataset_tr, self.batch_size, [int(i) for i in initial_patch_size],
+                                      self.configuration_manager.patch_size, self.label_manager,
+                                      oversample_foreground_percent=self.oversample_foreground_percent,
+                                      mirror_axes=mirror_axes, deep_supervision_scales=self._get_deep_supervision_scales(),
+                                      device=self.device if device is None else device, rotation_for_DA=rotation_for_DA,
+                                      scale_range=(0.7, 1.4))
         use_mask_for_norm = getattr(self.configuration_manager, 'use_mask_for_norm', None)
         mask_channels = use_mask_for_norm if intensity_augmentation and use_mask_for_norm else None
         return DeviceDataLoader3D(dataset_tr, self.batch_size, [int(i) for i in initial_patch_size],
@@ -753,6 +777,9 @@ class ContrastiveTrainerMI355(nnUNetTrainerMI355):
     def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=torch.device('cuda'),
                  specified_cfg=''):
         super().__init__(plans, configuration, fold, dataset_json, unpack_dataset, device, specified_cfg)
+        if len(self.configuration_manager.patch_size) != 3:
+            raise NotImplementedError("ContrastiveTrainerMI355 on 2-D plans: the soft skeleton and the connected-component "
+                                      "count of its topology term are 3-D kernels")
         if self.label_manager.has_regions or self.label_manager.has_ignore_label:
             raise NotImplementedError("ContrastiveTrainerMI355 with regions or an ignore label: its vessel-channel terms "
                                       "(softmax channel select, KL, soft-clDice) are defined for softmax heads only")

@@ -761,8 +761,85 @@ def region_label_fixtures():
     print("wrote label_manager.json")
 
 
+# ------------------------------------------------------------------ 2-D training loader (data_loader_2d.py:7-86)
+def loader2d_fixture():
+    """tests/golden/loader2d.json: the reference's own nnUNetDataLoader2D.generate_train_batch and get_bbox bodies executed
+    on a stub loader over toy cases (numpy global RNG seeded per scenario).  Per batch: keys, the slice and box of every
+    sample, and one uniform drawn after the batch (pins the number and order of draws).  The slice is read back from the
+    returned data (channel 0 of a toy case holds z + 1), the box from the get_bbox call.  Data only; cases are stored as
+    shape + class_locations."""
+    import types
+    gtb, src1 = ref_function("training/dataloading/data_loader_2d.py", "generate_train_batch", "nnUNetDataLoader2D")
+    bbox, src2 = ref_function("training/dataloading/base_data_loader.py", "get_bbox", "nnUNetDataLoaderBase",
+                              print=lambda *a, **k: None)
+    rng = np.random.default_rng(23)
+    labels = (1, 2)
+
+    def locs(shape, n):
+        if n == 0:
+            return np.zeros((0, 4), dtype=np.int64)
+        return np.stack([np.zeros(n, dtype=np.int64)] + [rng.integers(0, s, n) for s in shape], 1)
+
+    scenarios = []
+    for name, has_ignore in (("plain", False), ("ignore", True)):
+        cases = {}
+        # a case larger than the patch, one smaller than it in both axes, one smaller in one axis, one without foreground
+        for key, shape, n1, n2 in (("a", (6, 48, 60), 30, 12), ("b", (5, 20, 30), 15, 0), ("c", (7, 64, 36), 20, 9),
+                                   ("d", (4, 50, 50), 0, 0)):
+            cl = {1: locs(shape, n1), 2: locs(shape, n2)}
+            if has_ignore:
+                cl[labels] = locs(shape, 25)   # the annotated-classes key: every case has annotated voxels
+            cases[key] = (shape, cl)
+        scenarios.append((name, has_ignore, cases))
+    out = []
+    for si, (name, has_ignore, cases) in enumerate(scenarios):
+        patch, final, bs, C = (40, 44), (32, 40), 6, 2
+        boxes = []
+
+        def load_case(key, cases=cases):
+            shape, cl = cases[key]
+            data = np.zeros((C, *shape), dtype=np.float32)
+            data[0] = (np.arange(shape[0], dtype=np.float32) + 1)[:, None, None]
+            return data, np.zeros((1, *shape), dtype=np.int16), {"class_locations": cl}
+
+        me = types.SimpleNamespace(
+            need_to_pad=(np.array(patch) - np.array(final)).astype(int), patch_size=patch, has_ignore=has_ignore,
+            annotated_classes_key=labels, data_shape=(bs, C, *patch), seg_shape=(bs, 1, *patch),
+            _data=types.SimpleNamespace(load_case=load_case),
+            get_indices=lambda cases=cases: np.random.choice(list(cases.keys()), bs, True, None),
+            get_do_oversample=lambda j: not j < round(bs * (1 - 0.33)))
+
+        def get_bbox(*a, **k):
+            r = bbox(me, *a, **k)
+            boxes.append(([int(v) for v in r[0]], [int(v) for v in r[1]]))
+            return r
+        me.get_bbox = get_bbox
+        seed = 500 + si
+        np.random.seed(seed)
+        batches = []
+        for _ in range(6):
+            del boxes[:]
+            b = gtb(me)
+            slices = [int(round(float(b["data"][j, 0].max()))) - 1 for j in range(bs)]
+            batches.append({"keys": [str(k) for k in b["keys"]], "slices": slices, "bbox_lbs": [x[0] for x in boxes],
+                            "bbox_ubs": [x[1] for x in boxes], "rng_tail": float(np.random.uniform())})
+        out.append({"name": name, "has_ignore": has_ignore, "seed": seed, "batch_size": bs, "channels": C,
+                    "patch_size": list(patch), "final_patch_size": list(final), "oversample_foreground_percent": 0.33,
+                    "all_labels": list(labels),
+                    "cases": {k: {"shape": list(sh), "class_locations": [[(list(c) if isinstance(c, tuple) else c), v.tolist()]
+                                                                         for c, v in cl.items()]}
+                              for k, (sh, cl) in cases.items()},
+                    "batches": batches})
+    json.dump({"source": "reference " + src1 + " and " + src2 + " (method bodies executed on a stub loader)",
+               "scenarios": out}, open(os.path.join(OUT, "loader2d.json"), "w"))
+    print("wrote loader2d.json")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == "loader2d":  # only tests/golden/loader2d.json
+        loader2d_fixture()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "regions":  # only tests/golden/label_manager.json
         region_label_fixtures()
         sys.exit(0)
@@ -782,3 +859,4 @@ if __name__ == "__main__":
     mvd_step_fixture()
     persistence_fixtures()
     oracle_check_fixtures()
+    loader2d_fixture()
