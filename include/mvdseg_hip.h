@@ -62,14 +62,37 @@ int mvd_conv3d_fwd(const float *x1, int C1, const float *x2, int C2, const float
 int mvd_conv3d_dgrad(const float *dy, const float *wb, float *dx1, int C1, float *dx2, int C2, int N, int D, int H,
                      int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream);
 /* wgrad: dw in TORCH layout [K][C1+C2][T], dbias [K] (may be NULL).  Fixed-order split reduction through `ws`. */
-/* Winograd variants of the two entries above for 3x3x3 stride-1 convs with C % 32 == 0, K % 32 == 0 (every conv of
+/* Winograd engines of the two entries above for 3x3x3 stride-1 convs with C % 32 == 0, K % 32 == 0 (every conv of
  * the network but the input layer and the strided ones): F(2x2,3x3) over H and W -- 4/9 of the multiply-adds of
  * the direct form (env MVD_WINO=1 selects F(2,3) along W only: 2/3) -- fp32 throughout, same results within fp32
  * round-off (tests: <= 1e-5 relative to fp64).
  * mvd_pack_weight_wino: torch weight [K][C][3][3][3] -> uf (forward) / ub (input gradient), mvd_wino_weight_elems(C, K)
- * floats each, in the MFMA operand order of the active mode.  The *_wino conv entries take the direct
- * packed weights as well and fall back to the direct engines (same results) for shapes the Winograd kernel does
- * not cover (strides, 1x1x1, fewer than 256 work items, uf/ub == NULL). */
+ * floats each, in the MFMA operand order of the active mode.
+ *
+ * One route for every fp32 conv.  An engine takes a pass (the forward, or the input gradient) when its predicate holds:
+ * kernel size, stride 1, 32-multiple channels and its minimum of work items; the mvd_conv_*_applicable queries return the
+ * predicate of one engine as forward (1) | input gradient (2) bits, and mvd_conv3d_route names the preferred engine of both
+ * passes (forward kind in bits 0-3, input-gradient kind in bits 4-7): F(2x2x2,3x3x3) over F(2x2,3x3), the in-plane engine
+ * for 1x3x3, direct otherwise.  mvd_conv3d_fwd_routed / mvd_conv3d_dgrad_routed are mvd_conv3d_fwd / mvd_conv3d_dgrad with a
+ * Winograd table and its kind: the table's engine runs if and only if its predicate holds for the pass, the direct engines
+ * (same results) otherwise -- strides, 1x1x1, too few work items, table == NULL.  An in-plane table requires kernel size
+ * (1,3,3).
+ * Statistics epilogue of the forward ("optional sum x / sum x^2 epilogue"): stats == NULL: none.  stats_tiles == 0:
+ * that of the F(2x2,3x3) / F(2x2x2,3x3x3) kernels, per-tile (sum y, sum y^2) per output channel to stats
+ * [N][mvd_conv_stats_tiles(D,H,W)][K][2] floats.  stats_tiles > 0: that of the direct engines, stats [N][stats_tiles][K][2]
+ * with stats_tiles from mvd_conv3d_fwd_stats_tiles (below; the table is not used).  stats_done is required with stats:
+ * *stats_done = 1 when they were written (0: not produced, run the plain norm). */
+#define MVD_CONV_DIRECT 0
+#define MVD_CONV_WINO2 1  /* F(2x2,3x3), table of mvd_pack_weight_wino */
+#define MVD_CONV_WINO3 2  /* F(2x2x2,3x3x3), table of mvd_pack_weight_wino3 */
+#define MVD_CONV_WINO2P 3 /* F(2x2,3x3) of a 1x3x3 kernel, table of mvd_pack_weight_wino2p */
+int mvd_conv3d_route(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]);
+int mvd_conv3d_fwd_routed(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *table, int table_kind,
+                          const float *bias, float *y, float *stats, long stats_tiles, int *stats_done, int N, int D, int H,
+                          int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream);
+int mvd_conv3d_dgrad_routed(const float *dy, const float *wb, const float *table, int table_kind, float *dx1, int C1, float *dx2,
+                            int C2, int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
+                            size_t ws_bytes, void *stream);
 /* bit 0: the forward would use the Winograd kernel, bit 1: the input gradient would (0: skip packing uf/ub) */
 int mvd_conv_wino_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]);
 /* floats in one uf / ub buffer (48*C*K for the default F(2x2,3x3) mode, 36*C*K for F(2,3) along W) */
@@ -77,35 +100,23 @@ size_t mvd_wino_weight_elems(int C, int K);
 /* 0 = direct engines only, 1 = F(2,3) along W, 2 = F(2x2,3x3) over H and W (default; env MVD_WINO) */
 int mvd_wino_mode(void);
 int mvd_pack_weight_wino(const float *w, float *uf, float *ub, int K, int C, void *stream);
-/* Every conv weight of a network re-packed in ONE launch (the per-layer pack entries are launch-bound; called by the
- * fused optimizer right after the SGD update).  Host tables of n jobs: w[q] the torch-layout weight, wf/wb the
- * mvd_pack_weight outputs, uf/ub the mvd_pack_weight_wino outputs (null entries are skipped; uf/ub need MVD_WINO=2). */
-int mvd_pack_weights_batch(int n, const float *const *w, float *const *wf, float *const *wb, float *const *uf,
-                           float *const *ub, const int *K, const int *C, const int *T, const int *transposed,
-                           void *stream);
+/* mvd_conv3d_fwd_routed with uf as an F(2x2,3x3) table (uf == NULL: the direct engines) and no statistics */
 int mvd_conv3d_fwd_wino(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *uf,
                         const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
                         const int stride[3], void *ws, size_t ws_bytes, void *stream);
-/* InstanceNorm statistics epilogue ("optional sum x / sum x^2 epilogue"): as mvd_conv3d_fwd_wino; when the
- * Winograd kernel runs it also writes per-tile (sum y, sum y^2) per output channel to stats
- * [N][mvd_conv_stats_tiles(D,H,W)][K][2] floats and sets *stats_done = 1 (0: not produced, run the plain norm). */
+/* tiles per sample of the Winograd engines' statistics epilogue (4x4x8 voxels each) */
 size_t mvd_conv_stats_tiles(int D, int H, int W);
-int mvd_conv3d_fwd_wino_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *uf,
-                              const float *bias, float *y, float *stats, int *stats_done, int N, int D, int H, int W,
-                              int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream);
-int mvd_conv3d_dgrad_wino(const float *dy, const float *wb, const float *ub, float *dx1, int C1, float *dx2, int C2, int N,
-                          int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes,
-                          void *stream);
 /* F(2x2x2,3x3x3) engine: Winograd F(2,3) along D as well -- 8 multiply-adds per output and channel pair instead of the
  * 12 of F(2x2,3x3) -- same coefficients (1 and 1/2), same results within fp32 round-off.  It refines the F(2x2,3x3)
  * engine: mvd_conv_wino3_applicable returns the bits of mvd_conv_wino_applicable for which the 3-D kernel also has
  * its own minimum of work items PER SAMPLE (4x8x8 voxels x 32 output channels, default 128: the choice does not
  * depend on the batch size; mvd_set_wino3_min_items, < 0 restores the default) and is on (env MVD_WINO3=0 turns it off; the F(2x2,3x3) entries above keep their meaning in every case).
  * mvd_pack_weight_wino3: torch weight -> vf (forward) / vb (input gradient), mvd_wino3_weight_elems(C, K) = 64*C*K
- * floats each.  mvd_pack_weights_batch3: mvd_pack_weights_batch with the 3-D tables vf / vb as well (null entries are
- * skipped), still one launch.  The *_wino3 conv entries take the 3-D table in place of uf / ub and fall back to the
- * direct engines (same results) where the 3-D kernel does not run; the statistics epilogue writes the layout of
- * mvd_conv3d_fwd_wino_stats. */
+ * floats each; the statistics epilogue writes the layout of the F(2x2,3x3) kernel.
+ * mvd_pack_weights_batch3: every conv weight of a network re-packed in ONE launch (the per-layer pack entries are
+ * launch-bound; called by the fused optimizer right after the update).  Host tables of n jobs: w[q] the torch-layout
+ * weight, wf / wb the mvd_pack_weight outputs, uf / ub the mvd_pack_weight_wino outputs (need MVD_WINO=2), vf / vb the 3-D
+ * tables; null entries are skipped. */
 int mvd_set_wino3_min_items(long n);
 int mvd_conv_wino3_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]);
 size_t mvd_wino3_weight_elems(int C, int K);
@@ -113,24 +124,12 @@ int mvd_pack_weight_wino3(const float *w, float *vf, float *vb, int K, int C, vo
 int mvd_pack_weights_batch3(int n, const float *const *w, float *const *wf, float *const *wb, float *const *uf,
                             float *const *ub, float *const *vf, float *const *vb, const int *K, const int *C,
                             const int *T, const int *transposed, void *stream);
-int mvd_conv3d_fwd_wino3(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *vf,
-                         const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
-                         const int stride[3], void *ws, size_t ws_bytes, void *stream);
-int mvd_conv3d_fwd_wino3_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *vf,
-                               const float *bias, float *y, float *stats, int *stats_done, int N, int D, int H, int W,
-                               int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream);
 /* The same epilogue in the direct fp32 engines (the narrow-input / chunked kernel k_fwd_mfma and the stride-2 kernel
  * k_fwd32s; a tile is one wave's plane of the workgroup tile, at most 64 values).  mvd_conv3d_fwd_stats_tiles: tiles per
- * sample of the kernel that would run for this conv, 0 when it has no epilogue; mvd_conv3d_fwd_stats: mvd_conv3d_fwd with
- * stats [N][stats_tiles][K][2]; *stats_done = 1 when they were written (a conv that would split its reduce channels over
- * workgroups runs unsplit then: ask only where a statistics pass would run otherwise). */
+ * sample of the kernel that would run for this conv, 0 when it has no epilogue: the stats_tiles of mvd_conv3d_fwd_routed (a
+ * conv that would split its reduce channels over workgroups runs unsplit then: ask only where a statistics pass would run
+ * otherwise). */
 long mvd_conv3d_fwd_stats_tiles(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]);
-int mvd_conv3d_fwd_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *bias, float *y,
-                         float *stats, long stats_tiles, int *stats_done, int N, int D, int H, int W, int K,
-                         const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream);
-int mvd_conv3d_dgrad_wino3(const float *dy, const float *wb, const float *vb, float *dx1, int C1, float *dx2, int C2,
-                           int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
-                           size_t ws_bytes, void *stream);
 /* F(2x2,3x3) engine of the 9-tap in-plane layers: kernel size (1,3,3), stride 1, 32-multiple channels -- the convs of a 2-D
  * network seen as [N,C,1,H,W] and the in-plane layers of anisotropic 3-D plans (4 multiply-adds per output and channel
  * pair instead of 9).  Other 9-tap kernels, e.g. (3,3,1), keep the direct engine.  mvd_conv_wino2p_applicable: forward (1)
@@ -138,20 +137,13 @@ int mvd_conv3d_dgrad_wino3(const float *dy, const float *wb, const float *vb, fl
  * channels over all N*D planes; mvd_set_wino2p_min_items, < 0 restores the default, a huge value turns the kernel off; env
  * MVD_WINO2P_MIN, MVD_WINO=0).  mvd_pack_weight_wino2p: torch weight [K][C][1][3][3] -> pf (forward) / pb (input gradient),
  * mvd_wino2p_weight_elems(C, K) = 16*C*K floats each; in mvd_pack_weights_batch3 a job with T = 9 takes them as uf / ub.
- * The *_wino2p conv entries take the table in place of uf / ub and fall back to the direct engines where the kernel does
- * not run.  No statistics epilogue.  mvd_conv_wino2p_applicable judges the shape alone: a call whose pointers are not
+ * No statistics epilogue.  mvd_conv_wino2p_applicable judges the shape alone: a call whose pointers are not
  * 16-byte aligned, or with more than 2^30 work items or K*32 >= 2^27, also falls back to the direct engines (same
  * results) although the bits were set. */
 int mvd_set_wino2p_min_items(long n);
 int mvd_conv_wino2p_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]);
 size_t mvd_wino2p_weight_elems(int C, int K);
 int mvd_pack_weight_wino2p(const float *w, float *pf, float *pb, int K, int C, void *stream);
-int mvd_conv3d_fwd_wino2p(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *pf,
-                          const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
-                          const int stride[3], void *ws, size_t ws_bytes, void *stream);
-int mvd_conv3d_dgrad_wino2p(const float *dy, const float *wb, const float *pb, float *dx1, int C1, float *dx2, int C2,
-                            int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
-                            size_t ws_bytes, void *stream);
 /* F(2x2x2,3x3x3) weight gradient: mvd_conv3d_wgrad runs it for fp32 3x3x3 stride-1 convs with 32-multiple channels
  * (two inputs included) that have at least the minimum of work items PER SAMPLE (2x8x8 dy voxels x 32 input x 32
  * output channels; mvd_set_wgrad_wino3_min_items, < 0 restores the default) unless MVD_WGRAD_WINO3=0 or MVD_WINO=0.
@@ -193,7 +185,7 @@ int mvd_convT3d_wgrad(const float *x, const float *dy, float *dw, float *dbias, 
  * [chunk32][tap][kstep][lane half][out channel][8]. */
 int mvd_pack_weight_bf16(const float *w, uint16_t *wf, uint16_t *wb, int K, int C, int T, int transposed, void *stream);
 /* Every bf16 pack of a network in ONE launch (called by the fused optimizer after its update, like
- * mvd_pack_weights_batch for the fp32 layouts): host tables of n jobs, outputs bit-identical to mvd_pack_weight_bf16. */
+ * mvd_pack_weights_batch3 for the fp32 layouts): host tables of n jobs, outputs bit-identical to mvd_pack_weight_bf16. */
 int mvd_pack_weights_bf16_batch(int n, const float *const *w, uint16_t *const *wf, uint16_t *const *wb, const int *K,
                                 const int *C, const int *T, const int *transposed, void *stream);
 /* The same launch with a source channel count per job: job q reads a [K][Csrc][T] weight and packs it as the [K][C][T]
@@ -330,7 +322,7 @@ int mvd_instnorm_lrelu_fwd(const float *x, const float *gamma, const float *beta
                            float *rstd, int N, long V, int C, float eps, float slope, void *ws, size_t ws_bytes,
                            void *stream);
 /* dx [N,V,C]; dgamma/dbeta [C] (overwritten).  Recomputes z = xhat*gamma+beta from x for the LeakyReLU mask. */
-/* forward with the statistics taken from the producing conv's epilogue (mvd_conv3d_fwd_wino_stats): no pass over x
+/* forward with the statistics taken from the producing conv's epilogue (mvd_conv3d_fwd_routed): no pass over x
  * for mean / variance; everything else as mvd_instnorm_lrelu_fwd */
 int mvd_instnorm_lrelu_fwd_prestats(const float *x, const float *tile_stats, long ntiles, const float *gamma,
                                     const float *beta, float *y, float *mean, float *rstd, int N, long V, int C, float eps,

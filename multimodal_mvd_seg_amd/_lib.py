@@ -13,6 +13,10 @@ LIB_PATH = os.path.join(_HERE, "libmvdseg_hip.so")
 _P = c_void_p
 _I3 = ctypes.c_int * 3
 
+# fp32 conv engines (MVD_CONV_* of the header): the kinds mvd_conv3d_route returns -- forward in bits 0-3, input gradient in
+# bits 4-7 -- and the table kinds of mvd_conv3d_fwd_routed / mvd_conv3d_dgrad_routed
+CONV_DIRECT, CONV_WINO2, CONV_WINO3, CONV_WINO2P = 0, 1, 2, 3
+
 # name -> (restype, argtypes); must list every symbol of include/mvdseg_hip.h (tests/test_abi.py checks it)
 SIGNATURES = {
     "mvd_version": (c_int, []),
@@ -33,40 +37,28 @@ SIGNATURES = {
     "mvd_convT3d_dgrad": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _P, c_size_t, _P]),
     "mvd_convT3d_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "mvd_convT3d_wgrad": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _P, c_size_t, _P]),
+    "mvd_conv3d_route": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
+    "mvd_conv3d_fwd_routed": (c_int, [_P, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, c_long, _P, c_int, c_int, c_int, c_int,
+                                      c_int, _I3, _I3, _P, c_size_t, _P]),
+    "mvd_conv3d_dgrad_routed": (c_int, [_P, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
+                                        c_size_t, _P]),
     "mvd_conv_wino_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
     "mvd_wino_mode": (c_int, []),
     "mvd_wino_weight_elems": (c_size_t, [c_int, c_int]),
     "mvd_pack_weight_wino": (c_int, [_P, _P, _P, c_int, c_int, _P]),
-    "mvd_pack_weights_batch": (c_int, [c_int] + [_P] * 9 + [_P]),
     "mvd_conv3d_fwd_wino": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
                                     c_size_t, _P]),
     "mvd_conv_stats_tiles": (c_size_t, [c_int, c_int, c_int]),
     "mvd_conv3d_fwd_stats_tiles": (c_long, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
-    "mvd_conv3d_fwd_stats": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_long, _P, c_int, c_int, c_int, c_int, c_int, _I3,
-                                     _I3, _P, c_size_t, _P]),
-    "mvd_conv3d_fwd_wino_stats": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
-                                          _I3, _I3, _P, c_size_t, _P]),
-    "mvd_conv3d_dgrad_wino": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
-                                      c_size_t, _P]),
     "mvd_set_wino3_min_items": (c_int, [c_long]),
     "mvd_conv_wino3_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
     "mvd_wino3_weight_elems": (c_size_t, [c_int, c_int]),
     "mvd_pack_weight_wino3": (c_int, [_P, _P, _P, c_int, c_int, _P]),
     "mvd_pack_weights_batch3": (c_int, [c_int] + [_P] * 11 + [_P]),
-    "mvd_conv3d_fwd_wino3": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
-                                     c_size_t, _P]),
-    "mvd_conv3d_fwd_wino3_stats": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
-                                           _I3, _I3, _P, c_size_t, _P]),
-    "mvd_conv3d_dgrad_wino3": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
-                                       c_size_t, _P]),
     "mvd_set_wino2p_min_items": (c_int, [c_long]),
     "mvd_conv_wino2p_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
     "mvd_wino2p_weight_elems": (c_size_t, [c_int, c_int]),
     "mvd_pack_weight_wino2p": (c_int, [_P, _P, _P, c_int, c_int, _P]),
-    "mvd_conv3d_fwd_wino2p": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
-                                      c_size_t, _P]),
-    "mvd_conv3d_dgrad_wino2p": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3, _P,
-                                        c_size_t, _P]),
     "mvd_set_wgrad_wino3_min_items": (c_int, [c_long]),
     "mvd_conv_wgrad_wino3_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _I3, _I3]),
     "mvd_wgrad_wino3_launches": (c_long, []),

@@ -23,7 +23,56 @@ static long g_wino3_min_items = getenv("MVD_WINO3_MIN") ? atol(getenv("MVD_WINO3
 // x 4 x 8 outputs x 32 channels, over all N * D planes: its tile spans samples when D = 1); MVD_WINO2P_MIN overrides
 static const long kWino2pMinItemsDefault = 256;
 static long g_wino2p_min_items = getenv("MVD_WINO2P_MIN") ? atol(getenv("MVD_WINO2P_MIN")) : kWino2pMinItemsDefault;
+
+// ----------------------------------------------------------------------------------------- fp32 Winograd engine route
+// One forward-type pass as the engine predicates see it: output grid, the parts of its reduce and of its produce channels
+// (forward: C1, C2 -> K; input gradient: K -> C1, C2), kernel size and stride of the conv
+struct ConvPass {
+    int N, D, H, W, R1, R2, P1, P2;
+    const int *ks, *st;
+};
+static ConvPass fwd_pass(int N, int D, int H, int W, int C1, int C2, int K, const int ks[3], const int st[3]) {
+    return {N, D, H, W, C1, C2, K, 0, ks, st};
+}
+static ConvPass dgrad_pass(int N, int D, int H, int W, int C1, int C2, int K, const int ks[3], const int st[3]) {
+    return {N, D, H, W, K, 0, C1, C2, ks, st};
+}
+// what the three engines share: engines on, a kd x 3 x 3 stride-1 conv, every channel part a multiple of 32
+static bool wino_pass_ok(const ConvPass &p, int kd) {
+    if (g_engine_mode != 0 || g_wino_off || !p.ks || !p.st) return false;
+    if (p.ks[0] != kd || p.ks[1] != 3 || p.ks[2] != 3 || p.st[0] != 1 || p.st[1] != 1 || p.st[2] != 1) return false;
+    if (p.N <= 0 || p.D <= 0 || p.H <= 0 || p.W <= 0 || p.R1 <= 0 || p.R2 < 0 || p.P1 <= 0 || p.P2 < 0) return false;
+    return !(p.R1 % 32 || p.R2 % 32 || p.P1 % 32 || p.P2 % 32);
+}
+// "would engine E take this pass?" -- asked by the mvd_conv_*_applicable queries, by mvd_conv3d_route and by run_fwd, each
+// with the engine's work-item count next to it
+static long wino2_items(int N, int D, int H, int W, int K) { return (long)N * ((D + 3) / 4) * ((H + 3) / 4) * ((W + 7) / 8) * (K / 32); }
+static bool wino2_takes(const ConvPass &p) {
+    return wino_pass_ok(p, 3) && wino2_items(p.N, p.D, p.H, p.W, p.P1 + p.P2) >= g_wino_min_items;
+}
 static long wino3_items(int D, int H, int W, int K) { return (long)((D + 3) / 4) * ((H + 7) / 8) * ((W + 7) / 8) * (K / 32); }
+static bool wino3_takes(const ConvPass &p) {  // a refinement of F(2x2,3x3): that engine's minimum holds too
+    return wino3_enabled() && wino2_takes(p) && wino3_items(p.D, p.H, p.W, p.P1 + p.P2) >= g_wino3_min_items;
+}
+static bool wino2p_takes(const ConvPass &p) {
+    if (!wino_pass_ok(p, 1)) return false;
+    const int cmax = p.R1 + p.R2 > p.P1 + p.P2 ? p.R1 + p.R2 : p.P1 + p.P2;
+    if ((long)p.H * p.W * cmax * 4 >= (1L << 31) || (long)p.N * p.D > (1L << 30)) return false;
+    return wino2p_items(p.N, p.D, p.H, p.W, p.P1 + p.P2) >= g_wino2p_min_items;
+}
+static bool engine_takes(int kind, const ConvPass &p) {
+    return kind == MVD_CONV_WINO3 ? wino3_takes(p) : kind == MVD_CONV_WINO2 ? wino2_takes(p) : kind == MVD_CONV_WINO2P && wino2p_takes(p);
+}
+// the preferred engine of a pass: the 3-D engine over F(2x2,3x3), the in-plane engine for 1x3x3, direct otherwise
+static int route_of(const ConvPass &p) {
+    return wino3_takes(p) ? MVD_CONV_WINO3 : wino2_takes(p) ? MVD_CONV_WINO2 : wino2p_takes(p) ? MVD_CONV_WINO2P : MVD_CONV_DIRECT;
+}
+// a Winograd-domain weight table and the engine it belongs to (u == nullptr: none), with the conv's kernel size and stride
+struct WinoTable {
+    const float *u;
+    int kind;
+    const int *ks, *st;
+};
 
 // =============================================================================================== scalar forward-type
 // one thread per (n, o, k); k fastest so weight reads and output writes are coalesced and A is a wave broadcast
@@ -270,9 +319,8 @@ static int colsum(const float *x, float *out, long rows, int K, void *ws, hipStr
     return reduce_partials(partial, out, nb, K, s);
 }
 
-// =============================================================================================== geometry builders
-static inline int out_dim(int in, int k, int s) { return (in + 2 * ((k - 1) / 2) - k) / s + 1; }
-
+// =============================================================================================== engine dispatch
+// (the geometry builders are in conv_geom.h)
 static int check_ks(const int ks[3], const int st[3], const char *who) {
     for (int a = 0; a < 3; a++) {
         if (!(ks[a] == 1 || ks[a] == 3)) {
@@ -286,40 +334,16 @@ static int check_ks(const int ks[3], const int st[3], const char *who) {
     }
     return 0;
 }
-
-static void conv_fwd_geom(FwdGeom &g, int N, int D, int H, int W, int C1, int C2, int K, const int ks[3],
-                          const int st[3]) {
-    memset(&g, 0, sizeof(g));
-    g.N = N;
-    g.Di = D; g.Hi = H; g.Wi = W;
-    g.Do = out_dim(D, ks[0], st[0]); g.Ho = out_dim(H, ks[1], st[1]); g.Wo = out_dim(W, ks[2], st[2]);
-    g.Dy = g.Do; g.Hy = g.Ho; g.Wy = g.Wo;
-    g.C1 = C1; g.C2 = C2; g.K1 = K; g.K2 = 0;
-    int t = 0;
-    for (int a = 0; a < ks[0]; a++)
-        for (int b = 0; b < ks[1]; b++)
-            for (int c = 0; c < ks[2]; c++) {
-                g.off[t][0] = a - (ks[0] - 1) / 2;
-                g.off[t][1] = b - (ks[1] - 1) / 2;
-                g.off[t][2] = c - (ks[2] - 1) / 2;
-                g.wt[t] = t;
-                t++;
-            }
-    g.ntaps = g.T = t;
-    for (int a = 0; a < 3; a++) {
-        g.sa[a] = st[a];
-        g.so[a] = 1;
-        g.oo[a] = 0;
-    }
+// the shape queries: 0 / "no" for arguments the entry points would refuse
+static bool conv_args_ok(int N, int D, int H, int W, int C1, int C2, int K, const int ks[3], const int st[3], const char *who) {
+    return N > 0 && D > 0 && H > 0 && W > 0 && C1 > 0 && C2 >= 0 && K > 0 && ks && st && !check_ks(ks, st, who);
 }
 
-// u (optional): Winograd-domain weights of mvd_pack_weight_wino for this pass (uf for the forward, ub for the input
-// gradient); used for plain 3x3x3 stride-1 problems with enough tiles to fill the chip, the direct engines otherwise
-// u3d: u is the F(2x2x2,3x3x3) table of mvd_pack_weight_wino3 (the 3-D engine runs when it has enough work items,
-// the direct engines otherwise)
+// tab (optional): a Winograd table of this pass (uf of the forward, ub of the input gradient).  Its engine runs if and only
+// if that engine's predicate holds for the pass; the direct engines run otherwise, and when the engine itself refuses (-1)
 static int run_fwd(const FwdGeom &g, const float *a1, const float *a2, const float *w, const float *bias, float *y1,
-                   float *y2, void *ws, size_t ws_bytes, hipStream_t s, const float *u = nullptr, float *stats = nullptr,
-                   int *stats_done = nullptr, bool u3d = false, long direct_tiles = 0) {
+                   float *y2, void *ws, size_t ws_bytes, hipStream_t s, const WinoTable *tab = nullptr, float *stats = nullptr,
+                   int *stats_done = nullptr, long direct_tiles = 0) {
     if (stats_done) *stats_done = 0;
     if (direct_tiles > 0) {  // statistics from the direct engine's epilogue ([N][direct_tiles][K][2], fwd_mfma)
         if (g_engine_mode == 0) {
@@ -329,30 +353,12 @@ static int run_fwd(const FwdGeom &g, const float *a1, const float *a2, const flo
         }
         return fwd_scalar(g, a1, a2, w, bias, y1, y2, s);
     }
-    if (u && g.T == 9) {  // the table of a 1x3x3 layer (mvd_pack_weight_wino2p); 27-tap problems never come here
-        if (g_engine_mode == 0 && !g_wino_off && !u3d &&
-            wino2p_items(g.N, g.Do, g.Ho, g.Wo, g.K1 + g.K2) >= g_wino2p_min_items) {
-            int r = fwd_wino2p(g, a1, a2, u, bias, y1, y2, s);
-            if (r >= 0) return r;
-        }
-        u = nullptr;
-    }
-    if (u3d) {
-        if (g_engine_mode == 0 && u && !g_wino_off && wino3_enabled() &&
-            wino3_items(g.Do, g.Ho, g.Wo, g.K1 + g.K2) >= g_wino3_min_items) {
-            int r = fwd_wino3(g, a1, a2, u, bias, y1, y2, s, stats, stats_done);
-            if (r >= 0) return r;
-            if (stats_done) *stats_done = 0;
-        }
-        u = nullptr;
-    }
-    if (g_engine_mode == 0 && u && !g_wino_off) {
-        const long tiles = (long)g.N * ((g.Do + 3) / 4) * ((g.Ho + 3) / 4) * ((g.Wo + 7) / 8) * ((g.K1 + g.K2) / 32);
-        if (tiles >= g_wino_min_items) {
-            int r = fwd_wino(g, a1, a2, u, bias, y1, y2, s, stats, stats_done);
-            if (r >= 0) return r;
-            if (stats_done) *stats_done = 0;
-        }
+    if (tab && tab->u && engine_takes(tab->kind, ConvPass{g.N, g.Do, g.Ho, g.Wo, g.C1, g.C2, g.K1, g.K2, tab->ks, tab->st})) {
+        int r = tab->kind == MVD_CONV_WINO3   ? fwd_wino3(g, a1, a2, tab->u, bias, y1, y2, s, stats, stats_done)
+                : tab->kind == MVD_CONV_WINO2 ? fwd_wino(g, a1, a2, tab->u, bias, y1, y2, s, stats, stats_done)
+                                              : fwd_wino2p(g, a1, a2, tab->u, bias, y1, y2, s);
+        if (r >= 0) return r;
+        if (stats_done) *stats_done = 0;
     }
     if (g_engine_mode == 0) {
         int r = fwd_mfma(g, a1, a2, w, bias, y1, y2, ws, ws_bytes, s);
@@ -419,40 +425,59 @@ int mvd_set_wino_min_items(long n) {
 
 size_t mvd_conv_fwd_workspace_bytes(int N, long out_voxels, int K) { return fwd_mfma_ws(N, out_voxels, K); }
 
-static int conv3d_fwd_impl(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *uf,
-                           const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
-                           const int stride[3], void *ws, size_t ws_bytes, void *stream, float *stats = nullptr,
-                           int *stats_done = nullptr, bool u3d = false, long direct_tiles = 0) {
+/* The general fp32 forward.  table / table_kind: a Winograd table of the weight and the engine it is for (MVD_CONV_*;
+ * NULL: none).  stats == NULL: no statistics epilogue; stats_tiles == 0: that of the Winograd engines (the 4x4x8-tile layout
+ * of mvd_conv_stats_tiles); stats_tiles > 0: that of the direct engines (mvd_conv3d_fwd_stats_tiles; the table is not used) */
+int mvd_conv3d_fwd_routed(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *table, int table_kind,
+                          const float *bias, float *y, float *stats, long stats_tiles, int *stats_done, int N, int D, int H,
+                          int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {
     MVD_REQUIRE(x1 && wf && y && C1 > 0 && C2 >= 0 && (C2 == 0 || x2), "conv3d_fwd: null pointer / bad channels");
     MVD_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && K > 0, "conv3d_fwd: bad shape");
     if (check_ks(ksize, stride, "conv3d_fwd")) return 2;
+    MVD_REQUIRE(table_kind >= MVD_CONV_DIRECT && table_kind <= MVD_CONV_WINO2P, "conv3d_fwd: unknown table kind");
+    MVD_REQUIRE(!(table && table_kind == MVD_CONV_WINO2P) || (ksize[0] == 1 && ksize[1] == 3 && ksize[2] == 3),
+                "conv3d_fwd: the in-plane table is that of a 1x3x3 kernel");
+    MVD_REQUIRE(!stats || stats_done, "conv3d_fwd: stats_done is required with stats");
+    MVD_REQUIRE(stats_tiles == 0 || (stats && stats_tiles > 0), "conv3d_fwd: stats_tiles > 0 comes with stats and stats_done");
     FwdGeom g;
     conv_fwd_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
-    return run_fwd(g, x1, x2, wf, bias, y, nullptr, ws, ws_bytes, as_stream(stream), uf, stats, stats_done, u3d, direct_tiles);
+    const WinoTable tab = {table, table_kind, ksize, stride};
+    return run_fwd(g, x1, x2, wf, bias, y, nullptr, ws, ws_bytes, as_stream(stream), &tab, stats, stats_done, stats_tiles);
 }
 
 int mvd_conv3d_fwd(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *bias, float *y, int N,
                    int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes,
                    void *stream) {
-    return conv3d_fwd_impl(x1, C1, x2, C2, wf, nullptr, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream);
+    return mvd_conv3d_fwd_routed(x1, C1, x2, C2, wf, nullptr, MVD_CONV_DIRECT, bias, y, nullptr, 0, nullptr, N, D, H, W, K, ksize,
+                                 stride, ws, ws_bytes, stream);
 }
 
 int mvd_conv3d_fwd_wino(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *uf,
                         const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
                         const int stride[3], void *ws, size_t ws_bytes, void *stream) {
-    return conv3d_fwd_impl(x1, C1, x2, C2, wf, uf, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream);
+    return mvd_conv3d_fwd_routed(x1, C1, x2, C2, wf, uf, uf ? MVD_CONV_WINO2 : MVD_CONV_DIRECT, bias, y, nullptr, 0, nullptr, N, D, H,
+                                 W, K, ksize, stride, ws, ws_bytes, stream);
 }
 
-/* 1 when mvd_conv3d_fwd_wino / mvd_conv3d_dgrad_wino would run the Winograd kernel for this conv (the caller can skip
- * packing uf/ub otherwise).  Cin/Cout: reduce / produce channel counts of the pass (swap them for the dgrad). */
+/* forward (1) | input gradient (2) bits: the engine would take that pass with its table (the caller can skip packing the
+ * table otherwise) */
+static int pass_bits(bool (*takes)(const ConvPass &), int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3],
+                     const int stride[3]) {
+    return (takes(fwd_pass(N, D, H, W, C1, C2, K, ksize, stride)) ? 1 : 0) |
+           (takes(dgrad_pass(N, D, H, W, C1, C2, K, ksize, stride)) ? 2 : 0);
+}
 int mvd_conv_wino_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
-    if (g_engine_mode != 0 || g_wino_off) return 0;
-    for (int a = 0; a < 3; a++)
-        if (ksize[a] != 3 || stride[a] != 1) return 0;
-    if (C1 % 32 || C2 % 32 || K % 32 || C1 <= 0 || K <= 0) return 0;
-    const long tiles_f = (long)N * ((D + 3) / 4) * ((H + 3) / 4) * ((W + 7) / 8) * (K / 32);
-    const long tiles_b = (long)N * ((D + 3) / 4) * ((H + 3) / 4) * ((W + 7) / 8) * ((C1 + C2) / 32);
-    return (tiles_f >= g_wino_min_items ? 1 : 0) | (tiles_b >= g_wino_min_items ? 2 : 0);
+    return pass_bits(wino2_takes, N, D, H, W, C1, C2, K, ksize, stride);
+}
+int mvd_conv_wino3_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
+    return pass_bits(wino3_takes, N, D, H, W, C1, C2, K, ksize, stride);
+}
+int mvd_conv_wino2p_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
+    return pass_bits(wino2p_takes, N, D, H, W, C1, C2, K, ksize, stride);
+}
+/* the preferred engine (MVD_CONV_*) of the forward in bits 0-3 and of the input gradient in bits 4-7 */
+int mvd_conv3d_route(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
+    return route_of(fwd_pass(N, D, H, W, C1, C2, K, ksize, stride)) | (route_of(dgrad_pass(N, D, H, W, C1, C2, K, ksize, stride)) << 4);
 }
 
 size_t mvd_wino_weight_elems(int C, int K) { return wino_weight_elems(C, K); }
@@ -461,20 +486,10 @@ int mvd_wino_mode(void) { return wino_mode(); }
 /* InstanceNorm statistics epilogue: tiles per sample of the partial-statistics buffer [N][tiles][K][2] floats */
 size_t mvd_conv_stats_tiles(int D, int H, int W) { return (size_t)((D + 3) / 4) * ((H + 3) / 4) * ((W + 7) / 8); }
 
-int mvd_conv3d_fwd_wino_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *uf,
-                              const float *bias, float *y, float *stats, int *stats_done, int N, int D, int H, int W,
-                              int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {
-    MVD_REQUIRE(stats_done, "conv3d_fwd_wino_stats: stats_done is required");
-    return conv3d_fwd_impl(x1, C1, x2, C2, wf, uf, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, stats,
-                           stats_done);
-}
-
 /* The direct fp32 engines' statistics epilogue (the narrow-input / chunked kernel and the stride-2 kernel): tiles per sample
- * of the kernel that would run for this conv, 0 when it has none (Winograd layers use mvd_conv3d_fwd_wino*_stats) */
+ * of the kernel that would run for this conv, 0 when it has none (Winograd layers take theirs with stats_tiles = 0) */
 long mvd_conv3d_fwd_stats_tiles(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || K <= 0 || !ksize || !stride || g_engine_mode != 0) return 0;
-    for (int a = 0; a < 3; a++)
-        if (!(ksize[a] == 1 || ksize[a] == 3) || !(stride[a] == 1 || stride[a] == 2)) return 0;
+    if (g_engine_mode != 0 || !conv_args_ok(N, D, H, W, C1, C2, K, ksize, stride, "conv3d_fwd_stats_tiles")) return 0;
     FwdGeom g;
     conv_fwd_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
     long tiles = 0;
@@ -483,30 +498,6 @@ long mvd_conv3d_fwd_stats_tiles(int N, int D, int H, int W, int C1, int C2, int 
     if (fwd_mfma(g, al, C2 ? al : nullptr, al, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, &tiles) != 0)
         return 0;
     return tiles;
-}
-
-int mvd_conv3d_fwd_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *bias, float *y,
-                         float *stats, long stats_tiles, int *stats_done, int N, int D, int H, int W, int K,
-                         const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {
-    MVD_REQUIRE(stats && stats_done && stats_tiles > 0, "conv3d_fwd_stats: stats, stats_tiles and stats_done are required");
-    return conv3d_fwd_impl(x1, C1, x2, C2, wf, nullptr, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, stats,
-                           stats_done, false, stats_tiles);
-}
-
-int mvd_pack_weights_batch(int n, const float *const *w, float *const *wf, float *const *wb, float *const *uf,
-                           float *const *ub, const int *K, const int *C, const int *T, const int *transposed,
-                           void *stream) {
-    MVD_REQUIRE(n > 0 && w && wf && wb && uf && ub && K && C && T && transposed, "pack_weights_batch: null table");
-    for (int q = 0; q < n; q++) {
-        MVD_REQUIRE(w[q] && (wf[q] || wb[q] || uf[q] || ub[q]), "pack_weights_batch: job without source or destination");
-        MVD_REQUIRE(K[q] > 0 && C[q] > 0 && T[q] > 0 && T[q] <= MVD_MAX_TAPS, "pack_weights_batch: bad K / C / T");
-        if (uf[q] || ub[q]) {
-            MVD_REQUIRE(wino_mode() == 2, "pack_weights_batch: Winograd tables need MVD_WINO=2 (F(2x2,3x3) layout)");
-            MVD_REQUIRE(T[q] == 27 && !transposed[q] && K[q] % 32 == 0 && C[q] % 32 == 0,
-                        "pack_weights_batch: Winograd tables need a 3x3x3 conv with C %% 32 == 0 and K %% 32 == 0");
-        }
-    }
-    return pack_weights_batch(n, w, wf, wb, uf, ub, K, C, T, transposed, as_stream(stream));
 }
 
 int mvd_pack_weight_wino(const float *w, float *uf, float *ub, int K, int C, void *stream) {
@@ -519,13 +510,6 @@ int mvd_pack_weight_wino(const float *w, float *uf, float *ub, int K, int C, voi
 int mvd_set_wino3_min_items(long n) {
     g_wino3_min_items = n < 0 ? kWino3MinItemsDefault : n;
     return 0;
-}
-
-int mvd_conv_wino3_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
-    if (!wino3_enabled()) return 0;
-    const int two = mvd_conv_wino_applicable(N, D, H, W, C1, C2, K, ksize, stride);
-    return two & ((wino3_items(D, H, W, K) >= g_wino3_min_items ? 1 : 0) |
-                  (wino3_items(D, H, W, C1 + C2) >= g_wino3_min_items ? 2 : 0));
 }
 
 size_t mvd_wino3_weight_elems(int C, int K) { return (size_t)64 * C * K; }
@@ -555,42 +539,10 @@ int mvd_pack_weights_batch3(int n, const float *const *w, float *const *wf, floa
     return pack_weights_batch(n, w, wf, wb, uf, ub, K, C, T, transposed, as_stream(stream), vf, vb);
 }
 
-int mvd_conv3d_fwd_wino3(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *vf,
-                         const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
-                         const int stride[3], void *ws, size_t ws_bytes, void *stream) {
-    return conv3d_fwd_impl(x1, C1, x2, C2, wf, vf, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, nullptr,
-                           nullptr, true);
-}
-
-int mvd_conv3d_fwd_wino3_stats(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *vf,
-                               const float *bias, float *y, float *stats, int *stats_done, int N, int D, int H, int W,
-                               int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {
-    MVD_REQUIRE(stats_done, "conv3d_fwd_wino3_stats: stats_done is required");
-    return conv3d_fwd_impl(x1, C1, x2, C2, wf, vf, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, stats,
-                           stats_done, true);
-}
-
-static int conv3d_dgrad_impl(const float *dy, const float *wb, const float *ub, float *dx1, int C1, float *dx2, int C2,
-                             int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
-                             size_t ws_bytes, void *stream, bool u3d = false);
-
 // ------------------------------------------------------------------------------------- F(2x2,3x3) engine of 1x3x3 layers
 int mvd_set_wino2p_min_items(long n) {
     g_wino2p_min_items = n < 0 ? kWino2pMinItemsDefault : n;
     return 0;
-}
-
-/* forward (1) | input gradient (2) bits: mvd_conv3d_fwd_wino2p / mvd_conv3d_dgrad_wino2p would run k_fwd_wino2p */
-int mvd_conv_wino2p_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
-    if (g_engine_mode != 0 || g_wino_off || !ksize || !stride) return 0;
-    if (ksize[0] != 1 || ksize[1] != 3 || ksize[2] != 3) return 0;
-    for (int a = 0; a < 3; a++)
-        if (stride[a] != 1) return 0;
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 % 32 || C2 % 32 || K % 32 || C1 <= 0 || C2 < 0 || K <= 0) return 0;
-    const int cmax = C1 + C2 > K ? C1 + C2 : K;
-    if ((long)H * W * cmax * 4 >= (1L << 31) || (long)N * D > (1L << 30)) return 0;
-    return (wino2p_items(N, D, H, W, K) >= g_wino2p_min_items ? 1 : 0) |
-           (wino2p_items(N, D, H, W, C1 + C2) >= g_wino2p_min_items ? 2 : 0);
 }
 
 size_t mvd_wino2p_weight_elems(int C, int K) { return (size_t)16 * C * K; }
@@ -601,130 +553,51 @@ int mvd_pack_weight_wino2p(const float *w, float *uf, float *ub, int K, int C, v
     return pack_weight_wino2p(w, uf, ub, K, C, as_stream(stream));
 }
 
-int mvd_conv3d_fwd_wino2p(const float *x1, int C1, const float *x2, int C2, const float *wf, const float *pf,
-                          const float *bias, float *y, int N, int D, int H, int W, int K, const int ksize[3],
-                          const int stride[3], void *ws, size_t ws_bytes, void *stream) {
-    MVD_REQUIRE(ksize && ksize[0] == 1 && ksize[1] == 3 && ksize[2] == 3, "conv3d_fwd_wino2p: the table is that of a 1x3x3 kernel");
-    return conv3d_fwd_impl(x1, C1, x2, C2, wf, pf, bias, y, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream);
+// ------------------------------------------------------------------------------------------------ input gradient
+static bool k3s2(const int ks[3], const int st[3]) {
+    return ks[0] == 3 && ks[1] == 3 && ks[2] == 3 && st[0] == 2 && st[1] == 2 && st[2] == 2;
+}
+// the fused fp32 kernel (k_dgrad32s: all eight parity classes of a 3x3x3 stride-2 conv with a single input in one launch) is
+// tried from this many dy voxels on, and under mvd_set_wino_min_items(1) (the tests' "every engine" switch); MVD_DGRAD2=0: off
+static const long kDgrad32sMinVoxels = 4096;
+static bool dgrad32s_eligible(int N, int D, int H, int W, int C2, const int ks[3], const int st[3]) {
+    static const int dg2 = getenv("MVD_DGRAD2") ? atoi(getenv("MVD_DGRAD2")) : 1;
+    if (!dg2 || g_engine_mode != 0 || C2 != 0 || !k3s2(ks, st)) return false;
+    return (long)N * conv_out_dim(D, 3, 2) * conv_out_dim(H, 3, 2) * conv_out_dim(W, 3, 2) >= kDgrad32sMinVoxels || g_wino_min_items <= 1;
 }
 
-int mvd_conv3d_dgrad_wino2p(const float *dy, const float *wb, const float *pb, float *dx1, int C1, float *dx2, int C2,
-                            int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
+/* The general fp32 input gradient; table / table_kind as in mvd_conv3d_fwd_routed (the ub-side table of the weight) */
+int mvd_conv3d_dgrad_routed(const float *dy, const float *wb, const float *table, int table_kind, float *dx1, int C1, float *dx2,
+                            int C2, int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
                             size_t ws_bytes, void *stream) {
-    MVD_REQUIRE(ksize && ksize[0] == 1 && ksize[1] == 3 && ksize[2] == 3, "conv3d_dgrad_wino2p: the table is that of a 1x3x3 kernel");
-    return conv3d_dgrad_impl(dy, wb, pb, dx1, C1, dx2, C2, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream);
-}
-
-int mvd_conv3d_dgrad(const float *dy, const float *wb, float *dx1, int C1, float *dx2, int C2, int N, int D, int H, int W,
-                     int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {
-    return conv3d_dgrad_impl(dy, wb, nullptr, dx1, C1, dx2, C2, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream);
-}
-
-int mvd_conv3d_dgrad_wino(const float *dy, const float *wb, const float *ub, float *dx1, int C1, float *dx2, int C2, int N,
-                          int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes,
-                          void *stream) {
-    return conv3d_dgrad_impl(dy, wb, ub, dx1, C1, dx2, C2, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream);
-}
-
-int mvd_conv3d_dgrad_wino3(const float *dy, const float *wb, const float *vb, float *dx1, int C1, float *dx2, int C2,
-                           int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
-                           size_t ws_bytes, void *stream) {
-    return conv3d_dgrad_impl(dy, wb, vb, dx1, C1, dx2, C2, N, D, H, W, K, ksize, stride, ws, ws_bytes, stream, true);
-}
-
-static int conv3d_dgrad_impl(const float *dy, const float *wb, const float *ub, float *dx1, int C1, float *dx2, int C2,
-                             int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,
-                             size_t ws_bytes, void *stream, bool u3d) {
     MVD_REQUIRE(dy && wb && dx1 && C1 > 0 && C2 >= 0 && (C2 == 0 || dx2), "conv3d_dgrad: null pointer / bad channels");
     MVD_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && K > 0, "conv3d_dgrad: bad shape");
     if (check_ks(ksize, stride, "conv3d_dgrad")) return 2;
-    const int dims[3] = {D, H, W};
-    int od[3], pad[3];
-    for (int a = 0; a < 3; a++) {
-        od[a] = out_dim(dims[a], ksize[a], stride[a]);
-        pad[a] = (ksize[a] - 1) / 2;
-    }
-    // 3x3x3 stride-2 conv with 32-multiple channels and a single input: all eight parity classes in one kernel
-    static int dg2 = -1;
-    if (dg2 < 0) dg2 = getenv("MVD_DGRAD2") ? atoi(getenv("MVD_DGRAD2")) : 1;
-    if (dg2 && g_engine_mode == 0 && C2 == 0 && ksize[0] == 3 && ksize[1] == 3 && ksize[2] == 3 && stride[0] == 2 &&
-        stride[1] == 2 && stride[2] == 2 && ((long)N * od[0] * od[1] * od[2] >= 4096 || g_wino_min_items <= 1)) {
-        int r = dgrad32s(N, D, H, W, C1, K, od[0], od[1], od[2], dy, wb, dx1, as_stream(stream));
+    MVD_REQUIRE(table_kind >= MVD_CONV_DIRECT && table_kind <= MVD_CONV_WINO2P, "conv3d_dgrad: unknown table kind");
+    MVD_REQUIRE(!(table && table_kind == MVD_CONV_WINO2P) || (ksize[0] == 1 && ksize[1] == 3 && ksize[2] == 3),
+                "conv3d_dgrad: the in-plane table is that of a 1x3x3 kernel");
+    if (dgrad32s_eligible(N, D, H, W, C2, ksize, stride)) {
+        int r = dgrad32s(N, D, H, W, C1, K, conv_out_dim(D, 3, 2), conv_out_dim(H, 3, 2), conv_out_dim(W, 3, 2), dy, wb, dx1,
+                         as_stream(stream));
         if (r >= 0) return r;
     }
-    // one launch per output-parity class (1 class per stride-1 axis, 2 per stride-2 axis)
+    const WinoTable tab = {table, table_kind, ksize, stride};
     for (int pd = 0; pd < stride[0]; pd++)
         for (int ph = 0; ph < stride[1]; ph++)
             for (int pw = 0; pw < stride[2]; pw++) {
                 const int p[3] = {pd, ph, pw};
                 FwdGeom g;
-                memset(&g, 0, sizeof(g));
-                g.N = N;
-                g.Di = od[0]; g.Hi = od[1]; g.Wi = od[2];
-                g.Dy = D; g.Hy = H; g.Wy = W;
-                int grid[3];
-                bool empty = false;
-                for (int a = 0; a < 3; a++) {
-                    grid[a] = (dims[a] - p[a] + stride[a] - 1) / stride[a];
-                    if (grid[a] <= 0) empty = true;
-                    g.sa[a] = 1;
-                    g.so[a] = stride[a];
-                    g.oo[a] = p[a];
-                }
-                if (empty) continue;
-                g.Do = grid[0]; g.Ho = grid[1]; g.Wo = grid[2];
-                g.C1 = K; g.C2 = 0; g.K1 = C1; g.K2 = C2;
-                int nt = 0;
-                for (int ta = 0; ta < ksize[0]; ta++)
-                    for (int tb = 0; tb < ksize[1]; tb++)
-                        for (int tc = 0; tc < ksize[2]; tc++) {
-                            const int t3[3] = {ta, tb, tc};
-                            int off[3];
-                            bool ok = true;
-                            for (int a = 0; a < 3; a++) {
-                                int num = p[a] + pad[a] - t3[a];  // dy index q: q*s + t - pad = o*s + p
-                                if (num % stride[a] != 0) { ok = false; break; }
-                                off[a] = num / stride[a];
-                            }
-                            if (!ok) continue;
-                            for (int a = 0; a < 3; a++) g.off[nt][a] = (int8_t)off[a];
-                            g.wt[nt] = (int8_t)((ta * ksize[1] + tb) * ksize[2] + tc);
-                            nt++;
-                        }
-                g.ntaps = nt;
-                g.T = ksize[0] * ksize[1] * ksize[2];
-                if (nt == 0) continue;
-                int r = run_fwd(g, dy, nullptr, wb, nullptr, dx1, dx2, ws, ws_bytes, as_stream(stream), ub, nullptr, nullptr,
-                                u3d);
+                if (!conv_dgrad_class_geom(g, N, D, H, W, C1, C2, K, ksize, stride, p)) continue;
+                int r = run_fwd(g, dy, nullptr, wb, nullptr, dx1, dx2, ws, ws_bytes, as_stream(stream), &tab);
                 if (r) return r;
             }
     return 0;
 }
 
-static void conv_wgrad_geom(WgradGeom &g, int N, int D, int H, int W, int C1, int C2, int K, const int ks[3],
-                            const int st[3]) {
-    memset(&g, 0, sizeof(g));
-    g.N = N;
-    g.Di = D; g.Hi = H; g.Wi = W;
-    g.Do = out_dim(D, ks[0], st[0]); g.Ho = out_dim(H, ks[1], st[1]); g.Wo = out_dim(W, ks[2], st[2]);
-    g.Db = g.Do; g.Hb = g.Ho; g.Wb = g.Wo;
-    g.C1 = C1; g.C2 = C2; g.K = K;
-    int t = 0;
-    for (int a = 0; a < ks[0]; a++)
-        for (int b = 0; b < ks[1]; b++)
-            for (int c = 0; c < ks[2]; c++) {
-                g.off[t][0] = a - (ks[0] - 1) / 2;
-                g.off[t][1] = b - (ks[1] - 1) / 2;
-                g.off[t][2] = c - (ks[2] - 1) / 2;
-                g.wt[t] = t;
-                t++;
-            }
-    g.ntaps = g.T = t;
-    for (int a = 0; a < 3; a++) {
-        g.sa[a] = st[a];
-        g.sb[a] = 1;
-    }
-    g.transposed_out = 0;
+int mvd_conv3d_dgrad(const float *dy, const float *wb, float *dx1, int C1, float *dx2, int C2, int N, int D, int H, int W,
+                     int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream) {
+    return mvd_conv3d_dgrad_routed(dy, wb, nullptr, MVD_CONV_DIRECT, dx1, C1, dx2, C2, N, D, H, W, K, ksize, stride, ws, ws_bytes,
+                                   stream);
 }
 
 size_t mvd_conv3d_wgrad_workspace_bytes(int C, int K, int T, int N, int Do, int Ho, int Wo) {
@@ -742,7 +615,7 @@ int mvd_set_wgrad_wino3_min_items(long n) {
 
 int mvd_conv_wgrad_wino3_applicable(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3],
                                     const int stride[3]) {
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || K <= 0 || !ksize || !stride) return 0;
+    if (!conv_args_ok(N, D, H, W, C1, C2, K, ksize, stride, "conv_wgrad_wino3_applicable")) return 0;
     for (int a = 0; a < 3; a++)
         if (ksize[a] != 3 || stride[a] != 1) return 0;
     WgradGeom g;
@@ -787,21 +660,9 @@ int mvd_convT3d_fwd(const float *x, const float *wf, const float *bias, float *y
     for (int pd = 0; pd < stride[0]; pd++)
         for (int ph = 0; ph < stride[1]; ph++)
             for (int pw = 0; pw < stride[2]; pw++) {
-                FwdGeom g;
-                memset(&g, 0, sizeof(g));
-                g.N = N;
-                g.Di = g.Do = D; g.Hi = g.Ho = H; g.Wi = g.Wo = W;
-                g.Dy = D * stride[0]; g.Hy = H * stride[1]; g.Wy = W * stride[2];
-                g.C1 = C; g.K1 = K;
-                g.ntaps = 1;
-                g.T = stride[0] * stride[1] * stride[2];
-                g.wt[0] = (int8_t)((pd * stride[1] + ph) * stride[2] + pw);
                 const int p[3] = {pd, ph, pw};
-                for (int a = 0; a < 3; a++) {
-                    g.sa[a] = 1;
-                    g.so[a] = stride[a];
-                    g.oo[a] = p[a];
-                }
+                FwdGeom g;
+                convT_fwd_class_geom(g, N, D, H, W, C, K, stride, p);
                 int r = run_fwd(g, x, nullptr, wf, bias, y, nullptr, ws, ws_bytes, as_stream(stream));
                 if (r) return r;
             }
@@ -817,48 +678,8 @@ int mvd_convT3d_dgrad(const float *dy, const float *wb, float *dx, int N, int D,
         if (r >= 0) return r;
     }
     FwdGeom g;
-    memset(&g, 0, sizeof(g));
-    g.N = N;
-    g.Di = D * stride[0]; g.Hi = H * stride[1]; g.Wi = W * stride[2];
-    g.Do = g.Dy = D; g.Ho = g.Hy = H; g.Wo = g.Wy = W;
-    g.C1 = K; g.K1 = C;
-    int t = 0;
-    for (int pd = 0; pd < stride[0]; pd++)
-        for (int ph = 0; ph < stride[1]; ph++)
-            for (int pw = 0; pw < stride[2]; pw++) {
-                g.off[t][0] = pd; g.off[t][1] = ph; g.off[t][2] = pw;
-                g.wt[t] = t;
-                t++;
-            }
-    g.ntaps = g.T = t;
-    for (int a = 0; a < 3; a++) {
-        g.sa[a] = stride[a];
-        g.so[a] = 1;
-        g.oo[a] = 0;
-    }
+    convT_dgrad_geom(g, N, D, H, W, C, K, stride);
     return run_fwd(g, dy, nullptr, wb, nullptr, dx, nullptr, ws, ws_bytes, as_stream(stream));
-}
-
-static void convT_wgrad_geom(WgradGeom &g, int N, int D, int H, int W, int C, int K, const int st[3]) {
-    memset(&g, 0, sizeof(g));
-    g.N = N;
-    g.Di = g.Do = D; g.Hi = g.Ho = H; g.Wi = g.Wo = W;
-    g.Db = D * st[0]; g.Hb = H * st[1]; g.Wb = W * st[2];
-    g.C1 = C; g.C2 = 0; g.K = K;
-    int t = 0;
-    for (int pd = 0; pd < st[0]; pd++)
-        for (int ph = 0; ph < st[1]; ph++)
-            for (int pw = 0; pw < st[2]; pw++) {
-                g.ob[t][0] = pd; g.ob[t][1] = ph; g.ob[t][2] = pw;
-                g.wt[t] = t;
-                t++;
-            }
-    g.ntaps = g.T = t;
-    for (int a = 0; a < 3; a++) {
-        g.sa[a] = 1;
-        g.sb[a] = st[a];
-    }
-    g.transposed_out = 1;
 }
 
 size_t mvd_convT3d_wgrad_workspace_bytes(int C, int K, int T, int N, int D, int H, int W) {
@@ -951,8 +772,7 @@ int mvd_set_bf16_wgrad_kernel(int which) {
 
 int mvd_conv3d_fwd_bf16_stats_tiles(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3],
                                     const int stride[3]) {
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || K <= 0 || check_ks(ksize, stride, "conv3d_fwd_bf16_stats_tiles"))
-        return 0;
+    if (!conv_args_ok(N, D, H, W, C1, C2, K, ksize, stride, "conv3d_fwd_bf16_stats_tiles")) return 0;
     FwdGeom g;
     conv_fwd_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
     return fwd_bf16_stats_tiles(g);
@@ -960,8 +780,7 @@ int mvd_conv3d_fwd_bf16_stats_tiles(int N, int D, int H, int W, int C1, int C2, 
 
 int mvd_conv3d_fwd_bf16_prologue_ok(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3],
                                     const int stride[3]) {
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || K <= 0 || check_ks(ksize, stride, "conv3d_fwd_bf16_prologue_ok"))
-        return 0;
+    if (!conv_args_ok(N, D, H, W, C1, C2, K, ksize, stride, "conv3d_fwd_bf16_prologue_ok")) return 0;
     FwdGeom g;
     conv_fwd_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
     return fwd_bf16_prologue_ok(g);
@@ -988,21 +807,17 @@ int mvd_conv3d_fwd_bf16_fused(const uint16_t *x1, int C1, const uint16_t *x2, in
     return run_fwd16(g, x1, x2, wf, bias, y, nullptr, ws, ws_bytes, as_stream(stream), &f);
 }
 
+// the fused bf16 kernel (k_dgrad16s) is tried from this many dy voxels on
+static const long kDgrad16sMinVoxels = 512;
 static int dgrad_bf16_impl(const uint16_t *dy, const uint16_t *wb, uint16_t *dx1, int C1, uint16_t *dx2, int C2, int N, int D, int H,
                            int W, int K, const int ksize[3], const int stride[3], void *ws, size_t ws_bytes, void *stream,
                            int acc) {
     MVD_REQUIRE(dy && wb && dx1 && C1 > 0 && C2 >= 0 && (C2 == 0 || dx2), "conv3d_dgrad_bf16: null pointer / bad channels");
     MVD_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && K > 0, "conv3d_dgrad_bf16: bad shape");
     if (check_ks(ksize, stride, "conv3d_dgrad_bf16")) return 2;
-    const int dims[3] = {D, H, W};
-    int od[3], pad[3];
-    for (int a = 0; a < 3; a++) {
-        od[a] = out_dim(dims[a], ksize[a], stride[a]);
-        pad[a] = (ksize[a] - 1) / 2;
-    }
     // 3x3x3 stride-2 conv with 32-multiple channels and a single input: all eight parity classes in one kernel
-    if (g_engine_mode == 0 && C2 == 0 && ksize[0] == 3 && ksize[1] == 3 && ksize[2] == 3 && stride[0] == 2 && stride[1] == 2 &&
-        stride[2] == 2 && (long)N * od[0] * od[1] * od[2] >= 512) {
+    const int od[3] = {conv_out_dim(D, ksize[0], stride[0]), conv_out_dim(H, ksize[1], stride[1]), conv_out_dim(W, ksize[2], stride[2])};
+    if (g_engine_mode == 0 && C2 == 0 && k3s2(ksize, stride) && (long)N * od[0] * od[1] * od[2] >= kDgrad16sMinVoxels) {
         int r = dgrad16s(N, D, H, W, C1, K, od[0], od[1], od[2], dy, wb, dx1, as_stream(stream), acc);
         if (r >= 0) return r;
     }
@@ -1012,43 +827,8 @@ static int dgrad_bf16_impl(const uint16_t *dy, const uint16_t *wb, uint16_t *dx1
             for (int pw = 0; pw < stride[2]; pw++) {
                 const int p[3] = {pd, ph, pw};
                 FwdGeom g;
-                memset(&g, 0, sizeof(g));
-                g.N = N;
-                g.Di = od[0]; g.Hi = od[1]; g.Wi = od[2];
-                g.Dy = D; g.Hy = H; g.Wy = W;
-                int grid[3];
-                bool empty = false;
-                for (int a = 0; a < 3; a++) {
-                    grid[a] = (dims[a] - p[a] + stride[a] - 1) / stride[a];
-                    if (grid[a] <= 0) empty = true;
-                    g.sa[a] = 1;
-                    g.so[a] = stride[a];
-                    g.oo[a] = p[a];
-                }
-                if (empty) continue;
-                g.Do = grid[0]; g.Ho = grid[1]; g.Wo = grid[2];
-                g.C1 = K; g.C2 = 0; g.K1 = C1; g.K2 = C2;
-                int nt = 0;
-                for (int ta = 0; ta < ksize[0]; ta++)
-                    for (int tb = 0; tb < ksize[1]; tb++)
-                        for (int tc = 0; tc < ksize[2]; tc++) {
-                            const int t3[3] = {ta, tb, tc};
-                            int off[3];
-                            bool ok = true;
-                            for (int a = 0; a < 3; a++) {
-                                int num = p[a] + pad[a] - t3[a];  // dy index q: q*s + t - pad = o*s + p
-                                if (num % stride[a] != 0) { ok = false; break; }
-                                off[a] = num / stride[a];
-                            }
-                            if (!ok) continue;
-                            for (int a = 0; a < 3; a++) g.off[nt][a] = (int8_t)off[a];
-                            g.wt[nt] = (int8_t)((ta * ksize[1] + tb) * ksize[2] + tc);
-                            nt++;
-                        }
-                g.ntaps = nt;
-                g.T = ksize[0] * ksize[1] * ksize[2];
+                if (!conv_dgrad_class_geom(g, N, D, H, W, C1, C2, K, ksize, stride, p)) continue;
                 g.acc = (int8_t)acc;
-                if (nt == 0) continue;
                 int r = run_fwd16(g, dy, nullptr, wb, nullptr, dx1, dx2, ws, ws_bytes, as_stream(stream));
                 if (r) return r;
             }
@@ -1065,14 +845,12 @@ static bool strided3(const int ksize[3], const int stride[3]) {
 }
 
 int mvd_conv3d_dgrad_acc_ok(int is_bf16, int N, int D, int H, int W, int C1, int K, const int ksize[3], const int stride[3]) {
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 <= 0 || K <= 0 || check_ks(ksize, stride, "conv3d_dgrad_acc_ok")) return 0;
+    if (!conv_args_ok(N, D, H, W, C1, 0, K, ksize, stride, "conv3d_dgrad_acc_ok")) return 0;
     if (C1 % 32 || K % 32 || g_engine_mode != 0) return 0;
     if (is_bf16) return strided3(ksize, stride) ? 1 : 0;   // every parity class runs on the generic bf16 kernel
-    if (!(ksize[0] == 3 && ksize[1] == 3 && ksize[2] == 3 && stride[0] == 2 && stride[1] == 2 && stride[2] == 2)) return 0;
-    const long items = (long)N * out_dim(D, 3, 2) * out_dim(H, 3, 2) * out_dim(W, 3, 2);
-    static int dg2 = -1;
-    if (dg2 < 0) dg2 = getenv("MVD_DGRAD2") ? atoi(getenv("MVD_DGRAD2")) : 1;
-    return (dg2 && (items >= 4096 || g_wino_min_items <= 1) && (long)out_dim(D, 3, 2) * out_dim(H, 3, 2) * out_dim(W, 3, 2) * K * 4 < (1L << 31)) ? 1 : 0;
+    // fp32: the fused stride-2 kernel, and only with a dy sample below 2^31 bytes (a condition of this accumulating path alone)
+    return (dgrad32s_eligible(N, D, H, W, 0, ksize, stride) &&
+            (long)conv_out_dim(D, 3, 2) * conv_out_dim(H, 3, 2) * conv_out_dim(W, 3, 2) * K * 4 < (1L << 31)) ? 1 : 0;
 }
 
 int mvd_conv3d_dgrad_bf16_acc(const uint16_t *dy, const uint16_t *wb, uint16_t *dx1, int C1, int N, int D, int H, int W, int K,
@@ -1087,7 +865,7 @@ int mvd_conv3d_dgrad_acc(const float *dy, const float *wb, float *dx1, int C1, i
     MVD_REQUIRE(dy && wb && dx1, "conv3d_dgrad_acc: null pointer");
     MVD_REQUIRE(mvd_conv3d_dgrad_acc_ok(0, N, D, H, W, C1, K, ksize, stride), "conv3d_dgrad_acc: no accumulating kernel for this shape "
                 "(ask mvd_conv3d_dgrad_acc_ok first)");
-    int r = dgrad32s(N, D, H, W, C1, K, out_dim(D, 3, 2), out_dim(H, 3, 2), out_dim(W, 3, 2), dy, wb, dx1, as_stream(stream), 1);
+    int r = dgrad32s(N, D, H, W, C1, K, conv_out_dim(D, 3, 2), conv_out_dim(H, 3, 2), conv_out_dim(W, 3, 2), dy, wb, dx1, as_stream(stream), 1);
     if (r < 0) {
         set_error("conv3d_dgrad_acc: the fused stride-2 kernel refused the shape");
         return 3;
@@ -1106,21 +884,9 @@ int mvd_convT3d_fwd_bf16(const uint16_t *x, const uint16_t *wf, const float *bia
     for (int pd = 0; pd < stride[0]; pd++)
         for (int ph = 0; ph < stride[1]; ph++)
             for (int pw = 0; pw < stride[2]; pw++) {
-                FwdGeom g;
-                memset(&g, 0, sizeof(g));
-                g.N = N;
-                g.Di = g.Do = D; g.Hi = g.Ho = H; g.Wi = g.Wo = W;
-                g.Dy = D * stride[0]; g.Hy = H * stride[1]; g.Wy = W * stride[2];
-                g.C1 = C; g.K1 = K;
-                g.ntaps = 1;
-                g.T = stride[0] * stride[1] * stride[2];
-                g.wt[0] = (int8_t)((pd * stride[1] + ph) * stride[2] + pw);
                 const int p[3] = {pd, ph, pw};
-                for (int a = 0; a < 3; a++) {
-                    g.sa[a] = 1;
-                    g.so[a] = stride[a];
-                    g.oo[a] = p[a];
-                }
+                FwdGeom g;
+                convT_fwd_class_geom(g, N, D, H, W, C, K, stride, p);
                 int r = run_fwd16(g, x, nullptr, wf, bias, y, nullptr, ws, ws_bytes, as_stream(stream));
                 if (r) return r;
             }
@@ -1136,25 +902,7 @@ int mvd_convT3d_dgrad_bf16(const uint16_t *dy, const uint16_t *wb, uint16_t *dx,
         if (r >= 0) return r;
     }
     FwdGeom g;
-    memset(&g, 0, sizeof(g));
-    g.N = N;
-    g.Di = D * stride[0]; g.Hi = H * stride[1]; g.Wi = W * stride[2];
-    g.Do = g.Dy = D; g.Ho = g.Hy = H; g.Wo = g.Wy = W;
-    g.C1 = K; g.K1 = C;
-    int t = 0;
-    for (int pd = 0; pd < stride[0]; pd++)
-        for (int ph = 0; ph < stride[1]; ph++)
-            for (int pw = 0; pw < stride[2]; pw++) {
-                g.off[t][0] = pd; g.off[t][1] = ph; g.off[t][2] = pw;
-                g.wt[t] = t;
-                t++;
-            }
-    g.ntaps = g.T = t;
-    for (int a = 0; a < 3; a++) {
-        g.sa[a] = stride[a];
-        g.so[a] = 1;
-        g.oo[a] = 0;
-    }
+    convT_dgrad_geom(g, N, D, H, W, C, K, stride);
     return run_fwd16(g, dy, nullptr, wb, nullptr, dx, nullptr, ws, ws_bytes, as_stream(stream));
 }
 
@@ -1178,8 +926,7 @@ int mvd_conv3d_wgrad_bf16(const uint16_t *x1, int C1, const uint16_t *x2, int C2
 }
 
 int mvd_conv3d_wgrad_bf16_prologue_ok(int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3], const int stride[3]) {
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || K <= 0 || check_ks(ksize, stride, "conv3d_wgrad_bf16_prologue_ok"))
-        return 0;
+    if (!conv_args_ok(N, D, H, W, C1, C2, K, ksize, stride, "conv3d_wgrad_bf16_prologue_ok")) return 0;
     WgradGeom g;
     conv_wgrad_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
     return wgrad16z_prologue_ok(g) ? 1 : 0;

@@ -9,7 +9,9 @@
 //   dW[wt[t]][c][k] = sum_n sum_o A[n, o*sa + off[t], c] * B[n, o*sb + ob[t], k]
 // B [.,K] with spatial dims (Db,Hb,Wb) (reads outside are zero).
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 namespace mvd {
 
@@ -58,6 +60,163 @@ struct WgradGeom {
     int8_t wt[27];
     int transposed_out;  // 0: dw[k][c][T] (Conv3d), 1: dw[c][k][T] (ConvTranspose3d)
 };
+
+// ------------------------------------------------------------------------------------------------ geometry builders
+// The one place each descriptor is built: the fp32 and the bf16 entry points of conv.hip call the same builder
+// (tests/host/conv_geom_dump.cpp prints their bytes, tests/golden/conv_geom.txt pins them).  Kernel sizes are 1 or 3 and
+// strides 1 or 2 per axis (check_ks at the entry points); every builder clears the struct first, padding included.
+inline int conv_out_dim(int in, int k, int s) { return (in + 2 * ((k - 1) / 2) - k) / s + 1; }
+
+// every tap of a ks[0] x ks[1] x ks[2] kernel in raster order, offsets relative to the centre; returns their number
+inline int conv_full_taps(const int ks[3], int8_t off[27][3], int8_t wt[27]) {
+    int t = 0;
+    for (int a = 0; a < ks[0]; a++)
+        for (int b = 0; b < ks[1]; b++)
+            for (int c = 0; c < ks[2]; c++) {
+                off[t][0] = a - (ks[0] - 1) / 2;
+                off[t][1] = b - (ks[1] - 1) / 2;
+                off[t][2] = c - (ks[2] - 1) / 2;
+                wt[t] = t;
+                t++;
+            }
+    return t;
+}
+
+inline void conv_fwd_geom(FwdGeom &g, int N, int D, int H, int W, int C1, int C2, int K, const int ks[3], const int st[3]) {
+    memset(&g, 0, sizeof(g));
+    g.N = N;
+    g.Di = D; g.Hi = H; g.Wi = W;
+    g.Do = conv_out_dim(D, ks[0], st[0]); g.Ho = conv_out_dim(H, ks[1], st[1]); g.Wo = conv_out_dim(W, ks[2], st[2]);
+    g.Dy = g.Do; g.Hy = g.Ho; g.Wy = g.Wo;
+    g.C1 = C1; g.C2 = C2; g.K1 = K; g.K2 = 0;
+    g.ntaps = g.T = conv_full_taps(ks, g.off, g.wt);
+    for (int a = 0; a < 3; a++) {
+        g.sa[a] = st[a];
+        g.so[a] = 1;
+        g.oo[a] = 0;
+    }
+}
+
+inline void conv_wgrad_geom(WgradGeom &g, int N, int D, int H, int W, int C1, int C2, int K, const int ks[3], const int st[3]) {
+    memset(&g, 0, sizeof(g));
+    g.N = N;
+    g.Di = D; g.Hi = H; g.Wi = W;
+    g.Do = conv_out_dim(D, ks[0], st[0]); g.Ho = conv_out_dim(H, ks[1], st[1]); g.Wo = conv_out_dim(W, ks[2], st[2]);
+    g.Db = g.Do; g.Hb = g.Ho; g.Wb = g.Wo;
+    g.C1 = C1; g.C2 = C2; g.K = K;
+    g.ntaps = g.T = conv_full_taps(ks, g.off, g.wt);
+    for (int a = 0; a < 3; a++) {
+        g.sa[a] = st[a];
+        g.sb[a] = 1;
+    }
+    g.transposed_out = 0;
+}
+
+// Input gradient of the conv [N,D,H,W,C1+C2] -> K as forward-type problems: one per output-parity class p (1 class per
+// stride-1 axis, 2 per stride-2 axis), reading dy and writing the voxels o*st + p of dx1 / dx2.  false: the class has no
+// voxel or no tap (nothing to launch; g is then unspecified).  g.acc stays 0.
+inline bool conv_dgrad_class_geom(FwdGeom &g, int N, int D, int H, int W, int C1, int C2, int K, const int ks[3],
+                                  const int st[3], const int p[3]) {
+    const int dims[3] = {D, H, W};
+    memset(&g, 0, sizeof(g));
+    g.N = N;
+    g.Di = conv_out_dim(D, ks[0], st[0]); g.Hi = conv_out_dim(H, ks[1], st[1]); g.Wi = conv_out_dim(W, ks[2], st[2]);
+    g.Dy = D; g.Hy = H; g.Wy = W;
+    int grid[3];
+    for (int a = 0; a < 3; a++) {
+        grid[a] = (dims[a] - p[a] + st[a] - 1) / st[a];
+        if (grid[a] <= 0) return false;
+        g.sa[a] = 1;
+        g.so[a] = st[a];
+        g.oo[a] = p[a];
+    }
+    g.Do = grid[0]; g.Ho = grid[1]; g.Wo = grid[2];
+    g.C1 = K; g.C2 = 0; g.K1 = C1; g.K2 = C2;
+    int nt = 0;
+    for (int ta = 0; ta < ks[0]; ta++)
+        for (int tb = 0; tb < ks[1]; tb++)
+            for (int tc = 0; tc < ks[2]; tc++) {
+                const int t3[3] = {ta, tb, tc};
+                int off[3];
+                bool ok = true;
+                for (int a = 0; a < 3; a++) {
+                    int num = p[a] + (ks[a] - 1) / 2 - t3[a];  // dy index q: q*s + t - pad = o*s + p
+                    if (num % st[a] != 0) { ok = false; break; }
+                    off[a] = num / st[a];
+                }
+                if (!ok) continue;
+                for (int a = 0; a < 3; a++) g.off[nt][a] = (int8_t)off[a];
+                g.wt[nt] = (int8_t)((ta * ks[1] + tb) * ks[2] + tc);
+                nt++;
+            }
+    g.ntaps = nt;
+    g.T = ks[0] * ks[1] * ks[2];
+    return nt > 0;
+}
+
+// ConvTranspose3d with kernel == stride, x [N,D,H,W,C] -> y [N,D*st,...,K]: the forward is one single-tap problem per
+// output-parity class p ...
+inline void convT_fwd_class_geom(FwdGeom &g, int N, int D, int H, int W, int C, int K, const int st[3], const int p[3]) {
+    memset(&g, 0, sizeof(g));
+    g.N = N;
+    g.Di = g.Do = D; g.Hi = g.Ho = H; g.Wi = g.Wo = W;
+    g.Dy = D * st[0]; g.Hy = H * st[1]; g.Wy = W * st[2];
+    g.C1 = C; g.K1 = K;
+    g.ntaps = 1;
+    g.T = st[0] * st[1] * st[2];
+    g.wt[0] = (int8_t)((p[0] * st[1] + p[1]) * st[2] + p[2]);
+    for (int a = 0; a < 3; a++) {
+        g.sa[a] = 1;
+        g.so[a] = st[a];
+        g.oo[a] = p[a];
+    }
+}
+
+// ... its input gradient one strided problem over all the taps ...
+inline void convT_dgrad_geom(FwdGeom &g, int N, int D, int H, int W, int C, int K, const int st[3]) {
+    memset(&g, 0, sizeof(g));
+    g.N = N;
+    g.Di = D * st[0]; g.Hi = H * st[1]; g.Wi = W * st[2];
+    g.Do = g.Dy = D; g.Ho = g.Hy = H; g.Wo = g.Wy = W;
+    g.C1 = K; g.K1 = C;
+    int t = 0;
+    for (int pd = 0; pd < st[0]; pd++)
+        for (int ph = 0; ph < st[1]; ph++)
+            for (int pw = 0; pw < st[2]; pw++) {
+                g.off[t][0] = pd; g.off[t][1] = ph; g.off[t][2] = pw;
+                g.wt[t] = t;
+                t++;
+            }
+    g.ntaps = g.T = t;
+    for (int a = 0; a < 3; a++) {
+        g.sa[a] = st[a];
+        g.so[a] = 1;
+        g.oo[a] = 0;
+    }
+}
+
+// ... and its weight gradient
+inline void convT_wgrad_geom(WgradGeom &g, int N, int D, int H, int W, int C, int K, const int st[3]) {
+    memset(&g, 0, sizeof(g));
+    g.N = N;
+    g.Di = g.Do = D; g.Hi = g.Ho = H; g.Wi = g.Wo = W;
+    g.Db = D * st[0]; g.Hb = H * st[1]; g.Wb = W * st[2];
+    g.C1 = C; g.C2 = 0; g.K = K;
+    int t = 0;
+    for (int pd = 0; pd < st[0]; pd++)
+        for (int ph = 0; ph < st[1]; ph++)
+            for (int pw = 0; pw < st[2]; pw++) {
+                g.ob[t][0] = pd; g.ob[t][1] = ph; g.ob[t][2] = pw;
+                g.wt[t] = t;
+                t++;
+            }
+    g.ntaps = g.T = t;
+    for (int a = 0; a < 3; a++) {
+        g.sa[a] = 1;
+        g.sb[a] = st[a];
+    }
+    g.transposed_out = 1;
+}
 
 // engines (return 0 ok, >0 error, -1 = shape not supported by this engine)
 int fwd_scalar(const FwdGeom &g, const float *a1, const float *a2, const float *w, const float *bias, float *y1,

@@ -144,7 +144,7 @@ def pack_weight(weight, transposed):
 # storage pointer, version of that flat buffer).  torch in-place writes to the parameter or to optim.FlatParams.flat
 # (dist.broadcast, `flat -= ...`) bump a version; the fused optimizer -- which updates ITS flat buffer through a raw
 # pointer -- bumps that buffer's epoch and re-packs the weights that live in it in ONE launch (repack_all(fp):
-# mvd_pack_weights_batch); the weights of another optimizer in the process are not touched (round 3: they used to be
+# mvd_pack_weights_batch3); the weights of another optimizer in the process are not touched (round 3: they used to be
 # re-packed and their saved graphs invalidated too).  A stale or missing entry is packed on the spot by the per-layer
 # entries.  The one write torch cannot see is `p.data.copy_()` / any other raw-pointer writer: such code must call
 # invalidate_packs() (FlatParams.invalidate_packs), which bumps the global epoch.
@@ -597,60 +597,41 @@ class Conv3dFn(Function):
             wf, wb = _packed_bf16(weight, False)
             conv3d_fwd_bf16(x1, C1, x2, C2, wf, bias, y, N, D, H, W, K, ks, stride, ws)
         else:
-            # fp32 3x3x3 stride-1 layers with enough tiles run the Winograd kernels (4/9 of the MFMA work); the packed
-            # weights come from the per-weight cache (re-packed once per optimizer step, see repack_all)
-            # F(2x2x2,3x3x3) (mvd_conv_wino3_applicable: 2/3 of the F(2x2,3x3) MFMA work) where it has enough work items,
-            # F(2x2,3x3) on the other Winograd layers, the direct engines on the rest
-            wino = query("mvd_conv_wino_applicable", N, D, H, W, C1, C2, K, i3(ks), i3(stride)) if len(ks) == 3 else 0
-            wino3 = query("mvd_conv_wino3_applicable", N, D, H, W, C1, C2, K, i3(ks), i3(stride)) if wino else 0
-            wino2 = wino & ~wino3
-            # the 9-tap in-plane layers (1x3x3: a 2-D network's convs, anisotropic 3-D plans): F(2x2,3x3) per plane where
-            # mvd_conv_wino2p_applicable has it (uf / ub of such a weight are that engine's tables), the direct engines else
-            wino2p = query("mvd_conv_wino2p_applicable", N, D, H, W, C1, C2, K, i3(ks), i3(stride)) \
-                if tuple(ks) == (1, 3, 3) else 0
-            pk = _packed(weight, False, bool((wino2 | wino2p) & 1), bool((wino2 | wino2p) & 2), bool(wino3 & 1),
-                         bool(wino3 & 2))
+            # fp32: one route query names the engine of the forward and of the input gradient (mvd_conv3d_route): 3x3x3
+            # stride-1 layers run F(2x2x2,3x3x3) where it has enough work items and F(2x2,3x3) where that one has, the 9-tap
+            # in-plane layers (1x3x3: a 2-D network's convs, anisotropic 3-D plans) F(2x2,3x3) per plane, the rest the direct
+            # engines.  The packed weights and tables come from the per-weight cache (re-packed once per optimizer step, see
+            # repack_all); uf / ub of a 9-tap weight are the in-plane engine's tables
+            route = query("mvd_conv3d_route", N, D, H, W, C1, C2, K, i3(ks), i3(stride)) if len(ks) == 3 else 0
+            kf, kb = route & 15, route >> 4
+            two = (_lib.CONV_WINO2, _lib.CONV_WINO2P)
+            pk = _packed(weight, False, kf in two, kb in two, kf == _lib.CONV_WINO3, kb == _lib.CONV_WINO3)
             wf, wb = pk.wf, pk.wb
-            uf = pk.vf if wino3 & 1 else (pk.uf if wino2 & 1 else None)
-            ub = pk.vb if wino3 & 2 else (pk.ub if (wino2 | wino2p) & 2 else None)
-            sfx3 = "3" if wino3 & 1 else ""
-            ctx.ub3 = bool(wino3 & 2)
-            ctx.ub2p = bool(wino2p & 2)
-            if wino2p & 1:
-                # (no statistics epilogue in this kernel: the InstanceNorm behind it runs its statistics pass)
-                call("mvd_conv3d_fwd_wino2p", _p(x1), C1, _p(x2), C2, _p(wf), _p(pk.uf), _p(bias), _p(y), N, D, H, W, K,
-                     i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
-            elif uf is not None:
-                # the Winograd kernel also emits the per-tile (sum, sum of squares) of its output: the InstanceNorm that
-                # follows (InstanceNormLeakyReLUFn picks them up from the tensor) skips its statistics pass
+            uf = pk.vf if kf == _lib.CONV_WINO3 else (pk.uf if kf in two else None)
+            ub = pk.vb if kb == _lib.CONV_WINO3 else (pk.ub if kb in two else None)
+            ctx.ub_kind = kb
+            # statistics epilogue: the 3x3x3 Winograd kernels also emit the per-tile (sum, sum of squares) of their output, so
+            # the InstanceNorm that follows (InstanceNormLeakyReLUFn picks them up from the tensor) skips its statistics pass;
+            # the in-plane kernel has none (the norm behind it runs its pass).
+            # The direct engines of the narrow-input and the stride-2 layers have the same epilogue; asked for only where
+            # the norm behind the conv would otherwise run a statistics pass (a small volume takes its own, in one launch).
+            # The trade: a chunked conv that is asked for statistics does not split its reduce channels over workgroups
+            # (launch_fwd), which skinny problems -- few tiles, >= 32 reduce channels -- use to fill the chip.  In the
+            # benchmark network no layer is both split and asked (the skinny stride-2 layers feed small norms); at other
+            # patch sizes a chunked stride-2 layer with more than 1024 output voxels gives up its split for a statistics
+            # pass of a few microseconds (MVD_DIRECT_CONV_STATS=0 keeps the split).
+            ntiles = direct_tiles = 0
+            if kf in (_lib.CONV_WINO2, _lib.CONV_WINO3):
                 ntiles = query("mvd_conv_stats_tiles", od[0], od[1], od[2])
-                stats = torch.empty((N, ntiles, K, 2), dtype=torch.float32, device=x1.device)
-                done = ctypes.c_int(0)
-                call("mvd_conv3d_fwd_wino" + sfx3 + "_stats", _p(x1), C1, _p(x2), C2, _p(wf), _p(uf), _p(bias), _p(y),
-                     _p(stats), ctypes.byref(done), N, D, H, W, K, i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
-                if done.value:
-                    y._mvd_tile_stats = (stats, ntiles)
-            else:
-                # the direct engines of the narrow-input and the stride-2 layers have the same epilogue; asked for only where
-                # the norm behind the conv would otherwise run a statistics pass (a small volume takes its own, in one launch).
-                # The trade: a chunked conv that is asked for statistics does not split its reduce channels over workgroups
-                # (launch_fwd), which skinny problems -- few tiles, >= 32 reduce channels -- use to fill the chip.  In the
-                # benchmark network no layer is both split and asked (the skinny stride-2 layers feed small norms); at other
-                # patch sizes a chunked stride-2 layer with more than 1024 output voxels gives up its split for a statistics
-                # pass of a few microseconds (MVD_DIRECT_CONV_STATS=0 keeps the split).
-                ntiles = 0
-                if DIRECT_CONV_STATS[0] and len(ks) == 3 and not query("mvd_instnorm_single_launch", od[0] * od[1] * od[2], K):
-                    ntiles = query("mvd_conv3d_fwd_stats_tiles", N, D, H, W, C1, C2, K, i3(ks), i3(stride))
-                if ntiles > 0:
-                    stats = torch.empty((N, ntiles, K, 2), dtype=torch.float32, device=x1.device)
-                    done = ctypes.c_int(0)
-                    call("mvd_conv3d_fwd_stats", _p(x1), C1, _p(x2), C2, _p(wf), _p(bias), _p(y), _p(stats), ntiles,
-                         ctypes.byref(done), N, D, H, W, K, i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
-                    if done.value:
-                        y._mvd_tile_stats = (stats, ntiles)
-                else:
-                    call("mvd_conv3d_fwd_wino", _p(x1), C1, _p(x2), C2, _p(wf), _p(uf), _p(bias), _p(y), N, D, H, W, K, i3(ks),
-                         i3(stride), _p(ws), ws.numel(), _stream())
+            elif kf == _lib.CONV_DIRECT and DIRECT_CONV_STATS[0] and len(ks) == 3 \
+                    and not query("mvd_instnorm_single_launch", od[0] * od[1] * od[2], K):
+                ntiles = direct_tiles = query("mvd_conv3d_fwd_stats_tiles", N, D, H, W, C1, C2, K, i3(ks), i3(stride))
+            stats = torch.empty((N, ntiles, K, 2), dtype=torch.float32, device=x1.device) if ntiles > 0 else None
+            done = ctypes.c_int(0)
+            call("mvd_conv3d_fwd_routed", _p(x1), C1, _p(x2), C2, _p(wf), _p(uf), kf, _p(bias), _p(y), _p(stats), direct_tiles,
+                 ctypes.byref(done), N, D, H, W, K, i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
+            if done.value:
+                y._mvd_tile_stats = (stats, ntiles)
         if timed:
             ev1 = torch.cuda.Event(enable_timing=True)
             ev1.record()
@@ -699,9 +680,8 @@ class Conv3dFn(Function):
                 call("mvd_conv3d_dgrad_bf16", _p(dy), _p(wb), _p(dx1), C1, _p(dx2), C2, N, D, H, W, K, i3(ks), i3(stride),
                      _p(ws), ws.numel(), _stream())
             else:
-                call("mvd_conv3d_dgrad_wino3" if ctx.ub3 else ("mvd_conv3d_dgrad_wino2p" if ctx.ub2p else
-                                                               "mvd_conv3d_dgrad_wino"), _p(dy), _p(wb), _p(ub), _p(dx1), C1,
-                     _p(dx2), C2, N, D, H, W, K, i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
+                call("mvd_conv3d_dgrad_routed", _p(dy), _p(wb), _p(ub), ctx.ub_kind, _p(dx1), C1, _p(dx2), C2, N, D, H, W, K,
+                     i3(ks), i3(stride), _p(ws), ws.numel(), _stream())
             if need1:
                 _publish(ctx.share1, dx1)
             if need2:

@@ -96,9 +96,9 @@ def _float_case():
 
 
 def _plain_forward(x, w, b):
-    """mvd_conv3d_fwd_wino3, the entry point without the statistics epilogue, on the tables ops.py would pack"""
+    """mvd_conv3d_fwd_routed with the 3-D table and without the statistics epilogue, on the tables ops.py would pack"""
     from multimodal_mvd_seg_amd import ops
-    from multimodal_mvd_seg_amd._lib import call, i3, query
+    from multimodal_mvd_seg_amd._lib import CONV_WINO3, call, i3, query
     P = lambda t: ctypes.c_void_p(t.data_ptr())
     s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     N, C, D, H, W = x.shape
@@ -115,8 +115,8 @@ def _plain_forward(x, w, b):
         call("mvd_pack_weight_wino3", P(wd), P(vf), P(vb), K, C, s)
         y = ops.empty_cl3d((N, K, D, H, W), DEV)
         ws = torch.empty(max(query("mvd_conv_fwd_workspace_bytes", N, D * H * W, K), 1024), dtype=torch.uint8, device=DEV)
-        call("mvd_conv3d_fwd_wino3", P(xd), C, None, 0, P(wf), P(vf), P(bd), P(y), N, D, H, W, K, i3((3, 3, 3)), i3((1, 1, 1)),
-             P(ws), ws.numel(), s)
+        call("mvd_conv3d_fwd_routed", P(xd), C, None, 0, P(wf), P(vf), CONV_WINO3, P(bd), P(y), None, 0, None, N, D, H, W, K,
+             i3((3, 3, 3)), i3((1, 1, 1)), P(ws), ws.numel(), s)
         torch.cuda.synchronize()
         return y.cpu()
     finally:

@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--what", default="fwd,dgrad,wgrad")
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
-    ap.add_argument("--wino", type=int, default=1, help="fp32: 1 = F(2x2,3x3) Winograd entries (default), 3 = F(2x2x2,3x3x3) entries (k_fwd_wino3), 0 = direct")
+    ap.add_argument("--wino", type=int, default=1, help="fp32: 1 = F(2x2,3x3) Winograd tables (default), 3 = F(2x2x2,3x3x3) tables (k_fwd_wino3), 0 = direct")
     args = ap.parse_args()
     bf = args.dtype == "bf16"
     dt = torch.bfloat16 if bf else torch.float32
@@ -61,23 +61,24 @@ def main():
         ks, sd = i3((3, 3, 3)), i3((st, st, st))
         flops = 2.0 * 27 * (C1 + C2) * K * N * So ** 3
         uf = ub = None
-        e3 = ""  # "3": the *_wino3 entries with the 3-D tables in place of uf / ub
+        kind = 0  # the engine of the tables uf / ub (the MVD_CONV_* kinds: 0 direct, 1 F(2x2,3x3), 2 F(2x2x2,3x3x3))
         if not bf and args.wino == 3 and query("mvd_conv_wino3_applicable", N, S, S, S, C1, C2, K, i3((3, 3, 3)), i3((st, st, st))):
             uf = torch.empty(query("mvd_wino3_weight_elems", C1 + C2, K), device=dev)
             ub = torch.empty(query("mvd_wino3_weight_elems", C1 + C2, K), device=dev)
             call("mvd_pack_weight_wino3", P(w), P(uf), P(ub), K, C1 + C2, s)
-            e3 = "3"
+            kind = 2
         elif not bf and args.wino and query("mvd_conv_wino_applicable", N, S, S, S, C1, C2, K, i3((3, 3, 3)), i3((st, st, st))):
             uf = torch.empty(query("mvd_wino_weight_elems", C1 + C2, K), device=dev)
             ub = torch.empty(query("mvd_wino_weight_elems", C1 + C2, K), device=dev)
             call("mvd_pack_weight_wino", P(w), P(uf), P(ub), K, C1 + C2, s)
+            kind = 1
         fns = {
-            "fwd": (lambda: call("mvd_conv3d_fwd_wino" + e3, P(x1), C1, P(x2), C2, P(wf), P(uf), P(bias), P(y), N, S, S, S, K, ks,
-                                 sd, P(ws), ws.numel(), s)) if not bf else
+            "fwd": (lambda: call("mvd_conv3d_fwd_routed", P(x1), C1, P(x2), C2, P(wf), P(uf), kind, P(bias), P(y), None, 0, None,
+                                 N, S, S, S, K, ks, sd, P(ws), ws.numel(), s)) if not bf else
                    (lambda: call("mvd_conv3d_fwd_bf16", P(x1), C1, P(x2), C2, P(wf), P(bias), P(y), N, S, S, S, K, ks, sd,
                                  P(ws), ws.numel(), s)),
-            "dgrad": (lambda: call("mvd_conv3d_dgrad_wino" + e3, P(dy), P(wb), P(ub), P(dx1), C1, P(dx2), C2, N, S, S, S, K, ks,
-                                   sd, P(ws), ws.numel(), s)) if not bf else
+            "dgrad": (lambda: call("mvd_conv3d_dgrad_routed", P(dy), P(wb), P(ub), kind, P(dx1), C1, P(dx2), C2, N, S, S, S, K,
+                                   ks, sd, P(ws), ws.numel(), s)) if not bf else
                      (lambda: call("mvd_conv3d_dgrad_bf16", P(dy), P(wb), P(dx1), C1, P(dx2), C2, N, S, S, S, K, ks, sd,
                                    P(ws), ws.numel(), s)),
             "wgrad": lambda: call("mvd_conv3d_wgrad" + sfx, P(x1), C1, P(x2), C2, P(dy), P(dw), P(db), N, S, S, S, K, ks, sd,

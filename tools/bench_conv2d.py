@@ -15,7 +15,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from multimodal_mvd_seg_amd import ops  # noqa: E402
-from multimodal_mvd_seg_amd._lib import call, i3, query  # noqa: E402
+from multimodal_mvd_seg_amd._lib import CONV_WINO2P, call, i3, query  # noqa: E402
 
 # name: (N, C1, C2, K, D, H, W)
 LAYERS = {
@@ -92,12 +92,12 @@ def bench_layers(launches, layers=LAYERS, reps=1):
             return lambda: call("mvd_set_wino2p_min_items", 1 if on else 1 << 40)
 
         def fwd(on):
-            return select(on), lambda: call("mvd_conv3d_fwd_wino2p", P(x1), C1, P(x2), C2, P(wf), P(pf), P(bias), P(y), N, D,
-                                            H, W, K, ks, st, P(ws), ws.numel(), s)
+            return select(on), lambda: call("mvd_conv3d_fwd_routed", P(x1), C1, P(x2), C2, P(wf), P(pf), CONV_WINO2P, P(bias), P(y),
+                                            None, 0, None, N, D, H, W, K, ks, st, P(ws), ws.numel(), s)
 
         def dgrad(on):
-            return select(on), lambda: call("mvd_conv3d_dgrad_wino2p", P(dy), P(wb), P(pb), P(dx1), C1, P(dx2), C2, N, D, H,
-                                            W, K, ks, st, P(ws), ws.numel(), s)
+            return select(on), lambda: call("mvd_conv3d_dgrad_routed", P(dy), P(wb), P(pb), CONV_WINO2P, P(dx1), C1, P(dx2), C2, N,
+                                            D, H, W, K, ks, st, P(ws), ws.numel(), s)
 
         def wgrad():
             call("mvd_conv3d_wgrad", P(x1), C1, P(x2), C2, P(dy), P(dw), P(db), N, D, H, W, K, ks, st, P(ws), ws.numel(), s)
