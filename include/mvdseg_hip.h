@@ -315,7 +315,10 @@ int mvd_cast_bf16_to_f32(const uint16_t *src, float *dst, long n, void *stream);
  * InstanceNorm3d(eps, affine) + LeakyReLU(slope), fused (K3/K4).  Replaces nn.InstanceNorm3d + nn.LeakyReLU of
  * every ConvDropoutNormReLU (get_network_from_plans.py:41-44).  x,y: [N,V,C] NDHWC with V = D*H*W.
  * Biased variance over V, no running stats.  mean/rstd [N][C] are outputs (saved for backward).
- * ws: 2*N*nblk*C doubles (nblk from mvd_instnorm_nblk). */
+ * ws: 2*N*nblk*C doubles (nblk from mvd_instnorm_nblk).
+ * Alignment (every InstanceNorm entry point, fp32 and bf16): for C % 4 == 0 the kernels load and store four channels at a
+ * time, so x, y, dy and dx must be 16-byte aligned as fp32 and 8-byte aligned as bf16; a pointer that is not is refused
+ * before any launch.  C % 4 != 0 has no such requirement, nor has the planar logit gradient of mvd_instnorm_lrelu_bwd_head. */
 int mvd_instnorm_nblk(int N, long V, int C);
 size_t mvd_instnorm_workspace_bytes(int N, long V, int C);
 int mvd_instnorm_lrelu_fwd(const float *x, const float *gamma, const float *beta, float *y, float *mean,
@@ -341,6 +344,41 @@ long mvd_instnorm_stats_pass_launches(void);
 long mvd_instnorm_single_launches(void);
 /* A/B and test aid: the limit in voxels x channels per sample (0: never; < 0: back to MVD_IN_SMALL_MAX / the default) */
 int mvd_set_instnorm_small_max(long max_elems);
+/* The launch plan of the InstanceNorm entry points: host arithmetic only (no device call), the function the launch code
+ * itself consumes.  dir 0 forward, 1 backward; ntiles > 0: the statistics come from a conv's epilogue tiles; head: the
+ * forms of the fused seg head.  Which entry point the arguments describe:
+ *   forward   fp32 -> fp32          mvd_instnorm_lrelu_fwd; ntiles > 0: mvd_instnorm_lrelu_fwd_prestats
+ *             fp32 / bf16 -> bf16   mvd_instnorm_lrelu_fwd_bf16; bf16 -> bf16 with ntiles > 0: mvd_instnorm_finalize_tiles
+ *                                   followed by mvd_instnorm_lrelu_apply_bf16
+ *             head                  statistics only: mvd_instnorm_stats_bf16 (y_is_bf16 ignored, C % 4 == 0), ntiles > 0:
+ *                                   mvd_instnorm_stats_from_tiles (fp32)
+ *   backward  (x, dy) fp32, fp32    mvd_instnorm_lrelu_bwd; head: mvd_instnorm_lrelu_bwd_head
+ *             fp32 / bf16, bf16     mvd_instnorm_lrelu_bwd_bf16
+ * plan[MVD_IN_PLAN_LEN]: 0 statistics kernel, 1 apply kernel (MVD_IN_* below; the single launch names itself in both),
+ * 2 threads, 3 R (voxel rows per block), 4 CG (channel groups per row) of the row-mapped kernels, 5 the block partials per
+ * sample the finalize kernel sums, 6 voxels per statistics block (0: the partials come from tiles), 7 / 8 blocks per sample
+ * and voxels per block of the apply pass (chunk 0: k_in_apply<1> / k_in_bwd_apply<1>, 256 threads, grid stride), 9 / 10
+ * blocks per sample and tiles per block of the tile pass (k_in_finalize_tiles: one wave takes all tiles), 11 / 12 channels
+ * and tile rows per 256-thread block of k_in_tiles_reduce.  Returns 2, with a message, for what the entry point refuses
+ * by shape or type; the single launch follows mvd_set_instnorm_small_max as the entry points do. */
+#define MVD_IN_NONE 0
+#define MVD_IN_SMALL_FWD 1       /* k_in_small_fwd */
+#define MVD_IN_SMALL_BWD 2       /* k_in_small_bwd */
+#define MVD_IN_STATS4 3          /* k_in_stats<4, x type> + k_in_finalize */
+#define MVD_IN_STATS1 4          /* k_in_stats<1> + k_in_finalize */
+#define MVD_IN_TILES_REDUCE 5    /* k_in_tiles_reduce + k_in_finalize */
+#define MVD_IN_FINALIZE_TILES 6  /* k_in_finalize_tiles */
+#define MVD_IN_APPLY_ROWS 7      /* k_in_apply_rows<false, y type> */
+#define MVD_IN_APPLY1 8          /* k_in_apply<1> */
+#define MVD_IN_APPLY_SS16 9      /* k_in_apply_ss16 */
+#define MVD_IN_BWD_STATS4 10     /* k_in_bwd_stats<4, x type, dy type> + k_in_bwd_finalize */
+#define MVD_IN_BWD_STATS1 11     /* k_in_bwd_stats<1> + k_in_bwd_finalize */
+#define MVD_IN_BWD_STATS_HEAD 12 /* k_in_bwd_stats<4, false, false, K> + k_in_bwd_finalize */
+#define MVD_IN_BWD_APPLY_ROWS 13 /* k_in_bwd_apply_rows<x type, dy type> */
+#define MVD_IN_BWD_APPLY1 14     /* k_in_bwd_apply<1> */
+#define MVD_IN_BWD_APPLY_HEAD 15 /* k_in_bwd_apply_rows<false, false, K> */
+#define MVD_IN_PLAN_LEN 13
+int mvd_instnorm_plan(int dir, int N, long V, int C, int x_is_bf16, int y_is_bf16, long ntiles, int head, long *plan);
 /* The same backward for the block whose only consumer is the fused seg head (mvd_seghead_*_fused), from the head's planar
  * logit gradient dlogits [N,K,V] and weight w [K,C]: dy[v][c] = sum_k dlogits[k][v] * w[k][c] is formed inside the two
  * passes (the value mvd_seghead_bwd_fused stores as dx, bit for bit), so that tensor is neither written nor read back --

@@ -118,6 +118,7 @@ SIGNATURES = {
     "mvd_instnorm_single_launches": (c_long, []),
     "mvd_instnorm_stats_pass_launches": (c_long, []),
     "mvd_set_instnorm_small_max": (c_int, [c_long]),
+    "mvd_instnorm_plan": (c_int, [c_int, c_int, c_long, c_int, c_int, c_int, c_long, c_int, _P]),
     "mvd_instnorm_lrelu_bwd_head": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_float, _P,
                                             c_size_t, _P]),
     "mvd_batchnorm_nblk": (c_int, [c_int, c_long, c_int]),

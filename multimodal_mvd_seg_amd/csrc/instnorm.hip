@@ -15,10 +15,7 @@ static NormGeom norm_geom(int N, long V, int C) {
     g.C = C;
     g.V = V;
     int vec = (C % 4 == 0) ? 4 : 1;
-    g.CG = C / vec;
-    if (g.CG > 256) {  // very wide, not on the path; fall back to scalar columns of 256
-        g.CG = C;
-    }
+    g.CG = C / vec;  // at most 256 for C % 4 == 0 and at most 1024 otherwise: every entry point requires C <= 1024
     g.R = 256 / g.CG;
     if (g.R < 1) g.R = 1;
     g.threads = ((g.R * g.CG + 63) / 64) * 64;
@@ -858,7 +855,135 @@ static int in_small_ok(long V, int C, int nb = 0) {
     return in_small_threads(V);
 }
 
+// ---- the launch plan: which kernels an entry point runs and on which grids.  ALL of that arithmetic is here; the launch
+// code below consumes an InPlan and mvd_instnorm_plan copies it out (tests/instnorm_ref.py restates it).
+struct InPlan {
+    int stats = MVD_IN_NONE, apply = MVD_IN_NONE;  // MVD_IN_* of the header
+    int threads = 0, R = 0, CG = 0;                // block of the row-mapped kernels (norm_geom); the single launch: its own
+    long nblk = 0, chunk = 0;                      // block partials per sample the finalize kernel sums; voxels per block
+    long agrid = 0, achunk = 0;                    // apply pass: blocks per sample, voxels per block (0: grid stride)
+    long tgrid = 0, tchunk = 0;                    // tile pass: blocks per sample, tiles per block
+    int CW = 0, R2 = 0;                            // k_in_tiles_reduce: channels and tile rows of a 256-thread block
+    int wblk = 0;                                  // norm_geom's nblk: the workspace holds N * wblk * C * 2 doubles
+    size_t lds = 0;                                // LDS bytes of the statistics kernels
+};
+
+// row-mapped apply passes: more, smaller voxel chunks than the statistics pass (pure streaming, no reduction)
+static void plan_apply_rows(InPlan &p, int N, long V) {
+    long nb = V / ((long)p.R * 8);
+    if (nb < 1) nb = 1;
+    const long cap = 8192 / N > 0 ? 8192 / N : 1;
+    if (nb > cap) nb = cap;
+    p.achunk = cdiv(V, nb);
+    p.agrid = cdiv(V, p.achunk);
+}
+
+static void plan_apply_scalar(InPlan &p, int N, long V, int C) {  // C % 4 != 0: 256 threads, grid stride over the elements
+    const long bx = cdiv(V * C, 256), cap = 4096 / N > 0 ? 4096 / N : 1;
+    p.agrid = bx > cap ? cap : bx;
+    p.achunk = 0;
+}
+
+static void plan_tiles_reduce(InPlan &p, long ntiles, int C) {
+    long nb = (ntiles + 63) / 64;
+    if (nb > p.wblk) nb = p.wblk;  // the workspace holds N * wblk * C * 2 doubles
+    if (nb > 64) nb = 64;
+    p.tchunk = (ntiles + nb - 1) / nb;
+    p.tgrid = (ntiles + p.tchunk - 1) / p.tchunk;
+    p.CW = C < 256 ? C : 256;
+    p.R2 = 256 / p.CW;
+    p.nblk = p.tgrid;
+    p.chunk = 0;
+}
+
+// dir 0 forward, 1 backward (nb of in_small_ok: the batch); see mvd_instnorm_plan in the header for the entry point each
+// combination of arguments stands for.  Refuses (status 2, message) what that entry point refuses by shape or type.
+static int in_plan(InPlan &p, const char *who, int dir, int N, long V, int C, bool xb, bool yb, long ntiles, bool head) {
+    MVD_REQUIRE(N > 0 && N <= 65535 && V > 0 && C > 0 && C <= 1024, "%s: bad shape N=%d V=%ld C=%d", who, N, V, C);
+    MVD_REQUIRE(dir == 0 || dir == 1, "%s: direction %d", who, dir);
+    MVD_REQUIRE(ntiles >= 0 && (dir == 0 || ntiles == 0), "%s: tile statistics (%ld tiles) belong to the forward", who, ntiles);
+    const bool v4 = C % 4 == 0;
+    MVD_REQUIRE(v4 || !(xb || yb), "%s: bf16 I/O needs C %% 4 == 0", who);
+    MVD_REQUIRE(!xb || yb || (dir == 0 && head), "%s: a bf16 x goes with a bf16 y / dy", who);
+    const NormGeom g = norm_geom(N, V, C);
+    p = InPlan();
+    p.threads = g.threads;
+    p.R = g.R;
+    p.CG = g.CG;
+    p.nblk = p.wblk = g.nblk;
+    p.chunk = g.chunk;
+    p.lds = (size_t)g.R * C * 2 * sizeof(double);
+    MVD_REQUIRE(p.lds <= 64 * 1024, "%s: C too large for the LDS reduce", who);
+    if (dir == 0 && head) {  // statistics only: mvd_instnorm_stats_bf16 / mvd_instnorm_stats_from_tiles
+        MVD_REQUIRE(ntiles > 0 ? !xb : v4, "%s: statistics alone need fp32 tiles or C %% 4 == 0", who);
+        if (ntiles > 0) {
+            p.stats = MVD_IN_TILES_REDUCE;
+            plan_tiles_reduce(p, ntiles, C);
+        } else
+            p.stats = MVD_IN_STATS4;
+        return 0;
+    }
+    MVD_REQUIRE(!head || (v4 && !xb && !yb), "%s: the logit-gradient form needs fp32, C %% 4 == 0 and K <= 8", who);
+    if (!xb && !yb && !head) {
+        if (const int th = in_small_ok(V, C, dir ? N : 0)) {  // (tile statistics, if any, are not needed)
+            p.stats = p.apply = dir ? MVD_IN_SMALL_BWD : MVD_IN_SMALL_FWD;
+            p.threads = th;
+            p.R = th / SMW;
+            p.CG = SMW;
+            p.nblk = 1;
+            p.chunk = V;
+            p.agrid = cdiv(C / 4, SMW);  // workgroups of 16 channels: per sample forward, in all backward
+            p.achunk = V;
+            p.lds = 0;
+            return 0;
+        }
+    }
+    if (dir == 1) {
+        MVD_REQUIRE(!head || g.threads <= 256, "%s: block size of the logit-gradient form", who);
+        p.stats = head ? MVD_IN_BWD_STATS_HEAD : v4 ? MVD_IN_BWD_STATS4 : MVD_IN_BWD_STATS1;
+        p.apply = head ? MVD_IN_BWD_APPLY_HEAD : v4 ? MVD_IN_BWD_APPLY_ROWS : MVD_IN_BWD_APPLY1;
+    } else if (ntiles > 0 && yb) {  // mvd_instnorm_finalize_tiles, then mvd_instnorm_lrelu_apply_bf16
+        MVD_REQUIRE(xb, "%s: tile statistics with a bf16 output need a bf16 input", who);
+        p.stats = MVD_IN_FINALIZE_TILES;
+        p.apply = MVD_IN_APPLY_SS16;
+        p.nblk = p.chunk = 0;
+        p.lds = 0;
+        p.tgrid = 1;  // one wave per (n, c) takes all tiles
+        p.tchunk = ntiles;
+    } else {
+        if (ntiles > 0) {
+            p.stats = MVD_IN_TILES_REDUCE;
+            plan_tiles_reduce(p, ntiles, C);
+        } else
+            p.stats = v4 ? MVD_IN_STATS4 : MVD_IN_STATS1;
+        // bf16 in and out: the apply pass takes the scale / shift form -- ONE arithmetic for the stand-alone pass, the apply after
+        // a conv's statistics epilogue and the loader prologues (conv, weight gradient, seg head), so fused and un-fused
+        // networks agree bit for bit whichever kernel produced the statistics
+        p.apply = !v4 ? MVD_IN_APPLY1 : xb ? MVD_IN_APPLY_SS16 : MVD_IN_APPLY_ROWS;
+    }
+    if (v4)
+        plan_apply_rows(p, N, V);
+    else
+        plan_apply_scalar(p, N, V, C);
+    return 0;
+}
+
+// the VEC == 4 kernels load float4 (fp32) or uint2 (bf16) at base + v * C: a stated requirement of x, y, dy and dx
+static bool in_aligned(const void *ptr, bool bf16, int C) {
+    return C % 4 != 0 || (reinterpret_cast<uintptr_t>(ptr) & (bf16 ? 7 : 15)) == 0;
+}
+
 extern "C" {
+
+int mvd_instnorm_plan(int dir, int N, long V, int C, int x_is_bf16, int y_is_bf16, long ntiles, int head, long *plan) {
+    MVD_REQUIRE(plan, "instnorm_plan: null pointer");
+    InPlan p;
+    if (const int rc = in_plan(p, "instnorm_plan", dir, N, V, C, x_is_bf16 != 0, y_is_bf16 != 0, ntiles, head != 0)) return rc;
+    const long out[MVD_IN_PLAN_LEN] = {p.stats, p.apply,  p.threads, p.R,      p.CG, p.nblk, p.chunk,
+                                       p.agrid, p.achunk, p.tgrid,   p.tchunk, p.CW, p.R2};
+    for (int i = 0; i < MVD_IN_PLAN_LEN; i++) plan[i] = out[i];
+    return 0;
+}
 
 int mvd_instnorm_single_launch(long V, int C) { return in_small_ok(V, C) > 0 ? 1 : 0; }
 long mvd_instnorm_single_launches(void) { return g_in_small_launches; }
@@ -877,88 +1002,61 @@ size_t mvd_instnorm_workspace_bytes(int N, long V, int C) {
     return (size_t)N * g.nblk * C * 2 * sizeof(double) + (size_t)N * C * 2 * sizeof(float) + 256;
 }
 
+static int launch_tiles_reduce(const InPlan &p, const float *tile_stats, long ntiles, double *partial, float *mean, float *rstd,
+                               int N, long V, int C, float eps, hipStream_t s) {
+    hipLaunchKernelGGL(k_in_tiles_reduce, dim3((unsigned)p.tgrid, N), dim3(256), (size_t)p.R2 * p.CW * 2 * sizeof(double), s,
+                       tile_stats, partial, C, p.CW, p.R2, ntiles, p.tchunk);
+    if (check_launch("instnorm statistics from conv tiles")) return 1;
+    hipLaunchKernelGGL(k_in_finalize, dim3(C, N), dim3(64), 0, s, partial, mean, rstd, C, (int)p.nblk, V, eps);
+    return check_launch("instnorm finalize");
+}
+
 static int in_fwd(const float *x, bool xb, const float *gamma, const float *beta, float *y, bool yb, float *mean,
                   float *rstd, int N, long V, int C, float eps, float slope, void *ws, size_t ws_bytes, void *stream,
                   const float *tile_stats = nullptr, long ntiles = 0) {
     MVD_REQUIRE(x && gamma && beta && y && mean && rstd && ws, "instnorm_fwd: null pointer");
-    MVD_REQUIRE(N > 0 && N <= 65535 && V > 0 && C > 0 && C <= 1024, "instnorm_fwd: bad shape N=%d V=%ld C=%d", N, V, C);
+    InPlan p;
+    if (const int rc = in_plan(p, "instnorm_fwd", 0, N, V, C, xb, yb, tile_stats ? ntiles : 0, false)) return rc;
     MVD_REQUIRE(ws_bytes >= mvd_instnorm_workspace_bytes(N, V, C), "instnorm_fwd: workspace too small");
-    NormGeom g = norm_geom(N, V, C);
+    MVD_REQUIRE(in_aligned(x, xb, C) && in_aligned(y, yb, C),
+                "instnorm_fwd: x and y must be 16-byte (fp32) / 8-byte (bf16) aligned for C %% 4 == 0");
     hipStream_t s = as_stream(stream);
-    if (!xb && !yb) {
-        if (const int th = in_small_ok(V, C)) {  // (tile statistics, if any, are not needed)
-            hipLaunchKernelGGL(k_in_small_fwd<SM_MAXR>, dim3(cdiv(C / 4, SMW), N), dim3(th), 0, s, x, gamma, beta, y, mean, rstd,
-                               C, V, eps, slope);
-            g_in_small_launches++;
-            return check_launch("instnorm forward (single launch)");
-        }
+    if (p.stats == MVD_IN_SMALL_FWD) {
+        hipLaunchKernelGGL(k_in_small_fwd<SM_MAXR>, dim3(p.agrid, N), dim3(p.threads), 0, s, x, gamma, beta, y, mean, rstd, C, V,
+                           eps, slope);
+        g_in_small_launches++;
+        return check_launch("instnorm forward (single launch)");
     }
     double *partial = reinterpret_cast<double *>(ws);
-    size_t sm = (size_t)g.R * C * 2 * sizeof(double);
-    MVD_REQUIRE(sm <= 64 * 1024, "instnorm_fwd: C too large for the LDS reduce");
-    const bool v4 = (C % 4 == 0) && (g.CG * 4 == C);
-    MVD_REQUIRE(v4 || !(xb || yb), "instnorm_fwd: bf16 I/O needs C %% 4 == 0");
-    dim3 grid(g.nblk, N);
-    if (tile_stats) {
+    const dim3 grid(p.nblk, N), agrid((unsigned)p.agrid, N);
+    if (p.stats == MVD_IN_TILES_REDUCE) {
         // statistics came out of the producing conv's epilogue: no pass over x
-        long nb2 = (ntiles + 63) / 64;
-        if (nb2 > g.nblk) nb2 = g.nblk;  // the workspace holds N * g.nblk * C * 2 doubles
-        if (nb2 > 64) nb2 = 64;
-        const long chunk2 = (ntiles + nb2 - 1) / nb2;
-        nb2 = (ntiles + chunk2 - 1) / chunk2;
-        const int CW = C < 256 ? C : 256, R2 = 256 / CW;
-        hipLaunchKernelGGL(k_in_tiles_reduce, dim3((unsigned)nb2, N), dim3(256), (size_t)R2 * CW * 2 * sizeof(double), s,
-                           tile_stats, partial, C, CW, R2, ntiles, chunk2);
-        if (check_launch("instnorm statistics from conv tiles")) return 1;
-        hipLaunchKernelGGL(k_in_finalize, dim3(C, N), dim3(64), 0, s, partial, mean, rstd, C, (int)nb2, V, eps);
-        if (check_launch("instnorm finalize")) return 1;
+        if (launch_tiles_reduce(p, tile_stats, ntiles, partial, mean, rstd, N, V, C, eps, s)) return 1;
     } else {
-        if (v4 && xb)
-            hipLaunchKernelGGL((k_in_stats<4, true>), grid, dim3(g.threads), sm, s, x, partial, C, g.CG, g.R, V, g.chunk);
-        else if (v4)
-            hipLaunchKernelGGL((k_in_stats<4, false>), grid, dim3(g.threads), sm, s, x, partial, C, g.CG, g.R, V, g.chunk);
+        if (p.stats == MVD_IN_STATS1)
+            hipLaunchKernelGGL((k_in_stats<1, false>), grid, dim3(p.threads), p.lds, s, x, partial, C, p.CG, p.R, V, p.chunk);
+        else if (xb)
+            hipLaunchKernelGGL((k_in_stats<4, true>), grid, dim3(p.threads), p.lds, s, x, partial, C, p.CG, p.R, V, p.chunk);
         else
-            hipLaunchKernelGGL((k_in_stats<1, false>), grid, dim3(g.threads), sm, s, x, partial, C, g.CG, g.R, V, g.chunk);
+            hipLaunchKernelGGL((k_in_stats<4, false>), grid, dim3(p.threads), p.lds, s, x, partial, C, p.CG, p.R, V, p.chunk);
         g_in_stats_pass_launches++;
         if (check_launch("instnorm stats")) return 1;
-        // bf16 in and out: the apply pass takes the scale / shift form -- ONE arithmetic for the stand-alone pass, the apply after
-        // a conv's statistics epilogue and the loader prologues (conv, weight gradient, seg head), so fused and un-fused
-        // networks agree bit for bit whichever kernel produced the statistics
-        float *ss = reinterpret_cast<float *>(partial + (size_t)N * g.nblk * C * 2);
-        const bool ssf = v4 && xb && yb;
-        hipLaunchKernelGGL(k_in_finalize, dim3(C, N), dim3(64), 0, s, partial, mean, rstd, C, g.nblk, V, eps,
+        float *ss = reinterpret_cast<float *>(partial + (size_t)N * p.wblk * C * 2);
+        const bool ssf = p.apply == MVD_IN_APPLY_SS16;
+        hipLaunchKernelGGL(k_in_finalize, dim3(C, N), dim3(64), 0, s, partial, mean, rstd, C, (int)p.nblk, V, eps,
                            ssf ? gamma : nullptr, ssf ? beta : nullptr, ssf ? ss : nullptr, ssf ? ss + (size_t)N * C : nullptr);
         if (check_launch("instnorm finalize")) return 1;
         if (ssf) {
-            long nb2 = V / ((long)g.R * 8);
-            if (nb2 < 1) nb2 = 1;
-            long cap2 = 8192 / N > 0 ? 8192 / N : 1;
-            if (nb2 > cap2) nb2 = cap2;
-            const long chunk2 = cdiv(V, nb2);
-            hipLaunchKernelGGL(k_in_apply_ss16, dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, s,
-                               reinterpret_cast<const unsigned short *>(x), ss, ss + (size_t)N * C,
-                               reinterpret_cast<unsigned short *>(y), C, g.CG, g.R, V, chunk2, slope);
+            hipLaunchKernelGGL(k_in_apply_ss16, agrid, dim3(p.threads), 0, s, reinterpret_cast<const unsigned short *>(x), ss,
+                               ss + (size_t)N * C, reinterpret_cast<unsigned short *>(y), C, p.CG, p.R, V, p.achunk, slope);
             return check_launch("instnorm apply (scale / shift form)");
         }
     }
-    long per_n = V * C / (v4 ? 4 : 1);
-    long bx = cdiv(per_n, 256);
-    long cap = 4096 / N > 0 ? 4096 / N : 1;
-    if (bx > cap) bx = cap;
-    if (v4) {
-        // apply pass: more, smaller voxel chunks than the statistics pass (pure streaming, no reduction)
-        long nb2 = V / ((long)g.R * 8);
-        if (nb2 < 1) nb2 = 1;
-        long cap2 = 8192 / N > 0 ? 8192 / N : 1;
-        if (nb2 > cap2) nb2 = cap2;
-        const long chunk2 = cdiv(V, nb2);
-        auto kern = xb ? (yb ? k_in_apply_rows<true, true> : k_in_apply_rows<true, false>)
-                       : (yb ? k_in_apply_rows<false, true> : k_in_apply_rows<false, false>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, s, x, gamma, beta, mean, rstd, y, C,
-                           g.CG, g.R, V, chunk2, slope);
-    }
-    else
-        hipLaunchKernelGGL(k_in_apply<1>, dim3(bx, N), dim3(256), 0, s, x, gamma, beta, mean, rstd, y, C, V, slope);
+    if (p.apply == MVD_IN_APPLY_ROWS) {  // (a bf16 x takes k_in_apply_ss16 above: no bf16-input instantiation of this kernel)
+        auto kern = yb ? k_in_apply_rows<false, true> : k_in_apply_rows<false, false>;
+        hipLaunchKernelGGL(kern, agrid, dim3(p.threads), 0, s, x, gamma, beta, mean, rstd, y, C, p.CG, p.R, V, p.achunk, slope);
+    } else
+        hipLaunchKernelGGL(k_in_apply<1>, agrid, dim3(256), 0, s, x, gamma, beta, mean, rstd, y, C, V, slope);
     return check_launch("instnorm apply");
 }
 
@@ -966,81 +1064,62 @@ static int in_bwd(const float *x, bool xb, const float *dy, bool yb, const float
                   const float *mean, const float *rstd, float *dx, float *dgamma, float *dbeta, int N, long V, int C,
                   float slope, void *ws, size_t ws_bytes, void *stream, const float *head_w = nullptr, int K = 0) {
     MVD_REQUIRE(x && dy && gamma && beta && mean && rstd && dx && dgamma && dbeta && ws, "instnorm_bwd: null pointer");
-    MVD_REQUIRE(N > 0 && N <= 65535 && V > 0 && C > 0 && C <= 1024, "instnorm_bwd: bad shape");
+    InPlan p;
+    if (const int rc = in_plan(p, "instnorm_bwd", 1, N, V, C, xb, yb, 0, head_w != nullptr)) return rc;
+    MVD_REQUIRE(!head_w || (K > 0 && K <= HKMAX), "instnorm_bwd: the logit-gradient form needs fp32, C %% 4 == 0 and K <= 8");
     MVD_REQUIRE(ws_bytes >= mvd_instnorm_workspace_bytes(N, V, C), "instnorm_bwd: workspace too small");
-    NormGeom g = norm_geom(N, V, C);
+    // (the logit gradient of the head form is planar and read one float at a time)
+    MVD_REQUIRE(in_aligned(x, xb, C) && in_aligned(dx, xb, C) && (head_w || in_aligned(dy, yb, C)),
+                "instnorm_bwd: x, dy and dx must be 16-byte (fp32) / 8-byte (bf16) aligned for C %% 4 == 0");
     hipStream_t s = as_stream(stream);
-    if (!xb && !yb && !head_w) {
-        if (const int th = in_small_ok(V, C, N)) {
-            hipLaunchKernelGGL(k_in_small_bwd<SM_MAXR>, dim3(cdiv(C / 4, SMW)), dim3(th), 0, s, x, dy, gamma, beta, mean, rstd, dx,
-                               dgamma, dbeta, N, C, V, slope);
-            g_in_small_launches++;
-            return check_launch("instnorm backward (single launch)");
-        }
+    if (p.stats == MVD_IN_SMALL_BWD) {
+        hipLaunchKernelGGL(k_in_small_bwd<SM_MAXR>, dim3(p.agrid), dim3(p.threads), 0, s, x, dy, gamma, beta, mean, rstd, dx, dgamma,
+                           dbeta, N, C, V, slope);
+        g_in_small_launches++;
+        return check_launch("instnorm backward (single launch)");
     }
     double *partial = reinterpret_cast<double *>(ws);
-    float *sums = reinterpret_cast<float *>(partial + (size_t)N * g.nblk * C * 2);
-    size_t sm = (size_t)g.R * C * 2 * sizeof(double);
-    MVD_REQUIRE(sm <= 64 * 1024, "instnorm_bwd: C too large for the LDS reduce");
-    const bool v4 = (C % 4 == 0) && (g.CG * 4 == C);
-    dim3 grid(g.nblk, N);
-    MVD_REQUIRE(v4 || !(xb || yb), "instnorm_bwd: bf16 I/O needs C %% 4 == 0");
-    MVD_REQUIRE(!head_w || (v4 && !xb && !yb && K > 0 && K <= HKMAX),
-                "instnorm_bwd: the logit-gradient form needs fp32, C %% 4 == 0 and K <= 8");
-    if (head_w) {
-        MVD_REQUIRE(g.threads <= 256, "instnorm_bwd: block size of the logit-gradient form");
+    float *sums = reinterpret_cast<float *>(partial + (size_t)N * p.wblk * C * 2);
+    const dim3 grid(p.nblk, N), agrid((unsigned)p.agrid, N);
+    if (p.stats == MVD_IN_BWD_STATS_HEAD) {
 #define MVD_HEAD_STATS(KK)                                                                                                      \
     case KK:                                                                                                                    \
-        hipLaunchKernelGGL((k_in_bwd_stats<4, false, false, KK>), grid, dim3(g.threads), sm, s, x, dy, gamma, beta, mean, rstd, \
-                           partial, C, g.CG, g.R, V, g.chunk, slope, head_w);                                                   \
+        hipLaunchKernelGGL((k_in_bwd_stats<4, false, false, KK>), grid, dim3(p.threads), p.lds, s, x, dy, gamma, beta, mean,    \
+                           rstd, partial, C, p.CG, p.R, V, p.chunk, slope, head_w);                                             \
         break;
         switch (K) {
             MVD_HEAD_STATS(1) MVD_HEAD_STATS(2) MVD_HEAD_STATS(3) MVD_HEAD_STATS(4)
             MVD_HEAD_STATS(5) MVD_HEAD_STATS(6) MVD_HEAD_STATS(7) MVD_HEAD_STATS(8)
         }
 #undef MVD_HEAD_STATS
-    } else if (v4) {
-        auto kern = xb ? (yb ? k_in_bwd_stats<4, true, true> : k_in_bwd_stats<4, true, false>)
-                       : (yb ? k_in_bwd_stats<4, false, true> : k_in_bwd_stats<4, false, false>);
-        hipLaunchKernelGGL(kern, grid, dim3(g.threads), sm, s, x, dy, gamma, beta, mean, rstd, partial, C, g.CG, g.R, V,
-                           g.chunk, slope, (const float *)nullptr);
+    } else if (p.stats == MVD_IN_BWD_STATS4) {
+        auto kern = xb ? k_in_bwd_stats<4, true, true> : (yb ? k_in_bwd_stats<4, false, true> : k_in_bwd_stats<4, false, false>);
+        hipLaunchKernelGGL(kern, grid, dim3(p.threads), p.lds, s, x, dy, gamma, beta, mean, rstd, partial, C, p.CG, p.R, V,
+                           p.chunk, slope, (const float *)nullptr);
     } else
-        hipLaunchKernelGGL((k_in_bwd_stats<1, false, false>), grid, dim3(g.threads), sm, s, x, dy, gamma, beta, mean, rstd,
-                           partial, C, g.CG, g.R, V, g.chunk, slope);
+        hipLaunchKernelGGL((k_in_bwd_stats<1, false, false>), grid, dim3(p.threads), p.lds, s, x, dy, gamma, beta, mean, rstd,
+                           partial, C, p.CG, p.R, V, p.chunk, slope);
     if (check_launch("instnorm bwd stats")) return 1;
-    hipLaunchKernelGGL(k_in_bwd_finalize, dim3(C), dim3(64), 0, s, partial, sums, dgamma, dbeta, N, C,
-                       g.nblk);
+    hipLaunchKernelGGL(k_in_bwd_finalize, dim3(C), dim3(64), 0, s, partial, sums, dgamma, dbeta, N, C, (int)p.nblk);
     if (check_launch("instnorm bwd finalize")) return 1;
-    long per_n = V * C / (v4 ? 4 : 1);
-    long bx = cdiv(per_n, 256);
-    long cap = 4096 / N > 0 ? 4096 / N : 1;
-    if (bx > cap) bx = cap;
-    if (v4) {
-        long nb2 = V / ((long)g.R * 8);
-        if (nb2 < 1) nb2 = 1;
-        long cap2 = 8192 / N > 0 ? 8192 / N : 1;
-        if (nb2 > cap2) nb2 = cap2;
-        const long chunk2 = cdiv(V, nb2);
-        auto kern = xb ? (yb ? k_in_bwd_apply_rows<true, true> : k_in_bwd_apply_rows<true, false>)
-                       : (yb ? k_in_bwd_apply_rows<false, true> : k_in_bwd_apply_rows<false, false>);
-        if (head_w) {
-#define MVD_HEAD_APPLY(KK)                                                                                                        \
-    case KK:                                                                                                                      \
-        hipLaunchKernelGGL((k_in_bwd_apply_rows<false, false, KK>), dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, s, x, \
-                           dy, gamma, beta, mean, rstd, sums, dx, C, g.CG, g.R, V, chunk2, slope, head_w);                        \
+    if (p.apply == MVD_IN_BWD_APPLY_HEAD) {
+#define MVD_HEAD_APPLY(KK)                                                                                                      \
+    case KK:                                                                                                                    \
+        hipLaunchKernelGGL((k_in_bwd_apply_rows<false, false, KK>), agrid, dim3(p.threads), 0, s, x, dy, gamma, beta, mean,     \
+                           rstd, sums, dx, C, p.CG, p.R, V, p.achunk, slope, head_w);                                           \
         break;
-            switch (K) {
-                MVD_HEAD_APPLY(1) MVD_HEAD_APPLY(2) MVD_HEAD_APPLY(3) MVD_HEAD_APPLY(4)
-                MVD_HEAD_APPLY(5) MVD_HEAD_APPLY(6) MVD_HEAD_APPLY(7) MVD_HEAD_APPLY(8)
-            }
+        switch (K) {
+            MVD_HEAD_APPLY(1) MVD_HEAD_APPLY(2) MVD_HEAD_APPLY(3) MVD_HEAD_APPLY(4)
+            MVD_HEAD_APPLY(5) MVD_HEAD_APPLY(6) MVD_HEAD_APPLY(7) MVD_HEAD_APPLY(8)
+        }
 #undef MVD_HEAD_APPLY
-        } else
-            hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, s, x, dy, gamma, beta, mean, rstd,
-                               sums, dx, C, g.CG, g.R, V, chunk2, slope, (const float *)nullptr);
-    }
-    else
-        hipLaunchKernelGGL(k_in_bwd_apply<1>, dim3(bx, N), dim3(256), 0, s, x, dy, gamma, beta, mean, rstd, sums, dx, C,
-                           V, slope);
+    } else if (p.apply == MVD_IN_BWD_APPLY_ROWS) {  // (a bf16 x has a bf16 dy: no <true, false> instantiation)
+        auto kern = xb ? k_in_bwd_apply_rows<true, true>
+                       : (yb ? k_in_bwd_apply_rows<false, true> : k_in_bwd_apply_rows<false, false>);
+        hipLaunchKernelGGL(kern, agrid, dim3(p.threads), 0, s, x, dy, gamma, beta, mean, rstd, sums, dx, C, p.CG, p.R, V,
+                           p.achunk, slope, (const float *)nullptr);
+    } else
+        hipLaunchKernelGGL(k_in_bwd_apply<1>, agrid, dim3(256), 0, s, x, dy, gamma, beta, mean, rstd, sums, dx, C, V, slope);
     return check_launch("instnorm bwd apply");
 }
 
@@ -1098,21 +1177,20 @@ int mvd_instnorm_stats_bf16(const void *x, int x_is_bf16, const float *gamma, co
                             float *scale, float *shift, int N, long V, int C, float eps, void *ws, size_t ws_bytes,
                             void *stream) {
     MVD_REQUIRE(x && gamma && beta && mean && rstd && scale && shift && ws, "instnorm_stats: null pointer");
-    MVD_REQUIRE(N > 0 && N <= 65535 && V > 0 && C > 0 && C % 4 == 0 && C <= 1024, "instnorm_stats: bad shape (C %% 4 == 0)");
+    InPlan p;
+    if (const int rc = in_plan(p, "instnorm_stats", 0, N, V, C, x_is_bf16 != 0, x_is_bf16 != 0, 0, true)) return rc;
     MVD_REQUIRE(ws_bytes >= mvd_instnorm_workspace_bytes(N, V, C), "instnorm_stats: workspace too small");
-    NormGeom g = norm_geom(N, V, C);
-    MVD_REQUIRE(g.CG * 4 == C, "instnorm_stats: C too wide");
+    MVD_REQUIRE(in_aligned(x, x_is_bf16 != 0, C), "instnorm_stats: x must be 16-byte (fp32) / 8-byte (bf16) aligned");
     hipStream_t s = as_stream(stream);
     double *partial = reinterpret_cast<double *>(ws);
-    const size_t sm = (size_t)g.R * C * 2 * sizeof(double);
-    MVD_REQUIRE(sm <= 64 * 1024, "instnorm_stats: C too large for the LDS reduce");
     const float *xf = reinterpret_cast<const float *>(x);
     if (x_is_bf16)
-        hipLaunchKernelGGL((k_in_stats<4, true>), dim3(g.nblk, N), dim3(g.threads), sm, s, xf, partial, C, g.CG, g.R, V, g.chunk);
+        hipLaunchKernelGGL((k_in_stats<4, true>), dim3(p.nblk, N), dim3(p.threads), p.lds, s, xf, partial, C, p.CG, p.R, V, p.chunk);
     else
-        hipLaunchKernelGGL((k_in_stats<4, false>), dim3(g.nblk, N), dim3(g.threads), sm, s, xf, partial, C, g.CG, g.R, V, g.chunk);
+        hipLaunchKernelGGL((k_in_stats<4, false>), dim3(p.nblk, N), dim3(p.threads), p.lds, s, xf, partial, C, p.CG, p.R, V, p.chunk);
     if (check_launch("instnorm stats")) return 1;
-    hipLaunchKernelGGL(k_in_finalize, dim3(C, N), dim3(64), 0, s, partial, mean, rstd, C, g.nblk, V, eps, gamma, beta, scale, shift);
+    hipLaunchKernelGGL(k_in_finalize, dim3(C, N), dim3(64), 0, s, partial, mean, rstd, C, (int)p.nblk, V, eps, gamma, beta, scale,
+                       shift);
     return check_launch("instnorm finalize");
 }
 
@@ -1121,37 +1199,20 @@ int mvd_instnorm_stats_bf16(const void *x, int x_is_bf16, const float *gamma, co
 int mvd_instnorm_stats_from_tiles(const float *tile_stats, long ntiles, float *mean, float *rstd, int N, long V, int C, float eps,
                                   void *ws, size_t ws_bytes, void *stream) {
     MVD_REQUIRE(tile_stats && ntiles > 0 && mean && rstd && ws, "instnorm_stats_from_tiles: bad arguments");
-    MVD_REQUIRE(N > 0 && N <= 65535 && V > 0 && C > 0 && C <= 1024, "instnorm_stats_from_tiles: bad shape");
+    InPlan p;
+    if (const int rc = in_plan(p, "instnorm_stats_from_tiles", 0, N, V, C, false, false, ntiles, true)) return rc;
     MVD_REQUIRE(ws_bytes >= mvd_instnorm_workspace_bytes(N, V, C), "instnorm_stats_from_tiles: workspace too small");
-    NormGeom g = norm_geom(N, V, C);
-    hipStream_t s = as_stream(stream);
-    double *partial = reinterpret_cast<double *>(ws);
-    long nb2 = (ntiles + 63) / 64;
-    if (nb2 > g.nblk) nb2 = g.nblk;
-    if (nb2 > 64) nb2 = 64;
-    const long chunk2 = (ntiles + nb2 - 1) / nb2;
-    nb2 = (ntiles + chunk2 - 1) / chunk2;
-    const int CW = C < 256 ? C : 256, R2 = 256 / CW;
-    hipLaunchKernelGGL(k_in_tiles_reduce, dim3((unsigned)nb2, N), dim3(256), (size_t)R2 * CW * 2 * sizeof(double), s, tile_stats,
-                       partial, C, CW, R2, ntiles, chunk2);
-    if (check_launch("instnorm statistics from conv tiles")) return 1;
-    hipLaunchKernelGGL(k_in_finalize, dim3(C, N), dim3(64), 0, s, partial, mean, rstd, C, (int)nb2, V, eps);
-    return check_launch("instnorm finalize");
+    return launch_tiles_reduce(p, tile_stats, ntiles, reinterpret_cast<double *>(ws), mean, rstd, N, V, C, eps, as_stream(stream));
 }
 
 int mvd_instnorm_lrelu_apply_bf16(const uint16_t *x, const float *scale, const float *shift, uint16_t *y, int N, long V,
                                   int C, float slope, void *stream) {
     MVD_REQUIRE(x && scale && shift && y, "instnorm_apply_bf16: null pointer");
-    MVD_REQUIRE(N > 0 && N <= 65535 && V > 0 && C > 0 && C % 4 == 0 && C <= 1024, "instnorm_apply_bf16: bad shape (C %% 4 == 0)");
-    NormGeom g = norm_geom(N, V, C);
-    MVD_REQUIRE(g.CG * 4 == C, "instnorm_apply_bf16: C too wide");
-    long nb2 = V / ((long)g.R * 8);
-    if (nb2 < 1) nb2 = 1;
-    long cap2 = 8192 / N > 0 ? 8192 / N : 1;
-    if (nb2 > cap2) nb2 = cap2;
-    const long chunk2 = cdiv(V, nb2);
-    hipLaunchKernelGGL(k_in_apply_ss16, dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, as_stream(stream), x, scale,
-                       shift, y, C, g.CG, g.R, V, chunk2, slope);
+    InPlan p;  // (the apply half of the bf16 tile form: its grid does not depend on the tile count)
+    if (const int rc = in_plan(p, "instnorm_apply_bf16", 0, N, V, C, true, true, 1, false)) return rc;
+    MVD_REQUIRE(in_aligned(x, true, C) && in_aligned(y, true, C), "instnorm_apply_bf16: x and y must be 8-byte aligned");
+    hipLaunchKernelGGL(k_in_apply_ss16, dim3((unsigned)p.agrid, N), dim3(p.threads), 0, as_stream(stream), x, scale, shift, y, C,
+                       p.CG, p.R, V, p.achunk, slope);
     return check_launch("instnorm apply (scale / shift form)");
 }
 
