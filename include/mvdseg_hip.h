@@ -841,6 +841,44 @@ int mvd_export_resize_sigmoid_f32(const float *logits, float *out, const int *id
                                   int K, int d, int h, int w, int D, int H, int W, const int *full, const int *lo,
                                   const int *perm, void *stream);
 
+/* The bottleneck fusion block of FinalNetv2 (csrc/attention.hip): fp32, no atomics (bit-identical run to run).
+ * Dropout: `state` is a DEVICE long long[2] = {seed, t}.  Element e of site s is kept iff the 24-bit uniform (w >> 40) 2^-24
+ *   >= p, w = word e & 3 of Philox4x64-10 with key (seed, s) and counter ((e >> 2) + 1, t, 0, 0) (numpy.random.Philox(key =
+ *   (seed, s), counter = (0, t, 0, 0)).random_raw()[e]); kept values are scaled by 1 / (1 - p).  p == 0: no dropout, state
+ *   is not read.  mvd_dropout_tick: t += 1 (one launch at the head of a training-mode forward; the backward of that step
+ *   reads the same t).  mvd_dropout_mask: the keep mask (1 / 0 bytes) of n elements of (seed, t, site): for tests.
+ * mvd_layernorm_fwd: rows [M, C]; pos != NULL: xs = x + pos[m % Npos] first (xs is written when non-NULL), y = (xs - mean)
+ *   rstd gamma + beta with the variance as the mean of the centred squares (two passes), mean / rstd [M] saved.
+ * mvd_layernorm_bwd: dx = LayerNorm'(dy) [+ dres1] [+ dres2]; dxd != NULL: also dxd = dx * (dropout factor of element
+ *   m C + c of `site`): the input gradient of a linear whose epilogue dropped; dgamma, dbeta [C]; dpos != NULL:
+ *   dpos[n] = sum over the batch of dx (M = batch x Npos, batch <= 64).  One launch.
+ * mvd_linear_fwd: y[M, O] = (x[M, C] w[O, C]^T + bias) * (dropout factor of element m O + o) + res; bias, res optional.
+ *   v_mfma_f32_16x16x4_f32 through bounds-checked loaders: M arbitrary, C and O multiples of 8.
+ * mvd_linear_bwd: g = dy (already multiplied by the dropout factors): dx = g w (skipped when NULL), dw = g^T x,
+ *   db = sum_m g (optional): one launch per gradient, db in dw's.
+ * mvd_attention_fwd: H heads of dh over [B, N, 3 H dh] buffers (channel = which (H dh) + head dh + j): queries from qbuf,
+ *   keys and values from kvbuf (the same buffer for self-attention), out[B, N, H dh] = dropout(softmax(q k^T dh^-1/2)) v
+ *   [+ res]; the row maximum is subtracted; rowmax / rowsum [B H N] saved.  N <= 256, 4 <= dh <= 64, dh % 4 == 0.
+ * mvd_attention_bwd: recomputes the probabilities from q, k, rowmax and rowsum; dq into dqbuf's q section, dk and dv into
+ *   dkvbuf's k and v sections (same layout as the inputs); delta [B H N] is scratch.  Two launches. */
+int mvd_dropout_tick(long long *state, void *stream);
+int mvd_dropout_mask(unsigned long long seed, unsigned long long t, int site, float p, long n, unsigned char *out,
+                     void *stream);
+int mvd_layernorm_fwd(const float *x, const float *pos, float *xs, float *y, float *mean, float *rstd, const float *gamma,
+                      const float *beta, long M, int C, long Npos, float eps, void *stream);
+int mvd_layernorm_bwd(const float *dy, const float *xs, const float *mean, const float *rstd, const float *gamma,
+                      const float *dres1, const float *dres2, float *dx, float *dxd, float *dgamma, float *dbeta,
+                      float *dpos, long M, int C, long Npos, const long long *state, float p, int site, void *stream);
+int mvd_linear_fwd(const float *x, const float *w, const float *bias, const float *res, float *y, long M, int C, int O,
+                   const long long *state, float p, int site, void *stream);
+int mvd_linear_bwd(const float *g, const float *x, const float *w, float *dx, float *dw, float *db, long M, int C, int O,
+                   void *stream);
+int mvd_attention_fwd(const float *qbuf, const float *kvbuf, const float *res, float *out, float *rowmax, float *rowsum, int B,
+                      int N, int H, int dh, const long long *state, float p, int site, void *stream);
+int mvd_attention_bwd(const float *qbuf, const float *kvbuf, const float *dout, const float *rowmax, const float *rowsum,
+                      float *delta, float *dqbuf, float *dkvbuf, int B, int N, int H, int dh, const long long *state, float p,
+                      int site, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

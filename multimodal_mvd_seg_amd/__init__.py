@@ -12,7 +12,7 @@ __version__ = "0.1.0"
 
 __all__ = ["nnUNetTrainerBNMI355", "nnUNetTrainerAdamMI355", "nnUNetTrainerVanillaAdamMI355",
            "nnUNetTrainerAdam1en3MI355", "nnUNetTrainerAdam3en4MI355", "nnUNetTrainerVanillaAdam1en3MI355",
-           "nnUNetTrainerVanillaAdam3en4MI355", "nnUNetTrainerCosAnnealMI355"]
+           "nnUNetTrainerVanillaAdam3en4MI355", "nnUNetTrainerCosAnnealMI355", "FinalNetTrainerMI355"]
 
 
 def __getattr__(name):

@@ -134,6 +134,40 @@ __device__ inline void block_sum(double (&v)[NV], double *smem /* >= NV*16 doubl
     }
 }
 
+// Philox4x64-10 (Salmon et al. 2011), the generator of numpy.random.Philox: noise of the training feed (feed_intensity.hip)
+// and the dropout masks of the attention block (attention.hip).
+__device__ __forceinline__ void philox_round(unsigned long long (&c)[4], unsigned long long k0,
+                                             unsigned long long k1) {
+    const unsigned long long m0 = 0xD2E7470EE14C6C93ull, m1 = 0xCA5A826395121157ull;
+    const unsigned long long hi0 = __umul64hi(m0, c[0]), lo0 = m0 * c[0];
+    const unsigned long long hi1 = __umul64hi(m1, c[2]), lo1 = m1 * c[2];
+    const unsigned long long n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = lo1;
+    c[2] = n2;
+    c[3] = lo0;
+}
+
+// Philox4x64-10 of counter (ctr, ctr1, 0, 0): numpy.random.Philox(key=(k0, k1), counter=(0, ctr1, 0, 0)).random_raw()
+// output 4 (ctr - 1) + j is word j of counter ctr (numpy increments the counter before each block).
+__device__ __forceinline__ void philox4x64_10(unsigned long long ctr, unsigned long long ctr1, unsigned long long k0,
+                                              unsigned long long k1, unsigned long long (&c)[4]) {
+    c[0] = ctr;
+    c[1] = ctr1;
+    c[2] = c[3] = 0ull;
+    philox_round(c, k0, k1);
+#pragma unroll
+    for (int r = 1; r < 10; ++r) {
+        k0 += 0x9E3779B97F4A7C15ull;
+        k1 += 0xBB67AE8584CAA73Bull;
+        philox_round(c, k0, k1);
+    }
+}
+__device__ __forceinline__ void philox4x64_10(unsigned long long ctr, unsigned long long k0, unsigned long long k1,
+                                              unsigned long long (&c)[4]) {
+    philox4x64_10(ctr, 0ull, k0, k1, c);
+}
+
 // generic fixed-order second stage: out[j] = sum_b partial[b*stride + offset + j]  (double -> float), j < nv
 int reduce_partials(const double *partials, float *out, int nblk, int nv, hipStream_t s, int stride = 0, int offset = 0);
 

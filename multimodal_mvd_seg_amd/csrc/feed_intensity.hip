@@ -219,33 +219,7 @@ __global__ void __launch_bounds__(256) k_gaussian_blur_axis(const float *__restr
 }
 
 // ------------------------------------------------------------------------------------------------ noise
-__device__ __forceinline__ void philox_round(unsigned long long (&c)[4], unsigned long long k0,
-                                             unsigned long long k1) {
-    const unsigned long long m0 = 0xD2E7470EE14C6C93ull, m1 = 0xCA5A826395121157ull;
-    const unsigned long long hi0 = __umul64hi(m0, c[0]), lo0 = m0 * c[0];
-    const unsigned long long hi1 = __umul64hi(m1, c[2]), lo1 = m1 * c[2];
-    const unsigned long long n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = lo1;
-    c[2] = n2;
-    c[3] = lo0;
-}
-
-// Philox4x64-10 of counter (ctr, 0, 0, 0): numpy.random.Philox(key=(k0, k1)).random_raw() output 4 (ctr - 1) + j is
-// word j of counter ctr (numpy increments the counter before each block).
-__device__ __forceinline__ void philox4x64_10(unsigned long long ctr, unsigned long long k0, unsigned long long k1,
-                                              unsigned long long (&c)[4]) {
-    c[0] = ctr;
-    c[1] = c[2] = c[3] = 0ull;
-    philox_round(c, k0, k1);
-#pragma unroll
-    for (int r = 1; r < 10; ++r) {
-        k0 += 0x9E3779B97F4A7C15ull;
-        k1 += 0xBB67AE8584CAA73Bull;
-        philox_round(c, k0, k1);
-    }
-}
-
+// (Philox4x64-10: common.h)
 // One N(0, 1) per 64-bit word: u1 = (2 (w >> 41) + 1) 2^-24, u2 = (2 ((w >> 18) & (2^23 - 1)) + 1) 2^-24 (exact in
 // fp32, both in (0, 1)), z = sqrt(-2 ln u1) cos(2 pi u2).
 __device__ __forceinline__ float normal_of(unsigned long long w) {

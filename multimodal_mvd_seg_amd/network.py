@@ -529,6 +529,9 @@ def set_precision(module: nn.Module, precision: str):
         # the generic bf16 engines take the (1,3,3) / (1,2,2) / (1,1,1) layers, but the 2-D network's forward misses the
         # project's bf16 bar against fp64: refused until the layer behind that is found
         raise NotImplementedError("bf16 mixed precision is not built for 2-D networks (the 2d configuration runs fp32)")
+    if precision == "bf16" and any(isinstance(m, BottleneckFusion) for m in module.modules()):
+        raise NotImplementedError("bf16 mixed precision is not built for FinalNetv2: its bottleneck fusion block (LayerNorm, "
+                                  "token linears, attention) is fp32 only")
     for m in module.modules():
         if isinstance(m, ConvDropoutNormReLU):
             m.precision = precision
@@ -578,3 +581,267 @@ class MVDDualBranchNet(nn.Module):
 
     def parameters_in_execution_order(self):
         return self.branch1.parameters_in_execution_order() + self.branch2.parameters_in_execution_order()
+
+
+# ------------------------------------------------------------------------------------------------ FinalNetv2
+# The fork's modality-fusing network (my_network/selfattnNet.py:838-947): one PlainConvEncoder per modality, cross-attention
+# then self-attention over the bottleneck tokens, two decoders that start from the fused tokens.  Everything between the two
+# bottlenecks runs in csrc/attention.hip, fp32.
+class HipLayerNorm(nn.LayerNorm):
+    """nn.LayerNorm(C), eps 1e-5, affine, over the last axis (mvd_layernorm_fwd / _bwd)."""
+
+    def forward(self, x):
+        return ops.LayerNormFn.apply(x, self.weight, self.bias, self.eps)
+
+
+class HipLinear(nn.Linear):
+    """nn.Linear on tokens; the kernels read torch's [O, C] parameter itself (mvd_linear_fwd / _bwd)."""
+
+    def forward(self, x):
+        return ops.TokenLinearFn.apply(x, self.weight, self.bias)
+
+
+def _no_standalone_dropout(module, p):
+    if module.training and p > 0:
+        raise NotImplementedError(f"{type(module).__name__} called on its own in training mode with dropout {p}: the dropout "
+                                  f"state lives in BottleneckFusion, which runs the whole block; call eval() or use p = 0")
+
+
+class Cross_Attention(nn.Module):
+    """UNetDecoder.py:1087-1126: same members and state_dict keys.  x1 queries x2's keys / values and the other way round."""
+
+    def __init__(self, dim, num_heads=9, qkv_bias=False, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        self.num_heads = num_heads
+        self.scale = (dim // num_heads) ** -0.5
+        self.qkv1 = HipLinear(dim, dim * 3, bias=qkv_bias)
+        self.qkv2 = HipLinear(dim, dim * 3, bias=qkv_bias)
+        self.attn_drop1, self.attn_drop2 = nn.Dropout(attn_drop), nn.Dropout(attn_drop)
+        self.proj1, self.proj2 = HipLinear(dim, dim), HipLinear(dim, dim)
+        self.proj_drop1, self.proj_drop2 = nn.Dropout(proj_drop), nn.Dropout(proj_drop)
+
+    def forward(self, x1, x2):
+        _no_standalone_dropout(self, max(self.attn_drop1.p, self.proj_drop1.p))
+        qkv1, qkv2 = self.qkv1(x1), self.qkv2(x2)
+        return (self.proj1(ops.AttentionFn.apply(qkv1, qkv2, self.num_heads)),
+                self.proj2(ops.AttentionFn.apply(qkv2, qkv1, self.num_heads)))
+
+
+class Self_Attention(nn.Module):
+    """UNetDecoder.py:1129-1154, with its quirk: forward returns the tensor BEFORE proj (:1151-1154 compute the projection
+    and drop it), so `proj` exists for the state_dict only and proj_drop never acts."""
+
+    def __init__(self, dim, num_heads=9, qkv_bias=False, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        self.num_heads = num_heads
+        self.scale = (dim // num_heads) ** -0.5
+        self.qkv = HipLinear(dim, dim * 3, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.proj = HipLinear(dim, dim)
+        self.proj_drop = nn.Dropout(proj_drop)
+
+    def forward(self, x):
+        _no_standalone_dropout(self, self.attn_drop.p)
+        qkv = self.qkv(x)
+        return ops.AttentionFn.apply(qkv, qkv, self.num_heads)
+
+
+def _freeze(*items):
+    """Members the reference's forward never reaches: autograd leaves their .grad None there, so torch's optimizers skip
+    them, weight decay included, and they keep their initial values.  requires_grad = False keeps them out of
+    optim.FlatParams (which takes parameters that require a gradient), of the reducer's buckets and of the fused update."""
+    for it in items:
+        for p in ([it] if isinstance(it, nn.Parameter) else it.parameters()):
+            p.requires_grad_(False)
+
+
+class BottleneckFusion(nn.Module):
+    """The members FinalNetv2 keeps at its top level (selfattnNet.py:896-907) and the fused segment of its forward
+    (:917-939): forward(x1, x2) -> (y1, y2) on two NDHWC bottlenecks [B, C, D, H, W] of N = D H W tokens.
+    `mvd_dropout_state` (int64 {seed, t}) is the only key the reference does not have: the seed is drawn from torch's CPU
+    generator here, t counts the training-mode forwards (ops.dropout_tick)."""
+    num_heads = 8
+
+    def __init__(self, hidden_size, num_tokens, attn_drop=0.1, proj_drop=0.1):
+        super().__init__()
+        C, N, H = int(hidden_size), int(num_tokens), self.num_heads
+        lo, hi = ops.ATTN_HEAD_DIMS
+        if C % H != 0:
+            raise NotImplementedError(f"FinalNetv2: {C} bottleneck features do not split into {H} heads (C % 8 != 0)")
+        dh = C // H
+        if not (lo <= dh <= hi and dh % 4 == 0):
+            raise NotImplementedError(f"FinalNetv2: head dimension {dh} (= {C} / {H}): the attention kernel takes "
+                                      f"{lo}..{hi}, a multiple of 4")
+        if not 1 <= N <= ops.ATTN_MAX_TOKENS:
+            raise NotImplementedError(f"FinalNetv2: {N} bottleneck tokens: the attention kernel holds at most "
+                                      f"{ops.ATTN_MAX_TOKENS} (patch size / strides of the plans)")
+        self.hidden_size, self.num_tokens = C, N
+        for i in range(1, 5):
+            setattr(self, f"pos_embed{i}", nn.Parameter(torch.zeros(1, N, C)))
+        self.crossattn = Cross_Attention(dim=C, num_heads=H, qkv_bias=False, attn_drop=attn_drop, proj_drop=proj_drop)
+        self.selfattn1 = Self_Attention(dim=C, num_heads=H, qkv_bias=False, attn_drop=attn_drop, proj_drop=proj_drop)
+        self.selfattn2 = Self_Attention(dim=C, num_heads=H, qkv_bias=False, attn_drop=attn_drop, proj_drop=proj_drop)
+        self.norm1, self.norm2, self.norm3, self.norm4 = (HipLayerNorm(C) for _ in range(4))
+        _freeze(self.pos_embed3, self.pos_embed4, self.selfattn1.proj, self.selfattn2.proj)
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
+        self.register_buffer("mvd_dropout_state", torch.tensor([seed, 0], dtype=torch.int64))
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # a checkpoint of the reference has no dropout state: keep this module's
+        state_dict.setdefault(prefix + "mvd_dropout_state", self.mvd_dropout_state)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def fusion_parameters(self):
+        """The parameters the fused segment uses, in ops.FUSION_PARAMS order."""
+        ca = self.crossattn
+        return [self.pos_embed1, self.pos_embed2, self.norm1.weight, self.norm1.bias, self.norm2.weight, self.norm2.bias,
+                self.norm3.weight, self.norm3.bias, self.norm4.weight, self.norm4.bias, ca.qkv1.weight, ca.qkv2.weight,
+                ca.proj1.weight, ca.proj1.bias, ca.proj2.weight, ca.proj2.bias, self.selfattn1.qkv.weight,
+                self.selfattn2.qkv.weight]
+
+    def fusion_parameters_in_execution_order(self):
+        ca = self.crossattn
+        return [self.pos_embed1, self.pos_embed2, *self.norm2.parameters(), *self.norm1.parameters(), ca.qkv1.weight,
+                ca.qkv2.weight, *ca.proj1.parameters(), *ca.proj2.parameters(), *self.norm3.parameters(),
+                *self.norm4.parameters(), self.selfattn1.qkv.weight, self.selfattn2.qkv.weight]
+
+    def fuse(self, x1, x2):
+        if tuple(x1.shape) != tuple(x2.shape) or x1.dim() != 5:
+            raise RuntimeError(f"BottleneckFusion: two [B, C, D, H, W] bottlenecks of one shape, got {tuple(x1.shape)} and "
+                               f"{tuple(x2.shape)}")
+        if x1.shape[1] != self.hidden_size or x1[0, 0].numel() != self.num_tokens:
+            raise RuntimeError(f"BottleneckFusion: built for {self.num_tokens} tokens of {self.hidden_size} features, got "
+                               f"{x1[0, 0].numel()} of {x1.shape[1]}")
+        ca = self.crossattn
+        return ops.BottleneckFusionFn.apply(x1, x2, self.mvd_dropout_state, self.num_heads, ca.attn_drop1.p, ca.proj_drop1.p,
+                                            self.training, self.norm1.eps, *self.fusion_parameters())
+
+    def forward(self, x1, x2):
+        return self.fuse(x1, x2)
+
+
+class UNetDecoder6(UNetDecoder):
+    """UNetDecoder.py:797-895: the plain decoder with the fused tokens in the place of skips[-1].  Its attention members
+    (:859-868) are never used by its forward; they are kept, frozen, for state_dict parity."""
+
+    def __init__(self, encoder, num_classes, n_conv_per_stage, deep_supervision, nonlin_first=False, hidden_size=256,
+                 num_tokens=128):
+        super().__init__(encoder, num_classes, n_conv_per_stage, deep_supervision, nonlin_first)
+        for i in range(1, 4):
+            setattr(self, f"pos_embed{i}", nn.Parameter(torch.zeros(1, num_tokens, hidden_size)))
+        self.crossattn = Cross_Attention(dim=hidden_size, num_heads=8, qkv_bias=False, attn_drop=0.1, proj_drop=0.1)
+        self.selfattn = Self_Attention(dim=hidden_size, num_heads=8, qkv_bias=False, attn_drop=0.1, proj_drop=0.1)
+        self.hidden_size = hidden_size
+        self.norm1, self.norm2 = nn.LayerNorm(hidden_size), nn.LayerNorm(hidden_size)
+        _freeze(self.pos_embed1, self.pos_embed2, self.pos_embed3, self.crossattn, self.selfattn, self.norm1, self.norm2)
+
+    def forward(self, skips, attn_skip, return_last_feature=False):
+        return super().forward(list(skips[:-1]) + [attn_skip], return_last_feature)
+
+
+class MI355FinalNetv2(BottleneckFusion):
+    """selfattnNet.py:838-947 (constructor arguments in its order; `num_tokens` replaces the hard-coded 128 of :896-899,
+    hidden_size is the bottleneck width).  forward: with deep supervision on, MVDDualBranchNet's (out1, out2, feat1, feat2),
+    feat = the last decoder stage, so the dual-branch trainer's loss runs unchanged; with it off, (out1 + out2) / 2 (:943-945)."""
+
+    def __init__(self, conv_bias, norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs,
+                 features_per_stage, kernel_sizes, strides, n_conv_per_stage, n_conv_per_stage_decoder,
+                 input_channels: int = 2, out_channels: int = 4, n_stages: int = 5, conv_op=nn.Conv3d, pool: str = 'conv',
+                 hidden_size: int = None, num_tokens: int = 128, do_ds=True):
+        if input_channels != 2:
+            raise NotImplementedError(f"FinalNetv2 takes exactly 2 input channels (one modality per encoder, "
+                                      f"selfattnNet.py:911-914), got {input_channels}")
+        if conv_op is not nn.Conv3d:
+            raise NotImplementedError(f"FinalNetv2 on 2-D plans (conv_op {getattr(conv_op, '__name__', conv_op)}): only "
+                                      f"the 3-D network is built")
+        if isinstance(features_per_stage, int):
+            features_per_stage = [features_per_stage] * n_stages
+        hidden_size = features_per_stage[-1] if hidden_size is None else hidden_size
+        if hidden_size != features_per_stage[-1]:
+            raise NotImplementedError(f"FinalNetv2: hidden_size {hidden_size} must be the bottleneck width "
+                                      f"{features_per_stage[-1]} (the tokens are the bottleneck voxels)")
+        super().__init__(hidden_size, num_tokens)
+        if isinstance(n_conv_per_stage, int):
+            n_conv_per_stage = [n_conv_per_stage] * n_stages
+        if isinstance(n_conv_per_stage_decoder, int):
+            n_conv_per_stage_decoder = [n_conv_per_stage_decoder] * (n_stages - 1)
+        assert len(n_conv_per_stage) == n_stages and len(n_conv_per_stage_decoder) == n_stages - 1
+        enc = lambda: PlainConvEncoder(input_channels // 2, n_stages, features_per_stage, conv_op, kernel_sizes, strides,
+                                       n_conv_per_stage, conv_bias, norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs,
+                                       nonlin, nonlin_kwargs, return_skips=True, nonlin_first=False, pool=pool)
+        self.encoder1, self.encoder2 = enc(), enc()
+        dec = lambda e: UNetDecoder6(e, out_channels, n_conv_per_stage_decoder, do_ds, nonlin_first=False,
+                                     hidden_size=hidden_size, num_tokens=num_tokens)
+        self.decoder1, self.decoder2 = dec(self.encoder1), dec(self.encoder2)
+
+    @property
+    def do_ds(self):
+        return self.decoder1.deep_supervision
+
+    @do_ds.setter
+    def do_ds(self, v):
+        self.decoder1.deep_supervision = v
+        self.decoder2.deep_supervision = v
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("MI355FinalNetv2 runs on the MI355X only (no CPU path); move the input to cuda")
+        if x.dim() != 5 or x.shape[1] != 2:
+            raise RuntimeError(f"MI355FinalNetv2: input must be [B, 2, D, H, W] (one channel per modality), got {tuple(x.shape)}")
+        # a one-channel volume is its own NDHWC form
+        skips1 = self.encoder1(ops.to_ndhwc(x[:, 0:1].contiguous()))
+        skips2 = self.encoder2(ops.to_ndhwc(x[:, 1:2].contiguous()))
+        y1, y2 = self.fuse(skips1[-1], skips2[-1])
+        if not self.do_ds:
+            return ops.mean2(self.decoder1(skips1, y1), self.decoder2(skips2, y2))
+        o1, f1 = self.decoder1(skips1, y1, True)
+        o2, f2 = self.decoder2(skips2, y2, True)
+        return o1, o2, f1, f2
+
+    def unused_parameter_names(self):
+        """state_dict keys of the parameters the forward never reaches (frozen, outside the flat buffer)."""
+        return [n for n, p in self.named_parameters() if not p.requires_grad]
+
+    def parameters_in_execution_order(self):
+        """encoder1, encoder2, the fusion block in its order of use, decoder1, decoder2 (per level: transposed conv,
+        refining convs, seg layer); used parameters only (see MI355PlainConvUNet.parameters_in_execution_order)."""
+        out = list(self.encoder1.parameters()) + list(self.encoder2.parameters()) + self.fusion_parameters_in_execution_order()
+        for d in (self.decoder1, self.decoder2):
+            for up, refine, head in zip(d.transpconvs, d.stages, d.seg_layers):
+                out += list(up.parameters()) + list(refine.parameters()) + list(head.parameters())
+        return out
+
+
+def finalnet_num_tokens(patch_size, strides):
+    """Bottleneck voxels of a patch: the token count N (128 for the reference's plan, selfattnNet.py:896)."""
+    n = 1
+    for axis, size in enumerate(patch_size):
+        red = int(np.prod([_tup3(s, len(patch_size))[axis] for s in strides]))
+        if size % red:
+            raise NotImplementedError(f"patch size {list(patch_size)} is not divisible by the strides' product along axis {axis}")
+        n *= size // red
+    return n
+
+
+def get_finalnet_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels, deep_supervision=True):
+    """get_network_from_plans.py:94-205 (get_dual_network_from_plans) with FinalNetv2 selected; InitWeights_He touches the
+    convolutions only (network_initialization.py:4-12), the attention members keep torch's own initialisation."""
+    num_stages = len(configuration_manager.conv_kernel_sizes)
+    dim = len(configuration_manager.conv_kernel_sizes[0])
+    if dim != 3:
+        raise NotImplementedError(f"FinalNetv2 on {dim}-D plans: only the 3-D network is built")
+    label_manager = plans_manager.get_label_manager(dataset_json)
+    features = [min(configuration_manager.UNet_base_num_features * 2 ** i, configuration_manager.unet_max_num_features)
+                for i in range(num_stages)]
+    model = MI355FinalNetv2(
+        conv_bias=True, norm_op=nn.InstanceNorm3d, norm_op_kwargs={'eps': 1e-5, 'affine': True}, dropout_op=None,
+        dropout_op_kwargs=None, nonlin=nn.LeakyReLU, nonlin_kwargs={'inplace': True}, features_per_stage=features,
+        kernel_sizes=configuration_manager.conv_kernel_sizes, strides=configuration_manager.pool_op_kernel_sizes,
+        n_conv_per_stage=configuration_manager.n_conv_per_stage_encoder,
+        n_conv_per_stage_decoder=configuration_manager.n_conv_per_stage_decoder, input_channels=num_input_channels,
+        out_channels=label_manager.num_segmentation_heads, n_stages=num_stages, conv_op=nn.Conv3d,
+        hidden_size=features[-1],
+        num_tokens=finalnet_num_tokens(configuration_manager.patch_size, configuration_manager.pool_op_kernel_sizes),
+        do_ds=deep_supervision)
+    model.apply(InitWeights_He(1e-2))
+    return model

@@ -2038,6 +2038,308 @@ def seg_remove_components(seg, cc_labels, kept, background=0):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ attention (csrc/attention.hip)
+# The bottleneck fusion block of FinalNetv2: tokens are the [B, N, C] memory of an NDHWC bottleneck.  `drop` is None (no
+# dropout: eval mode, or p = 0) or (state, p, site): the module's device buffer {seed, t}, the probability and the site
+# number that keys the Philox stream (header: mvd_dropout_*).
+ATTN_MAX_TOKENS = 256
+ATTN_HEAD_DIMS = (4, 64)   # dh in [4, 64], a multiple of 4
+
+
+def _drop3(drop):
+    if drop is None or not drop[1] > 0:
+        return None, 0.0, 0
+    state, p, site = drop
+    if not (state.is_cuda and state.dtype == torch.int64 and state.numel() == 2):
+        raise RuntimeError("dropout state must be a cuda int64 tensor {seed, t}")
+    return _p(state), float(p), int(site)
+
+
+def _f32c(*ts):
+    for t in ts:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("attention ops take contiguous fp32 cuda tensors (the fusion block is fp32 only)")
+
+
+def dropout_tick(state):
+    """t += 1 in the device state {seed, t}: once at the head of a training-mode forward."""
+    _require_cuda(state)
+    call("mvd_dropout_tick", _p(state), _stream())
+
+
+def dropout_mask(seed, t, site, p, n, device):
+    """The keep mask (uint8, 1 = kept) of elements 0..n-1 of (seed, t, site): what the kernels regenerate (tests)."""
+    out = torch.empty(int(n), dtype=torch.uint8, device=device)
+    call("mvd_dropout_mask", int(seed), int(t), int(site), float(p), int(n), _p(out), _stream())
+    return out
+
+
+def layernorm_fwd(x, gamma, beta, eps, pos=None, want_sum=True):
+    """x [..., C] -> (y, xs, mean, rstd); with `pos` ([1, N, C] or [N, C]) xs = x + pos is what gets normalised (and is
+    returned for the residuals), else xs is x."""
+    _f32c(x, gamma, beta, pos)
+    C = x.shape[-1]
+    M = x.numel() // C
+    y = torch.empty_like(x)
+    xs = torch.empty_like(x) if pos is not None and want_sum else None
+    mean = torch.empty(M, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    npos = pos.numel() // C if pos is not None else 0
+    call("mvd_layernorm_fwd", _p(x), _p(pos), _p(xs), _p(y), _p(mean), _p(rstd), _p(gamma), _p(beta), M, C, npos, float(eps),
+         _stream())
+    return y, (xs if pos is not None else x), mean, rstd
+
+
+def layernorm_bwd(dy, xs, mean, rstd, gamma, dres1=None, dres2=None, npos=0, drop=None, dgamma=None, dbeta=None, dpos=None):
+    """-> (dx, dxd, dgamma, dbeta, dpos): dx includes the residual gradients dres1 / dres2; dxd (with `drop`) is dx times
+    the dropout factors of `drop`'s site; dpos ([npos, C], with npos > 0) sums dx over the batch."""
+    _f32c(dy, xs, gamma, dres1, dres2, dgamma, dbeta, dpos)
+    C = xs.shape[-1]
+    M = xs.numel() // C
+    dev = xs.device
+    dx = torch.empty_like(xs)
+    st, p, site = _drop3(drop)
+    dxd = torch.empty_like(xs) if drop is not None else None
+    dgamma = dgamma if dgamma is not None else torch.empty(C, dtype=torch.float32, device=dev)
+    dbeta = dbeta if dbeta is not None else torch.empty(C, dtype=torch.float32, device=dev)
+    if npos and dpos is None:
+        dpos = torch.empty((npos, C), dtype=torch.float32, device=dev)
+    call("mvd_layernorm_bwd", _p(dy), _p(xs), _p(mean), _p(rstd), _p(gamma), _p(dres1), _p(dres2), _p(dx), _p(dxd), _p(dgamma),
+         _p(dbeta), _p(dpos) if npos else None, M, C, int(npos), st, p, site, _stream())
+    return dx, dxd, dgamma, dbeta, (dpos if npos else None)
+
+
+def linear_fwd(x, w, bias=None, res=None, drop=None):
+    """y[..., O] = (x[..., C] w[O, C]^T + bias) * dropout + res: torch's nn.Linear weight itself, MFMA fp32."""
+    _f32c(x, w, bias, res)
+    O, C = w.shape
+    M = x.numel() // C
+    y = torch.empty(tuple(x.shape[:-1]) + (O,), dtype=torch.float32, device=x.device)
+    st, p, site = _drop3(drop)
+    call("mvd_linear_fwd", _p(x), _p(w), _p(bias), _p(res), _p(y), M, C, O, st, p, site, _stream())
+    return y
+
+
+def linear_bwd(g, x, w, need_dx=True, dw=None, db=None, has_bias=False):
+    """g = dy (times the dropout factors, where the forward dropped) -> (dx, dw, db); dw / db may be given (gradient sinks)."""
+    _f32c(g, x, w, dw, db)
+    O, C = w.shape
+    M = x.numel() // C
+    dev = x.device
+    dx = torch.empty_like(x) if need_dx else None
+    dw = dw if dw is not None else torch.empty((O, C), dtype=torch.float32, device=dev)
+    if has_bias and db is None:
+        db = torch.empty(O, dtype=torch.float32, device=dev)
+    call("mvd_linear_bwd", _p(g), _p(x), _p(w), _p(dx), _p(dw), _p(db) if has_bias else None, M, C, O, _stream())
+    return dx, dw, (db if has_bias else None)
+
+
+def _attn_dims(qbuf, heads):
+    B, N, C3 = qbuf.shape
+    C = C3 // 3
+    if C3 != 3 * C or C % heads:
+        raise RuntimeError(f"attention: a [B, N, 3C] qkv buffer with C a multiple of {heads} heads is needed, got {tuple(qbuf.shape)}")
+    return B, N, C, C // heads
+
+
+def attention_fwd(qbuf, kvbuf, heads, res=None, drop=None):
+    """out[B, N, C] = dropout(softmax(q k^T / sqrt(dh))) v [+ res]; q from qbuf, k and v from kvbuf ([B, N, 3C], read in
+    place through the head stride).  -> (out, rowmax, rowsum)"""
+    _f32c(qbuf, kvbuf, res)
+    B, N, C, dh = _attn_dims(qbuf, heads)
+    if kvbuf.shape != qbuf.shape:
+        raise RuntimeError("attention: the two qkv buffers differ in shape")
+    out = torch.empty((B, N, C), dtype=torch.float32, device=qbuf.device)
+    rowmax = torch.empty(B * heads * N, dtype=torch.float32, device=qbuf.device)
+    rowsum = torch.empty_like(rowmax)
+    st, p, site = _drop3(drop)
+    call("mvd_attention_fwd", _p(qbuf), _p(kvbuf), _p(res), _p(out), _p(rowmax), _p(rowsum), B, N, heads, dh, st, p, site,
+         _stream())
+    return out, rowmax, rowsum
+
+
+def attention_bwd(qbuf, kvbuf, dout, rowmax, rowsum, heads, dqbuf, dkvbuf, drop=None):
+    """dq into dqbuf's q section, dk / dv into dkvbuf's k / v sections (both [B, N, 3C]; one buffer for self-attention)."""
+    _f32c(qbuf, kvbuf, dout, dqbuf, dkvbuf)
+    B, N, C, dh = _attn_dims(qbuf, heads)
+    delta = torch.empty_like(rowmax)
+    st, p, site = _drop3(drop)
+    call("mvd_attention_bwd", _p(qbuf), _p(kvbuf), _p(dout), _p(rowmax), _p(rowsum), _p(delta), _p(dqbuf), _p(dkvbuf), B, N,
+         heads, dh, st, p, site, _stream())
+
+
+def mean2(a, b):
+    """(a + b) / 2 of two logits tensors (FinalNetv2 without deep supervision, selfattnNet.py:944); inference only."""
+    _require_cuda(a, b)
+    if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+        raise RuntimeError("mean2 has no backward: the averaged output of FinalNetv2 is its inference output (torch.no_grad())")
+    a, b = a.contiguous(), b.contiguous()
+    out = torch.zeros_like(a)
+    call("mvd_axpy", _p(out), _p(a), 0.5, a.numel(), _stream())
+    call("mvd_axpy", _p(out), _p(b), 0.5, a.numel(), _stream())
+    return out
+
+
+def _sink(param, shape, dev):
+    """(tensor the gradient kernel writes, what goes back to autograd): the parameter's flat-buffer slice and None when the
+    optimizer offers one (optim.FlatParams), else a fresh tensor twice."""
+    t = _take_grad(param)
+    if t is not None:
+        return t, None
+    t = torch.empty(shape, dtype=torch.float32, device=dev)
+    return t, t
+
+
+class LayerNormFn(Function):
+    """nn.LayerNorm(C) over the last axis."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        x = x.contiguous()
+        y, _, mean, rstd = layernorm_fwd(x, gamma.detach(), beta.detach(), eps)
+        ctx.save_for_backward(x, mean, rstd, gamma.detach())
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, mean, rstd, gamma = ctx.saved_tensors
+        dx, _, dg, db, _ = layernorm_bwd(dy.contiguous(), x, mean, rstd, gamma)
+        return dx, dg, db, None
+
+
+class TokenLinearFn(Function):
+    """nn.Linear on tokens: y = x W^T (+ b)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight.detach())
+        ctx.has_bias = bias is not None
+        return linear_fwd(x, weight.detach(), bias.detach() if bias is not None else None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dx, dw, db = linear_bwd(dy.contiguous(), x, w, need_dx=ctx.needs_input_grad[0], has_bias=ctx.has_bias)
+        return dx, dw, db
+
+
+class AttentionFn(Function):
+    """Multi-head attention without dropout over two [B, N, 3C] qkv buffers (queries of the first, keys / values of the
+    second)."""
+
+    @staticmethod
+    def forward(ctx, qbuf, kvbuf, heads):
+        qbuf, kvbuf = qbuf.contiguous(), kvbuf.contiguous()
+        out, rowmax, rowsum = attention_fwd(qbuf, kvbuf, heads)
+        ctx.save_for_backward(qbuf, kvbuf, rowmax, rowsum)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        qbuf, kvbuf, rowmax, rowsum = ctx.saved_tensors
+        dq, dkv = torch.zeros_like(qbuf), torch.zeros_like(kvbuf)   # (the sections the other buffer owns stay 0)
+        attention_bwd(qbuf, kvbuf, dout.contiguous(), rowmax, rowsum, ctx.heads, dq, dkv)
+        return dq, dkv, None
+
+
+# dropout sites of the fusion block (the six nn.Dropout calls that act in FinalNetv2.forward)
+SITE_ATTN1, SITE_ATTN2, SITE_PROJ1, SITE_PROJ2, SITE_SELF1, SITE_SELF2 = range(6)
+FUSION_PARAMS = ("pos1", "pos2", "n1w", "n1b", "n2w", "n2b", "n3w", "n3b", "n4w", "n4b", "qkv1", "qkv2", "p1w", "p1b", "p2w",
+                 "p2b", "sa1", "sa2")
+
+
+class BottleneckFusionFn(Function):
+    """selfattnNet.py:917-939 on two NDHWC bottlenecks [B, C, D, H, W] (tokens = voxels in raster order: a view):
+        xs1 = x1 + pos1, xs2 = x2 + pos2
+        a1 = drop(proj1(attn(q of qkv1(norm1 xs2), k / v of qkv2(norm2 xs1)))) + xs2,  a2 = the mirror image + xs1
+        y1 = xs1 + attn(qkv_sa1(norm3 a1)),  y2 = xs2 + attn(qkv_sa2(norm4 a2))
+    14 launches forward (+ 1 in training: the step counter), 24 backward; residual sums and the proj dropout's backward
+    ride in the producing kernels."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, state, heads, p_attn, p_proj, training, eps, *params):
+        P = dict(zip(FUSION_PARAMS, [q.detach() for q in params]))
+        x1, x2 = to_ndhwc(x1), to_ndhwc(x2)
+        if x1.dtype != torch.float32 or x2.dtype != torch.float32:
+            raise RuntimeError("the bottleneck fusion block is fp32 only")
+        B, C = x1.shape[:2]
+        N = x1[0, 0].numel()
+        t1, t2 = x1.permute(0, 2, 3, 4, 1).reshape(B, N, C), x2.permute(0, 2, 3, 4, 1).reshape(B, N, C)   # views
+        if training:
+            dropout_tick(state)
+        d = (lambda p, site: (state, p, site) if (training and p > 0) else None)
+        ctx.drops = {s: d(p_attn if s in (SITE_ATTN1, SITE_ATTN2, SITE_SELF1, SITE_SELF2) else p_proj, s) for s in range(6)}
+        n2x1, xs1, m2, r2 = layernorm_fwd(t1, P["n2w"], P["n2b"], eps, P["pos1"])
+        n1x2, xs2, m1, r1 = layernorm_fwd(t2, P["n1w"], P["n1b"], eps, P["pos2"])
+        qkv1 = linear_fwd(n1x2, P["qkv1"])
+        qkv2 = linear_fwd(n2x1, P["qkv2"])
+        o1, mx1, sm1 = attention_fwd(qkv1, qkv2, heads, None, ctx.drops[SITE_ATTN1])
+        o2, mx2, sm2 = attention_fwd(qkv2, qkv1, heads, None, ctx.drops[SITE_ATTN2])
+        a1 = linear_fwd(o1, P["p1w"], P["p1b"], xs2, ctx.drops[SITE_PROJ1])
+        a2 = linear_fwd(o2, P["p2w"], P["p2b"], xs1, ctx.drops[SITE_PROJ2])
+        n3, _, m3, r3 = layernorm_fwd(a1, P["n3w"], P["n3b"], eps)
+        n4, _, m4, r4 = layernorm_fwd(a2, P["n4w"], P["n4b"], eps)
+        qkv3 = linear_fwd(n3, P["sa1"])
+        qkv4 = linear_fwd(n4, P["sa2"])
+        y1, mx3, sm3 = attention_fwd(qkv3, qkv3, heads, xs1, ctx.drops[SITE_SELF1])
+        y2, mx4, sm4 = attention_fwd(qkv4, qkv4, heads, xs2, ctx.drops[SITE_SELF2])
+        ctx.save_for_backward(xs1, xs2, m1, r1, m2, r2, n1x2, n2x1, qkv1, qkv2, o1, o2, mx1, sm1, mx2, sm2, a1, a2, m3, r3, m4,
+                              r4, n3, n4, qkv3, qkv4, mx3, sm3, mx4, sm4, *P.values())
+        ctx.params = params
+        ctx.heads, ctx.geom = heads, (B, N, C)
+        ctx.sp = sp = tuple(x1.shape)
+        as5 = lambda y: y.view(B, *sp[2:], C).permute(0, 4, 1, 2, 3)   # [B, N, C] memory as NDHWC [B, C, D, H, W]
+        return as5(y1), as5(y2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy1, dy2):
+        sv = ctx.saved_tensors
+        (xs1, xs2, m1, r1, m2, r2, n1x2, n2x1, qkv1, qkv2, o1, o2, mx1, sm1, mx2, sm2, a1, a2, m3, r3, m4, r4, n3, n4, qkv3, qkv4,
+         mx3, sm3, mx4, sm4) = sv[:30]
+        P = dict(zip(FUSION_PARAMS, sv[30:]))
+        prm = dict(zip(FUSION_PARAMS, ctx.params))
+        B, N, C = ctx.geom
+        H, dr, dev = ctx.heads, ctx.drops, xs1.device
+        tok = lambda g: to_ndhwc(g).permute(0, 2, 3, 4, 1).reshape(B, N, C)
+        dy1, dy2 = tok(dy1), tok(dy2)
+        sink, ret = {}, {}
+        for k in FUSION_PARAMS:
+            sink[k], ret[k] = _sink(prm[k], tuple(prm[k].shape), dev)
+        # the two self-attentions and their qkv linears
+        dqkv3, dqkv4 = torch.empty_like(qkv3), torch.empty_like(qkv4)
+        attention_bwd(qkv3, qkv3, dy1, mx3, sm3, H, dqkv3, dqkv3, dr[SITE_SELF1])
+        attention_bwd(qkv4, qkv4, dy2, mx4, sm4, H, dqkv4, dqkv4, dr[SITE_SELF2])
+        dn3, _, _ = linear_bwd(dqkv3, n3, P["sa1"], dw=sink["sa1"])
+        dn4, _, _ = linear_bwd(dqkv4, n4, P["sa2"], dw=sink["sa2"])
+        # norm3 / norm4: d a (a residual gradient of xs2 / xs1 later) and its dropped copy for the proj linears
+        da1, g1, _, _, _ = layernorm_bwd(dn3, a1, m3, r3, P["n3w"], drop=dr[SITE_PROJ1], dgamma=sink["n3w"], dbeta=sink["n3b"])
+        da2, g2, _, _, _ = layernorm_bwd(dn4, a2, m4, r4, P["n4w"], drop=dr[SITE_PROJ2], dgamma=sink["n4w"], dbeta=sink["n4b"])
+        do1, _, _ = linear_bwd(g1 if g1 is not None else da1, o1, P["p1w"], dw=sink["p1w"], db=sink["p1b"], has_bias=True)
+        do2, _, _ = linear_bwd(g2 if g2 is not None else da2, o2, P["p2w"], dw=sink["p2w"], db=sink["p2b"], has_bias=True)
+        # the two cross-attentions: each qkv buffer gets dq from its own attention and dk, dv from the other one
+        dqkv1, dqkv2 = torch.empty_like(qkv1), torch.empty_like(qkv2)
+        attention_bwd(qkv1, qkv2, do1, mx1, sm1, H, dqkv1, dqkv2, dr[SITE_ATTN1])
+        attention_bwd(qkv2, qkv1, do2, mx2, sm2, H, dqkv2, dqkv1, dr[SITE_ATTN2])
+        dn1x2, _, _ = linear_bwd(dqkv1, n1x2, P["qkv1"], dw=sink["qkv1"])
+        dn2x1, _, _ = linear_bwd(dqkv2, n2x1, P["qkv2"], dw=sink["qkv2"])
+        # norm1 reads xs2, norm2 reads xs1; xs2 also feeds a1 and y2, xs1 feeds a2 and y1
+        dx2, _, _, _, _ = layernorm_bwd(dn1x2, xs2, m1, r1, P["n1w"], dy2, da1, npos=N, dgamma=sink["n1w"], dbeta=sink["n1b"],
+                                        dpos=sink["pos2"])
+        dx1, _, _, _, _ = layernorm_bwd(dn2x1, xs1, m2, r2, P["n2w"], dy1, da2, npos=N, dgamma=sink["n2w"], dbeta=sink["n2b"],
+                                        dpos=sink["pos1"])
+        for k in FUSION_PARAMS:
+            if ret[k] is None:
+                _grad_done(prm[k])
+        as5 = lambda g: g.view(B, *ctx.sp[2:], C).permute(0, 4, 1, 2, 3)
+        return (as5(dx1), as5(dx2), None, None, None, None, None, None) + tuple(ret[k] for k in FUSION_PARAMS)
+
+
 def set_conv_engine(mode):
     """'auto' (MFMA implicit GEMM when the shape allows) or 'scalar' (gather kernels only; cross-check)."""
     call("mvd_set_conv_engine", {"auto": 0, "scalar": 1}[mode])

@@ -23,7 +23,7 @@ from torch import nn
 
 from . import losses, ops
 from .dataloading import DeviceDataLoader2D, DeviceDataLoader3D, get_patch_size
-from .network import InitWeights_He, MI355PlainConvUNet, MVDDualBranchNet, set_precision
+from .network import InitWeights_He, MI355PlainConvUNet, MVDDualBranchNet, get_finalnet_from_plans, set_precision
 from .optim import CosineAnnealingLR, FlatParams, FusedAdam, FusedSGDNesterov, PolyLRScheduler
 from .parallel import BucketedGradReducer, broadcast_parameters, ddp_batch_split
 
@@ -846,3 +846,15 @@ class ContrastiveTrainerMI355(nnUNetTrainerMI355):
     def _graph_flags(self):
         return (bool(self.network.do_ds), self.use_topo, self.topo_cc, self.skel_iter, self.feat_kl, self.kl_T,
                 self.lambda1, self.lambda3, self.vessel_channel, self._label_mode())
+
+
+class FinalNetTrainerMI355(ContrastiveTrainerMI355):
+    """The dual-branch step on FinalNetv2 (network.MI355FinalNetv2): one encoder per modality, the two bottlenecks fused by
+    cross- and self-attention, two decoders.  The network returns MVDDualBranchNet's 4-tuple, so loss, graphed step,
+    validation and the optimizer paths are the parent's; fp32 only (set_precision refuses bf16 for this network)."""
+
+    @staticmethod
+    def build_network_architecture(plans_manager, dataset_json, configuration_manager, num_input_channels,
+                                   enable_deep_supervision: bool = True) -> nn.Module:
+        return get_finalnet_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
+                                       enable_deep_supervision)

@@ -835,8 +835,40 @@ def loader2d_fixture():
     print("wrote loader2d.json")
 
 
+# ------------------------------------------------------------------ Cross_Attention / Self_Attention (UNetDecoder.py:1087-1154)
+def cross_attention_fixture():
+    """The reference's own attention class bodies (they need only torch), eval mode, fp64, B = 2, N = 16, C = 32, 8 heads,
+    random weights.  Self_Attention is run twice, the second time with another `proj`: its output ignores proj
+    (UNetDecoder.py:1151-1154 return the tensor before the projection)."""
+    CA, ca_src = ref_function("training/my_network/UNetDecoder.py", "Cross_Attention", nn=torch.nn)
+    SA, sa_src = ref_function("training/my_network/UNetDecoder.py", "Self_Attention", nn=torch.nn)
+    B, N, C, H = 2, 16, 32, 8
+    g = gen(20260)
+    rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    ca = CA(dim=C, num_heads=H, qkv_bias=False, attn_drop=0.1, proj_drop=0.1).double().eval()
+    sa = SA(dim=C, num_heads=H, qkv_bias=False, attn_drop=0.1, proj_drop=0.1).double().eval()
+    with torch.no_grad():
+        for p in list(ca.parameters()) + list(sa.parameters()):
+            p.copy_(rnd(*p.shape) * 0.3)
+        x1, x2 = rnd(B, N, C), rnd(B, N, C)
+        o1, o2 = ca(x1, x2)
+        so = sa(x1)
+        proj_w, proj_b = sa.proj.weight.clone(), sa.proj.bias.clone()
+        sa.proj.weight.copy_(rnd(C, C))
+        sa.proj.bias.copy_(rnd(C))
+        so_other_proj = sa(x1)
+    arrs = {"ca/" + k: v for k, v in ca.state_dict().items()}
+    arrs.update({"sa/qkv.weight": sa.qkv.weight, "sa/proj.weight": proj_w, "sa/proj.bias": proj_b,
+                 "sa/proj2.weight": sa.proj.weight, "sa/proj2.bias": sa.proj.bias})
+    save("cross_attention.npz", x1=x1, x2=x2, ca_out1=o1, ca_out2=o2, sa_out=so, sa_out_other_proj=so_other_proj,
+         heads=np.int64(H), source=np.array(f"reference {ca_src}, {sa_src}"), **arrs)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == "cross_attention":  # only tests/golden/cross_attention.npz
+        cross_attention_fixture()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "loader2d":  # only tests/golden/loader2d.json
         loader2d_fixture()
         sys.exit(0)
@@ -860,3 +892,4 @@ if __name__ == "__main__":
     persistence_fixtures()
     oracle_check_fixtures()
     loader2d_fixture()
+    cross_attention_fixture()
