@@ -830,6 +830,34 @@ int mvd_argmax_counts_masked(const float *logits, const float *target, long long
                              int ignore_label, void *stream);
 int mvd_seg_to_regions(const float *seg, const uint32_t *lut_host, float *planes, int N, long V, int R, int with_ignore,
                        void *stream);
+/* ------------------------------------------------------------------------------------------------------------
+ * Top-k cross entropy (csrc/loss_topk.hip): TopKLoss (robust_ce_loss.py:19-32) and the CE half of upstream
+ * 2.1.1's DC_and_topk_loss, per deep-supervision level on planar fp32 logits [N,K,V], K <= 8, float label target [N,V].
+ * Every stage is one or more plain launches on `stream`: nothing waits for another workgroup, nothing synchronises, all
+ * state is in device memory -- capturable, and a replay repeats the eager step's bits (integer atomics, fixed-order sums).
+ * ce_fwd: ce[n*V+v] = (1-eps)(-log p_t) + eps/K sum_j (-log p_j) >= +0.0 in fp32; +0.0 where the label is ignore_index
+ *   (reduction='none': such voxels stay in the selection).
+ * select: the exact k-th largest of the n = N*V values by a radix descent over their bit patterns (11 + 11 + 10 bits, a
+ *   histogram launch and a one-workgroup scan launch per pass, after one launch that resets histograms and state).
+ *   state (DEVICE uint32[4]) = {t_bits, cnt_gt, cnt_eq, rank within the ties}: the threshold's bit pattern, how many
+ *   values lie strictly above it and how many equal it.  1 <= k <= n < 2^31; k == 0 is refused (the reference's mean
+ *   over an empty selection is NaN).
+ * finalize: loss[1] = (S_gt + (k - cnt_gt) t) / k with S_gt summed in fp64 in a fixed order, = torch.topk(ce, k).mean()
+ *   whichever tied elements torch picks; loss[0] = w_ce * loss[1] + (dice_loss ? dice_loss[0] : 0), dice_loss = the
+ *   loss[] of mvd_dcce_finalize / mvd_dcce_masked_finalize run with w_ce = 0.
+ * bwd: dlogits[n,c,v] = g ( w_ce s/k (p_c - ((1-eps) y_c + eps/K)) + p_c (q_c - sum_j p_j q_j) ), q from coef as in
+ *   mvd_dcce_bwd (coef may be NULL: no Dice term); s = 1 where ce > t, (k - cnt_gt)/cnt_eq where ce == t (ties share the
+ *   remaining weight equally), 0 below; a voxel labelled ignore_index is an exact 0.  ce is the buffer ce_fwd wrote.
+ * ws: mvd_topk_workspace_bytes, shared by select and finalize of one level (finalize does not touch the histograms). */
+size_t mvd_topk_workspace_bytes(int N, long V);
+int mvd_topk_ce_fwd(const float *logits, const float *target, float *ce, int N, long V, int K, int ignore_index,
+                    float label_smoothing, void *stream);
+int mvd_topk_select(const float *ce, long n, long k, uint32_t *state, void *ws, size_t ws_bytes, void *stream);
+int mvd_topk_finalize(const float *ce, long n, long k, const uint32_t *state, float w_ce, const float *dice_loss, float *loss,
+                      void *ws, size_t ws_bytes, void *stream);
+int mvd_topk_bwd(const float *logits, const float *target, const float *ce, const uint32_t *state, const float *coef,
+                 const float *gscale_dev, float gscale_host, float *dlogits, int N, long V, int K, long k, float w_ce,
+                 int ignore_index, float label_smoothing, void *stream);
 /* Region export (label_handling.py:163-171, :199-205), same tables / lerp order / walk as mvd_export_resize_argmax_u8:
  * mvd_export_resize_regions_u8: the label starts at 0; for i = 0..R-1 a voxel whose interpolated head i is > 0 (see
  *   mvd_sigmoid_counts for the rule) becomes class_order[i] (HOST int[R], 0..255): the last matching head wins.

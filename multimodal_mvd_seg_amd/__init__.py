@@ -12,7 +12,9 @@ __version__ = "0.1.0"
 
 __all__ = ["nnUNetTrainerBNMI355", "nnUNetTrainerAdamMI355", "nnUNetTrainerVanillaAdamMI355",
            "nnUNetTrainerAdam1en3MI355", "nnUNetTrainerAdam3en4MI355", "nnUNetTrainerVanillaAdam1en3MI355",
-           "nnUNetTrainerVanillaAdam3en4MI355", "nnUNetTrainerCosAnnealMI355", "FinalNetTrainerMI355"]
+           "nnUNetTrainerVanillaAdam3en4MI355", "nnUNetTrainerCosAnnealMI355", "FinalNetTrainerMI355",
+           "nnUNetTrainerDiceLossMI355", "nnUNetTrainerDiceCELoss_noSmoothMI355", "nnUNetTrainerCELossMI355",
+           "nnUNetTrainerTopk10LossMI355", "nnUNetTrainerTopk10LossLS01MI355", "nnUNetTrainerDiceTopK10LossMI355"]
 
 
 def __getattr__(name):

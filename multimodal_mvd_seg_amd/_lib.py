@@ -224,6 +224,12 @@ SIGNATURES = {
     "mvd_sigmoid_counts": (c_int, [_P, _P, c_int, _P, _P, c_int, c_long, c_int, _P]),
     "mvd_argmax_counts_masked": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_int, _P]),
     "mvd_seg_to_regions": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_int, _P]),
+    "mvd_topk_workspace_bytes": (c_size_t, [c_int, c_long]),
+    "mvd_topk_ce_fwd": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_int, c_float, _P]),
+    "mvd_topk_select": (c_int, [_P, c_long, c_long, _P, _P, c_size_t, _P]),
+    "mvd_topk_finalize": (c_int, [_P, c_long, c_long, _P, c_float, _P, _P, _P, c_size_t, _P]),
+    "mvd_topk_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_float, _P, c_int, c_long, c_int, c_long, c_float, c_int, c_float,
+                             _P]),
     "mvd_export_resize_regions_u8": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P, _P]),
     "mvd_export_resize_sigmoid_f32": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P]),
     "mvd_dropout_tick": (c_int, [_P, _P]),

@@ -44,14 +44,25 @@ class _FusedDCCE(nn.Module):
 
 
 class RobustCrossEntropyLoss(_FusedDCCE):
-    """robust_ce_loss.py:6-16: float target with a singleton channel, mean over voxels."""
+    """robust_ce_loss.py:6-16: float target with a singleton channel, mean over voxels.  ignore_index other than torch's
+    default -100 (nnUNetTrainerCELoss.py:10-11 passes the ignore label) takes the masked kernels of DESIGN 17 with
+    weight_dice = 0: the mean over the valid voxels, and 0 where torch's 0 / 0 gives NaN (no voxel valid)."""
 
-    def __init__(self):
+    def __init__(self, weight=None, ignore_index: int = -100):
+        if weight is not None:
+            raise NotImplementedError("RobustCrossEntropyLoss: class weights are not built (weight=None at every call site)")
         super().__init__(weight_ce=1.0, weight_dice=0.0)
+        self.ignore_index = int(ignore_index)
+
+    def _fused_apply(self, weights, targets, outputs):
+        if self.ignore_index == -100:
+            return super()._fused_apply(weights, targets, outputs)
+        return ops.DeepSupervisedMaskedFn.apply(weights, ('ce', *self._cfg(), self.ignore_index), None, targets, *outputs)
 
 
 class MemoryEfficientSoftDiceLoss(_FusedDCCE):
-    """App. B; apply_nonlin is always softmax over dim 1 on this path (nnUNetTrainer.py:359-361)."""
+    """App. B; apply_nonlin is always softmax over dim 1 on this path (nnUNetTrainer.py:359-361).  The sigmoid form of
+    nnUNetTrainerDiceLoss's region case is DC_and_BCE_loss with weight_ce = 0 (trainer.nnUNetTrainerDiceLossMI355)."""
 
     def __init__(self, apply_nonlin=None, batch_dice: bool = False, do_bg: bool = True, smooth: float = 1.,
                  ddp: bool = True):
@@ -107,6 +118,47 @@ class DC_and_BCE_loss(_FusedDCCE):
     def _fused_apply(self, weights, targets, outputs):
         return ops.DeepSupervisedMaskedFn.apply(weights, ('bce', *self._cfg(), self._extra), self._gather(), targets,
                                                 *outputs)
+
+
+class TopKLoss(_FusedDCCE):
+    """robust_ce_loss.py:19-32: per-voxel cross entropy (reduction='none': ignored voxels count with the value 0), then
+    the mean of its largest int(num_voxels * k / 100) values, selected exactly on the device.  Elements that
+    tie with the threshold share the remaining weight equally; k == 0 (fewer than 100 / k voxels) is refused."""
+
+    def __init__(self, weight=None, ignore_index: int = -100, k: float = 10, label_smoothing: float = 0):
+        if weight is not None:
+            raise NotImplementedError("TopKLoss: class weights are not built (weight=None at every reference call site)")
+        if not 0 < k <= 100:
+            raise ValueError(f"TopKLoss: k is a percentage in (0, 100], got {k}")
+        if not 0 <= label_smoothing <= 1:
+            raise ValueError(f"TopKLoss: label_smoothing must lie in [0, 1], got {label_smoothing}")
+        super().__init__(weight_ce=1.0, weight_dice=0.0)
+        self.k, self.ignore_index, self.label_smoothing = k, int(ignore_index), float(label_smoothing)
+
+    def _fused_apply(self, weights, targets, outputs):
+        return ops.DeepSupervisedTopKFn.apply(weights, (self.k, self.label_smoothing, self.ignore_index, None), None, targets,
+                                              *outputs)
+
+
+class DC_and_topk_loss(_FusedDCCE):
+    """Upstream 2.1.1 DC_and_topk_loss (the class is missing from the fork: parity unpinned, semantics pinned by
+    tests/topk_ref.py): weight_ce * TopKLoss(**ce_kwargs) + weight_dice * soft Dice over softmax.  ignore_label goes into
+    ce_kwargs['ignore_index'], masks the Dice by target != ignore_label and relabels the ignored voxels 0 for it."""
+
+    def __init__(self, soft_dice_kwargs, ce_kwargs, weight_ce=1, weight_dice=1, ignore_label=None):
+        kw = dict(batch_dice=False, do_bg=True, smooth=1., ddp=True)
+        kw.update(soft_dice_kwargs)
+        super().__init__(kw['batch_dice'], kw['do_bg'], kw['smooth'], kw['ddp'], float(weight_ce), float(weight_dice))
+        ce_kwargs = dict(ce_kwargs)
+        if ignore_label is not None:
+            ce_kwargs['ignore_index'] = int(ignore_label)
+        self.ce = TopKLoss(**ce_kwargs)
+        self.ignore_label = None if ignore_label is None else int(ignore_label)
+
+    def _fused_apply(self, weights, targets, outputs):
+        ce = self.ce
+        return ops.DeepSupervisedTopKFn.apply(weights, (ce.k, ce.label_smoothing, ce.ignore_index,
+                                                        (*self._cfg(), self.ignore_label)), self._gather(), targets, *outputs)
 
 
 class DeepSupervisionWrapper(nn.Module):

@@ -1531,6 +1531,127 @@ class DeepSupervisedMaskedFn(Function):
         return (None, None, None, None, *grads)
 
 
+def topk_count(n, k_percent):
+    """robust_ce_loss.py:30-31: int(num_voxels * k / 100) with num_voxels an np.int64."""
+    return int(np.int64(n) * k_percent / 100)
+
+
+class DeepSupervisedTopKFn(Function):
+    """sum_i w_i * (w_ce * TopK(x_i, t_i) [+ w_dice * (-softDice)]) in one autograd node: TopKLoss
+    (robust_ce_loss.py:19-32) and upstream 2.1.1's DC_and_topk_loss.  cfg = (k_percent, label_smoothing, ignore_index,
+    dice) with dice None or (batch_dice, do_bg, smooth, w_ce, w_dice, ignore_label): the Dice statistics and coefficients
+    come from mvd_dcce_fwd / mvd_dcce_finalize (their _masked_ forms with an ignore label) run with w_ce = 0, the
+    gradient is written once by mvd_topk_bwd.  `gather` as in DeepSupervisedDCCEFn, for the Dice half only: the top-k is
+    local to the rank.  Levels with w_i == 0 contribute exact-zero gradients.  Per level the forward saves the per-voxel
+    CE (4 B per voxel) and the selection state {t_bits, cnt_gt, cnt_eq}: the backward reads them, it recomputes neither."""
+
+    @staticmethod
+    def forward(ctx, weights, cfg, gather, targets, *logits):
+        k_percent, eps, ignore_index, dice = cfg
+        dev = logits[0].device
+        total = torch.zeros((1,), dtype=torch.float32, device=dev)
+        saved = []
+        ctx.levels = []
+        for i, (x, t) in enumerate(zip(logits, targets)):
+            if weights[i] == 0:
+                ctx.levels.append(None)
+                continue
+            _require_cuda(x, t)
+            x = x.contiguous()
+            N, K = x.shape[:2]
+            _check_heads(K)
+            V = x[0, 0].numel()
+            k = topk_count(N * V, k_percent)
+            if k < 1:
+                raise ValueError(f"top-k loss: k = int({N * V} voxels * {k_percent} / 100) = 0; the reference's mean over an "
+                                 f"empty selection is NaN.  A level needs at least {int(np.ceil(100 / k_percent))} voxels")
+            t = _flat_target(t, N, V)
+            coef, w_ce, mult, dloss = None, 1.0, 1.0, None
+            if dice is not None:
+                batch_dice, do_bg, smooth, w_ce, w_dice, ignore_label = dice
+                masked = ignore_label is not None
+                stats = torch.empty((N, 3 * K + (2 if masked else 1)), dtype=torch.float32, device=dev)
+                if masked:
+                    ws = _Workspace.get(query("mvd_dcce_masked_workspace_bytes", N, V, K), dev)
+                    call("mvd_dcce_masked_fwd", _p(x), _p(t), _p(stats), N, V, K, int(ignore_label), _p(ws), ws.numel(),
+                         _stream())
+                else:
+                    ws = _Workspace.get(query("mvd_dcce_workspace_bytes", N, V, K), dev)
+                    call("mvd_dcce_fwd", _p(x), _p(t), _p(stats), N, V, K, _p(ws), ws.numel(), _stream())
+                dstats, off = stats, 0
+                if gather is not None and batch_dice:
+                    dstats, off, mult = gather(stats)
+                Nd = dstats.shape[0]
+                dloss = torch.empty((4,), dtype=torch.float32, device=dev)
+                coef = torch.empty((Nd, K, 2), dtype=torch.float32, device=dev)
+                call("mvd_dcce_masked_finalize" if masked else "mvd_dcce_finalize", _p(stats), N, _p(dstats), Nd, _p(dloss),
+                     _p(coef), V, K, int(batch_dice), int(do_bg), float(smooth), 0.0, float(w_dice), _stream())
+                if off or Nd != N:
+                    coef = coef[off:off + N].contiguous()
+                if mult != 1.0:
+                    coef = coef * mult   # ddp batch-dice: AllGatherGrad.backward sums the (identical) grads of all ranks
+            ce = torch.empty((N, V), dtype=torch.float32, device=dev)
+            state = torch.empty((4,), dtype=torch.int32, device=dev)
+            loss = torch.empty((2,), dtype=torch.float32, device=dev)
+            call("mvd_topk_ce_fwd", _p(x), _p(t), _p(ce), N, V, K, int(ignore_index), float(eps), _stream())
+            ws = _Workspace.get(query("mvd_topk_workspace_bytes", N, V), dev)
+            call("mvd_topk_select", _p(ce), N * V, k, _p(state), _p(ws), ws.numel(), _stream())
+            call("mvd_topk_finalize", _p(ce), N * V, k, _p(state), float(w_ce), _p(dloss), _p(loss), _p(ws), ws.numel(),
+                 _stream())
+            call("mvd_axpy", _p(total), _p(loss), float(weights[i]), 1, _stream())
+            saved += [x, t, ce, state] + ([coef] if coef is not None else [])
+            ctx.levels.append((N, K, V, k, float(weights[i]), float(w_ce), coef is not None))
+        ctx.save_for_backward(*saved)
+        ctx.eps, ctx.ignore_index = float(eps), int(ignore_index)
+        ctx.shapes = [tuple(x.shape) for x in logits]
+        return total.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        g = g.contiguous()
+        grads = []
+        j = 0
+        for lvl, shp in zip(ctx.levels, ctx.shapes):
+            if lvl is None:
+                grads.append(torch.zeros(shp, dtype=torch.float32, device=g.device))
+                continue
+            N, K, V, k, w, w_ce, has_dice = lvl
+            x, t, ce, state = saved[j:j + 4]
+            coef = saved[j + 4] if has_dice else None
+            j += 5 if has_dice else 4
+            dl = torch.empty(shp, dtype=torch.float32, device=g.device)
+            call("mvd_topk_bwd", _p(x), _p(t), _p(ce), _p(state), _p(coef), _p(g), w, _p(dl), N, V, K, k, w_ce,
+                 ctx.ignore_index, ctx.eps, _stream())
+            grads.append(dl)
+        return (None, None, None, None, *grads)
+
+
+def topk_ce(logits, target, ignore_index=-100, label_smoothing=0.0):
+    """The per-voxel CE buffer [N,V] the top-k selection runs on (cross_entropy(reduction='none'), ignored voxels +0.0)."""
+    _require_cuda(logits, target)
+    x = logits.contiguous()
+    N, K = x.shape[:2]
+    _check_heads(K)
+    V = x[0, 0].numel()
+    ce = torch.empty((N, V), dtype=torch.float32, device=x.device)
+    call("mvd_topk_ce_fwd", _p(x), _p(_flat_target(target, N, V)), _p(ce), N, V, K, int(ignore_index), float(label_smoothing),
+         _stream())
+    return ce
+
+
+def topk_select(ce, k):
+    """The selection alone on a device buffer of non-negative fp32 values: int64 [3] = (t_bits, cnt_gt, cnt_eq) of its
+    k-th largest (what DeepSupervisedTopKFn runs per level; the tests check it against a host sort of the same buffer)."""
+    _require_cuda(ce)
+    ce = ce.contiguous().reshape(-1)
+    state = torch.empty((4,), dtype=torch.int32, device=ce.device)
+    ws = _Workspace.get(query("mvd_topk_workspace_bytes", 1, ce.numel()), ce.device)
+    call("mvd_topk_select", _p(ce), ce.numel(), int(k), _p(state), _p(ws), ws.numel(), _stream())
+    return state[:3].to(torch.int64) & 0xffffffff
+
+
 def argmax_counts_masked(logits, target, ignore_label):
     """validation_step with an ignore label and softmax heads (nnUNetTrainer.py:980-990): argmax_counts over the voxels
     whose target is not ignore_label.  int64 [K,3]."""

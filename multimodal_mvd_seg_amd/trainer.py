@@ -769,6 +769,125 @@ class nnUNetTrainerCosAnnealMI355(nnUNetTrainerMI355):
         return optimizer, lr_scheduler
 
 
+# ------------------------------------------------------------------------------------------------ loss variants
+def _variant_checks(tr, what, regions_ok=False):
+    """What every loss variant refuses before it builds anything: cascades (as the base trainer), more heads than the loss
+    kernels hold, and -- where the reference's class asserts it -- regions."""
+    if getattr(tr.configuration_manager, 'previous_stage_name', None) is not None:
+        raise NotImplementedError("cascade configurations (previous_stage_name) and their transforms are not built")
+    if not regions_ok:
+        assert not tr.label_manager.has_regions, 'regions not supported by this trainer'
+    if tr.label_manager.num_segmentation_heads > ops.REGION_KMAX:
+        raise NotImplementedError(f"{what}: {tr.label_manager.num_segmentation_heads} segmentation heads: the fused loss "
+                                  f"kernels hold at most {ops.REGION_KMAX}")
+
+
+def _wrap_every_level(tr, loss):
+    """variants/loss/*.py: weights 1 / 2^i over ALL deep-supervision levels, normalised -- the base trainer's
+    `weights[-1] = 0` is absent from these classes, so the coarsest level contributes too."""
+    if not tr.enable_deep_supervision:
+        return loss
+    weights = np.array([1 / (2 ** i) for i in range(len(tr._get_deep_supervision_scales()))])
+    return losses.DeepSupervisionWrapper(loss, weights / weights.sum())
+
+
+def _check_topk_levels(tr, what, k_percent):
+    """k = int(voxels of the level * k / 100) must be >= 1 on every level the loss sees (the reference returns NaN there)."""
+    cm = tr.configuration_manager
+    scales = tr._get_deep_supervision_scales() or [[1] * len(cm.patch_size)]
+    batch = 1 if tr.is_ddp else int(cm.batch_size)   # (a rank of a data-parallel run holds at least one sample)
+    for s in scales:
+        n = batch * int(np.prod([int(i * j) for i, j in zip(cm.patch_size, s)]))
+        if ops.topk_count(n, k_percent) < 1:
+            raise NotImplementedError(f"{what}: a deep-supervision level of {n} voxels gives k = int({n} * {k_percent} / 100) "
+                                      f"= 0, where the reference's loss is NaN; use a larger patch or fewer levels")
+
+
+class nnUNetTrainerDiceLossMI355(nnUNetTrainerMI355):
+    """variants/loss/nnUNetTrainerDiceLoss.py:11-27: soft Dice alone, do_bg = has_regions, sigmoid heads for regions
+    (DC_and_BCE_loss with weight_ce = 0: the same Dice over the same heads).  With an ignore label the reference's loss
+    has no mask (the target then carries one plane more than the network has heads) and cannot run: refused."""
+
+    def _build_loss(self):
+        _variant_checks(self, "nnUNetTrainerDiceLossMI355", regions_ok=True)
+        if self.label_manager.has_ignore_label:
+            raise NotImplementedError("nnUNetTrainerDiceLossMI355: the reference's Dice-only loss has no mask for the ignore "
+                                      "label and cannot run on such plans")
+        kw = {'batch_dice': self.configuration_manager.batch_dice, 'do_bg': self.label_manager.has_regions, 'smooth': 1e-5,
+              'ddp': self.is_ddp}
+        if self.label_manager.has_regions:
+            loss = losses.DC_and_BCE_loss({}, kw, weight_ce=0, weight_dice=1, use_ignore_label=False,
+                                          dice_class=losses.MemoryEfficientSoftDiceLoss,
+                                          regions=self.label_manager.foreground_regions, ignore_label=None)
+        else:
+            loss = losses.MemoryEfficientSoftDiceLoss(**kw)
+        return _wrap_every_level(self, loss)
+
+
+class nnUNetTrainerDiceCELoss_noSmoothMI355(nnUNetTrainerMI355):
+    """nnUNetTrainerDiceLoss.py:30-55: the base trainer's loss with smooth = 0 (the 1e-8 clip of the denominator stays)."""
+
+    def _build_loss(self):
+        _variant_checks(self, "nnUNetTrainerDiceCELoss_noSmoothMI355", regions_ok=True)
+        if self.label_manager.has_regions:
+            loss = losses.DC_and_BCE_loss({}, {'batch_dice': self.configuration_manager.batch_dice, 'do_bg': True,
+                                               'smooth': 0, 'ddp': self.is_ddp},
+                                          use_ignore_label=self.label_manager.ignore_label is not None,
+                                          dice_class=losses.MemoryEfficientSoftDiceLoss,
+                                          regions=self.label_manager.foreground_regions,
+                                          ignore_label=self.label_manager.ignore_label)
+        else:
+            loss = losses.DC_and_CE_loss({'batch_dice': self.configuration_manager.batch_dice, 'smooth': 0, 'do_bg': False,
+                                          'ddp': self.is_ddp}, {}, weight_ce=1, weight_dice=1,
+                                         ignore_label=self.label_manager.ignore_label,
+                                         dice_class=losses.MemoryEfficientSoftDiceLoss)
+        return _wrap_every_level(self, loss)
+
+
+class nnUNetTrainerCELossMI355(nnUNetTrainerMI355):
+    """variants/loss/nnUNetTrainerCELoss.py: cross entropy alone, the ignore label as its ignore_index."""
+
+    def _build_loss(self):
+        _variant_checks(self, "nnUNetTrainerCELossMI355")
+        lm = self.label_manager
+        loss = losses.RobustCrossEntropyLoss(weight=None, ignore_index=lm.ignore_label if lm.has_ignore_label else -100)
+        return _wrap_every_level(self, loss)
+
+
+class nnUNetTrainerTopk10LossMI355(nnUNetTrainerMI355):
+    """variants/loss/nnUNetTrainerTopkLoss.py:8-24: the mean of the largest 10 % of the per-voxel cross entropy."""
+
+    def _build_loss(self):
+        _variant_checks(self, "nnUNetTrainerTopk10LossMI355")
+        _check_topk_levels(self, "nnUNetTrainerTopk10LossMI355", 10)
+        lm = self.label_manager
+        loss = losses.TopKLoss(ignore_index=lm.ignore_label if lm.has_ignore_label else -100, k=10)
+        return _wrap_every_level(self, loss)
+
+
+class nnUNetTrainerTopk10LossLS01MI355(nnUNetTrainerMI355):
+    """nnUNetTrainerTopkLoss.py:27-43: the same with label_smoothing = 0.1."""
+
+    def _build_loss(self):
+        _variant_checks(self, "nnUNetTrainerTopk10LossLS01MI355")
+        _check_topk_levels(self, "nnUNetTrainerTopk10LossLS01MI355", 10)
+        lm = self.label_manager
+        loss = losses.TopKLoss(ignore_index=lm.ignore_label if lm.has_ignore_label else -100, k=10, label_smoothing=0.1)
+        return _wrap_every_level(self, loss)
+
+
+class nnUNetTrainerDiceTopK10LossMI355(nnUNetTrainerMI355):
+    """nnUNetTrainerTopkLoss.py:46-66: soft Dice (no background, smooth 1e-5) + top-10 % cross entropy."""
+
+    def _build_loss(self):
+        _variant_checks(self, "nnUNetTrainerDiceTopK10LossMI355")
+        _check_topk_levels(self, "nnUNetTrainerDiceTopK10LossMI355", 10)
+        loss = losses.DC_and_topk_loss({'batch_dice': self.configuration_manager.batch_dice, 'smooth': 1e-5, 'do_bg': False,
+                                        'ddp': self.is_ddp}, {'k': 10, 'label_smoothing': 0.0}, weight_ce=1, weight_dice=1,
+                                       ignore_label=self.label_manager.ignore_label)
+        return _wrap_every_level(self, loss)
+
+
 # ------------------------------------------------------------------------------------------------ MVD dual branch
 class ContrastiveTrainerMI355(nnUNetTrainerMI355):
     """Dual-branch mutual-distillation step (MVDTrainer.py:879-925):

@@ -864,8 +864,69 @@ def cross_attention_fixture():
          heads=np.int64(H), source=np.array(f"reference {ca_src}, {sa_src}"), **arrs)
 
 
+# ------------------------------------------------------------------ TopKLoss (training/loss/robust_ce_loss.py:19-32)
+TOPK_CASES = [
+    # name, N, K, spatial, kwargs of TopKLoss, ignored fraction (of the voxels, relabelled `ignore_index`), logit scale
+    ("plain_n1_k2", 1, 2, (5, 7, 9), {}, 0.0, 2.0),
+    ("smooth_n3_k3", 3, 3, (5, 7, 9), {"label_smoothing": 0.1}, 0.0, 2.0),
+    ("ignore_few_n1_k5", 1, 5, (5, 7, 9), {"ignore_index": 5}, 0.05, 2.0),
+    ("plain_n3_k8", 3, 8, (5, 7, 9), {}, 0.0, 2.0),
+    ("ignore_most_n1_k3", 1, 3, (5, 7, 9), {"ignore_index": 3}, 0.95, 2.0),
+    ("ignore_smooth_n1_k5", 1, 5, (5, 7, 9), {"ignore_index": 5, "label_smoothing": 0.1}, 0.3, 2.0),
+    ("k_is_1", 1, 2, (2, 2, 3), {}, 0.0, 2.0),
+    ("scaled40_n1_k3", 1, 3, (5, 7, 9), {}, 0.0, 80.0),
+]
+
+
+def topk_loss_fixture():
+    """The reference's own TopKLoss class, executed in fp64 on the small cases of tests/test_gpu_topk.py: inputs, loss and
+    dlogits per case, and the 'mostly ignored' case of DESIGN 29 (2 x 3 x 4^3, three valid voxels, k = 12).  No tie with a
+    non-zero gradient occurs in these cases (torch.topk's choice among ties is unspecified), which the generator asserts."""
+    m = ref_module("training/loss/robust_ce_loss.py", "ref_robust_ce_loss")
+    arrs, names = {}, []
+    cases = list(TOPK_CASES) + [("mostly_ignored", 2, 3, (4, 4, 4), {"ignore_index": 3}, None, 2.0)]
+    for ci, (name, N, K, sp, kw, frac, scale) in enumerate(cases):
+        g = gen(29000 + ci)
+        z32 = (torch.randn((N, K, *sp), generator=g) * scale).float()
+        t = torch.randint(0, K, (N, 1, *sp), generator=g).float()
+        ign = kw.get("ignore_index", -100)
+        if frac is None:            # all but three voxels ignored
+            keep = torch.randperm(t.numel(), generator=g)[:3]
+            flat = torch.full((t.numel(),), float(ign))
+            flat[keep] = t.reshape(-1)[keep]
+            t = flat.reshape(t.shape)
+        elif frac > 0:
+            t[torch.rand(t.shape, generator=g) < frac] = float(ign)
+        z = z32.double().requires_grad_(True)
+        loss = m.TopKLoss(**kw)(z, t)
+        loss.backward()
+        with torch.no_grad():
+            ce = F.cross_entropy(z, t[:, 0].long(), ignore_index=ign, reduction='none',
+                                 label_smoothing=kw.get("label_smoothing", 0)).reshape(-1)
+            k = int(np.int64(ce.numel()) * 10 / 100)
+            thr = torch.sort(ce, descending=True).values[k - 1]
+            assert float(thr) == 0.0 or int((ce == thr).sum()) == 1, name   # ties only among zeros (zero gradient)
+        names.append(name)
+        arrs[f"{name}/logits"] = z32
+        arrs[f"{name}/target"] = t
+        arrs[f"{name}/loss"] = loss.detach()
+        arrs[f"{name}/dlogits"] = z.grad
+        arrs[f"{name}/ignore_index"] = np.int64(ign)
+        arrs[f"{name}/label_smoothing"] = np.float64(kw.get("label_smoothing", 0))
+        arrs[f"{name}/k"] = np.int64(k)
+    # k == 0: the reference's own answer, NaN (n = 8 voxels)
+    z0 = torch.randn((1, 2, 2, 2, 2), generator=gen(29100), dtype=torch.float64)
+    nan_loss = m.TopKLoss()(z0, torch.zeros((1, 1, 2, 2, 2)))
+    assert bool(torch.isnan(nan_loss))
+    save("topk_loss.npz", cases=np.array(names), k_zero_is_nan=np.bool_(True),
+         source=np.array("reference training/loss/robust_ce_loss.py TopKLoss, fp64"), **arrs)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == "topk_loss":  # only tests/golden/topk_loss.npz
+        topk_loss_fixture()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "cross_attention":  # only tests/golden/cross_attention.npz
         cross_attention_fixture()
         sys.exit(0)
@@ -893,3 +954,4 @@ if __name__ == "__main__":
     oracle_check_fixtures()
     loader2d_fixture()
     cross_attention_fixture()
+    topk_loss_fixture()
