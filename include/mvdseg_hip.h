@@ -569,6 +569,9 @@ long mvd_h0_pair_host(const float *f_host, const uint64_t *keys_host, long n_edg
  * smaller canonical label (first in scan order).  label_set is a HOST array of 1..16 labels.  kept: int32[4] on the
  * device = {label0, label1, size0, size1} (0 = none).  workspace: mvd_cc_keep_workspace_bytes(n) device bytes. */
 int mvd_seg_label_mask(const int32_t *seg, uint8_t *mask, long n, const int32_t *label_set, int nlabels, void *stream);
+/* sizes int32[n]: sizes[root] = voxel count of the component whose canonical label is root + 1, 0 everywhere else (the
+ * size pass of mvd_cc_keep_largest on its own; integer atomics, exact). */
+int mvd_cc_component_sizes(const int32_t *cc_labels, int32_t *sizes, long n, void *stream);
 size_t mvd_cc_keep_workspace_bytes(long n);
 int mvd_cc_keep_largest(const int32_t *cc_labels, long n, int keep, int32_t *kept, void *workspace, void *stream);
 int mvd_seg_remove_components(const int32_t *seg, const int32_t *cc_labels, const int32_t *kept, int32_t *out, long n,
@@ -719,6 +722,34 @@ int mvd_feed_lowres_gather2d_f32(const float *x, float *dpad, int D, int H, int 
                                  int flip_mask, void *stream);
 int mvd_feed_mask_remove_label(float *data, float *seg, int C, int Cs, long V, int chmask, int replace,
                                int replace_from, int replace_to, void *stream);
+
+/* Cascade stage of the feed (nnUNetTrainer.py:740-755, custom_transforms/cascade_transforms.py) on the
+ * one-hot channels of the previous stage's segmentation.  Planes are [D][H][W] float 0/1 (n = D*H*W voxels) or bit-planes
+ * [D][H][Wq] of 64-bit words, Wq = ceil(W/64), bit b of word q = voxel x = 64 q + b, pad bits 0
+ * (mvd_feed_cascade_plane_words(D,H,W) words per plane).  Label lists and element tables are HOST arrays copied into
+ * the kernel arguments (capturable calls).  Bit-exact against scipy.ndimage.
+ * mvd_feed_cascade_onehot: out[k][v] = (seg[v] == labels[k]) for the K <= 8 labels (MoveSegAsOneHotToData).
+ * mvd_feed_cascade_pack / _unpack: K float planes (non-zero = set) <-> K bit-planes.
+ * mvd_feed_cascade_morph: op 0 binary_dilation, 1 binary_erosion(border_value=True), 2 closing (dilation, erosion),
+ *   3 opening (erosion, dilation) of bit-plane c of the K planes with the element given as `nrows` <= 256 rows
+ *   {dz, dy, lo, hi}: the erosion reads in[z+dz][y+dy][x+lo .. x+hi] (scipy: offset = index - n/2), the dilation the
+ *   negated offsets; all offsets within +-8.  Outside the volume is 0 for the dilation, 1 for the erosion.  Then every
+ *   other plane loses the voxels the operator added, other &= ~(res & ~before).  tmp: 2 planes of scratch.
+ * mvd_feed_cascade_remove: RemoveRandomConnectedComponentFromOneHotEncodingTransform on the float plane chan: label its
+ *   26-connected components, call a component valid when its voxel count is < threshold, and clear valid component
+ *   number floor(u n_valid) in the order of the components' smallest linear index (scipy.ndimage.label's order); when
+ *   `other` is not NULL the same voxels are set to 1 there.  n_valid == 0: nothing changes.  chosen: int32[2] on the
+ *   device = {1 + smallest linear index of the removed component or 0, n_valid}.  Fixed-order counts: two runs give
+ *   the same bits.  ws: mvd_feed_cascade_remove_workspace_bytes(n) device bytes. */
+int mvd_feed_cascade_onehot(const float *seg, float *out, long n, const int *labels, int K, void *stream);
+size_t mvd_feed_cascade_plane_words(int D, int H, int W);
+int mvd_feed_cascade_pack(const float *planes, uint64_t *bits, int K, int D, int H, int W, void *stream);
+int mvd_feed_cascade_unpack(const uint64_t *bits, float *planes, int K, int D, int H, int W, void *stream);
+int mvd_feed_cascade_morph(uint64_t *planes, uint64_t *tmp, int K, int c, int op, int D, int H, int W, const int *rows,
+                           int nrows, void *stream);
+size_t mvd_feed_cascade_remove_workspace_bytes(long n);
+int mvd_feed_cascade_remove(float *chan, float *other, int D, int H, int W, long threshold, double u, void *ws,
+                            size_t ws_bytes, int32_t *chosen, void *stream);
 
 /* Segmentation export and evaluation after sliding-window inference (the tail of perform_actual_validation,
  * nnUNetTrainer.py:1135-1260).  logits: float [K][d][h][w] in network space.  The resampled size (D,H,W), the

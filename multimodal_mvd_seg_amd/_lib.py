@@ -202,6 +202,14 @@ SIGNATURES = {
     "mvd_feed_lowres_gather_f32": (c_int, [_P, _P] + [c_int] * 8 + [_P]),
     "mvd_feed_lowres_gather2d_f32": (c_int, [_P, _P] + [c_int] * 7 + [_P]),
     "mvd_feed_mask_remove_label": (c_int, [_P, _P, c_int, c_int, c_long] + [c_int] * 4 + [_P]),
+    "mvd_feed_cascade_onehot": (c_int, [_P, _P, c_long, _P, c_int, _P]),
+    "mvd_feed_cascade_plane_words": (c_size_t, [c_int, c_int, c_int]),
+    "mvd_feed_cascade_pack": (c_int, [_P, _P] + [c_int] * 4 + [_P]),
+    "mvd_feed_cascade_unpack": (c_int, [_P, _P] + [c_int] * 4 + [_P]),
+    "mvd_feed_cascade_morph": (c_int, [_P, _P] + [c_int] * 6 + [_P, c_int, _P]),
+    "mvd_feed_cascade_remove_workspace_bytes": (c_size_t, [c_long]),
+    "mvd_feed_cascade_remove": (c_int, [_P, _P, c_int, c_int, c_int, c_long, c_double, _P, c_size_t, _P, _P]),
+    "mvd_cc_component_sizes": (c_int, [_P, _P, c_long, _P]),
     "mvd_export_resize_argmax_u8": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P]),
     "mvd_export_resize_softmax_f32": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, c_int, _P]),
     "mvd_seg_confusion_counts": (c_int, [_P, _P, c_int, c_long, _P, _P, c_int, c_int, c_int, _P, _P]),

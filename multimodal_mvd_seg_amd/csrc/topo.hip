@@ -729,6 +729,19 @@ int mvd_seg_label_mask(const int32_t *seg, uint8_t *mask, long n, const int32_t 
     return check_launch("seg_label_mask");
 }
 
+int mvd_cc_component_sizes(const int32_t *cc_labels, int32_t *sizes, long n, void *stream) {
+    MVD_REQUIRE(cc_labels && sizes, "cc_component_sizes: null pointer");
+    MVD_REQUIRE(n > 0 && n < 2147483647L, "cc_component_sizes: bad size (int32 labels)");
+    hipStream_t s = as_stream(stream);
+    if (hipMemsetAsync(sizes, 0, (size_t)n * sizeof(int32_t), s) != hipSuccess) {
+        set_error("cc_component_sizes: memset failed");
+        return 1;
+    }
+    constexpr int RUN = 16;
+    hipLaunchKernelGGL(k_cc_sizes<RUN>, dim3(ew_grid(cdiv(n, RUN))), dim3(256), 0, s, cc_labels, sizes, n);
+    return check_launch("cc_component_sizes");
+}
+
 size_t mvd_cc_keep_workspace_bytes(long n) { return (size_t)n * sizeof(int32_t) + 2 * 1024 * sizeof(uint64_t); }
 
 int mvd_cc_keep_largest(const int32_t *cc_labels, long n, int keep, int32_t *kept, void *workspace, void *stream) {
@@ -737,12 +750,7 @@ int mvd_cc_keep_largest(const int32_t *cc_labels, long n, int keep, int32_t *kep
     hipStream_t s = as_stream(stream);
     unsigned long long *cand = (unsigned long long *)workspace;  // 2 * 1024 keys, then n sizes
     int32_t *sizes = (int32_t *)(cand + 2 * 1024);
-    if (hipMemsetAsync(sizes, 0, (size_t)n * sizeof(int32_t), s) != hipSuccess) {
-        set_error("cc_keep_largest: memset failed");
-        return 1;
-    }
-    constexpr int RUN = 16;
-    hipLaunchKernelGGL(k_cc_sizes<RUN>, dim3(ew_grid(cdiv(n, RUN))), dim3(256), 0, s, cc_labels, sizes, n);
+    if (mvd_cc_component_sizes(cc_labels, sizes, n, stream)) return 1;
     long nb = cdiv(n, 256);
     int blocks = (int)(nb > 1024 ? 1024 : nb);
     hipLaunchKernelGGL(k_cc_top2_part, dim3(blocks), dim3(256), 0, s, sizes, n, cand);

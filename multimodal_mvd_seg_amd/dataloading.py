@@ -318,6 +318,111 @@ def mask_remove_label(data, seg, channels, replace=(-1, 0)):
          _chmask(int(data.shape[0]), channels), int(replace is not None), int(rf), int(rt), _stream())
 
 
+CASCADE_OPS = ('dilation', 'erosion', 'closing', 'opening')  # ApplyRandomBinaryOperatorTransform's any_of_these, in order
+CASCADE_MAX_LABELS = 8
+
+
+def ball_rows(radius):
+    """skimage.morphology.ball(radius) for a float radius (restated: side n = int(2r + 1), grid linspace(-r, r, n) per
+    axis, inside when x^2 + y^2 + z^2 <= r^2) as the table mvd_feed_cascade_morph takes: one row (dz, dy, lo, hi) per
+    non-empty (z, y) line of the element, READ offsets of the erosion = index - n // 2, where scipy.ndimage centres an
+    even-sided element (the dilation reads the negated offsets).  Every line of a ball is one interval."""
+    radius = float(radius)
+    n = int(2 * radius + 1)
+    if not 1 <= n <= 16:
+        raise ValueError("ball_rows: the side int(2 r + 1) must be within 1..16 (r < 8)")
+    # summed as skimage does, (x^2 + y^2) + z^2: grid points lie exactly on the sphere for many radii (e.g. (2, 3, 6) / 7
+    # of r at n = 15), where the order of the additions decides the rounding and with it the voxel
+    g = np.linspace(-radius, radius, n)
+    g = g * g
+    inside = ((g[None, None, :] + g[None, :, None]) + g[:, None, None]) <= radius * radius
+    c = n // 2
+    rows = []
+    for iz in range(n):
+        for iy in range(n):
+            xs = np.flatnonzero(inside[iz, iy])
+            if len(xs) == 0:
+                continue
+            if int(xs[-1]) - int(xs[0]) + 1 != len(xs):
+                raise ValueError("ball_rows: an element line is not one interval")
+            rows.append((iz - c, iy - c, int(xs[0]) - c, int(xs[-1]) - c))
+    return rows
+
+
+def cascade_removal_threshold(num_voxels, fraction=0.15):
+    """The integer T with (size < T) == (size < num_voxels * fraction) for every integer size, where the right side is
+    the reference's fp64 test (cascade_transforms.py:71-72, num_voxels a np.uint64): T = ceil of that fp64 product."""
+    return int(np.ceil(float(np.uint64(num_voxels) * float(fraction))))
+
+
+def cascade_onehot(seg_plane, out, labels):
+    """MoveSegAsOneHotToData: out[k] = (seg_plane == labels[k]) as 0/1 floats; seg_plane [D,H,W], out [K,D,H,W]."""
+    _dev_f32(seg_plane, "cascade_onehot", 3)
+    _dev_f32(out, "cascade_onehot", 4)
+    K = len(labels)
+    if not 1 <= K <= CASCADE_MAX_LABELS or out.shape[0] != K or tuple(out.shape[1:]) != tuple(seg_plane.shape):
+        raise RuntimeError("cascade_onehot: out is [K,D,H,W] for 1..8 labels")
+    call("mvd_feed_cascade_onehot", _p(seg_plane), _p(out), seg_plane.numel(), (ctypes.c_int * K)(*[int(l) for l in labels]),
+         K, _stream())
+
+
+def cascade_bitplanes(K, shape, device):
+    """Zeroed bit-plane storage for K planes of `shape` (int64 words: [K, words per plane])."""
+    words = int(query("mvd_feed_cascade_plane_words", *[int(v) for v in shape]))
+    return torch.zeros((int(K), words), dtype=torch.int64, device=device)
+
+
+def _check_bitplanes(bits, K, shape, name):
+    words = int(query("mvd_feed_cascade_plane_words", *[int(v) for v in shape]))
+    if not (bits.is_cuda and bits.dtype == torch.int64 and bits.is_contiguous() and bits.numel() >= K * words):
+        raise RuntimeError(f"{name}: bit-planes are a contiguous int64 device tensor of >= K * plane words")
+
+
+def cascade_pack(planes, bits):
+    """K float planes [K,D,H,W] (non-zero = set) -> bit-planes along W (cascade_bitplanes)."""
+    _dev_f32(planes, "cascade_pack", 4)
+    _check_bitplanes(bits, planes.shape[0], planes.shape[1:], "cascade_pack")
+    call("mvd_feed_cascade_pack", _p(planes), _p(bits), *[int(v) for v in planes.shape], _stream())
+
+
+def cascade_unpack(bits, planes):
+    """bit-planes -> K float planes [K,D,H,W] of 0/1."""
+    _dev_f32(planes, "cascade_unpack", 4)
+    _check_bitplanes(bits, planes.shape[0], planes.shape[1:], "cascade_unpack")
+    call("mvd_feed_cascade_unpack", _p(bits), _p(planes), *[int(v) for v in planes.shape], _stream())
+
+
+def cascade_morph(bits, tmp, K, shape, c, op, rows):
+    """One channel step of ApplyRandomBinaryOperatorTransform on the K bit-planes of `shape`: operator `op` (index into
+    CASCADE_OPS) with the element `rows` (ball_rows) on plane c, then every other plane loses the added voxels.
+    tmp: 2 planes of scratch (cascade_bitplanes(2, ...))."""
+    _check_bitplanes(bits, K, shape, "cascade_morph")
+    _check_bitplanes(tmp, 2, shape, "cascade_morph")
+    flat = [int(v) for r in rows for v in r]
+    call("mvd_feed_cascade_morph", _p(bits), _p(tmp), int(K), int(c), int(op), *[int(v) for v in shape],
+         (ctypes.c_int * len(flat))(*flat), len(rows), _stream())
+
+
+def cascade_remove_workspace(shape, device):
+    n = int(np.prod([int(v) for v in shape]))
+    return torch.empty(int(query("mvd_feed_cascade_remove_workspace_bytes", n)), dtype=torch.uint8, device=device)
+
+
+def cascade_remove(chan, u, threshold, ws, chosen, other=None):
+    """RemoveRandomConnectedComponentFromOneHotEncodingTransform on the float plane chan [D,H,W], in place: clears valid
+    component number floor(u n_valid) (26-connected, valid: voxel count < threshold, in the order of the smallest linear
+    index); `other` [D,H,W] is set to 1 there when given.  chosen: int32[2] device tensor <- (label, n_valid)."""
+    _dev_f32(chan, "cascade_remove", 3)
+    if other is not None:
+        _dev_f32(other, "cascade_remove", 3)
+        if tuple(other.shape) != tuple(chan.shape):
+            raise RuntimeError("cascade_remove: chan and other differ in shape")
+    if not (chosen.is_cuda and chosen.dtype == torch.int32 and chosen.numel() >= 2 and ws.is_cuda):
+        raise RuntimeError("cascade_remove: chosen is an int32[2] device tensor, ws a device buffer")
+    call("mvd_feed_cascade_remove", _p(chan), _p(other) if other is not None else None, *[int(v) for v in chan.shape],
+         int(threshold), float(u), _p(ws), ws.numel() * ws.element_size(), _p(chosen), _stream())
+
+
 def lowres_target_shape(shape, zoom):
     """np.round(shape * zoom) (augment_linear_downsampling_scipy), at least 1 per axis (the reference cannot resize a
     length-1 axis to 0 either)."""
@@ -353,8 +458,28 @@ class DeviceDataLoader3D:
                  p_rot_per_sample=0.2, p_scale_per_sample=0.2, p_rot_per_axis=1.0, do_dummy_2d_data_aug=False,
                  intensity_augmentation=False, mask_channels=None, p_noise=0.1, p_blur=0.2, p_blur_per_channel=0.5,
                  p_brightness=0.15, p_contrast=0.15, p_lowres=0.25, p_lowres_per_channel=0.5, p_gamma_inverted=0.1,
-                 p_gamma=0.3):
+                 p_gamma=0.3, cascade_labels=None, cascade_augmentation=False, p_cascade_binary=0.4,
+                 cascade_strel_size=(1, 8), p_cascade_remove=0.2, cascade_fill_with_other_class_p=0.0,
+                 cascade_max_component_fraction=0.15):
         self._data = data
+        # cascade mode (nnUNetTrainer.py:740-755, :783-784): load_case returns a seg of two channels, channel 1 the previous
+        # stage's segmentation; cascade_labels = label_manager.foreground_labels become that many one-hot input channels
+        # behind the modalities.  cascade_augmentation adds the binary operators and the component removal (training);
+        # without it only the one-hot move runs (get_validation_transforms)
+        self.cascade_labels = None if cascade_labels is None else [int(l) for l in cascade_labels]
+        if self.cascade_labels is not None and not 1 <= len(self.cascade_labels) <= CASCADE_MAX_LABELS:
+            raise NotImplementedError(f"DeviceDataLoader3D: the cascade stage takes 1..{CASCADE_MAX_LABELS} foreground "
+                                      f"labels, got {len(self.cascade_labels)}")
+        self.cascade_augmentation = bool(cascade_augmentation) and self.cascade_labels is not None
+        self.p_cascade_binary, self.p_cascade_remove = float(p_cascade_binary), float(p_cascade_remove)
+        self.cascade_strel_size = tuple(float(v) for v in cascade_strel_size)
+        if not 1 <= self.cascade_strel_size[0] <= self.cascade_strel_size[1] <= 8:
+            raise ValueError("DeviceDataLoader3D: cascade_strel_size within [1, 8] (the kernel's elements are 16^3 at most)")
+        self.cascade_fill_with_other_class_p = float(cascade_fill_with_other_class_p)
+        self.cascade_max_component_fraction = float(cascade_max_component_fraction)
+        # ApplyRandomBinaryOperatorTransform shuffles its stored channel list in place: the order persists between batches
+        self._cascade_order = list(range(len(self.cascade_labels or ())))
+        self._cstate = None
         self.batch_size = int(batch_size)
         self.indices = list(data.keys())
         self.oversample_foreground_percent = oversample_foreground_percent
@@ -407,8 +532,17 @@ class DeviceDataLoader3D:
         self._scratch = None  # initial-patch buffers of the modified samples, reused across samples and batches
         d0, s0, _ = self._case(self.indices[0])  # determine_shapes (:55-62)
         # the batch leaves SpatialTransform at the final patch size (== patch_size without it)
+        self.num_modalities = int(d0.shape[0])
         self.data_shape = (self.batch_size, d0.shape[0], *self.final_patch_size)
         self.seg_shape = (self.batch_size, s0.shape[0], *self.final_patch_size)
+        if self.cascade_labels is not None:
+            if s0.shape[0] != 2:
+                raise ValueError("DeviceDataLoader3D: in cascade mode load_case returns a seg of two channels (channel 1: "
+                                 "the previous stage's segmentation)")
+            if self.mask_channels is not None and max(self.mask_channels) >= self.num_modalities:
+                raise ValueError("DeviceDataLoader3D: mask_channels name modality channels")
+            self.data_shape = (self.batch_size, self.num_modalities + len(self.cascade_labels), *self.final_patch_size)
+            self.seg_shape = (self.batch_size, 1, *self.final_patch_size)
 
     # ------------------------------------------------------------------ residency
     def _case(self, key):
@@ -577,11 +711,58 @@ class DeviceDataLoader3D:
                     it[key] = [float(two_sided(0.7, 1.5)) for _ in range(nchannels)]
         return out
 
+    def draw_cascade(self, nsamples):
+        """The two cascade transforms' draws for a batch (nnUNetTrainer.py:741-755), each over all samples as Compose runs
+        them.
+          binary operators  ApplyRandomBinaryOperatorTransform's own draws, restated exactly (none depends on the data):
+                            per sample a uniform (< 0.4), np.random.shuffle of the stored channel list in place, then per
+                            channel a uniform (< p_per_label = 1), np.random.choice among the four operators and
+                            uniform(1, 8) for the ball radius.  -> per sample None or [(channel, op, radius), ...]
+          removal           the reference's draws depend on the data (np.any, the number of valid components, a choice
+                            over them); here a fixed set per sample: a uniform (< 0.2), then per channel a uniform
+                            (< p_per_label = 1), u for the pick, a uniform (< fill_with_other_class_p) and -- with more
+                            than one channel -- the other class; the device does the data-dependent part.  The
+                            distribution is the reference's, the RNG stream is not.
+                            -> per sample None or [(channel, u, other channel or None), ...]
+        Channels are indices into the K one-hot channels."""
+        K = len(self.cascade_labels)
+        u = np.random.uniform
+        binary, remove = [], []
+        for _ in range(nsamples):
+            steps = None
+            if u() < self.p_cascade_binary:
+                np.random.shuffle(self._cascade_order)
+                steps = []
+                for c in self._cascade_order:
+                    if u() < 1:
+                        op = int(np.random.choice(len(CASCADE_OPS)))
+                        steps.append((int(c), op, float(u(*self.cascade_strel_size))))
+            binary.append(steps)
+        for _ in range(nsamples):
+            steps = None
+            if u() < self.p_cascade_remove:
+                steps = []
+                for c in range(K):
+                    if u() < 1:
+                        pick = float(u())
+                        fill = u() < self.cascade_fill_with_other_class_p
+                        other = int(np.random.choice([i for i in range(K) if i != c])) if K > 1 else None
+                        steps.append((c, pick, other if fill else None))
+            remove.append(steps)
+        return {'cascade': True, 'binary': binary, 'remove': remove}
+
     # ------------------------------------------------------------------ the batch
     def plan_batch(self):
         """The host decisions of one batch, in the reference's RNG order: keys, then per sample (oversample?, bbox),
         then per sample the SpatialTransform draws (only with rotation_for_DA), then the intensity draws (only with
-        intensity_augmentation, draw_intensity), then per sample the mirror draw."""
+        intensity_augmentation, draw_intensity), then per sample the mirror draw.  In cascade mode with
+        cascade_augmentation the plan gains a last element, draw_cascade's dict, drawn after the mirrors."""
+        plan = self._plan_base()
+        if self.cascade_augmentation:
+            plan = plan + (self.draw_cascade(len(plan[0])),)
+        return plan
+
+    def _plan_base(self):
         keys = self.get_indices()
         boxes = []
         for j, k in enumerate(keys):
@@ -591,7 +772,7 @@ class DeviceDataLoader3D:
             boxes.append([int(v) for v in lbs])
         if self.intensity_augmentation:
             spatial = [self.draw_spatial() if self.rotation_for_DA is not None else None for _ in keys]
-            intensity = self.draw_intensity(len(keys), self.data_shape[1])
+            intensity = self.draw_intensity(len(keys), self.num_modalities)
             flips = [self.draw_mirror() for _ in keys]
             return list(keys), boxes, spatial, intensity, flips
         if self.rotation_for_DA is None:
@@ -667,9 +848,42 @@ class DeviceDataLoader3D:
                 channel_stats(x, sb, st['ws'], pre_op=op, gammas=it[key], pre_stats=sa)
                 intensity_apply(x, op, it[key], sa, sb)
 
+    def _cascade_state(self):
+        st = self._cstate
+        if st is None:
+            K = len(self.cascade_labels)
+            st = {'bits': cascade_bitplanes(K, self.final_patch_size, self.device),
+                  'tmp': cascade_bitplanes(2, self.final_patch_size, self.device),
+                  'ws': cascade_remove_workspace(self.final_patch_size, self.device),
+                  'chosen': torch.zeros(2, dtype=torch.int32, device=self.device),
+                  'threshold': cascade_removal_threshold(int(np.prod(self.final_patch_size)),
+                                                         self.cascade_max_component_fraction)}
+            self._cstate = st
+        return st
+
+    def apply_cascade(self, onehot, binary, remove):
+        """The two cascade augmentations on one sample's K one-hot channels [K,D,H,W], in place: the binary operators on
+        the packed bit-planes (packed once, unpacked once), then the component removal per drawn channel."""
+        K = int(onehot.shape[0])
+        shape = tuple(int(v) for v in onehot.shape[1:])
+        st = self._cascade_state()
+        if binary:
+            cascade_pack(onehot, st['bits'])
+            for c, op, radius in binary:
+                cascade_morph(st['bits'], st['tmp'], K, shape, c, op, ball_rows(radius))
+            cascade_unpack(st['bits'], onehot)
+        for c, u, other in (remove or ()):
+            cascade_remove(onehot[c], u, st['threshold'], st['ws'], st['chosen'],
+                           other=None if other is None else onehot[other])
+
     def generate_train_batch(self, plan=None):
         plan = plan if plan is not None else self.plan_batch()
         intensity = None
+        cascade = None
+        if isinstance(plan[-1], dict) and plan[-1].get('cascade'):
+            plan, cascade = plan[:-1], plan[-1]
+            if self.cascade_labels is None:
+                raise ValueError("generate_train_batch: a cascade plan needs a loader in cascade mode")
         if len(plan) == 3:
             keys, boxes, flips = plan
             spatial = [None] * len(keys)
@@ -679,17 +893,22 @@ class DeviceDataLoader3D:
             keys, boxes, spatial, intensity, flips = plan
         # MaskTransform reads the seg before RemoveLabel: keep the -1 in the stores and replace in the mask pass
         remove = (-1, 0) if self.mask_channels is None else None
+        M = self.num_modalities
         data_all = torch.empty(self.data_shape, dtype=torch.float32, device=self.device)
-        target = torch.empty(self.seg_shape, dtype=torch.float32, device=self.device)
+        # cascade mode: both seg channels are cropped, padded and warped together; channel 0 becomes the target
+        # (MoveSegAsOneHotToData removes channel 1 from the seg)
+        nseg = self.seg_shape[1] if self.cascade_labels is None else 2
+        target = torch.empty((self.seg_shape[0], nseg, *self.seg_shape[2:]), dtype=torch.float32, device=self.device)
         # an unmodified sample is the centre crop of the initial patch at (n - f) // 2 (center_crop_aug): cut straight
         # from the resident case (no-op shift when patch_size == final_patch_size)
         shift = [(n - f) // 2 for n, f in zip(self.patch_size, self.final_patch_size)]
         props = []
         for j, k in enumerate(keys):
             data, seg, properties = self._case(k)
+            mod = data_all[j] if self.cascade_labels is None else data_all[j, :M]
             if spatial[j] is None:
                 lbs = [b + s for b, s in zip(boxes[j], shift)]
-                crop_pad_data(data, data_all[j], lbs, flips[j], 0.0)
+                crop_pad_data(data, mod, lbs, flips[j], 0.0)
                 crop_pad_seg(seg, target[j], lbs, flips[j], -1, replace=remove)
             else:
                 pdata, pseg = self._scratch_for(data, seg)
@@ -698,18 +917,24 @@ class DeviceDataLoader3D:
                 if self.do_dummy_2d_data_aug:
                     bspline_prefilter(pdata, 6)
                     affine = spatial_affine_2d(spatial[j], self.patch_size[1:])
-                    spatial_transform_data_2d(pdata, data_all[j], affine, flips[j], 0.0)
+                    spatial_transform_data_2d(pdata, mod, affine, flips[j], 0.0)
                     spatial_transform_seg_2d(pseg, target[j], affine, flips[j], replace=remove)
                 else:
                     bspline_prefilter(pdata, 7)
                     affine = spatial_affine(spatial[j], self.patch_size)
-                    spatial_transform_data(pdata, data_all[j], affine, flips[j], 0.0)
+                    spatial_transform_data(pdata, mod, affine, flips[j], 0.0)
                     spatial_transform_seg(pseg, target[j], affine, flips[j], replace=remove)
             if intensity is not None:
-                self.apply_intensity(data_all[j], intensity[j], flips[j])
+                self.apply_intensity(mod, intensity[j], flips[j])
             if self.mask_channels is not None:
-                mask_remove_label(data_all[j], target[j], self.mask_channels, replace=(-1, 0))
+                mask_remove_label(mod, target[j], self.mask_channels, replace=(-1, 0))
+            if self.cascade_labels is not None:
+                cascade_onehot(target[j, 1], data_all[j, M:], self.cascade_labels)
+                if cascade is not None:
+                    self.apply_cascade(data_all[j, M:], cascade['binary'][j], cascade['remove'][j])
             props.append(properties)
+        if self.cascade_labels is not None:
+            target = target[:, :1].contiguous()
         if self.deep_supervision_scales is not None:
             target = [downsample_seg(target, s) for s in self.deep_supervision_scales]
         return {'data': data_all, 'target': target, 'properties': props, 'keys': keys}
@@ -736,9 +961,12 @@ class DeviceDataLoader2D(DeviceDataLoader3D):
                  sampling_probabilities=None, pad_sides=None, probabilistic_oversampling=False, mirror_axes=None,
                  deep_supervision_scales=None, device="cuda:0", rotation_for_DA=None, scale_range=(0.7, 1.4),
                  p_rot_per_sample=0.2, p_scale_per_sample=0.2, p_rot_per_axis=1.0, intensity_augmentation=False,
-                 mask_channels=None):
+                 mask_channels=None, cascade_labels=None, cascade_augmentation=False):
         if len(patch_size) != 2 or len(final_patch_size) != 2:
             raise ValueError("DeviceDataLoader2D: patch_size and final_patch_size have two axes")
+        if cascade_labels is not None or cascade_augmentation:
+            raise NotImplementedError("DeviceDataLoader2D: the cascade mode (cascade_labels) is not built for the 2d "
+                                      "configuration; nnU-Net plans no 2-D cascade")
         if intensity_augmentation:
             # the blur kernel filters all three axes of a volume; on an extent-1 axis that is a multiplication by the sum of
             # the weights, which the 2-D transform does not do -- not routed around yet, so not offered

@@ -235,3 +235,25 @@ def convert_predicted_logits_to_segmentation_with_correct_shape(predicted_logits
                                          [b[0] for b in bbox], plans_manager.transpose_backward, axis,
                                          return_probabilities,
                                          label_manager.regions_class_order if has_regions else None)
+
+
+def resample_logits_for_next_stage(predicted_logits: torch.Tensor, target_shape: Sequence[int], configuration_manager,
+                                   label_manager=None) -> torch.Tensor:
+    """export_prediction.py:109-141 (resample_and_save) without the file: the logits [K, d, h, w] of a stage that has
+    next_stage_names, resampled to the next stage's preprocessed shape with the configuration's probability resampling
+    and arg-maxed to uint8 [target_shape] -- what the next stage loads as its previous-stage segmentation.  No bbox paste
+    and no transpose: the result stays in preprocessed axis order.  As in the reference, current and target spacing are
+    both the configuration's own spacing, which is what decides the separate-z axis."""
+    if label_manager is not None and getattr(label_manager, 'has_regions', False):
+        raise NotImplementedError("cascade with region-based labels: the next-stage export is built for plain labels")
+    target_shape = [int(v) for v in target_shape]
+    if len(target_shape) != 3:
+        raise NotImplementedError("3-D cases only")
+    spacing = list(configuration_manager.spacing)
+    if len(spacing) != 3:
+        raise NotImplementedError("the next-stage export needs a 3-D configuration spacing")
+    kwargs = dict(configuration_manager.resampling_fn_probabilities_kwargs)
+    _check_resampling_kwargs(kwargs.get('is_seg', False), kwargs.get('order', 1), kwargs.get('order_z', 0))
+    _, axis = determine_separate_z(spacing, spacing, kwargs.get('force_separate_z'),
+                                   kwargs.get('separate_z_anisotropy_threshold', ANISO_THRESHOLD))
+    return resize_logits_to_segmentation(predicted_logits, target_shape, target_shape, (0, 0, 0), (0, 1, 2), axis)

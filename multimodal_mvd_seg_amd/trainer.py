@@ -197,23 +197,46 @@ class PlansManager:
 
 
 def determine_num_input_channels(plans_manager, configuration_manager, dataset_json):
-    """label_handling.py:283-301 without the cascade branch."""
+    """label_handling.py:283-301: the modalities, plus one one-hot channel per foreground label of the previous stage's
+    segmentation for a cascaded configuration (previous_stage_name set, :294-297)."""
     key = 'channel_names' if 'channel_names' in dataset_json else 'modality'
-    return len(dataset_json[key])
+    num_modalities = len(dataset_json[key])
+    if getattr(configuration_manager, 'previous_stage_name', None) is not None:
+        return num_modalities + len(plans_manager.get_label_manager(dataset_json).foreground_labels)
+    return num_modalities
 
 
 def make_plans(patch_size, strides, batch_size=2, base_features=32, max_features=320, n_conv=2, batch_dice=False,
-               conv_kernel_sizes=None, configuration='3d_fullres'):
+               conv_kernel_sizes=None, configuration='3d_fullres', spacing=None, previous_stage_name=None,
+               next_stage_names=None, cascade_configuration=None, cascade_spacing=None):
     """A minimal nnUNetPlans.json-shaped dict for the synthetic configurations of BASELINE.json.  `configuration`: the name
-    of the entry ('2d' with a 2-tuple patch size and 2-tuple strides writes a 2-D plan)."""
+    of the entry ('2d' with a 2-tuple patch size and 2-tuple strides writes a 2-D plan).  spacing / previous_stage_name /
+    next_stage_names are written into the entry when given.  cascade_configuration names a second entry that inherits
+    from the first (`inherits_from`, as the planner writes 3d_cascade_fullres), has it as its previous stage and is
+    listed as its next stage: a two-stage plan."""
     n = len(strides)
-    return {'plans_name': 'nnUNetPlans', 'configurations': {configuration: {
+    cfg = {
         'patch_size': list(patch_size), 'batch_size': batch_size, 'UNet_class_name': 'PlainConvUNet',
         'UNet_base_num_features': base_features, 'unet_max_num_features': max_features,
         'n_conv_per_stage_encoder': [n_conv] * n, 'n_conv_per_stage_decoder': [n_conv] * (n - 1),
         'conv_kernel_sizes': conv_kernel_sizes or [[3] * len(patch_size)] * n,
         'pool_op_kernel_sizes': [list(s) for s in strides],
-        'batch_dice': batch_dice}}}
+        'batch_dice': batch_dice}
+    if spacing is not None:
+        cfg['spacing'] = [float(v) for v in spacing]
+    if previous_stage_name is not None:
+        cfg['previous_stage_name'] = previous_stage_name
+    if next_stage_names is not None:
+        cfg['next_stage_names'] = list(next_stage_names)
+    configurations = {configuration: cfg}
+    if cascade_configuration is not None:
+        cfg['next_stage_names'] = list(cfg.get('next_stage_names', [])) + [cascade_configuration]
+        # the inherited next_stage_names is overwritten: the last stage has none
+        second = {'inherits_from': configuration, 'previous_stage_name': configuration, 'next_stage_names': None}
+        if cascade_spacing is not None:
+            second['spacing'] = [float(v) for v in cascade_spacing]
+        configurations[cascade_configuration] = second
+    return {'plans_name': 'nnUNetPlans', 'configurations': configurations}
 
 
 def get_network_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
@@ -346,9 +369,29 @@ class nnUNetTrainerMI355(object):
             self.batch_size = bs[dist.get_rank()]
             self.oversample_foreground_percent = ov[dist.get_rank()]
 
+    @property
+    def is_cascaded(self) -> bool:
+        """nnUNetTrainer.py:135-140."""
+        return getattr(self.configuration_manager, 'previous_stage_name', None) is not None
+
+    def _check_cascade(self):
+        """The cascade is built for plain labels without an ignore label in a 3-D configuration."""
+        if not self.is_cascaded:
+            return
+        if self.label_manager.has_regions:
+            raise NotImplementedError("cascade configurations (previous_stage_name) with region-based labels are not built: "
+                                      "the cascade stage one-hot encodes plain labels")
+        if self.label_manager.has_ignore_label:
+            raise NotImplementedError("cascade configurations (previous_stage_name) with an ignore label are not built")
+        if len(self.configuration_manager.patch_size) != 3:
+            raise NotImplementedError("cascade configurations (previous_stage_name) need a 3-D plan: nnU-Net plans no 2-D "
+                                      "cascade")
+        if len(self.label_manager.foreground_labels) > 8:
+            raise NotImplementedError(f"cascade configurations with {len(self.label_manager.foreground_labels)} foreground "
+                                      f"labels: the cascade stage of the feed holds at most 8")
+
     def _build_loss(self):
-        if getattr(self.configuration_manager, 'previous_stage_name', None) is not None:
-            raise NotImplementedError("cascade configurations (previous_stage_name) and their transforms are not built")
+        self._check_cascade()
         if (self.label_manager.has_regions or self.label_manager.has_ignore_label) and \
                 self.label_manager.num_segmentation_heads > ops.REGION_KMAX:
             # the limit is the loss kernels'; a network with more heads can still be built for inference and export, and
@@ -532,11 +575,14 @@ class nnUNetTrainerMI355(object):
         self.inference_allowed_mirroring_axes = mirror_axes
         return rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, mirror_axes
 
-    def get_device_dataloader(self, dataset_tr, device=None, intensity_augmentation=False):
+    def get_device_dataloader(self, dataset_tr, device=None, intensity_augmentation=False, cascade_augmentation=True):
         """The training loader of get_dataloaders (:600-630) with its transforms' geometric part on the device: initial
         patch, SpatialTransform (rotation, scaling 0.7-1.4), mirroring, RemoveLabel and the deep-supervision targets.
         intensity_augmentation=True adds the intensity transforms (:719-736) and, where the plans set
-        use_mask_for_norm, MaskTransform: the reference's whole training recipe."""
+        use_mask_for_norm, MaskTransform: the reference's whole training recipe.  A cascaded trainer's loader runs in
+        cascade mode (dataset cases carry the previous stage's segmentation as seg channel 1): the one-hot move and, unless
+        cascade_augmentation=False, the binary operators and the component removal (:740-755)."""
+        self._check_cascade()
         rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, mirror_axes = \
             self.configure_rotation_dummyDA_mirroring_and_inital_patch_size()
         if len(self.configuration_manager.patch_size) == 2:
@@ -557,7 +603,28 @@ class nnUNetTrainerMI355(object):
                                   mirror_axes=mirror_axes, deep_supervision_scales=self._get_deep_supervision_scales(),
                                   device=self.device if device is None else device, rotation_for_DA=rotation_for_DA,
                                   scale_range=(0.7, 1.4), do_dummy_2d_data_aug=do_dummy_2d_data_aug,
-                                  intensity_augmentation=intensity_augmentation, mask_channels=mask_channels)
+                                  intensity_augmentation=intensity_augmentation, mask_channels=mask_channels,
+                                  cascade_labels=self.label_manager.foreground_labels if self.is_cascaded else None,
+                                  cascade_augmentation=cascade_augmentation and self.is_cascaded)
+
+    def get_device_validation_dataloader(self, dataset_val, device=None):
+        """The validation loader of get_dataloaders with get_validation_transforms (:771-802): final patch straight from
+        the case, no spatial, intensity or mirror stage, RemoveLabel, for a cascaded trainer the one-hot move alone
+        (:783-784), and the deep-supervision targets."""
+        self._check_cascade()
+        if len(self.configuration_manager.patch_size) == 2:
+            return DeviceDataLoader2D(dataset_val, self.batch_size, self.configuration_manager.patch_size,
+                                      self.configuration_manager.patch_size, self.label_manager,
+                                      oversample_foreground_percent=self.oversample_foreground_percent,
+                                      deep_supervision_scales=self._get_deep_supervision_scales(),
+                                      device=self.device if device is None else device)
+        return DeviceDataLoader3D(dataset_val, self.batch_size, self.configuration_manager.patch_size,
+                                  self.configuration_manager.patch_size, self.label_manager,
+                                  oversample_foreground_percent=self.oversample_foreground_percent,
+                                  deep_supervision_scales=self._get_deep_supervision_scales(),
+                                  device=self.device if device is None else device,
+                                  cascade_labels=self.label_manager.foreground_labels if self.is_cascaded else None,
+                                  cascade_augmentation=False)
 
     def train_step(self, batch: dict, return_device_loss: bool = False) -> dict:
         data, target = batch['data'], batch['target']
@@ -604,7 +671,7 @@ class nnUNetTrainerMI355(object):
     def perform_actual_validation(self, cases, save_probabilities: bool = False, pp_fns=None, pp_fn_kwargs=None,
                                   tile_step_size: float = 0.5, use_gaussian: bool = True, use_mirroring: bool = True,
                                   return_segmentations: bool = False, surface_metrics: bool = False,
-                                  surface_connectivity: int = 1):
+                                  surface_connectivity: int = 1, return_next_stage: bool = False):
         """`cases`: dicts {'data': preprocessed image [C, d, h, w], 'properties': the case's properties dict
         (shape_before_cropping, bbox_used_for_cropping, shape_after_cropping_and_before_resampling, spacing), 'seg':
         ground truth in the original space (uint8 / int16, [D, H, W] or [1, D, H, W])}.  Per case: sliding-window
@@ -615,7 +682,13 @@ class nnUNetTrainerMI355(object):
         save_probabilities the list of probability volumes).  surface_metrics adds 'HD', 'HD95' and 'ASSD' (evaluation.
         compute_surface_metrics, spacing = properties['spacing'], footprint surface_connectivity) to every per-case,
         per-label dict, and with them to the means.  Deep supervision is off for the duration and restored.
-        Files, the next-stage export and the worker pool are out of scope."""
+        A cascaded trainer (:1175-1177) needs case['seg_prev'], the previous stage's segmentation in this stage's
+        preprocessed space [d, h, w]: it is one-hot encoded on the device and stacked behind the image.  For a
+        configuration with next_stage_names (:1207-1238) a case may carry 'next_stage_shapes' = {stage name: preprocessed
+        shape of the case in that stage}; with return_next_stage the logits are resampled to each
+        (export.resample_logits_for_next_stage) and the result gains a last element, one {stage name: uint8 [shape]} dict
+        per case -- a stage without a shape is skipped, as the reference skips a case whose preprocessed file is missing.
+        Files and the worker pool are out of scope."""
         from . import evaluation, export, postprocessing
         from .inference import SlidingWindowPredictor
         if not hasattr(self, 'inference_allowed_mirroring_axes'):
@@ -628,7 +701,9 @@ class nnUNetTrainerMI355(object):
         self.network.eval()
         labels = self.label_manager.foreground_regions if self.label_manager.has_regions \
             else self.label_manager.foreground_labels
-        results, segs, probs = [], [], []
+        results, segs, probs, next_stage = [], [], [], []
+        self._check_cascade()
+        next_stages = getattr(self.configuration_manager, 'next_stage_names', None)
         try:
             predictor = SlidingWindowPredictor(self.network, self.configuration_manager.patch_size,
                                                self.label_manager.num_segmentation_heads, tile_step_size=tile_step_size,
@@ -636,7 +711,15 @@ class nnUNetTrainerMI355(object):
                                                allowed_mirroring_axes=self.inference_allowed_mirroring_axes,
                                                device=self.device)
             for case in cases:
-                prediction = predictor.predict_sliding_window_return_logits(case['data'])
+                data = case['data']
+                if self.is_cascaded:
+                    data = self._stack_previous_stage(data, case.get('seg_prev'))
+                prediction = predictor.predict_sliding_window_return_logits(data)
+                if return_next_stage:
+                    shapes = case.get('next_stage_shapes') or {}
+                    next_stage.append({n: export.resample_logits_for_next_stage(
+                        prediction, shapes[n], self.configuration_manager, self.label_manager)
+                        for n in (next_stages or []) if n in shapes})
                 out = export.convert_predicted_logits_to_segmentation_with_correct_shape(
                     prediction, self.plans_manager, self.configuration_manager, self.label_manager, case['properties'],
                     return_probabilities=save_probabilities)
@@ -668,9 +751,35 @@ class nnUNetTrainerMI355(object):
         if not results:
             raise ValueError("perform_actual_validation: no cases")
         metrics = evaluation.aggregate_metrics(results, labels)
+        ret = (metrics,)
         if return_segmentations:
-            return (metrics, segs, probs) if save_probabilities else (metrics, segs)
-        return metrics
+            ret = (metrics, segs, probs) if save_probabilities else (metrics, segs)
+        if return_next_stage:
+            ret = ret + (next_stage,)
+        return ret if len(ret) > 1 else metrics
+
+    def _stack_previous_stage(self, data, seg_prev):
+        """:1175-1177: data [C, d, h, w] with convert_labelmap_to_one_hot(seg_prev, foreground_labels) behind it, built on
+        the device by the feed's one-hot kernel."""
+        from .dataloading import cascade_onehot
+        if seg_prev is None:
+            raise ValueError("perform_actual_validation: a cascaded trainer (previous_stage_name "
+                             f"'{self.configuration_manager.previous_stage_name}') needs case['seg_prev'], the previous "
+                             "stage's segmentation in this stage's preprocessed space")
+        data = torch.as_tensor(np.ascontiguousarray(data) if isinstance(data, np.ndarray) else data,
+                               dtype=torch.float32).to(self.device)
+        prev = torch.as_tensor(np.ascontiguousarray(seg_prev) if isinstance(seg_prev, np.ndarray) else seg_prev)
+        prev = prev.to(self.device).to(torch.float32).contiguous()
+        if prev.dim() == 4 and prev.shape[0] == 1:
+            prev = prev[0]
+        if tuple(prev.shape) != tuple(data.shape[1:]):
+            raise ValueError(f"perform_actual_validation: seg_prev {tuple(prev.shape)} and the image {tuple(data.shape[1:])} "
+                             "differ in shape")
+        labels = self.label_manager.foreground_labels
+        out = torch.empty((data.shape[0] + len(labels), *data.shape[1:]), dtype=torch.float32, device=self.device)
+        out[:data.shape[0]] = data
+        cascade_onehot(prev, out[data.shape[0]:], labels)
+        return out
 
     @staticmethod
     def dice_from_counts(tp, fp, fn):
@@ -774,7 +883,8 @@ def _variant_checks(tr, what, regions_ok=False):
     """What every loss variant refuses before it builds anything: cascades (as the base trainer), more heads than the loss
     kernels hold, and -- where the reference's class asserts it -- regions."""
     if getattr(tr.configuration_manager, 'previous_stage_name', None) is not None:
-        raise NotImplementedError("cascade configurations (previous_stage_name) and their transforms are not built")
+        raise NotImplementedError(f"{what}: cascade configurations (previous_stage_name) are built for the base trainer's "
+                                  "loss only, not for the loss variants")
     if not regions_ok:
         assert not tr.label_manager.has_regions, 'regions not supported by this trainer'
     if tr.label_manager.num_segmentation_heads > ops.REGION_KMAX:
@@ -916,6 +1026,11 @@ class ContrastiveTrainerMI355(nnUNetTrainerMI355):
         b2 = get_network_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
                                     enable_deep_supervision)
         return MVDDualBranchNet(b1, b2)
+
+    def _check_cascade(self):
+        if self.is_cascaded:
+            raise NotImplementedError(f"{type(self).__name__}: cascade configurations (previous_stage_name) are built for "
+                                      "the single-network trainers, not for the dual-branch ones")
 
     def set_deep_supervision_enabled(self, enabled: bool):
         self.network.do_ds = enabled  # MVDTrainer.py:802-806

@@ -922,8 +922,91 @@ def topk_loss_fixture():
          source=np.array("reference training/loss/robust_ce_loss.py TopKLoss, fp64"), **arrs)
 
 
+# ------------------------------------------------------------------ cascade transforms
+def cascade_fixture():
+    """tests/golden/cascade_transforms.npz: the reference's own ApplyRandomBinaryOperatorTransform and
+    RemoveRandomConnectedComponentFromOneHotEncodingTransform class bodies (cascade_transforms.py), executed over the
+    stand-ins of tools/cascade_standins.py for their three absent imports, with the trainer's parameters
+    (nnUNetTrainer.py:741-755) on seeded inputs: 1 modality + K = 3 one-hot channels of 12 x 14 x 16, batch 2.  Per seed one
+    transform instance is called twice (the shuffled channel list persists).  np.random.shuffle / np.random.choice are
+    wrapped to record the channel order after each shuffle and the ordinal of the removed component; the wrappers call
+    the originals, so the stream is untouched."""
+    import cascade_standins
+    cascade_standins.install()
+    CT = ref_module("training/data_augmentation/custom_transforms/cascade_transforms.py", "ref_cascade_transforms")
+    K, shape, B = 3, (12, 14, 16), 2
+    idx = list(range(-K, 0))
+
+    def inputs(seed):
+        rng = np.random.RandomState(1000 + seed)
+        coarse = rng.randint(0, K + 1, size=(B, 4, 5, 6))
+        lab = coarse.repeat(3, 1).repeat(3, 2).repeat(3, 3)[:, :shape[0], :shape[1], :shape[2]]
+        data = np.zeros((B, 1 + K, *shape), dtype=np.float32)
+        data[:, 0] = rng.randint(0, 7, size=(B, *shape))
+        for k in range(K):
+            data[:, 1 + k] = lab == k + 1
+        return data
+
+    orig_shuffle, orig_choice = np.random.shuffle, np.random.choice
+    arrs, bin_seeds, rem_seeds = {}, [], []
+    for seed in range(60):
+        # binary operators: two calls of one instance
+        orders = []
+
+        def shuffle(x):
+            orig_shuffle(x)
+            orders.append(list(x))
+        np.random.shuffle = shuffle
+        try:
+            np.random.seed(seed)
+            tr = CT.ApplyRandomBinaryOperatorTransform(channel_idx=list(idx), p_per_sample=0.4, key="data",
+                                                       strel_size=(1, 8), p_per_label=1)
+            d0 = inputs(seed)
+            d1 = tr(data=d0.copy())["data"]
+            d2 = tr(data=d1.copy())["data"]
+        finally:
+            np.random.shuffle = orig_shuffle
+        if len(bin_seeds) < 6 and (len(orders) >= 2 or (seed % 7 == 0 and len(orders) == 0)):
+            bin_seeds.append(seed)
+            arrs[f"bin{seed}_in"], arrs[f"bin{seed}_out1"], arrs[f"bin{seed}_out2"] = d0, d1, d2
+            arrs[f"bin{seed}_orders"] = np.asarray(orders, dtype=np.int64).reshape(-1, K)
+        # removal: one call; the first choice of each event is the component
+        picks = []
+
+        def choice(a, *args, **kw):
+            r = orig_choice(a, *args, **kw)
+            picks.append((list(a).index(r), len(a)))
+            return r
+        np.random.choice = choice
+        try:
+            np.random.seed(seed)
+            tr = CT.RemoveRandomConnectedComponentFromOneHotEncodingTransform(
+                channel_idx=list(idx), key="data", p_per_sample=0.2, fill_with_other_class_p=0,
+                dont_do_if_covers_more_than_x_percent=0.15)
+            r0 = inputs(seed)
+            r1 = tr(data=r0.copy())["data"]
+        finally:
+            np.random.choice = orig_choice
+        if len(rem_seeds) < 5 and picks:
+            changed = [(b, c) for b in range(B) for c in range(1, 1 + K) if not np.array_equal(r0[b, c], r1[b, c])]
+            assert len(changed) == len(picks), "every removal changes exactly its own channel"
+            rem_seeds.append(seed)
+            arrs[f"rem{seed}_in"], arrs[f"rem{seed}_out"] = r0, r1
+            arrs[f"rem{seed}_events"] = np.asarray([(b, c - 1 - K, o, n) for (b, c), (o, n) in zip(changed, picks)],
+                                                  dtype=np.int64)
+    assert len(bin_seeds) == 6 and len(rem_seeds) == 5
+    assert any(len(arrs[f"bin{s}_orders"]) == 0 for s in bin_seeds), "one seed where the operator never fires"
+    save("cascade_transforms.npz", source=np.array(
+        "reference training/data_augmentation/custom_transforms/cascade_transforms.py (class bodies executed over "
+        "tools/cascade_standins.py), p_per_sample 0.4 / strel (1, 8) and 0.2 / fill 0 / 0.15"),
+        bin_seeds=np.asarray(bin_seeds), rem_seeds=np.asarray(rem_seeds), channel_idx=np.asarray(idx), **arrs)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == "cascade":  # only tests/golden/cascade_transforms.npz
+        cascade_fixture()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "topk_loss":  # only tests/golden/topk_loss.npz
         topk_loss_fixture()
         sys.exit(0)
@@ -955,3 +1038,4 @@ if __name__ == "__main__":
     loader2d_fixture()
     cross_attention_fixture()
     topk_loss_fixture()
+    cascade_fixture()
