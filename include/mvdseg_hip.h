@@ -900,6 +900,29 @@ int mvd_export_resize_sigmoid_f32(const float *logits, float *out, const int *id
                                   int K, int d, int h, int w, int D, int H, int W, const int *full, const int *lo,
                                   const int *perm, void *stream);
 
+/* Model ensembling (nnunetv2/ensembling/ensemble.py:17-46, predict_from_raw_data.py:483-497).
+ * mvd_export_ensemble_argmax_u8: the fused ensemble export for plain labels.  M members (1..8), K heads (2..8).  logits,
+ *   idx0, idx1, weight: HOST arrays of M DEVICE pointers -- member m's logits [K, dims[3m], dims[3m+1], dims[3m+2]] (dims:
+ *   HOST int[3 M]) and its own tables as mvd_export_resize_argmax_u8 takes them; (D, H, W), full, lo, perm: the one output
+ *   geometry all members share.  Per output voxel, members ascending, in fp32: the K logits interpolated as the single
+ *   export does, softmax as mvd_export_resize_softmax_f32 (max, expf(v - max), sum with k ascending, e / sum), acc_k += p_k;
+ *   mean_k = acc_k / M (a division; none for M == 1); out = the argmax with a strict > (the first index wins an exact
+ *   tie), 0 outside the bbox.  mean != NULL: also the float [K] mean planes of the same volume, channel 0 is 1 outside
+ *   the bbox.  Bit-identical to mvd_export_resize_softmax_f32 per member followed by mvd_ensemble_mean_argmax.
+ * mvd_ensemble_mean_argmax: probs = HOST array of M (1..8) DEVICE pointers to float [K, n] volumes (K 1..8):
+ *   avg = p_0; avg += p_m (m ascending); avg /= M; seg = uint8 argmax (strict >), mean != NULL: float [K, n] avg.
+ *   16-byte loads when n % 4 == 0 and every base is 16-byte aligned, scalar otherwise.
+ * mvd_sw_normalize_add: sum = first ? acc / npred : sum + acc / npred; with last != 0 and M > 1 then sum *= fp32(1 / M),
+ *   which is what torch's device `sum /= M` computes.  sum may be acc. */
+int mvd_export_ensemble_argmax_u8(const float *const *logits, const int *const *idx0, const int *const *idx1,
+                                  const float *const *weight, const int *dims, int M, int K, int D, int H, int W,
+                                  const int *full, const int *lo, const int *perm, unsigned char *out, float *mean,
+                                  void *stream);
+int mvd_ensemble_mean_argmax(const float *const *probs, int M, int K, long n, unsigned char *seg, float *mean,
+                             void *stream);
+int mvd_sw_normalize_add(float *sum, const float *acc, const float *npred, int K, long V, int first, int last, int M,
+                         void *stream);
+
 /* The bottleneck fusion block of FinalNetv2 (csrc/attention.hip): fp32, no atomics (bit-identical run to run).
  * Dropout: `state` is a DEVICE long long[2] = {seed, t}.  Element e of site s is kept iff the 24-bit uniform (w >> 40) 2^-24
  *   >= p, w = word e & 3 of Philox4x64-10 with key (seed, s) and counter ((e >> 2) + 1, t, 0, 0) (numpy.random.Philox(key =

@@ -240,6 +240,9 @@ SIGNATURES = {
                              _P]),
     "mvd_export_resize_regions_u8": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P, _P]),
     "mvd_export_resize_sigmoid_f32": (c_int, [_P] * 5 + [c_int] * 7 + [_I3, _I3, _I3, _P]),
+    "mvd_export_ensemble_argmax_u8": (c_int, [_P] * 5 + [c_int] * 5 + [_I3, _I3, _I3, _P, _P, _P]),
+    "mvd_ensemble_mean_argmax": (c_int, [_P, c_int, c_int, c_long, _P, _P, _P]),
+    "mvd_sw_normalize_add": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_int, c_int, _P]),
     "mvd_dropout_tick": (c_int, [_P, _P]),
     "mvd_dropout_mask": (c_int, [c_uint64, c_uint64, c_int, c_float, c_long, _P, _P]),
     "mvd_layernorm_fwd": (c_int, [_P] * 8 + [c_long, c_int, c_long, c_float, _P]),

@@ -208,6 +208,171 @@ __global__ void __launch_bounds__(256) k_export_resize_sigmoid_f32(const float *
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- ensemble export
+// DESIGN 31.  M members (their own logits extent and tables) onto ONE output geometry: per output voxel and member the K
+// logits are interpolated (export_taps / export_interp), soft-maxed with the operations of k_export_resize_f32 (max,
+// expf(v - max), sum with k ascending, e / sum) and added to K register accumulators, members ascending; mean = acc / M
+// (a division; none for M == 1), argmax with a strict >.  K is a template parameter and every k loop is unrolled, so that
+// v[] and acc[] stay in registers; the member tables are a by-value argument read with a wave-uniform index.
+constexpr int ENS_MMAX = 8;
+constexpr int ENS_KMAX = 8;
+
+struct EnsembleMembers {
+    const float *logits[ENS_MMAX];
+    const int *i0[ENS_MMAX];
+    const int *i1[ENS_MMAX];
+    const float *tw[ENS_MMAX];
+    int d[ENS_MMAX], h[ENS_MMAX], w[ENS_MMAX];
+};
+
+// g: the shared output geometry (its d / h / w are filled per member).  PROB: also the fp32 mean planes [K][total].
+template <int K, bool PROB>
+__global__ void __launch_bounds__(256) k_export_ensemble(EnsembleMembers mem, int M, uint8_t *__restrict__ out,
+                                                         float *__restrict__ mean, ExportGeom g, long total) {
+    const long nquad = (total + 3) >> 2;
+    const float fM = (float)M;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (long)gridDim.x * blockDim.x) {
+        const long lin = q << 2;
+        long r = lin / g.O2;
+        int a2 = (int)(lin - r * g.O2);
+        int a0 = (int)(r / g.O1);
+        int a1 = (int)(r - (long)a0 * g.O1);
+        const int nv = total - lin < 4 ? (int)(total - lin) : 4;
+        unsigned pack = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (j < nv) {
+                float acc[K];
+#pragma unroll
+                for (int k = 0; k < K; k++) acc[k] = k == 0 ? 1.f : 0.f;  // outside the bbox: channel 0 is 1
+                bool in = false;
+                for (int m = 0; m < M; m++) {
+                    ExportGeom gm = g;
+                    gm.d = mem.d[m];
+                    gm.h = mem.h[m];
+                    gm.w = mem.w[m];
+                    Taps t;
+                    in = export_taps(gm, mem.i0[m], mem.i1[m], mem.tw[m], a0, a1, a2, t);  // the same answer for every m
+                    if (!in) break;
+                    const float *__restrict__ p = mem.logits[m];
+                    const size_t dhw = (size_t)gm.d * gm.h * gm.w;
+                    float v[K];
+#pragma unroll
+                    for (int k = 0; k < K; k++) v[k] = export_interp(p + (size_t)k * dhw, t);
+                    float vmax = v[0];
+#pragma unroll
+                    for (int k = 1; k < K; k++) vmax = fmaxf(vmax, v[k]);
+                    float sum = 0.f;
+#pragma unroll
+                    for (int k = 0; k < K; k++) {
+                        v[k] = expf(v[k] - vmax);
+                        sum += v[k];
+                    }
+#pragma unroll
+                    for (int k = 0; k < K; k++) {
+                        const float pk = v[k] / sum;
+                        acc[k] = m == 0 ? pk : acc[k] + pk;  // avg = p_0; avg += p_m
+                    }
+                }
+                unsigned best = 0;
+                if (in) {
+                    if (M > 1) {
+#pragma unroll
+                        for (int k = 0; k < K; k++) acc[k] = acc[k] / fM;
+                    }
+                    float vbest = acc[0];
+#pragma unroll
+                    for (int k = 1; k < K; k++) {
+                        if (acc[k] > vbest) {  // strict: the first index wins an exact tie
+                            vbest = acc[k];
+                            best = (unsigned)k;
+                        }
+                    }
+                }
+                if (PROB) {
+#pragma unroll
+                    for (int k = 0; k < K; k++) mean[(size_t)k * total + lin + j] = acc[k];
+                }
+                pack |= best << (8 * j);
+                if (++a2 == g.O2) {
+                    a2 = 0;
+                    if (++a1 == g.O1) {
+                        a1 = 0;
+                        ++a0;
+                    }
+                }
+            }
+        }
+        if (nv == 4) {
+            *reinterpret_cast<unsigned *>(out + lin) = pack;
+        } else {
+            for (int j = 0; j < nv; j++) out[lin + j] = (uint8_t)(pack >> (8 * j));
+        }
+    }
+}
+
+// The stored-probabilities route (ensemble.py:17-29): avg = p_0; avg += p_m (m ascending); avg /= M; argmax with a strict >.
+// M volumes [K][n] in, uint8 labels and (mean != nullptr) the fp32 mean [K][n] out.  Four voxels per lane: VEC (n % 4 == 0
+// and every base 16-byte aligned) through 16-byte loads and stores, otherwise scalar; the labels leave as one dword per
+// quad where seg is 4-byte aligned (seg4) and the quad is whole.
+struct MeanMembers {
+    const float *p[ENS_MMAX];
+};
+
+template <int K, bool VEC>
+__global__ void __launch_bounds__(256) k_ensemble_mean_argmax(MeanMembers mem, int M, long n, uint8_t *__restrict__ seg,
+                                                              float *__restrict__ mean, int seg4) {
+    const long nquad = (n + 3) >> 2;
+    const float fM = (float)M;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (long)gridDim.x * blockDim.x) {
+        const long lin = q << 2;
+        const int nv = VEC ? 4 : (n - lin < 4 ? (int)(n - lin) : 4);
+        float best[4] = {0.f, 0.f, 0.f, 0.f};
+        unsigned pack = 0;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            float a[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int m = 0; m < M; m++) {
+                const float *__restrict__ p = mem.p[m] + (size_t)k * n + lin;
+                float x[4] = {0.f, 0.f, 0.f, 0.f};
+                if (VEC) {
+                    const float4 f = *reinterpret_cast<const float4 *>(p);
+                    x[0] = f.x; x[1] = f.y; x[2] = f.z; x[3] = f.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+                        if (j < nv) x[j] = p[j];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) a[j] = m == 0 ? x[j] : a[j] + x[j];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                a[j] = a[j] / fM;
+                if (k == 0 || a[j] > best[j]) {  // strict: the first index wins an exact tie
+                    if (k != 0) pack = (pack & ~(0xffu << (8 * j))) | ((unsigned)k << (8 * j));
+                    best[j] = a[j];
+                }
+            }
+            if (mean) {
+                float *__restrict__ o = mean + (size_t)k * n + lin;
+                if (VEC) {
+                    *reinterpret_cast<float4 *>(o) = make_float4(a[0], a[1], a[2], a[3]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+                        if (j < nv) o[j] = a[j];
+                }
+            }
+        }
+        if (nv == 4 && seg4) {
+            *reinterpret_cast<unsigned *>(seg + lin) = pack;
+        } else {
+            for (int j = 0; j < nv; j++) seg[lin + j] = (uint8_t)(pack >> (8 * j));
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- confusion counts
 struct RegionLut {
     uint32_t m[256];  // bit r of m[label]: label belongs to label set r
@@ -401,6 +566,85 @@ int mvd_export_resize_sigmoid_f32(const float *logits, float *out, const int *id
                        idx0, idx1, weight, g, total);
     return check_launch("export_resize_sigmoid_f32");
 }
+
+#define ENS_LAUNCH(KK)                                                                                                  \
+    case KK:                                                                                                            \
+        if (mean)                                                                                                       \
+            hipLaunchKernelGGL((k_export_ensemble<KK, true>), grid, dim3(256), 0, s, mem, M, out, mean, g, total);      \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_export_ensemble<KK, false>), grid, dim3(256), 0, s, mem, M, out, mean, g, total);     \
+        break;
+
+int mvd_export_ensemble_argmax_u8(const float *const *logits, const int *const *idx0, const int *const *idx1,
+                                  const float *const *weight, const int *dims, int M, int K, int D, int H, int W,
+                                  const int *full, const int *lo, const int *perm, unsigned char *out, float *mean,
+                                  void *stream) {
+    MVD_REQUIRE(M >= 1 && M <= ENS_MMAX, "export_ensemble_argmax_u8: %d members: 1..%d", M, ENS_MMAX);
+    MVD_REQUIRE(K >= 2 && K <= ENS_KMAX, "export_ensemble_argmax_u8: %d heads: 2..%d (the per-lane accumulators)", K,
+                ENS_KMAX);
+    MVD_REQUIRE(logits && idx0 && idx1 && weight && dims && out, "export_ensemble_argmax_u8: null pointer");
+    MVD_REQUIRE(((uintptr_t)out & 3) == 0, "export_ensemble_argmax_u8: the output must be 4-byte aligned");
+    EnsembleMembers mem;
+    memset(&mem, 0, sizeof(mem));
+    for (int m = 0; m < M; m++) {  // host arrays
+        MVD_REQUIRE(logits[m] && idx0[m] && idx1[m] && weight[m], "export_ensemble_argmax_u8: null pointer in member %d", m);
+        MVD_REQUIRE(dims[3 * m] > 0 && dims[3 * m + 1] > 0 && dims[3 * m + 2] > 0,
+                    "export_ensemble_argmax_u8: empty logits in member %d", m);
+        mem.logits[m] = logits[m];
+        mem.i0[m] = idx0[m];
+        mem.i1[m] = idx1[m];
+        mem.tw[m] = weight[m];
+        mem.d[m] = dims[3 * m];
+        mem.h[m] = dims[3 * m + 1];
+        mem.w[m] = dims[3 * m + 2];
+    }
+    ExportGeom g;
+    long total = 0;
+    if (int rc = export_geom("export_ensemble_argmax_u8", g, K, mem.d[0], mem.h[0], mem.w[0], D, H, W, full, lo, perm, &total))
+        return rc;
+    hipStream_t s = as_stream(stream);
+    const dim3 grid(export_grid(cdiv(total, 4)));
+    switch (K) {
+        ENS_LAUNCH(2) ENS_LAUNCH(3) ENS_LAUNCH(4) ENS_LAUNCH(5) ENS_LAUNCH(6) ENS_LAUNCH(7) ENS_LAUNCH(8)
+    }
+    return check_launch("export_ensemble_argmax_u8");
+}
+#undef ENS_LAUNCH
+
+#define MEAN_LAUNCH(KK)                                                                                                 \
+    case KK:                                                                                                            \
+        if (vec)                                                                                                        \
+            hipLaunchKernelGGL((k_ensemble_mean_argmax<KK, true>), grid, dim3(256), 0, s, mem, M, n, seg, mean, seg4);  \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_ensemble_mean_argmax<KK, false>), grid, dim3(256), 0, s, mem, M, n, seg, mean, seg4); \
+        break;
+
+int mvd_ensemble_mean_argmax(const float *const *probs, int M, int K, long n, unsigned char *seg, float *mean,
+                             void *stream) {
+    MVD_REQUIRE(M >= 1 && M <= ENS_MMAX, "ensemble_mean_argmax: %d members: 1..%d", M, ENS_MMAX);
+    MVD_REQUIRE(K >= 1 && K <= ENS_KMAX, "ensemble_mean_argmax: %d channels: 1..%d", K, ENS_KMAX);
+    MVD_REQUIRE(probs && seg, "ensemble_mean_argmax: null pointer");
+    MVD_REQUIRE(n > 0 && n < (1L << 40), "ensemble_mean_argmax: bad voxel count");
+    MeanMembers mem;
+    memset(&mem, 0, sizeof(mem));
+    uintptr_t bits = (uintptr_t)mean;
+    for (int m = 0; m < M; m++) {  // host array
+        MVD_REQUIRE(probs[m], "ensemble_mean_argmax: null pointer in member %d", m);
+        MVD_REQUIRE(((uintptr_t)probs[m] & 3) == 0, "ensemble_mean_argmax: member %d is not 4-byte aligned", m);
+        mem.p[m] = probs[m];
+        bits |= (uintptr_t)probs[m];
+    }
+    MVD_REQUIRE(((uintptr_t)mean & 3) == 0, "ensemble_mean_argmax: the mean is not 4-byte aligned");
+    const bool vec = (n & 3) == 0 && (bits & 15) == 0;
+    const int seg4 = ((uintptr_t)seg & 3) == 0 ? 1 : 0;
+    hipStream_t s = as_stream(stream);
+    const dim3 grid(export_grid(cdiv(n, 4)));
+    switch (K) {
+        MEAN_LAUNCH(1) MEAN_LAUNCH(2) MEAN_LAUNCH(3) MEAN_LAUNCH(4) MEAN_LAUNCH(5) MEAN_LAUNCH(6) MEAN_LAUNCH(7) MEAN_LAUNCH(8)
+    }
+    return check_launch("ensemble_mean_argmax");
+}
+#undef MEAN_LAUNCH
 
 int mvd_seg_confusion_counts(const unsigned char *pred, const void *gt, int gt_is_i16, long n, const int32_t *label_sets,
                              const int *set_sizes, int R, int has_ignore, int ignore_label, long long *counts,

@@ -46,6 +46,21 @@ __global__ void k_sw_normalize(float *__restrict__ logits, const float *__restri
         logits[idx] = logits[idx] / npred[idx % V];
 }
 
+// The fold loop's tail (predict_from_raw_data.py:483-497) in one pass: sum = first ? acc / npred : sum + acc / npred, and
+// with scale != 0 (the last of M > 1 folds) sum *= scale.  scale = 1 / M rounded to fp32: torch's device division by a host
+// scalar is this multiplication, so the pass equals mvd_sw_normalize + `sum += acc` + `sum /= M` bit for bit.
+// sum may be acc itself (one fold in place): an element is read and written by the same lane only.
+__global__ void k_sw_normalize_add(float *sum, const float *acc, const float *__restrict__ npred, int K, long V, int first,
+                                   float scale) {
+    const long total = (long)K * V;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const float v = acc[idx] / npred[idx % V];
+        float s = first ? v : sum[idx] + v;
+        if (scale != 0.f) s = s * scale;
+        sum[idx] = s;
+    }
+}
+
 }  // namespace mvd
 
 using namespace mvd;
@@ -79,5 +94,15 @@ int mvd_sw_normalize(float *logits, const float *npred, int K, long V, void *str
     MVD_REQUIRE(logits && npred && K > 0 && V > 0, "sw_normalize: bad arguments");
     hipLaunchKernelGGL(k_sw_normalize, dim3(sw_grid((long)K * V)), dim3(256), 0, as_stream(stream), logits, npred, K, V);
     return check_launch("sw_normalize");
+}
+
+int mvd_sw_normalize_add(float *sum, const float *acc, const float *npred, int K, long V, int first, int last, int M,
+                         void *stream) {
+    MVD_REQUIRE(sum && acc && npred && K > 0 && V > 0, "sw_normalize_add: bad arguments");
+    MVD_REQUIRE(M >= 1, "sw_normalize_add: %d folds", M);
+    const float scale = (last && M > 1) ? 1.0f / (float)M : 0.f;
+    hipLaunchKernelGGL(k_sw_normalize_add, dim3(sw_grid((long)K * V)), dim3(256), 0, as_stream(stream), sum, acc, npred, K, V,
+                       first ? 1 : 0, scale);
+    return check_launch("sw_normalize_add");
 }
 }

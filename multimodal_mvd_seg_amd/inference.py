@@ -79,7 +79,7 @@ class SlidingWindowPredictor:
     def __init__(self, network: torch.nn.Module, patch_size: Sequence[int], num_segmentation_heads: int,
                  tile_step_size: float = 0.5, use_gaussian: bool = True, use_mirroring: bool = True,
                  allowed_mirroring_axes: Tuple[int, ...] = (0, 1, 2), device: torch.device = torch.device('cuda'),
-                 slice_batch: int = 8):
+                 slice_batch: int = 8, list_of_parameters=None):
         if torch.device(device).type != 'cuda':
             raise RuntimeError("SlidingWindowPredictor needs an MI355X (device type 'cuda'); there is no CPU path")
         self.network = network
@@ -94,6 +94,10 @@ class SlidingWindowPredictor:
         self.allowed_mirroring_axes = tuple(allowed_mirroring_axes)
         self.device = torch.device(device)
         self._gaussian = None
+        # one state_dict per fold (nnUNetPredictor.list_of_parameters); None: the network as it stands is the only member
+        self.list_of_parameters = None if list_of_parameters is None else list(list_of_parameters)
+        if self.list_of_parameters is not None and not self.list_of_parameters:
+            raise ValueError("list_of_parameters is empty: give one state_dict per fold, or None")
 
     # predict_from_raw_data.py:528-560: the 3-D branch, and the slice-wise 2-D branch (:530-547: for each slice d, for sx,
     # for sy) whose entries are (d, sx, sy)
@@ -148,7 +152,7 @@ class SlidingWindowPredictor:
             call("mvd_flip_add", P(pm), P(total), K, d, h, w, m, 1, self._s())
         return total, len(masks) + 1
 
-    def _predict_2d(self, img):
+    def _accumulate_2d(self, img):
         """The slice-wise branch: accumulation into the 3-D volume with mvd_sw_accumulate(pd = 1, sx = d).  Tiles are
         grouped by in-plane origin and batched over slices; a voxel of slice d only ever receives tiles of slice d, in the
         (sx, sy) order of the reference's loop, so the grouping does not change the order of its sums."""
@@ -178,13 +182,39 @@ class SlidingWindowPredictor:
                 for b in range(d1 - d0):
                     call("mvd_sw_accumulate", P(total[b]), P(g), 1.0 / npasses, P(logits), P(npred), K, 1, ph, pw, D, H, W,
                          d0 + b, sx, sy, self._s())
-        call("mvd_sw_normalize", P(logits), P(npred), K, D * H * W, self._s())
-        return logits[:, :, below[1]:below[1] + shape[1], below[2]:below[2] + shape[2]]
+        return logits, npred, (slice(None), slice(None), slice(below[1], below[1] + shape[1]),
+                               slice(below[2], below[2] + shape[2]))
 
-    def predict_sliding_window_return_logits(self, input_image: torch.Tensor) -> torch.Tensor:
-        assert isinstance(input_image, torch.Tensor)
-        assert input_image.dim() == 4, 'input_image must be a 4D torch.Tensor (c, x, y, z)'
+    def _accumulate_3d(self, img):
+        """The 3-D branch up to the normalisation: (weighted logit sums [K,D,H,W], weight sums [D,H,W], the crop that undoes
+        the padding)."""
         P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        # pad to at least the patch size, centred (pad_nd_image(..., 'constant', value 0), :665-667)
+        shape = tuple(img.shape[1:])
+        new = [max(s, p) for s, p in zip(shape, self.patch_size)]
+        below = [(n - s) // 2 for n, s in zip(new, shape)]
+        data = torch.zeros((img.shape[0], *new), dtype=torch.float32, device=self.device)
+        data[:, below[0]:below[0] + shape[0], below[1]:below[1] + shape[1], below[2]:below[2] + shape[2]] = img
+        D, H, W = new
+        K = self.num_heads
+        logits = torch.zeros((K, D, H, W), dtype=torch.float32, device=self.device)
+        npred = torch.zeros((D, H, W), dtype=torch.float32, device=self.device)
+        if self.use_gaussian and self._gaussian is None:
+            self._gaussian = torch.from_numpy(compute_gaussian(self.patch_size, 1. / 8, 1000.0)).to(self.device)
+        g = self._gaussian if self.use_gaussian else None
+        pd, ph, pw = self.patch_size
+        for (sx, sy, sz) in self._internal_get_sliding_window_slicers((D, H, W)):
+            workon = data[:, sx:sx + pd, sy:sy + ph, sz:sz + pw][None].contiguous()
+            total, npasses = self._internal_maybe_mirror_and_predict(workon)
+            call("mvd_sw_accumulate", P(total), P(g), 1.0 / npasses, P(logits), P(npred), K, pd, ph, pw, D, H, W,
+                 sx, sy, sz, self._s())
+        return logits, npred, (slice(None), slice(below[0], below[0] + shape[0]), slice(below[1], below[1] + shape[1]),
+                               slice(below[2], below[2] + shape[2]))
+
+    def _accumulate(self, img):
+        return self._accumulate_2d(img) if len(self.patch_size) == 2 else self._accumulate_3d(img)
+
+    def _in_eval_mode(self, fn):
         was_training = self.network.training
         ds = getattr(getattr(self.network, 'decoder', None), 'deep_supervision', None)
         self.network.eval()
@@ -192,32 +222,48 @@ class SlidingWindowPredictor:
             self.network.decoder.deep_supervision = False  # inference returns the full-resolution head only
         try:
             with torch.no_grad():
-                img = input_image.to(self.device, dtype=torch.float32)
-                if len(self.patch_size) == 2:
-                    return self._predict_2d(img)
-                # pad to at least the patch size, centred (pad_nd_image(..., 'constant', value 0), :665-667)
-                shape = tuple(img.shape[1:])
-                new = [max(s, p) for s, p in zip(shape, self.patch_size)]
-                below = [(n - s) // 2 for n, s in zip(new, shape)]
-                data = torch.zeros((img.shape[0], *new), dtype=torch.float32, device=self.device)
-                data[:, below[0]:below[0] + shape[0], below[1]:below[1] + shape[1], below[2]:below[2] + shape[2]] = img
-                D, H, W = new
-                K = self.num_heads
-                logits = torch.zeros((K, D, H, W), dtype=torch.float32, device=self.device)
-                npred = torch.zeros((D, H, W), dtype=torch.float32, device=self.device)
-                if self.use_gaussian and self._gaussian is None:
-                    self._gaussian = torch.from_numpy(compute_gaussian(self.patch_size, 1. / 8, 1000.0)).to(self.device)
-                g = self._gaussian if self.use_gaussian else None
-                pd, ph, pw = self.patch_size
-                for (sx, sy, sz) in self._internal_get_sliding_window_slicers((D, H, W)):
-                    workon = data[:, sx:sx + pd, sy:sy + ph, sz:sz + pw][None].contiguous()
-                    total, npasses = self._internal_maybe_mirror_and_predict(workon)
-                    call("mvd_sw_accumulate", P(total), P(g), 1.0 / npasses, P(logits), P(npred), K, pd, ph, pw, D, H, W,
-                         sx, sy, sz, self._s())
-                call("mvd_sw_normalize", P(logits), P(npred), K, D * H * W, self._s())
-                return logits[:, below[0]:below[0] + shape[0], below[1]:below[1] + shape[1],
-                              below[2]:below[2] + shape[2]]
+                return fn()
         finally:
             if ds is not None:
                 self.network.decoder.deep_supervision = ds
             self.network.train(was_training)
+
+    def predict_sliding_window_return_logits(self, input_image: torch.Tensor) -> torch.Tensor:
+        assert isinstance(input_image, torch.Tensor)
+        assert input_image.dim() == 4, 'input_image must be a 4D torch.Tensor (c, x, y, z)'
+        P = lambda t: ctypes.c_void_p(t.data_ptr())
+
+        def run():
+            logits, npred, crop = self._accumulate(input_image.to(self.device, dtype=torch.float32))
+            call("mvd_sw_normalize", P(logits), P(npred), logits.shape[0], npred.numel(), self._s())
+            return logits[crop]
+        return self._in_eval_mode(run)
+
+    def predict_logits_from_preprocessed_data(self, data: torch.Tensor) -> torch.Tensor:
+        """predict_from_raw_data.py:464-526 (the loop of :483-497): for every entry of `list_of_parameters`, in order, load
+        it into the network (`network.load_state_dict`), predict with the sliding window, sum the logits and divide by the
+        number of folds.  Each fold's normalisation, the sum and the final division are one pass (mvd_sw_normalize_add);
+        the result equals `predict_sliding_window_return_logits` per fold, torch `+=` and `/= M` bit for bit, and with
+        `list_of_parameters` None (the network as it stands) or of length 1 it equals
+        `predict_sliding_window_return_logits` itself.  As in the reference, the LAST fold stays loaded in the network
+        afterwards.  The packed copies of the conv weights follow every load: `load_state_dict` writes the parameters in
+        place, which the pack stamps see (ops.py).  The logits stay on the device."""
+        assert isinstance(data, torch.Tensor)
+        assert data.dim() == 4, 'data must be a 4D torch.Tensor (c, x, y, z)'
+        P = lambda t: ctypes.c_void_p(t.data_ptr())
+        folds = self.list_of_parameters if self.list_of_parameters is not None else [None]
+        M = len(folds)
+
+        def run():
+            img = data.to(self.device, dtype=torch.float32)
+            total = crop = None
+            for i, params in enumerate(folds):
+                if params is not None:
+                    self.network.load_state_dict(params)
+                logits, npred, crop = self._accumulate(img)
+                if total is None:
+                    total = logits          # the first fold is normalised in place
+                call("mvd_sw_normalize_add", P(total), P(logits), P(npred), logits.shape[0], npred.numel(),
+                     1 if i == 0 else 0, 1 if i == M - 1 else 0, M, self._s())
+            return total[crop]
+        return self._in_eval_mode(run)

@@ -1002,8 +1002,46 @@ def cascade_fixture():
         bin_seeds=np.asarray(bin_seeds), rem_seeds=np.asarray(rem_seeds), channel_idx=np.asarray(idx), **arrs)
 
 
+# ------------------------------------------------------------------ ensembling
+def ensemble_fixture():
+    """tests/golden/ensemble.npz: the reference's own average_probabilities body (ensembling/ensemble.py) run on temporary
+    .npz files of M = 3 softmax volumes [3, 6, 7, 9], and LabelManager.convert_logits_to_segmentation (the call merge_files
+    makes) on the result.  A second mean has member 0 stored as float16 (the `avg.dtype != np.float32` branch).  Inputs and
+    outputs only."""
+    import tempfile
+    avg_fn, avg_src = ref_function("ensembling/ensemble.py", "average_probabilities")
+    LM, lm_src = ref_function("utilities/label_handling/label_handling.py", "LabelManager",
+                              softmax_helper_dim0=lambda x: torch.softmax(x, 0),
+                              bounding_box_to_slice=lambda bb: tuple(slice(*i) for i in bb))
+    M, K, shape = 3, 3, (6, 7, 9)
+    rng = np.random.default_rng(31)
+    probs = [torch.softmax(torch.from_numpy((rng.standard_normal((K, *shape)) * 2).astype(np.float32)), 0).numpy()
+             for _ in range(M)]
+    lm = LM({"background": 0, "a": 1, "b": 2}, None)
+    arrs = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for tag, first in (("", probs[0]), ("_f16first", probs[0].astype(np.float16))):
+            files = []
+            for m, p in enumerate([first] + probs[1:]):
+                files.append(os.path.join(tmp, f"m{m}{tag}.npz"))
+                np.savez(files[-1], probabilities=p)
+            mean = avg_fn(files)
+            assert mean.dtype == np.float32
+            seg = lm.convert_logits_to_segmentation(mean)
+            assert np.array_equal(np.asarray(seg), mean.argmax(0)), "the second softmax changed an argmax: pick another seed"
+            arrs["mean" + tag] = mean
+            arrs["segmentation" + tag] = np.asarray(seg).astype(np.uint8)
+    assert len(np.unique(arrs["segmentation"])) == K
+    save("ensemble.npz", source=np.array(f"reference {avg_src} on temporary .npz files and {lm_src} "
+                                         f"convert_logits_to_segmentation"),
+         probabilities=np.stack(probs), first_f16=probs[0].astype(np.float16), **arrs)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == "ensemble":  # only tests/golden/ensemble.npz
+        ensemble_fixture()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "cascade":  # only tests/golden/cascade_transforms.npz
         cascade_fixture()
         sys.exit(0)
@@ -1039,3 +1077,4 @@ if __name__ == "__main__":
     cross_attention_fixture()
     topk_loss_fixture()
     cascade_fixture()
+    ensemble_fixture()
