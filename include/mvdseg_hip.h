@@ -961,6 +961,50 @@ int mvd_attention_bwd(const float *qbuf, const float *kvbuf, const float *dout, 
                       float *delta, float *dqbuf, float *dkvbuf, int B, int N, int H, int dh, const long long *state, float p,
                       int site, void *stream);
 
+/* Level-set persistence, dimensions 0 and 1, of P = B * n_channels planes of a [B,C,H,W] tensor on the Freudenthal
+ * triangulation (nn/levelset.py:64-93: vertices row-major, width = W; edges horizontal, vertical, one diagonal
+ * (ind, ind+W+1) per square; the two triangles of each square), and the persistence topological loss on top of it
+ * (loss/Topo_Loss.py:16-85).  Lower-star filtration of g = f or -f (-0 folded to +0), total order (value, dimension,
+ * index within the dimension); the critical vertex of a cell is its first maximal vertex (complex.cpp:142).
+ *   mvd_ls2d_num_cells: n = V + E (+ T for maxdim 1) cells per problem; V, E, T through the pointers (may be NULL).
+ *   mvd_ls2d_sorted_keys (device): keys_sorted [P][n], ascending per problem, key = ord(value) << 32 | dimension << 30 |
+ *       index; problem p = b * n_channels + j is plane (b, channels[j]).  One key kernel + one in-place merge sort per
+ *       problem (no kernel of either waits on another workgroup).
+ *   mvd_ls2d_pair_host (host, plain C++, <= 16 threads): bars [P][V+T][4] int32 = {bits of the birth value, bits of the
+ *       death value, birth critical vertex, death critical vertex}: rows [0,V) the dimension-0 bars in vertex order (the
+ *       essential bar dies at +inf, -inf for super-level, death vertex -1), rows [V,V+T) the dimension-1 bars in the
+ *       order of their killing triangles; values carry the sign of the input.  edge_row [P][E]: the bar row each edge
+ *       is an endpoint of (< V: death of a dimension-0 bar, >= V: birth of a dimension-1 bar; -1 with maxdim 0 for an edge
+ *       that opens a cycle).
+ *   mvd_ls2d_topk: lengths / index [P][2][k], the k longest bars per dimension, descending (end - start of
+ *       get_start_end, infinite and NaN -> 0, zero padded; index = bar row, -1 for padding and zero-length bars), 1<=k<=64.
+ *   mvd_ls2d_topk_bwd: g_bars [P][V+T][2] = d lengths scattered onto the (birth, death) entries, zero elsewhere.
+ *   mvd_ls2d_topoloss_fwd: out[0] = (1/B) sum_{b,i,dim,j} s * lengths^2, s = -1 for j < label[b][idx[i]][dim] else +1
+ *       (label int32 [B][n_label][2]); fp64, fixed order.   mvd_ls2d_topoloss_bwd: its gradient times g_out[0], written
+ *       into grad [B][C][H][W] (class idx[i] is channel idx[i] + 1), every vertex summed in a fixed order.
+ *   mvd_ls2d_diagram_bwd: persistence_backward (cohom.cpp:148-196) as a gather per vertex; g0 [P][V][2], g1 [P][T][2].
+ *   mvd_ls2d_count_bars: counts [P][2] = bars of non-zero length per dimension (the essential bar iff born != 0).
+ *   mvd_ls2d_onehot: planes [B][C][V] = (label [B][V] == c). */
+long mvd_ls2d_num_cells(int H, int W, int maxdim, long *nv, long *ne, long *nt);
+size_t mvd_ls2d_workspace_bytes(int P, int H, int W, int maxdim);
+int mvd_ls2d_sorted_keys(const float *x, int B, int C, int H, int W, const int *channels, int n_channels, int sublevel,
+                         int maxdim, uint64_t *keys_sorted, void *ws, size_t ws_bytes, void *stream);
+int mvd_ls2d_pair_host(const uint64_t *keys_host, int P, int H, int W, int sublevel, int maxdim, int32_t *bars,
+                       int32_t *edge_row, int n_threads);
+int mvd_ls2d_topk(const int32_t *bars, int P, int H, int W, int maxdim, int sublevel, int k, float *lengths, int32_t *index,
+                  void *stream);
+int mvd_ls2d_topk_bwd(const float *g_lengths, const int32_t *index, int P, int H, int W, int maxdim, int sublevel, int k,
+                      float *g_bars, void *stream);
+int mvd_ls2d_topoloss_fwd(const float *lengths, const int32_t *label, int B, const int *idx, int n_idx, int n_label, int k,
+                          float *out, void *stream);
+int mvd_ls2d_topoloss_bwd(const float *lengths, const int32_t *index, const int32_t *bars, const int32_t *label,
+                          const float *g_out, int B, int C, int H, int W, const int *idx, int n_idx, int n_label, int k,
+                          int sublevel, float *grad, void *stream);
+int mvd_ls2d_diagram_bwd(const float *g0, const float *g1, const int32_t *bars, const int32_t *edge_row, int B, int C, int H,
+                         int W, const int *channels, int n_channels, int maxdim, float *grad, void *stream);
+int mvd_ls2d_count_bars(const int32_t *bars, int P, int H, int W, int sublevel, int32_t *counts, void *stream);
+int mvd_ls2d_onehot(const float *label, float *planes, int B, int C, long V, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

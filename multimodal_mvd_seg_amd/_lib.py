@@ -251,6 +251,17 @@ SIGNATURES = {
     "mvd_linear_bwd": (c_int, [_P] * 6 + [c_long, c_int, c_int, _P]),
     "mvd_attention_fwd": (c_int, [_P] * 6 + [c_int] * 4 + [_P, c_float, c_int, _P]),
     "mvd_attention_bwd": (c_int, [_P] * 8 + [c_int] * 4 + [_P, c_float, c_int, _P]),
+    "mvd_ls2d_num_cells": (c_long, [c_int, c_int, c_int, _P, _P, _P]),
+    "mvd_ls2d_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mvd_ls2d_sorted_keys": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "mvd_ls2d_pair_host": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int]),
+    "mvd_ls2d_topk": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "mvd_ls2d_topk_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "mvd_ls2d_topoloss_fwd": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, _P, _P]),
+    "mvd_ls2d_topoloss_bwd": (c_int, [_P] * 5 + [c_int] * 4 + [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "mvd_ls2d_diagram_bwd": (c_int, [_P] * 4 + [c_int] * 4 + [_P, c_int, c_int, _P, _P]),
+    "mvd_ls2d_count_bars": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "mvd_ls2d_onehot": (c_int, [_P, _P, c_int, c_int, c_long, _P]),
 }
 
 _lib = None

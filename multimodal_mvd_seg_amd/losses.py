@@ -243,3 +243,81 @@ def soft_cldice(pred, target, iter_=3, smooth=1.0):
     with torch.no_grad():
         skel_true = soft_skel(target, iter_)
     return ops.ClDiceFn.apply(skel_pred, target, skel_true, pred, smooth)
+
+
+# ------------------------------------------------------------------------------------ persistence topological loss (2-D)
+class LevelSetLayer2D(nn.Module):
+    """LevelSetLayer2D of the vendored TopologyLayer (nn/levelset.py:137-163) on the Freudenthal triangulation
+    (init_freudenthal_2d, :64-93).  size = (width, height) as in the reference; forward(f [H,W]) returns
+    (dgms, issublevel) with dgms = (dgm0 [V,2], dgm1 [T,2]) DEVICE tensors (dgm0 alone for maxdim 0), differentiable
+    (ops.LevelSetDiagram2DFn).  `alg` is accepted and ignored: 'hom', 'hom2' and 'cohom' give the same diagram."""
+
+    def __init__(self, size, maxdim=1, sublevel=True, complex="freudenthal", alg='hom'):
+        super().__init__()
+        if complex != "freudenthal":
+            raise NotImplementedError(f"LevelSetLayer2D(complex='{complex}'): only the 'freudenthal' triangulation is built; "
+                                      f"'grid' is no triangulated disc and 'delaunay' has no fixed diagonals, so the "
+                                      f"dual-graph pairing of dimension 1 does not apply to them")
+        if maxdim not in (0, 1):
+            raise ValueError("LevelSetLayer2D: maxdim must be 0 or 1")
+        self.size, self.maxdim, self.sublevel, self.alg = tuple(int(s) for s in size), int(maxdim), bool(sublevel), alg
+
+    def forward(self, f):
+        width, height = self.size
+        if f.numel() != width * height:
+            raise RuntimeError(f"LevelSetLayer2D(size={self.size}): the input has {f.numel()} values")
+        dgms = ops.LevelSetDiagram2DFn.apply(f.reshape(1, 1, height, width), [0], self.sublevel, self.maxdim)
+        return tuple(d[0] for d in dgms), self.sublevel
+
+
+class TopKBarcodeLengths(nn.Module):
+    """nn/features.py:128-150: the k longest bars of dimension `dim` of (dgms, issublevel), end - start with the
+    sub-/super-level swap of get_start_end, infinite and NaN lengths 0, descending, truncated or zero padded to k.
+    dgms[dim] may be one diagram [n,2] (-> [k]) or a batch [P,n,2] (-> [P,k]); selected on the device."""
+
+    def __init__(self, dim, k):
+        super().__init__()
+        if not 1 <= int(k) <= ops.LS2D_MAX_K:
+            raise ValueError(f"TopKBarcodeLengths: k must be in 1..{ops.LS2D_MAX_K} (got {k})")
+        self.dim, self.k = int(dim), int(k)
+
+    def forward(self, dgminfo):
+        dgms, issublevel = dgminfo
+        dgm = dgms[self.dim]
+        if dgm.dim() == 2:
+            return ops.TopKBarLengths2DFn.apply(dgm[None], self.dim, self.k, issublevel)[0]
+        return ops.TopKBarLengths2DFn.apply(dgm, self.dim, self.k, issublevel)
+
+
+class TopoLoss(nn.Module):
+    """TopoLoss of the reference (training/loss/Topo_Loss.py:16-85): per sample and class of interest the super-level
+    diagram of y_pred[b, idx+1], its max_k longest bars per dimension squared, the first beta0 / beta1 of them (topo_label
+    [B,C,2], read on the device) signed -1 and the rest +1, the mean over the batch, the sum over idx;
+    topo_weight * l_topo / len(idx) + sqdiff_weight * MSE(y_raw, y_pred).  All samples and classes are ONE batch of
+    persistence problems (one host round trip per forward, ops.TopoLossFn).  y_raw = None leaves the MSE term out (the
+    reference defines it for fine-tuning against a frozen first network)."""
+
+    def __init__(self, img_size, topo_weight=1, sqdiff_weight=10, max_k=20):
+        super().__init__()
+        if not 1 <= int(max_k) <= ops.LS2D_MAX_K:
+            raise ValueError(f"TopoLoss: max_k must be in 1..{ops.LS2D_MAX_K} (got {max_k})")
+        self.img_size = tuple(int(s) for s in img_size)
+        self.sqdiff_weight, self.topo_weight, self.max_k = sqdiff_weight, topo_weight, int(max_k)
+
+    def forward(self, y_pred, y_raw, topo_label, idx=[1]):
+        width, height = self.img_size
+        if tuple(y_pred.shape[2:]) != (height, width):
+            raise RuntimeError(f"TopoLoss(img_size={self.img_size}) takes [B,C,{height},{width}] probabilities, got "
+                               f"{tuple(y_pred.shape)}")
+        l = self.topo_weight * ops.TopoLossFn.apply(y_pred, topo_label, list(idx), self.max_k) / len(idx)
+        if y_raw is not None:
+            l = l + self.sqdiff_weight * ops.MseFn.apply(y_raw, y_pred)
+        return l
+
+
+def betti_topo_label(target, num_classes):
+    """The topo_label TopoLoss expects, from a label map [B,1,H,W] / [B,H,W]: int32 [B, num_classes, 2] = (beta0, beta1)
+    of every class's binary mask on the Freudenthal triangulation -- components joined along the grid axes and the
+    (+1,+1) diagonal, and the holes they enclose -- counted as the bars of non-zero length of the mask's super-level
+    diagram, the essential component included (an empty mask has none)."""
+    return ops.ls2d_betti_numbers(target, num_classes)

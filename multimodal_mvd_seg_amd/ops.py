@@ -2118,6 +2118,231 @@ class H0DiagramFn(Function):
         return grad.view(ctx.shape).to(ctx.device), None, None
 
 
+# ------------------------------------------------------------------------- level-set persistence of 2-D images, H0 + H1
+LS2D_MAX_K = 64
+LS2D_HOST_THREADS = 16   # upper bound of the host pairing pool (never sized by the machine's core count)
+
+
+def _ls2d_ints(vals):
+    vals = [int(v) for v in vals]
+    return (ctypes.c_int * len(vals))(*vals), len(vals)
+
+
+def ls2d_num_cells(H, W, maxdim=1):
+    """(n, V, E, T) of the Freudenthal triangulation of an [H, W] image (T = 0 for maxdim 0)."""
+    nv, ne, nt = ctypes.c_long(), ctypes.c_long(), ctypes.c_long()
+    n = query("mvd_ls2d_num_cells", int(H), int(W), int(maxdim), ctypes.byref(nv), ctypes.byref(ne), ctypes.byref(nt))
+    if n < 0:
+        raise RuntimeError("levelset2d: H, W >= 1 and maxdim in (0, 1)")
+    return n, nv.value, ne.value, nt.value
+
+
+class Ls2dTimes:
+    """Optional split of one levelset2d_persistence call (tools/bench_topoloss.py): set `Ls2dTimes.on = True`.  The timed
+    call synchronises after the sort, so that the D2H copy is timed alone."""
+    on = False
+    last = None
+
+
+def levelset2d_persistence(x, channels, sublevel, maxdim=1):
+    """Dimension-0 and -1 level-set persistence of the planes (b, c), c in `channels`, of a [B,C,H,W] fp32 device tensor
+    on the Freudenthal triangulation (LevelSetLayer2D of the reference, once per plane): P = B * len(channels) problems
+    in one batch, problem p = b * len(channels) + j.  Device: keys + one merge sort per problem; one D2H copy; host: the
+    elder-rule pairing of every problem (mvd_ls2d_pair_host); one H2D copy.
+    Returns (bars, edge_row): DEVICE int32 tensors [P, V+T, 4] = (birth value bits, death value bits, birth critical vertex,
+    death critical vertex) -- rows [0,V) dimension 0 in vertex order, rows [V,V+T) dimension 1 -- and [P, E]."""
+    _require_cuda(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise RuntimeError("levelset2d_persistence takes a [B,C,H,W] float32 tensor")
+    if maxdim not in (0, 1):
+        raise RuntimeError("levelset2d_persistence: maxdim must be 0 or 1 (a 2-D image has no higher homology)")
+    x = x.detach().contiguous()
+    B, C, H, W = x.shape
+    ch, nch = _ls2d_ints(channels)
+    n, V, E, T = ls2d_num_cells(H, W, maxdim)
+    P = B * nch
+    nb = query("mvd_ls2d_workspace_bytes", P, H, W, int(maxdim))
+    if nb == 0:
+        raise RuntimeError(f"levelset2d_persistence: {P} problems of {W}x{H} do not fit one sort (2^31 cells)")
+    ws = _Workspace.get(nb, x.device)
+    keys = torch.empty((P, n), dtype=torch.int64, device=x.device)
+    timed = Ls2dTimes.on
+    if timed:
+        import time
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+    call("mvd_ls2d_sorted_keys", _p(x), B, C, H, W, ch, nch, int(bool(sublevel)), int(maxdim), _p(keys), _p(ws), ws.numel(),
+         _stream())
+    if timed:
+        ev[1].record()
+        ev[1].synchronize()
+        tc = time.perf_counter()
+    keys_h = keys.cpu()               # the one D2H copy; synchronises the stream
+    if timed:
+        t0 = time.perf_counter()
+    out_h = torch.empty((P * (V + T) * 4 + P * E,), dtype=torch.int32)
+    bars_h, er_h = out_h[:P * (V + T) * 4], out_h[P * (V + T) * 4:]
+    call("mvd_ls2d_pair_host", _p(keys_h), P, H, W, int(bool(sublevel)), int(maxdim), _p(bars_h), _p(er_h),
+         LS2D_HOST_THREADS)
+    if timed:
+        t1 = time.perf_counter()
+        ev[2].record()
+    out = out_h.to(x.device)          # the one H2D copy
+    if timed:
+        ev[3].record()
+        ev[3].synchronize()
+        t2 = time.perf_counter()
+        Ls2dTimes.last = {"keys_sort_ms": ev[0].elapsed_time(ev[1]), "d2h_ms": (t0 - tc) * 1e3,
+                          "host_sweep_ms": (t1 - t0) * 1e3, "h2d_ms": (t2 - t1) * 1e3}
+    return out[:P * (V + T) * 4].view(P, V + T, 4), out[P * (V + T) * 4:].view(P, E)
+
+
+def _ls2d_dgms(bars, V):
+    vals = bars[:, :, :2].view(torch.float32)
+    return vals[:, :V].contiguous(), vals[:, V:].contiguous()
+
+
+class LevelSetDiagram2DFn(Function):
+    """Differentiable level-set diagrams of the planes (b, channels[j]) of x [B,C,H,W]: (dgm0 [P,V,2], dgm1 [P,T,2]) device
+    tensors of (birth, death) rows in the sign of x (the flip of LevelSetLayer.forward for super-level undone), dgm0 in vertex
+    order with the essential bar dying at +-inf, dgm1 in the order of the killing triangles.  maxdim 0 returns dgm0 alone.
+    backward is the reference's persistence_backward (cohom.cpp:148-196): every finite entry's gradient is added onto its
+    critical vertex -- as a gather per vertex in a fixed order, so the result is bit-identical from run to run."""
+
+    @staticmethod
+    def forward(ctx, x, channels, sublevel, maxdim=1):
+        bars, edge_row = levelset2d_persistence(x, channels, sublevel, maxdim)
+        B, C, H, W = x.shape
+        ctx.save_for_backward(bars, edge_row)
+        ctx.cfg = (B, C, H, W, [int(c) for c in channels], int(maxdim))
+        dgm0, dgm1 = _ls2d_dgms(bars, H * W)
+        return (dgm0, dgm1) if maxdim >= 1 else (dgm0,)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gs):
+        bars, edge_row = ctx.saved_tensors
+        B, C, H, W, channels, maxdim = ctx.cfg
+        ch, nch = _ls2d_ints(channels)
+        g0 = gs[0].contiguous().float()
+        g1 = gs[1].contiguous().float() if maxdim >= 1 and bars.shape[1] > H * W else None
+        grad = torch.empty((B, C, H, W), dtype=torch.float32, device=bars.device)
+        call("mvd_ls2d_diagram_bwd", _p(g0), _p(g1), _p(bars), _p(edge_row), B, C, H, W, ch, nch,
+             maxdim if g1 is not None else 0, _p(grad), _stream())
+        return grad, None, None, None
+
+
+def _ls2d_check_k(k):
+    if not 1 <= int(k) <= LS2D_MAX_K:
+        raise ValueError(f"top-k bar lengths: k must be in 1..{LS2D_MAX_K} (got {k}); the selection kernel holds one "
+                         f"problem's bars of both endpoints in one workgroup")
+    return int(k)
+
+
+def ls2d_topk(bars, H, W, maxdim, sublevel, k):
+    """(lengths [P,2,k] fp32, index [P,2,k] int32) of the k longest bars per problem and dimension, descending."""
+    k = _ls2d_check_k(k)
+    P = bars.shape[0]
+    lengths = torch.empty((P, 2, k), dtype=torch.float32, device=bars.device)
+    index = torch.empty((P, 2, k), dtype=torch.int32, device=bars.device)
+    call("mvd_ls2d_topk", _p(bars), P, int(H), int(W), int(maxdim), int(bool(sublevel)), k, _p(lengths), _p(index), _stream())
+    return lengths, index
+
+
+class TopKBarLengths2DFn(Function):
+    """TopKBarcodeLengths (nn/features.py:128-150) of batched diagrams dgm0 [P,V,2] / dgm1 [P,T,2]: [P,k] lengths of
+    dimension `dim`.  `size` = (W, H) of the image the diagrams come from."""
+
+    @staticmethod
+    def forward(ctx, dgm, dim, k, sublevel):
+        _require_cuda(dgm)
+        if dgm.dim() != 3 or dgm.shape[2] != 2 or dgm.dtype != torch.float32:
+            raise RuntimeError("top-k bar lengths take a [P,n,2] float32 diagram")
+        k = _ls2d_check_k(k)
+        P, n = dgm.shape[:2]
+        # the kernel's bar layout with this diagram alone as a 1 x n "image" of dimension 0 (vertex columns unused)
+        bars = torch.zeros((P, n, 4), dtype=torch.int32, device=dgm.device)
+        bars[:, :, :2] = dgm.detach().contiguous().view(torch.int32)
+        lengths, index = ls2d_topk(bars, 1, n, 0, sublevel, k)
+        ctx.save_for_backward(index)
+        ctx.cfg = (P, n, k, bool(sublevel))
+        return lengths[:, 0].contiguous()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (index,) = ctx.saved_tensors
+        P, n, k, sublevel = ctx.cfg
+        gl = torch.zeros((P, 2, k), dtype=torch.float32, device=g.device)
+        gl[:, 0] = g
+        gb = torch.empty((P, n, 2), dtype=torch.float32, device=g.device)
+        call("mvd_ls2d_topk_bwd", _p(gl), _p(index), P, 1, n, 0, int(sublevel), k, _p(gb), _stream())
+        return gb, None, None, None
+
+
+class TopoLossFn(Function):
+    """l_topo of TopoLoss.forward (loss/Topo_Loss.py:39-41,49-85) summed over `idx`: for every sample b and class i in idx the
+    super-level diagram of y_pred[b, i+1], its max_k longest bars per dimension squared, the first label[b,i,dim] of them
+    signed -1, the mean over the batch.  ONE batch of B * len(idx) problems -> one host round trip in the forward, none in
+    the backward, which writes grad y_pred directly."""
+
+    @staticmethod
+    def forward(ctx, y_pred, topo_label, idx, max_k):
+        _require_cuda(y_pred, topo_label)
+        k = _ls2d_check_k(max_k)
+        if y_pred.dim() != 4 or y_pred.dtype != torch.float32:
+            raise RuntimeError("TopoLoss takes y_pred [B,C,H,W] float32 (the reference's layer is 2-D)")
+        B, C, H, W = y_pred.shape
+        idx = [int(i) for i in idx]
+        if topo_label.dim() != 3 or topo_label.shape[0] != B or topo_label.shape[2] != 2 or topo_label.is_floating_point():
+            raise RuntimeError(f"TopoLoss: topo_label must be an integer [B={B}, C, 2] tensor")
+        n_label = topo_label.shape[1]
+        if not idx or min(idx) < 0 or max(idx) >= n_label or max(idx) + 1 >= C or len(set(idx)) != len(idx):
+            raise RuntimeError(f"TopoLoss: idx {idx} must be distinct classes with a row in topo_label ({n_label}) and a channel "
+                               f"idx+1 in y_pred ({C})")
+        label = topo_label.to(torch.int32).contiguous()
+        bars, _ = levelset2d_persistence(y_pred, [i + 1 for i in idx], False, 1)
+        lengths, index = ls2d_topk(bars, H, W, 1, False, k)
+        ci, ni = _ls2d_ints(idx)
+        out = torch.empty((1,), dtype=torch.float32, device=y_pred.device)
+        call("mvd_ls2d_topoloss_fwd", _p(lengths), _p(label), B, ci, ni, n_label, k, _p(out), _stream())
+        ctx.save_for_backward(lengths, index, bars, label)
+        ctx.cfg = (B, C, H, W, idx, n_label, k)
+        return out.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        lengths, index, bars, label = ctx.saved_tensors
+        B, C, H, W, idx, n_label, k = ctx.cfg
+        ci, ni = _ls2d_ints(idx)
+        g = g.contiguous().float()
+        grad = torch.empty((B, C, H, W), dtype=torch.float32, device=g.device)
+        call("mvd_ls2d_topoloss_bwd", _p(lengths), _p(index), _p(bars), _p(label), _p(g), B, C, H, W, ci, ni, n_label, k, 0,
+             _p(grad), _stream())
+        return grad, None, None, None
+
+
+def ls2d_betti_numbers(target, num_classes):
+    """int32 [B, num_classes, 2]: (beta0, beta1) of every class's binary mask of a [B,1,H,W] / [B,H,W] label map = the bars
+    of non-zero length of the mask's super-level diagram (the essential dimension-0 bar closed at the floor 0)."""
+    _require_cuda(target)
+    t = target
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3:
+        raise RuntimeError("betti_topo_label takes a [B,1,H,W] or [B,H,W] label map")
+    B, H, W = t.shape
+    t = t.to(torch.float32).contiguous()
+    C = int(num_classes)
+    planes = torch.empty((B, C, H, W), dtype=torch.float32, device=t.device)
+    call("mvd_ls2d_onehot", _p(t), _p(planes), B, C, H * W, _stream())
+    bars, _ = levelset2d_persistence(planes, list(range(C)), False, 1)
+    counts = torch.empty((B * C, 2), dtype=torch.int32, device=t.device)
+    call("mvd_ls2d_count_bars", _p(bars), B * C, H, W, 0, _p(counts), _stream())
+    return counts.view(B, C, 2)
+
+
 def threshold_mask(f, thr, ge=False):
     _require_cuda(f)
     x = f.contiguous()

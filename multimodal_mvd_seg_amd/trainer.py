@@ -998,6 +998,87 @@ class nnUNetTrainerDiceTopK10LossMI355(nnUNetTrainerMI355):
         return _wrap_every_level(self, loss)
 
 
+# ------------------------------------------------------------------------------------------------ persistence topological loss
+class nnUNetTrainerTopoLossMI355(nnUNetTrainerMI355):
+    """The base trainer's loss plus the reference's persistence topological loss (training/loss/Topo_Loss.py:16-85) on the
+    full-resolution output of a 2d plan with plain labels:
+
+        l = L(out, t) + topo_lambda * l_topo(softmax(out[0]), betti_topo_label(t[0]), topo_classes)
+
+    topo_lambda = 1 is the fork's lambda3 (MVDTrainer.py:134); topo_classes defaults to every foreground class; the Betti
+    numbers of the label map are counted per step on the device (losses.betti_topo_label).  The loss, the layers and the
+    diagrams are pinned to the reference's own code; THIS COMPOSITION IS NOT: the fork's step is broken at exactly this line
+    (MVDTrainer.py:920 uses `self.topo_loss`, which is defined nowhere), so where and with which weight the term enters a
+    step is this project's choice.  The y_raw (squared-difference) term of TopoLoss is left out of the step: the reference
+    defines it for fine-tuning against a frozen first network; losses.TopoLoss itself keeps accepting it.
+    The step runs eagerly: the pairing of the diagrams is a host sweep between two copies, which a captured graph cannot
+    hold.  Refused with a message: 3-D plans, regions, an ignore label, cascades, bf16, and the graphed step."""
+
+    def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=torch.device('cuda'),
+                 specified_cfg=''):
+        super().__init__(plans, configuration, fold, dataset_json, unpack_dataset, device, specified_cfg)
+        what = type(self).__name__
+        if len(self.configuration_manager.patch_size) != 2:
+            raise NotImplementedError(f"{what} on 3-D plans: the reference's persistence layer (LevelSetLayer2D) is the "
+                                      "Freudenthal triangulation of a 2-D image; 3-D cubical persistence is not built")
+        if self.label_manager.has_regions:
+            raise NotImplementedError(f"{what} with regions: the topological loss reads softmax probabilities of plain labels")
+        if self.label_manager.has_ignore_label:
+            raise NotImplementedError(f"{what} with an ignore label: the Betti numbers of a partly unlabelled map are undefined")
+        if self.is_cascaded:
+            raise NotImplementedError(f"{what}: cascade configurations (previous_stage_name) are 3-D; nnU-Net plans no 2-D "
+                                      "cascade")
+        self.use_hip_graph = False
+        self.topo_lambda = 1
+        self.topo_classes = None     # None: every foreground class
+        self.topo_max_k = 20
+        self.topo_loss = None
+        self.last_topo = None        # the (detached, device) topological term of the last forward
+
+    def _check_precision(self):
+        if self.precision != 'fp32':
+            raise NotImplementedError(f"{type(self).__name__} in {self.precision}: the bar lengths are differences of "
+                                      "probabilities and the pairing compares them exactly; only fp32 is built")
+
+    def initialize(self):
+        self._check_precision()
+        super().initialize()
+
+    def _build_loss(self):
+        self._check_precision()
+        h, w = self.configuration_manager.patch_size
+        self.topo_loss = losses.TopoLoss((int(w), int(h)), topo_weight=1, sqdiff_weight=0, max_k=self.topo_max_k)
+        return super()._build_loss()
+
+    def _graph_allowed(self):
+        if self.use_hip_graph:
+            raise RuntimeError(f"{type(self).__name__}: use_hip_graph = True, but the step cannot be captured: the persistence "
+                               "pairing runs on the host between a D2H and an H2D copy.  Leave use_hip_graph = False")
+        return False
+
+    def _topo_term(self, output, target):
+        top = output[0] if isinstance(output, (list, tuple)) else output
+        t = target[0] if isinstance(target, (list, tuple)) else target
+        C = top.shape[1]
+        classes = list(range(1, C)) if self.topo_classes is None else [int(c) for c in self.topo_classes]
+        if not classes or min(classes) < 1 or max(classes) >= C:
+            raise ValueError(f"topo_classes {classes}: foreground classes 1..{C - 1}")
+        y_pred = torch.cat([ops.SoftmaxSelectFn.apply(top, c) for c in range(C)], 1)
+        with torch.no_grad():
+            # row i of the label belongs to class i + 1, as TopoLoss pairs `idx` with channel idx + 1
+            label = losses.betti_topo_label(t, C)[:, 1:]
+        return self.topo_loss(y_pred, None, label, idx=[c - 1 for c in classes])
+
+    def _forward_loss(self, data, target):
+        output = self.network(data)
+        l = self.loss(output, target)
+        if self.topo_lambda:
+            lt = self._topo_term(output, target)
+            self.last_topo = lt.detach()
+            l = l + self.topo_lambda * lt
+        return l, output
+
+
 # ------------------------------------------------------------------------------------------------ MVD dual branch
 class ContrastiveTrainerMI355(nnUNetTrainerMI355):
     """Dual-branch mutual-distillation step (MVDTrainer.py:879-925):
