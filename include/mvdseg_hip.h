@@ -1005,6 +1005,50 @@ int mvd_ls2d_diagram_bwd(const float *g0, const float *g1, const int32_t *bars, 
 int mvd_ls2d_count_bars(const int32_t *bars, int P, int H, int W, int sublevel, int32_t *counts, void *stream);
 int mvd_ls2d_onehot(const float *label, float *planes, int B, int C, long V, void *stream);
 
+/* 3-D cubical persistence, dimensions 0 and 2, of N fields f [N,D,H,W] (sublevel filtration, voxels as closed
+ * top-dimensional cells: gudhi's top_dimensional_cells, CubicalComplex(dim=3) of MVDTrainer.py:94-97), and the
+ * q-Wasserstein loss (L-inf ground metric, the diagonal allowed) against the diagram of a binary mask, m copies of the
+ * point (0, 1) (MVDTrainer.py:907-925, training/loss/TopoLoss.py).  Dimension 0 = elder-rule H0 of the 26-neighbourhood
+ * graph with edge value max; dimension 2 = by Alexander duality the elder-rule H0 of the voxels in descending order on
+ * the 6-neighbourhood with edge value min and one outside vertex of value +inf joined to every border voxel.  Dimension 1
+ * needs a boundary-matrix reduction and is refused.  Ties: vertices by (value, linear index), edges by (value,
+ * enumeration index), -0 folded to +0, as mvd_h0_*.  Essential bars are dropped.
+ *   mvd_cub3d_num_keys: slots per sample (V * 13 or V * 4); *n_valid (may be NULL) of them are edges and sort first.
+ *   mvd_cub3d_sorted_keys (device): keys_sorted [N][slots] ascending per sample, key = ord(value) << 32 | (v * n_off + k).
+ *   mvd_cub3d_pair_host (host, plain C++, <= 16 threads): from f_host [N][V] and the first n_keys = n_valid sorted keys of
+ *       every sample, bars [N][V][2] int32 = (birth voxel, death voxel) of the bars with death > birth in sweep order,
+ *       counts [N] of them.  Dimension 0: birth = the dying component's minimum, death = the arg-max vertex of the
+ *       merging edge; dimension 2: birth = the arg-min vertex of the merging edge, death = the dying component's maximum.
+ *   mvd_cub3d_target_count (device): m [N] int32 -- dimension 2: 6-connected foreground components touching no face of
+ *       the volume; dimension 0: 26-connected background components - 1, floored at 0.
+ *   mvd_cub3d_match_fwd: per bar c0 = (d-b)/2, c1 = max(|b|, |1-d|), gain = c0^q + 2^-q - c1^q in fp64; selected = the
+ *       <= m bars of largest strictly positive gain (ties to the lower bar index); wq [N] = W^q in fp64, fixed order;
+ *       out[0] = mean_n wq[n]^(1/q).  bars [n_total][2] of all samples, sample n = rows [offsets[n], offsets[n+1]).
+ *   mvd_cub3d_scatter_plan: the gradient entries (2 per bar) sorted by the voxel they land on (selected == NULL: all).
+ *   mvd_cub3d_match_bwd: grad [N][V] zeroed, then one launch; one thread sums a voxel's run in a fixed order.
+ *   mvd_cub3d_diagram_bwd: the same scatter of a diagram gradient g_diag [n_total][2]. */
+long mvd_cub3d_num_keys(int D, int H, int W, int dim, long *n_valid);
+size_t mvd_cub3d_workspace_bytes(int D, int H, int W, int dim);
+int mvd_cub3d_sorted_keys(const float *f, int N, int D, int H, int W, int dim, uint64_t *keys_sorted, void *ws,
+                          size_t ws_bytes, void *stream);
+int mvd_cub3d_pair_host(const float *f_host, const uint64_t *keys_host, long n_keys, int N, int D, int H, int W, int dim,
+                        int32_t *bars, int32_t *counts, int n_threads);
+size_t mvd_cub3d_target_workspace_bytes(int D, int H, int W);
+int mvd_cub3d_target_count(const float *target, int N, int D, int H, int W, int dim, int32_t *m, void *ws, size_t ws_bytes,
+                           void *stream);
+size_t mvd_cub3d_match_workspace_bytes(long n_total);
+int mvd_cub3d_match_fwd(const float *field, const int32_t *bars, const int32_t *offsets_host, const int32_t *offsets_dev,
+                        const int32_t *m, int N, long V, double q, uint8_t *selected, double *wq, float *out, void *ws,
+                        size_t ws_bytes, void *stream);
+int mvd_cub3d_scatter_plan(const float *field, const int32_t *bars, const int32_t *offsets_dev, const uint8_t *selected, int N,
+                           long V, long n_total, uint32_t *key_sorted, uint32_t *order, void *ws, size_t ws_bytes,
+                           void *stream);
+int mvd_cub3d_match_bwd(const float *field, const int32_t *bars, const int32_t *offsets_dev, const uint8_t *selected,
+                        const double *wq, const float *g_out, const uint32_t *key_sorted, const uint32_t *order, int N, long V,
+                        long n_total, double q, float *grad, void *stream);
+int mvd_cub3d_diagram_bwd(const float *g_diag, const uint32_t *key_sorted, const uint32_t *order, int N, long V, long n_total,
+                          float *grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

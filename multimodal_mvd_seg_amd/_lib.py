@@ -262,6 +262,17 @@ SIGNATURES = {
     "mvd_ls2d_diagram_bwd": (c_int, [_P] * 4 + [c_int] * 4 + [_P, c_int, c_int, _P, _P]),
     "mvd_ls2d_count_bars": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "mvd_ls2d_onehot": (c_int, [_P, _P, c_int, c_int, c_long, _P]),
+    "mvd_cub3d_num_keys": (c_long, [c_int, c_int, c_int, c_int, _P]),
+    "mvd_cub3d_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mvd_cub3d_sorted_keys": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "mvd_cub3d_pair_host": (c_int, [_P, _P, c_long, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int]),
+    "mvd_cub3d_target_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mvd_cub3d_target_count": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "mvd_cub3d_match_workspace_bytes": (c_size_t, [c_long]),
+    "mvd_cub3d_match_fwd": (c_int, [_P] * 5 + [c_int, c_long, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "mvd_cub3d_scatter_plan": (c_int, [_P] * 4 + [c_int, c_long, c_long, _P, _P, _P, c_size_t, _P]),
+    "mvd_cub3d_match_bwd": (c_int, [_P] * 8 + [c_int, c_long, c_long, c_double, _P, _P]),
+    "mvd_cub3d_diagram_bwd": (c_int, [_P] * 3 + [c_int, c_long, c_long, _P, _P]),
 }
 
 _lib = None

@@ -321,3 +321,39 @@ def betti_topo_label(target, num_classes):
     (+1,+1) diagonal, and the holes they enclose -- counted as the bars of non-zero length of the mask's super-level
     diagram, the essential component included (an empty mask has none)."""
     return ops.ls2d_betti_numbers(target, num_classes)
+
+
+# ------------------------------------------------------------------------ 3-D cubical persistence loss (dual-branch trainer)
+class CubicalComplex3D(nn.Module):
+    """CubicalComplex(dim=3, superlevel=False) of MVDTrainer.py:94-97 restricted to one homology dimension: forward(field
+    [N,D,H,W] fp32) returns per sample the differentiable diagram [n,2] of (birth, death) rows of dimension `dim`, gathered
+    from the field (ops.CubicalDiagram3DFn).  Voxels are closed top-dimensional cells; bars of zero length and essential
+    bars are dropped.  dim 0 and dim 2 (the trainer's topo_feat_d) reduce to union-find; dim 1 is not built."""
+
+    def __init__(self, dim=2):
+        super().__init__()
+        self.dim = ops.cub3d_check_dim(dim)
+
+    def forward(self, field):
+        dgm, offsets = ops.CubicalDiagram3DFn.apply(field, self.dim)
+        return list(torch.split(dgm, [int(c) for c in (offsets[1:] - offsets[:-1])]))
+
+
+class CubicalWassersteinLoss(nn.Module):
+    """The topological term of MVDTrainer.py:907-925 / training/loss/TopoLoss.py as one fused path: the q-Wasserstein
+    distance (L-inf ground metric, the diagonal allowed) between the dimension-`dim` cubical diagram of field [N,D,H,W] and
+    that of the binary target mask [N,D,H,W], averaged over the batch.  `last_m` holds the target's point counts (device)."""
+
+    def __init__(self, dim=2, q=2):
+        super().__init__()
+        self.dim = ops.cub3d_check_dim(dim)
+        if not float(q) >= 1.0:
+            raise ValueError(f"CubicalWassersteinLoss: q must be >= 1 (got {q})")
+        self.q = float(q)
+        self.last_m = None
+
+    def forward(self, field, target_mask):
+        if bool(((target_mask != 0) & (target_mask != 1)).any()):
+            raise ValueError("CubicalWassersteinLoss: the target must be a binary mask (its diagram is m copies of (0, 1))")
+        loss, self.last_m = ops.CubicalWassersteinFn.apply(field, target_mask, self.dim, self.q)
+        return loss

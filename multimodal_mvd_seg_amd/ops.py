@@ -2343,6 +2343,202 @@ def ls2d_betti_numbers(target, num_classes):
     return counts.view(B, C, 2)
 
 
+# ------------------------------------------------------------------------- 3-D cubical persistence, dimensions 0 and 2
+CUB3D_HOST_THREADS = 16   # upper bound of the host pairing pool (never sized by the machine's core count)
+
+
+class Cub3dTimes:
+    """Optional split of one cubical loss step (tools/bench_cubical_topo.py): set `Cub3dTimes.on = True`.  The timed calls
+    synchronise between the parts, so that each is timed alone."""
+    on = False
+    last = None
+
+
+def cub3d_check_dim(dim):
+    if int(dim) == 1:
+        raise NotImplementedError("3-D cubical persistence of dimension 1 needs a boundary-matrix reduction; dimensions 0 and 2 "
+                                  "reduce to union-find and are the ones built")
+    if int(dim) not in (0, 2):
+        raise ValueError(f"3-D cubical persistence: dimension must be 0 or 2 (got {dim})")
+    return int(dim)
+
+
+def _cub3d_field(field):
+    _require_cuda(field)
+    if field.dim() != 4 or field.dtype != torch.float32:
+        raise RuntimeError("3-D cubical persistence takes a [N,D,H,W] float32 field")
+    x = field.detach().contiguous()
+    if x.numel() == 0:
+        raise RuntimeError("3-D cubical persistence: empty field")
+    if bool(torch.isnan(x).any()):
+        raise ValueError("3-D cubical persistence: the field contains NaN (a filtration needs a total order)")
+    return x
+
+
+def _cub3d_bars(x, dim):
+    """(bars [n_total,2] int32 device, offsets int32 numpy [N+1], offsets on the device) of a checked field x [N,D,H,W]:
+    device keys + one radix sort per sample, one D2H copy, the host sweep (mvd_cub3d_pair_host), one H2D copy."""
+    N, D, H, W = x.shape
+    V = D * H * W
+    nv = ctypes.c_long()
+    slots = query("mvd_cub3d_num_keys", D, H, W, dim, ctypes.byref(nv))
+    nb = query("mvd_cub3d_workspace_bytes", D, H, W, dim)
+    if slots < 0 or nb == 0:
+        raise RuntimeError(f"3-D cubical persistence: a {D}x{H}x{W} grid does not fit one sort (2^31 edge slots)")
+    nv = nv.value
+    ws = _Workspace.get(nb, x.device)
+    keys = torch.empty((N, slots), dtype=torch.int64, device=x.device)
+    timed = Cub3dTimes.on
+    if timed:
+        import time
+        torch.cuda.synchronize()
+        t = [time.perf_counter()]
+    call("mvd_cub3d_sorted_keys", _p(x), N, D, H, W, dim, _p(keys), _p(ws), ws.numel(), _stream())
+    if timed:
+        torch.cuda.synchronize()
+        t.append(time.perf_counter())
+    keys_h = keys[:, :nv].cpu()       # synchronises the stream
+    f_h = x.cpu()
+    if timed:
+        t.append(time.perf_counter())
+    bars_h = torch.empty((N, V, 2), dtype=torch.int32)
+    counts = torch.empty((N,), dtype=torch.int32)
+    call("mvd_cub3d_pair_host", _p(f_h), _p(keys_h), nv, N, D, H, W, dim, _p(bars_h), _p(counts), CUB3D_HOST_THREADS)
+    if timed:
+        t.append(time.perf_counter())
+    cnt = counts.numpy().astype(np.int64)
+    offsets = np.zeros(N + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum(cnt)
+    packed = torch.cat([bars_h[n, :int(cnt[n])] for n in range(N)]) if N > 1 else bars_h[0, :int(cnt[0])]
+    bars = packed.contiguous().to(x.device)
+    offsets_dev = torch.from_numpy(offsets).to(x.device)
+    if timed:
+        torch.cuda.synchronize()
+        t.append(time.perf_counter())
+        Cub3dTimes.last = {"keys_sort_ms": (t[1] - t[0]) * 1e3, "d2h_ms": (t[2] - t[1]) * 1e3,
+                           "host_sweep_ms": (t[3] - t[2]) * 1e3, "h2d_ms": (t[4] - t[3]) * 1e3, "bars": int(offsets[-1])}
+    return bars, offsets, offsets_dev
+
+
+def cubical3d_persistence(field, dim):
+    """Bars of non-zero length of the dimension-`dim` (0 or 2) sublevel cubical persistence of every sample of a
+    [N,D,H,W] fp32 device field, voxels as top-dimensional cells: a list of N device int32 tensors [n,2] of unpadded linear
+    voxel indices (birth voxel, death voxel) -- the bar is (f[birth voxel], f[death voxel]).  Essential bars are dropped."""
+    dim = cub3d_check_dim(dim)
+    bars, offsets, _ = _cub3d_bars(_cub3d_field(field), dim)
+    return [bars[int(offsets[n]):int(offsets[n + 1])] for n in range(field.shape[0])]
+
+
+def _cub3d_plan(x, bars, offsets_dev, selected, n_total):
+    N, V = x.shape[0], x[0].numel()
+    ws = _Workspace.get(query("mvd_cub3d_match_workspace_bytes", n_total), x.device)
+    key = torch.empty((2 * n_total,), dtype=torch.int32, device=x.device)
+    order = torch.empty((2 * n_total,), dtype=torch.int32, device=x.device)
+    call("mvd_cub3d_scatter_plan", _p(x), _p(bars), _p(offsets_dev), _p(selected), N, V, n_total, _p(key), _p(order), _p(ws),
+         ws.numel(), _stream())
+    return key, order
+
+
+class CubicalDiagram3DFn(Function):
+    """Differentiable diagram of dimension `dim` of field [N,D,H,W]: (dgm [n_total,2] fp32 of (birth, death) rows gathered
+    from the field, offsets [N+1]): sample n owns rows [offsets[n], offsets[n+1]).  backward adds every entry's gradient onto
+    its voxel -- one thread per voxel run in a fixed order, bit-identical from run to run."""
+
+    @staticmethod
+    def forward(ctx, field, dim):
+        dim = cub3d_check_dim(dim)
+        x = _cub3d_field(field)
+        bars, offsets, offsets_dev = _cub3d_bars(x, dim)
+        N, V = x.shape[0], x[0].numel()
+        base = torch.repeat_interleave(torch.arange(N, device=x.device, dtype=torch.int64) * V,
+                                       torch.from_numpy(np.diff(offsets).astype(np.int64)).to(x.device))
+        dgm = x.reshape(-1)[bars.to(torch.int64) + base[:, None]]
+        ctx.save_for_backward(x, bars, offsets_dev)
+        ctx.shape = tuple(field.shape)
+        off_t = torch.from_numpy(offsets.astype(np.int64))
+        ctx.mark_non_differentiable(off_t)
+        return dgm, off_t
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _):
+        x, bars, offsets_dev = ctx.saved_tensors
+        N, V, n_total = x.shape[0], x[0].numel(), bars.shape[0]
+        grad = torch.empty(ctx.shape, dtype=torch.float32, device=x.device)
+        key = order = None
+        if n_total:
+            key, order = _cub3d_plan(x, bars, offsets_dev, None, n_total)
+        call("mvd_cub3d_diagram_bwd", _p(g.contiguous().float()), _p(key), _p(order), N, V, n_total, _p(grad), _stream())
+        return grad, None
+
+
+def cubical3d_target_count(target, dim):
+    """m [N] int32 on the device: the number of points (0, 1) of the dimension-`dim` diagram of a binary [N,D,H,W] mask."""
+    dim = cub3d_check_dim(dim)
+    _require_cuda(target)
+    if target.dim() != 4:
+        raise RuntimeError("cubical3d_target_count takes a [N,D,H,W] mask")
+    t = target.detach().to(torch.float32).contiguous()
+    N, D, H, W = t.shape
+    ws = _Workspace.get(query("mvd_cub3d_target_workspace_bytes", D, H, W), t.device)
+    m = torch.empty((N,), dtype=torch.int32, device=t.device)
+    call("mvd_cub3d_target_count", _p(t), N, D, H, W, dim, _p(m), _p(ws), ws.numel(), _stream())
+    return m
+
+
+class CubicalWassersteinFn(Function):
+    """mean over the batch of the q-Wasserstein distance (L-inf ground metric, the diagonal allowed) between the
+    dimension-`dim` cubical diagram of field [N,D,H,W] and the diagram of the binary target mask [N,D,H,W], m copies of (0, 1).
+    Against m identical points the optimal matching is the selection of the <= m bars of largest positive gain
+    c0^q + 2^-q - c1^q, so no assignment problem is solved.  One host round trip (the pairing sweep) in the forward, none in
+    the backward, which is one memset and one launch."""
+
+    @staticmethod
+    def forward(ctx, field, target, dim, q):
+        dim = cub3d_check_dim(dim)
+        q = float(q)
+        if not q >= 1.0:
+            raise ValueError(f"Wasserstein exponent q must be >= 1 (got {q})")
+        x = _cub3d_field(field)
+        if tuple(target.shape) != tuple(x.shape):
+            raise RuntimeError(f"cubical Wasserstein loss: field {tuple(x.shape)} and target {tuple(target.shape)} differ")
+        m = cubical3d_target_count(target, dim)
+        bars, offsets, offsets_dev = _cub3d_bars(x, dim)
+        timed = Cub3dTimes.on
+        if timed:
+            import time
+            t0 = time.perf_counter()
+        N, V, n_total = x.shape[0], x[0].numel(), int(offsets[-1])
+        ws = _Workspace.get(query("mvd_cub3d_match_workspace_bytes", n_total), x.device)
+        selected = torch.empty((max(n_total, 1),), dtype=torch.uint8, device=x.device)
+        wq = torch.empty((N,), dtype=torch.float64, device=x.device)
+        out = torch.empty((1,), dtype=torch.float32, device=x.device)
+        call("mvd_cub3d_match_fwd", _p(x), _p(bars), ctypes.c_void_p(offsets.ctypes.data), _p(offsets_dev), _p(m), N, V, q,
+             _p(selected), _p(wq), _p(out), _p(ws), ws.numel(), _stream())
+        key = order = None
+        if n_total and ctx.needs_input_grad[0]:
+            key, order = _cub3d_plan(x, bars, offsets_dev, selected, n_total)
+        if timed:
+            torch.cuda.synchronize()
+            Cub3dTimes.last["match_loss_ms"] = (time.perf_counter() - t0) * 1e3
+        ctx.save_for_backward(x, bars, offsets_dev, selected, wq, key, order)
+        ctx.cfg = (q, tuple(field.shape))
+        ctx.mark_non_differentiable(m)
+        return out.reshape(()), m
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _):
+        x, bars, offsets_dev, selected, wq, key, order = ctx.saved_tensors
+        q, shape = ctx.cfg
+        N, V, n_total = x.shape[0], x[0].numel(), bars.shape[0]
+        grad = torch.empty(shape, dtype=torch.float32, device=x.device)
+        g = g.reshape(1).contiguous().float()
+        call("mvd_cub3d_match_bwd", _p(x), _p(bars), _p(offsets_dev), _p(selected), _p(wq), _p(g), _p(key), _p(order), N, V,
+             n_total, q, _p(grad), _stream())
+        return grad, None, None, None
+
+
 def threshold_mask(f, thr, ge=False):
     _require_cuda(f)
     x = f.contiguous()

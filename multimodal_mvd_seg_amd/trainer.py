@@ -1082,7 +1082,10 @@ class nnUNetTrainerTopoLossMI355(nnUNetTrainerMI355):
 # ------------------------------------------------------------------------------------------------ MVD dual branch
 class ContrastiveTrainerMI355(nnUNetTrainerMI355):
     """Dual-branch mutual-distillation step (MVDTrainer.py:879-925):
-    l = L(out1,t) + L(out2,t) + lambda3 * L_topo(out1[0][:,v], onehot(t)[:,v]) + lambda1 * L_KL."""
+    l = L(out1,t) + L(out2,t) + lambda3 * L_topo(out1[0][:,v], onehot(t)[:,v]) + lambda1 * L_KL.
+    L_topo is soft-clDice on the softmax channel (topo_term = 'cldice', the default) or the reference's own term
+    (topo_term = 'cubical'): losses.CubicalWassersteinLoss(topo_feat_d, topo_q) on the raw logit channel; that mode has a
+    host sweep in the forward and runs eagerly only."""
 
     def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=torch.device('cuda'),
                  specified_cfg=''):
@@ -1098,6 +1101,10 @@ class ContrastiveTrainerMI355(nnUNetTrainerMI355):
         self.use_topo, self.skel_iter, self.feat_kl, self.kl_T = True, 3, True, 1
         self.topo_cc = True          # with use_topo: the integer connected-component count beside the soft-clDice term
         self.last_topology = None
+        # 'cldice': the soft-clDice stand-in; 'cubical': the reference's own term, the Wasserstein distance between the 3-D
+        # cubical diagrams of dimension topo_feat_d of the vessel logits and of the vessel mask (MVDTrainer.py:94-97, 907-925)
+        self.topo_term, self.topo_feat_d, self.topo_q = 'cldice', 2, 2
+        self.last_cubical = None     # the (detached, device) cubical term of the last forward
 
     @staticmethod
     def build_network_architecture(plans_manager, dataset_json, configuration_manager, num_input_channels,
@@ -1127,13 +1134,34 @@ class ContrastiveTrainerMI355(nnUNetTrainerMI355):
         if self.feat_kl:
             mutual = mutual + losses.l2_loss(f1, f2, channel_wise=True, T=self.kl_T)
         l = l + self.lambda1 * mutual
-        if self.use_topo:
+        if self.use_topo and self.topo_term == 'cubical':
+            tmask = ops.label_mask(tgt0, v).reshape(top1[:, v].shape)
+            # the raw logit channel, as MVDTrainer.py:907 passes it; fp32 also under bf16 networks
+            lt = losses.CubicalWassersteinLoss(self.topo_feat_d, self.topo_q)(top1[:, v].float(), tmask)
+            self.last_cubical = lt.detach()
+            l = l + self.lambda3 * lt
+            if self.topo_cc:
+                with torch.no_grad():
+                    prob = ops.SoftmaxSelectFn.apply(top1, v)
+                    self.last_topology = self._component_counts(prob, tmask.reshape(prob.shape))
+        elif self.use_topo:
+            if self.topo_term != 'cldice':
+                raise ValueError(f"topo_term must be 'cldice' or 'cubical' (got {self.topo_term!r})")
             prob = ops.SoftmaxSelectFn.apply(top1, v)
             tmask = ops.label_mask(tgt0, v).reshape(prob.shape)
             l = l + self.lambda3 * losses.soft_cldice(prob, tmask, self.skel_iter)
             if self.topo_cc:
                 self.last_topology = self._component_counts(prob.detach(), tmask)
         return l, o1
+
+    def _graph_allowed(self):
+        if self.use_topo and self.topo_term == 'cubical':
+            if self.use_hip_graph:
+                raise RuntimeError(f"{type(self).__name__}: topo_term = 'cubical' with use_hip_graph = True, but the step cannot "
+                                   "be captured: the persistence pairing runs on the host between a D2H and an H2D copy.  Set "
+                                   "use_hip_graph = False")
+            return False
+        return super()._graph_allowed()
 
     def _component_counts(self, prob, tmask):
         """The integer topology step of configs[3] ("cfg 3 + soft-clDice + CC count"; the reference's
