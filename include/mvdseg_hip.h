@@ -723,6 +723,40 @@ int mvd_feed_lowres_gather2d_f32(const float *x, float *dpad, int D, int H, int 
 int mvd_feed_mask_remove_label(float *data, float *seg, int C, int Cs, long V, int chmask, int replace,
                                int replace_from, int replace_to, void *stream);
 
+/* The DA5 recipe of the feed (variants/data_augmentation/nnUNetTrainerDA5.py: MedianFilter, Sharpening, the two
+ * LocalTransforms, BlankRectangle, Rot90 / TransposeAxes / Mirror, the wider GaussianBlur, additive Brightness and the
+ * unclipped Contrast) on the batch patch [C][D][H][W], C <= 16.  Per-channel parameters are HOST arrays copied
+ * into the kernel arguments; statistics ({mean, std, min, max} per channel, mvd_feed_channel_stats_f32) stay on the
+ * device.  No float atomics: results are bit-identical from run to run.  Inputs are finite (NaN is unsupported).
+ * mvd_feed_median_filter_f32: out[c] = scipy.ndimage.median_filter(x[c], size=sizes[c]) (mode 'reflect'), sizes 2..7:
+ *   the element of rank s^3 / 2 of the window i - s/2 .. i + (s-1) - s/2 per axis, exactly; sizes[c] == 0 copies the
+ *   channel.  out != x.
+ * mvd_feed_sharpen_f32: in place, clip(scipy.signal.convolve(x[c], strength[c] L + delta, 'same'), min, max) with L the
+ *   3x3x3 filter 6 at the centre, -1 at the six face neighbours, zero border, min / max of the channel from stats;
+ *   strength[c] == 0 skips the channel.  ws: C * V floats.
+ * mvd_feed_local_gauss_f32: in place on the channels of chmask with g = prod_d exp(-(i_d - loc[c][d])^2 /
+ *   (2 scale[c][d]^2)) / max g over the grid: mode 0 x += amount[c] g; mode 1 x01 = (x - mn) / max(mx - mn, 1e-8),
+ *   x = x01 ^ (1 + (amount[c] - 1) g) (mx - mn) + mn with mn, mx from stats (mode 0 takes stats == NULL).
+ * mvd_feed_blank_rectangle_f32: the box lb .. lb + size of channel c becomes its own mean (fp64 sum in a fixed order,
+ *   rounded once).  ws: 64 doubles on the device.
+ * mvd_feed_signed_permute_f32: out = flip(transpose(in, perm), flip_mask) over the spatial axes of every channel (any
+ *   C <= 4096); permuted axes must have equal extents.  out != in.
+ * mvd_feed_gaussian_blur_wide_f32: mvd_feed_gaussian_blur_f32 for sigma <= 1.5 (radius <= 6), the same arithmetic.
+ * mvd_feed_da5_apply_f32: in place, op 0 x += p[c]; op 1 (x - mean) p[c] + mean (ContrastAugmentation with
+ *   preserve_range=False; stats). */
+int mvd_feed_median_filter_f32(const float *x, float *out, int C, int D, int H, int W, const int *sizes, void *stream);
+int mvd_feed_sharpen_f32(float *x, float *ws, int C, int D, int H, int W, const double *strength, const double *stats,
+                         void *stream);
+int mvd_feed_local_gauss_f32(float *x, int C, int D, int H, int W, int chmask, int mode, const double *loc,
+                             const double *scale, const float *amount, const double *stats, void *stream);
+int mvd_feed_blank_rectangle_f32(float *x, int C, int D, int H, int W, int c, const int *lb, const int *size, double *ws,
+                                 void *stream);
+int mvd_feed_signed_permute_f32(const float *in, float *out, int C, int D, int H, int W, const int *perm, int flip_mask,
+                                void *stream);
+int mvd_feed_gaussian_blur_wide_f32(float *x, float *ws, int C, int D, int H, int W, const double *sigma, void *stream);
+int mvd_feed_da5_apply_f32(float *x, int C, long V, int chmask, int op, const float *params, const double *stats,
+                           void *stream);
+
 /* Cascade stage of the feed (nnUNetTrainer.py:740-755, custom_transforms/cascade_transforms.py) on the
  * one-hot channels of the previous stage's segmentation.  Planes are [D][H][W] float 0/1 (n = D*H*W voxels) or bit-planes
  * [D][H][Wq] of 64-bit words, Wq = ceil(W/64), bit b of word q = voxel x = 64 q + b, pad bits 0

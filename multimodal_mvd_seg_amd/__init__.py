@@ -15,7 +15,8 @@ __all__ = ["nnUNetTrainerBNMI355", "nnUNetTrainerAdamMI355", "nnUNetTrainerVanil
            "nnUNetTrainerVanillaAdam3en4MI355", "nnUNetTrainerCosAnnealMI355", "FinalNetTrainerMI355",
            "nnUNetTrainerDiceLossMI355", "nnUNetTrainerDiceCELoss_noSmoothMI355", "nnUNetTrainerCELossMI355",
            "nnUNetTrainerTopk10LossMI355", "nnUNetTrainerTopk10LossLS01MI355", "nnUNetTrainerDiceTopK10LossMI355",
-           "ensembling"]
+           "nnUNetTrainerDA5MI355", "nnUNetTrainerDA5_10epochsMI355", "nnUNetTrainerNoMirroringMI355",
+           "nnUNetTrainerNoDAMI355", "ensembling"]
 
 
 def __getattr__(name):

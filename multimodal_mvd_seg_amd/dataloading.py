@@ -15,7 +15,9 @@ contrast, low-resolution simulation, the two gammas) and MaskTransform run on th
 numpy / scipy.ndimage, their batchgenerators glue (which values are drawn, in which order) is restated in
 `draw_intensity`.  Anisotropic plans (`do_dummy_2d_data_aug=True`, nnUNetTrainer.py:695-717) take the in-plane form of both
 stages: one 2-D map per sample moves every slice of every channel, and the low-resolution simulation leaves axis 0 alone
-(DESIGN 19).
+(DESIGN 19).  `da5=True` runs nnUNetTrainerDA5's recipe instead of the default one (csrc/feed_da5.hip): per-axis
+scaling, Rot90 / Transpose / mirror as signed permutations, an exact median filter, blank rectangles, the local
+brightness gradient and gamma, sharpening; its glue is restated in `draw_da5`.
 """
 import ctypes
 
@@ -102,9 +104,16 @@ def get_patch_size(final_patch_size, rot_x, rot_y, rot_z, scale_range):
 
 def spatial_affine(spatial, patch_size):
     """The 12 doubles of the kernels' coordinate map p = A (o - (f-1)/2) + off for spatial = (ax, ay, az, sc): A = sc R^T
-    (augment_spatial: rotate_coords_3d, then scale_coords, then + ctr), off = n/2 - 0.5 (random_crop=False)."""
+    (augment_spatial: rotate_coords_3d, then scale_coords, then + ctr), off = n/2 - 0.5 (random_crop=False).  sc may be
+    one factor per axis (independent_scale_for_each_axis, the DA5 recipe): scale_coords multiplies coordinate i by sc_i,
+    so row i of R^T is scaled by sc_i."""
     ax, ay, az, sc = spatial
-    a = sc * rotation_matrix_3d(ax, ay, az).T
+    if np.ndim(sc) == 0:
+        a = sc * rotation_matrix_3d(ax, ay, az).T
+    else:
+        if len(sc) != 3:
+            raise ValueError("spatial_affine: a per-axis scale has three factors")
+        a = np.asarray(sc, dtype=np.float64)[:, None] * rotation_matrix_3d(ax, ay, az).T
     off = np.asarray(patch_size, dtype=np.float64) / 2. - 0.5
     return [float(v) for v in a.reshape(-1)] + [float(v) for v in off]
 
@@ -268,6 +277,139 @@ def gaussian_blur(x, sigmas, ws):
         raise ValueError("gaussian_blur: 0 < sigma <= 1.1")
     call("mvd_feed_gaussian_blur_f32", _p(x), _p(ws), C, *[int(v) for v in x.shape[1:]],
          _chan_arg(sigmas, C, ctypes.c_double), _stream())
+
+
+def gaussian_blur_wide(x, sigmas, ws):
+    """gaussian_blur for 0 < sigma <= 1.5 (radius int(4 sigma + 0.5) <= 6, the DA5 range): the same arithmetic."""
+    _dev_f32(x, "gaussian_blur_wide")
+    C = int(x.shape[0])
+    nsel = sum(s is not None for s in sigmas)
+    if not (ws.is_cuda and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= 2 * nsel * x[0].numel()):
+        raise RuntimeError("gaussian_blur_wide: ws is a float32 device tensor of >= 2 * selected * D*H*W values")
+    if any(s is not None and not 0 < float(s) <= 1.5 for s in sigmas):
+        raise ValueError("gaussian_blur_wide: 0 < sigma <= 1.5")
+    call("mvd_feed_gaussian_blur_wide_f32", _p(x), _p(ws), C, *[int(v) for v in x.shape[1:]],
+         _chan_arg(sigmas, C, ctypes.c_double), _stream())
+
+
+OP_DA5_ADD, OP_DA5_CONTRAST_NOCLIP = range(2)
+LOCAL_ADDITIVE, LOCAL_GAMMA = range(2)
+
+
+def da5_apply(x, op, params, stats=None, channels=None):
+    """In place on the selected channels of x [C,D,H,W]: OP_DA5_ADD x += p (BrightnessTransform); OP_DA5_CONTRAST_NOCLIP
+    (x - mean) p + mean with stats (ContrastAugmentationTransform, preserve_range=False)."""
+    _dev_f32(x, "da5_apply")
+    C = int(x.shape[0])
+    if stats is not None and not (stats.is_cuda and stats.dtype == torch.float64 and stats.numel() >= 4 * C):
+        raise RuntimeError("da5_apply: stats is a float64 device tensor of >= 4 C values")
+    call("mvd_feed_da5_apply_f32", _p(x), C, x[0].numel(), _chmask(C, channels), int(op), _chan_arg(params, C),
+         _p(stats) if stats is not None else None, _stream())
+
+
+def median_filter(x, out, sizes):
+    """out[c] <- scipy.ndimage.median_filter(x[c], size=sizes[c]) (mode 'reflect') for sizes 2..7, exactly; a size of
+    0 / None copies the channel.  x, out [C,D,H,W], distinct buffers.  Finite inputs (NaN is unsupported)."""
+    _dev_f32(x, "median_filter")
+    _dev_f32(out, "median_filter")
+    C = int(x.shape[0])
+    if tuple(out.shape) != tuple(x.shape) or out.data_ptr() == x.data_ptr():
+        raise RuntimeError("median_filter: out has the shape of x and is another buffer")
+    if C > 16 or len(sizes) != C:
+        raise ValueError(f"median_filter: one size per channel (at most 16), got {len(sizes)} for {C}")
+    call("mvd_feed_median_filter_f32", _p(x), _p(out), C, *[int(v) for v in x.shape[1:]],
+         (ctypes.c_int * C)(*[0 if v is None else int(v) for v in sizes]), _stream())
+
+
+def sharpen(x, ws, strengths, stats):
+    """In place: SharpeningTransform on every channel of x [C,D,H,W] whose strength is not None / 0 --
+    clip(scipy.signal.convolve(x[c], strength L + delta, 'same'), min, max), L the 3x3x3 Laplacian (6, -1 on the faces);
+    stats: channel_stats of x taken before; ws: float32 scratch of >= C*D*H*W values."""
+    _dev_f32(x, "sharpen")
+    C = int(x.shape[0])
+    if not (ws.is_cuda and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= x.numel()
+            and ws.data_ptr() != x.data_ptr()):
+        raise RuntimeError("sharpen: ws is a float32 device tensor of >= C*D*H*W values, not x itself")
+    if not (stats.is_cuda and stats.dtype == torch.float64 and stats.numel() >= 4 * C):
+        raise RuntimeError("sharpen: stats is a float64 device tensor of >= 4 C values")
+    call("mvd_feed_sharpen_f32", _p(x), _p(ws), C, *[int(v) for v in x.shape[1:]],
+         _chan_arg(strengths, C, ctypes.c_double), _p(stats), _stream())
+
+
+def local_gauss(x, mode, params, stats=None):
+    """In place: the Gaussian-field LocalTransforms on x [C,D,H,W].  params: per channel None or (scale[3], loc[3],
+    amount); g = prod_d exp(-(i_d - loc_d)^2 / (2 scale_d^2)) / max g.  LOCAL_ADDITIVE x += amount g
+    (BrightnessGradientAdditiveTransform, mean_centered=False); LOCAL_GAMMA x01 ^ (1 + (amount - 1) g) rescaled to the
+    channel's own range, stats = channel_stats of x taken before (LocalGammaTransform)."""
+    _dev_f32(x, "local_gauss")
+    C = int(x.shape[0])
+    if len(params) != C:
+        raise ValueError(f"local_gauss: one entry per channel ({C}) expected, got {len(params)}")
+    if mode == LOCAL_GAMMA and not (stats is not None and stats.is_cuda and stats.dtype == torch.float64
+                                    and stats.numel() >= 4 * C):
+        raise RuntimeError("local_gauss: the local gamma needs float64 stats of >= 4 C values")
+    loc, scale, amount = [0.0] * (3 * C), [1.0] * (3 * C), [0.0] * C
+    for c, prm in enumerate(params):
+        if prm is not None:
+            scale[3 * c:3 * c + 3] = [float(v) for v in prm[0]]
+            loc[3 * c:3 * c + 3] = [float(v) for v in prm[1]]
+            amount[c] = float(prm[2])
+    call("mvd_feed_local_gauss_f32", _p(x), C, *[int(v) for v in x.shape[1:]],
+         _chmask(C, [c for c, prm in enumerate(params) if prm is not None]), int(mode),
+         (ctypes.c_double * (3 * C))(*loc), (ctypes.c_double * (3 * C))(*scale), (ctypes.c_float * C)(*amount),
+         _p(stats) if stats is not None else None, _stream())
+
+
+RECT_WS_DOUBLES = 64  # the first-level partial sums of blank_rectangle
+
+
+def blank_rectangle(x, c, lb, size, ws):
+    """In place: the box lb .. lb + size of channel c of x [C,D,H,W] becomes its own mean (fp64 sum, fixed order);
+    ws: float64 device scratch of >= RECT_WS_DOUBLES values."""
+    _dev_f32(x, "blank_rectangle")
+    if not (ws.is_cuda and ws.dtype == torch.float64 and ws.numel() >= RECT_WS_DOUBLES):
+        raise RuntimeError("blank_rectangle: ws is a float64 device tensor of >= 64 values")
+    call("mvd_feed_blank_rectangle_f32", _p(x), *[int(v) for v in x.shape], int(c), (ctypes.c_int * 3)(*[int(v) for v in lb]),
+         (ctypes.c_int * 3)(*[int(v) for v in size]), _p(ws), _stream())
+
+
+def signed_permute(inp, out, perm, flip_mask=0):
+    """out <- flip(transpose(inp, perm), flip_mask) over the spatial axes of every channel of inp [C,D,H,W] (bit k of
+    flip_mask flips output axis k); permuted axes must have equal extents.  Distinct buffers."""
+    _dev_f32(inp, "signed_permute")
+    _dev_f32(out, "signed_permute")
+    if tuple(out.shape) != tuple(inp.shape) or out.data_ptr() == inp.data_ptr():
+        raise RuntimeError("signed_permute: out has the shape of inp and is another buffer")
+    call("mvd_feed_signed_permute_f32", _p(inp), _p(out), *[int(v) for v in inp.shape],
+         (ctypes.c_int * 3)(*[int(v) for v in perm]), int(flip_mask), _stream())
+
+
+def compose_signed_permutation(rot90=None, transpose=None, flip_mask=0):
+    """(perm, mask) with flip(transpose(x, perm), mask) == the spatial ops np.rot90(x, k, axes) [rot90 = (k, axes)], then
+    np.transpose(x, transpose), then the flips of flip_mask, on arrays whose moved axes have equal extents.  Found by
+    running those numpy calls on the three coordinate grids of a 2^3 cube: output axis k reads input axis perm[k],
+    reversed when the coordinate there starts at 1."""
+    grids = np.indices((2, 2, 2))
+    res = []
+    for g in grids:
+        if rot90 is not None:
+            g = np.rot90(g, int(rot90[0]), tuple(int(a) for a in rot90[1]))
+        if transpose is not None:
+            g = np.transpose(g, tuple(int(a) for a in transpose))
+        for ax in range(3):
+            if flip_mask & (1 << ax):
+                g = np.flip(g, ax)
+        res.append(g)
+    perm, mask = [None] * 3, 0
+    for k in range(3):
+        step = [0, 0, 0]
+        step[k] = 1
+        for a in range(3):
+            if res[a][tuple(step)] != res[a][0, 0, 0]:
+                perm[k] = a
+                if res[a][0, 0, 0] == 1:
+                    mask |= 1 << k
+    return tuple(perm), mask
 
 
 def gaussian_noise(x, sigma, key, channels=None):
@@ -444,6 +586,10 @@ def lowres_affine_2d(shape_2d, target_2d):
 
 
 INTENSITY_KEYS = ('noise', 'blur', 'brightness', 'contrast', 'lowres', 'gamma_inverted', 'gamma')
+# p_per_sample of the DA5 transforms as nnUNetTrainerDA5 sets them, and their common p_per_channel
+DA5_PROBABILITIES = {'rot90': 0.5, 'transpose': 0.5, 'median': 0.2, 'blur': 0.2, 'noise': 0.1, 'brightness': 0.1,
+                     'contrast': 0.2, 'lowres': 0.15, 'gamma': 0.1, 'blank': 0.4, 'gradient': 0.3, 'local_gamma': 0.3,
+                     'sharpen': 0.2, 'per_channel': 0.5}
 
 
 class DeviceDataLoader3D:
@@ -460,8 +606,25 @@ class DeviceDataLoader3D:
                  p_brightness=0.15, p_contrast=0.15, p_lowres=0.25, p_lowres_per_channel=0.5, p_gamma_inverted=0.1,
                  p_gamma=0.3, cascade_labels=None, cascade_augmentation=False, p_cascade_binary=0.4,
                  cascade_strel_size=(1, 8), p_cascade_remove=0.2, cascade_fill_with_other_class_p=0.0,
-                 cascade_max_component_fraction=0.15):
+                 cascade_max_component_fraction=0.15, da5=False, da5_probabilities=None):
         self._data = data
+        # the DA5 recipe (nnUNetTrainerDA5.get_training_transforms) in place of the default intensity stage
+        self.da5 = bool(da5)
+        self.da5_p = dict(DA5_PROBABILITIES)
+        if da5_probabilities is not None:
+            unknown = set(da5_probabilities) - set(DA5_PROBABILITIES)
+            if unknown:
+                raise ValueError(f"DeviceDataLoader3D: unknown DA5 probabilities {sorted(unknown)}")
+            self.da5_p.update({k: float(v) for k, v in da5_probabilities.items()})
+        if self.da5:
+            if len(patch_size) != 3 or len(final_patch_size) != 3 or int(final_patch_size[0]) == 1:
+                raise NotImplementedError("DeviceDataLoader3D: DA5 is built for 3-D plans only (a 2-D plan is refused)")
+            if do_dummy_2d_data_aug:
+                raise NotImplementedError("DeviceDataLoader3D: DA5 with do_dummy_2d_data_aug=True (the in-plane form of "
+                                          "the recipe) is not built")
+            if cascade_labels is not None or cascade_augmentation:
+                raise NotImplementedError("DeviceDataLoader3D: DA5 in cascade mode is not built")
+        self._dstate = None  # DA5 scratch (ping-pong sample buffers, rectangle partial sums), reused across batches
         # cascade mode (nnUNetTrainer.py:740-755, :783-784): load_case returns a seg of two channels, channel 1 the previous
         # stage's segmentation; cascade_labels = label_manager.foreground_labels become that many one-hot input channels
         # behind the modalities.  cascade_augmentation adds the binary operators and the component removal (training);
@@ -506,7 +669,7 @@ class DeviceDataLoader3D:
             raise ValueError("DeviceDataLoader3D: patch_size must not be smaller than final_patch_size")
         # the intensity stage (nnUNetTrainer.py:719-736) with its per-sample / per-channel probabilities, and
         # MaskTransform: mask_channels is the plans' use_mask_for_norm (one bool per input channel)
-        self.intensity_augmentation = bool(intensity_augmentation)
+        self.intensity_augmentation = bool(intensity_augmentation) or self.da5  # DA5 implies the stage
         self.p_noise, self.p_blur, self.p_blur_per_channel = float(p_noise), float(p_blur), float(p_blur_per_channel)
         self.p_brightness, self.p_contrast = float(p_brightness), float(p_contrast)
         self.p_lowres, self.p_lowres_per_channel = float(p_lowres), float(p_lowres_per_channel)
@@ -652,12 +815,23 @@ class DeviceDataLoader3D:
             modified = True
         if np.random.uniform() < self.p_scale_per_sample:
             lo, hi = self.scale_range
-            if np.random.random() < 0.5 and lo < 1:
-                sc = np.random.uniform(lo, 1)
+
+            def factor():
+                if np.random.random() < 0.5 and lo < 1:
+                    return np.random.uniform(lo, 1)
+                return np.random.uniform(max(lo, 1), hi)
+
+            if self.da5:
+                # independent_scale_for_each_axis=True: one uniform (< p_independent_scale_per_axis = 1), then the
+                # down/up draw of every axis in turn
+                np.random.uniform()
+                sc = tuple(float(factor()) for _ in range(3))
             else:
-                sc = np.random.uniform(max(lo, 1), hi)
+                sc = factor()
             modified = True
-        return (float(rot[0]), float(rot[1]), float(rot[2]), float(sc)) if modified else None
+        if not modified:
+            return None
+        return (float(rot[0]), float(rot[1]), float(rot[2]), sc if isinstance(sc, tuple) else float(sc))
 
     def draw_intensity(self, nsamples, nchannels):
         """The intensity transforms' draws for a batch (batchgenerators, absent from the reference tree -- restated from
@@ -711,6 +885,142 @@ class DeviceDataLoader3D:
                     it[key] = [float(two_sided(0.7, 1.5)) for _ in range(nchannels)]
         return out
 
+    def da5_valid_axes(self):
+        """Rot90Transform's / TransposeAxesTransform's axes as nnUNetTrainerDA5 chooses them: the axes of the final patch
+        that share its most frequent extent; () when every extent occurs once (then neither transform is added)."""
+        p = self.final_patch_size
+        counts = [sum(q == v for q in p) for v in p]
+        if max(counts) < 2:
+            return ()
+        return tuple(i for i, n in enumerate(counts) if n == max(counts))
+
+    def draw_da5(self, nsamples, nchannels):
+        """The draws of the DA5 recipe behind its SpatialTransform (nnUNetTrainerDA5.get_training_transforms;
+        batchgenerators is absent from the reference tree -- its glue is restated from the published source without the
+        package at hand, so parity with batchgenerators itself is unpinned).  Transform by transform, each
+        over all samples (as Compose runs them), every draw from np.random.  p = self.da5_p[...], pc = p['per_channel']:
+          rot90        (only with da5_valid_axes) per sample a uniform (< p), np.random.choice((0, 1, 2, 3)), then
+                       np.random.choice(valid_axes, 2, replace=False), sorted
+          transpose    (same condition) per sample a uniform (< p), np.random.shuffle of a copy of valid_axes; the
+                       shuffled axes fill the valid positions of the transpose
+          median|blur  ONE np.random.choice(2) per batch (OneOfTransform); then the chosen transform alone draws:
+                       median per sample a uniform (< p), per channel a uniform (< pc) and np.random.randint(2, 8);
+                       blur per sample a uniform (< p), per channel a uniform (<= pc) and sigma ~ U(0.3, 1.5)
+          noise        as draw_intensity: a uniform (< p), sigma ~ U(0, 0.1), a uniform per channel, one key
+          brightness   a uniform (< p), per channel a uniform (<= pc) and np.random.normal(0, 0.5)
+          contrast     ONE np.random.choice(2) per batch (0: preserve_range=True, 1: False); per sample a uniform (< p),
+                       per channel a uniform (< pc) and the two-sided factor over (0.5, 2)
+          low-res      a uniform (< p), per channel a uniform (< pc) and the zoom ~ U(0.25, 1)
+          gamma, twice a uniform (< p), per channel the two-sided factor over (0.7, 1.5); both run inverted
+          mirror       draw_mirror
+          blank        a uniform (< p), per channel a uniform (< pc), n = np.random.randint(1, 5) rectangles, each: per
+                       axis size_d = randint(max(1, p_d // 10), p_d // 3 + 1), then per axis lb_d = randint(0,
+                       max(p_d - size_d, 1))
+          gradient     a uniform (< p), per channel a uniform (< pc), per axis scale_d = exp(U(log(max(1, p_d // 6)),
+                       log(p_d))), then per axis loc_d = U(-0.5, 1.5) p_d, then a uniform (< 0.5: U(-5, -1), else U(1, 5))
+          local gamma  the same with the gamma: a uniform (< 0.5: U(0.01, 0.8), else U(1.5, 4))
+          sharpen      a uniform (< p), per channel a uniform (< pc) and the strength ~ U(0.1, 1)
+        With every probability at 0 that is 2 np.random.choice calls, and per sample 11 uniforms (13 with valid axes)
+        plus draw_mirror's one per mirror axis.  Returns a dict of per-sample lists (None: the transform skips the
+        sample; per-channel lists hold None for a channel that is not selected), 'oneof_blur' / 'oneof_contrast' the two
+        batch choices, 'signed' the (perm, mask) of rot90 and transpose composed (None: identity)."""
+        P = self.da5_p
+        pc = P['per_channel']
+        u = np.random.uniform
+        ps = self.final_patch_size
+        rng = range(nsamples)
+        d = {'da5': True}
+
+        def two_sided(lo, hi):
+            return u(lo, 1) if np.random.random() < 0.5 and lo < 1 else u(max(lo, 1), hi)
+
+        valid = self.da5_valid_axes()
+        d['rot90'], d['transpose'] = [None] * nsamples, [None] * nsamples
+        if valid:
+            for j in rng:
+                if u() < P['rot90']:
+                    k = int(np.random.choice((0, 1, 2, 3)))
+                    axes = sorted(int(a) for a in np.random.choice(valid, size=2, replace=False))
+                    d['rot90'][j] = (k, tuple(axes))
+            for j in rng:
+                if u() < P['transpose']:
+                    shuffled = list(valid)
+                    np.random.shuffle(shuffled)
+                    t = [0, 1, 2]
+                    for pos, a in zip(valid, shuffled):
+                        t[pos] = int(a)
+                    d['transpose'][j] = tuple(t)
+        d['signed'] = []
+        for j in rng:
+            perm, mask = compose_signed_permutation(d['rot90'][j], d['transpose'][j])
+            d['signed'].append(None if perm == (0, 1, 2) and mask == 0 else (perm, mask))
+
+        d['oneof_blur'] = int(np.random.choice(2))
+        d['median'], d['blur'] = [None] * nsamples, [None] * nsamples
+        for j in rng:
+            if d['oneof_blur'] == 0:
+                if u() < P['median']:
+                    d['median'][j] = [int(np.random.randint(2, 8)) if u() < pc else None for _ in range(nchannels)]
+            elif u() < P['blur']:
+                d['blur'][j] = [float(u(0.3, 1.5)) if u() <= pc else None for _ in range(nchannels)]
+        d['noise'] = [None] * nsamples
+        for j in rng:
+            if u() < P['noise']:
+                sigma = u(0, 0.1)
+                for _ in range(nchannels):
+                    u()  # p_per_channel = 1
+                d['noise'][j] = (float(sigma), int(np.random.randint(0, 2 ** 63, dtype=np.int64)))
+        d['brightness'] = [None] * nsamples
+        for j in rng:
+            if u() < P['brightness']:
+                d['brightness'][j] = [float(np.random.normal(0, 0.5)) if u() <= pc else None for _ in range(nchannels)]
+        d['oneof_contrast'] = int(np.random.choice(2))
+        d['contrast'] = [None] * nsamples
+        for j in rng:
+            if u() < P['contrast']:
+                d['contrast'][j] = [float(two_sided(0.5, 2)) if u() < pc else None for _ in range(nchannels)]
+        d['lowres'] = [None] * nsamples
+        for j in rng:
+            if u() < P['lowres']:
+                d['lowres'][j] = [float(u(0.25, 1)) if u() < pc else None for _ in range(nchannels)]
+        for key in ('gamma1', 'gamma2'):
+            d[key] = [None] * nsamples
+            for j in rng:
+                if u() < P['gamma']:
+                    d[key][j] = [float(two_sided(0.7, 1.5)) for _ in range(nchannels)]
+        d['mirror'] = [self.draw_mirror() for _ in rng]
+        d['blank'] = [None] * nsamples
+        for j in rng:
+            if u() < P['blank']:
+                chans = []
+                for _ in range(nchannels):
+                    rects = None
+                    if u() < pc:
+                        rects = []
+                        for _r in range(int(np.random.randint(1, 5))):
+                            size = [int(np.random.randint(max(1, p // 10), p // 3 + 1)) for p in ps]
+                            lb = [int(np.random.randint(0, max(p - s, 1))) for p, s in zip(ps, size)]
+                            rects.append((lb, size))
+                    chans.append(rects)
+                d['blank'][j] = chans
+
+        def local(amount):
+            scale = [float(np.exp(u(np.log(max(1, p // 6)), np.log(p)))) for p in ps]
+            loc = [float(u(-0.5, 1.5) * p) for p in ps]
+            return scale, loc, float(amount())
+
+        for key, amount in (('gradient', lambda: u(-5, -1) if u() < 0.5 else u(1, 5)),
+                            ('local_gamma', lambda: u(0.01, 0.8) if u() < 0.5 else u(1.5, 4))):
+            d[key] = [None] * nsamples
+            for j in rng:
+                if u() < P[key]:
+                    d[key][j] = [local(amount) if u() < pc else None for _ in range(nchannels)]
+        d['sharpen'] = [None] * nsamples
+        for j in rng:
+            if u() < P['sharpen']:
+                d['sharpen'][j] = [float(u(0.1, 1)) if u() < pc else None for _ in range(nchannels)]
+        return d
+
     def draw_cascade(self, nsamples):
         """The two cascade transforms' draws for a batch (nnUNetTrainer.py:741-755), each over all samples as Compose runs
         them.
@@ -755,7 +1065,8 @@ class DeviceDataLoader3D:
     def plan_batch(self):
         """The host decisions of one batch, in the reference's RNG order: keys, then per sample (oversample?, bbox),
         then per sample the SpatialTransform draws (only with rotation_for_DA), then the intensity draws (only with
-        intensity_augmentation, draw_intensity), then per sample the mirror draw.  In cascade mode with
+        intensity_augmentation, draw_intensity), then per sample the mirror draw.  With da5 the intensity draws are
+        draw_da5's dict, which holds the mirror draws at their place in the recipe (flips repeats them).  In cascade mode with
         cascade_augmentation the plan gains a last element, draw_cascade's dict, drawn after the mirrors."""
         plan = self._plan_base()
         if self.cascade_augmentation:
@@ -770,6 +1081,11 @@ class DeviceDataLoader3D:
             data, _, properties = self._case(k)
             lbs, _ = self.get_bbox(tuple(data.shape[1:]), force_fg, properties['class_locations'])
             boxes.append([int(v) for v in lbs])
+        if self.da5:
+            # the mirror is drawn inside draw_da5, at its place in the recipe; the crop and the warp run un-mirrored
+            spatial = [self.draw_spatial() if self.rotation_for_DA is not None else None for _ in keys]
+            da5 = self.draw_da5(len(keys), self.num_modalities)
+            return list(keys), boxes, spatial, da5, list(da5['mirror'])
         if self.intensity_augmentation:
             spatial = [self.draw_spatial() if self.rotation_for_DA is not None else None for _ in keys]
             intensity = self.draw_intensity(len(keys), self.num_modalities)
@@ -848,6 +1164,100 @@ class DeviceDataLoader3D:
                 channel_stats(x, sb, st['ws'], pre_op=op, gammas=it[key], pre_stats=sa)
                 intensity_apply(x, op, it[key], sa, sb)
 
+    def _da5_state(self, C, Cs):
+        st = self._dstate
+        if st is None or st['shape'] != (C, Cs):
+            f = self.final_patch_size
+            st = {'shape': (C, Cs), 'a': torch.empty((C, *f), dtype=torch.float32, device=self.device),
+                  'b': torch.empty((C, *f), dtype=torch.float32, device=self.device),
+                  'seg': torch.empty((Cs, *f), dtype=torch.float32, device=self.device),
+                  'rect': torch.empty(RECT_WS_DOUBLES, dtype=torch.float64, device=self.device)}
+            self._dstate = st
+        return st
+
+    @staticmethod
+    def _da5_moves(d, j):
+        """The out-of-place passes of sample j's data, in order: signed permutation, median, mirror."""
+        med = d['median'][j] is not None and any(v is not None for v in d['median'][j])
+        return [d['signed'][j] is not None, med, d['mirror'][j] != 0]
+
+    def apply_da5(self, bufs, d, j):
+        """The DA5 recipe behind the SpatialTransform on sample j.  bufs: the buffers [C,D,H,W] the sample walks through,
+        one more than _da5_moves counts -- the un-mirrored crop / warp result sits in bufs[0], every out-of-place pass
+        (signed permutation of Rot90 + Transpose, median, mirror) moves it on, the last one is the batch slot.  Order:
+        rot90 + transpose, median | blur, noise, additive brightness, contrast (clipped | not), low-res, gamma (inverted)
+        twice, mirror, blank rectangles, brightness gradient, local gamma, sharpening."""
+        bufs = list(bufs)
+        x = bufs.pop(0)
+        C = int(x.shape[0])
+        shape = tuple(int(v) for v in x.shape[1:])
+        st = self._intensity_state(C, x[0].numel())
+        ds = self._dstate if self._dstate is not None and self._dstate['shape'][0] == C else self._da5_state(C, 1)
+        sa, sb = st['stats'][0], st['stats'][1]
+
+        def selected(vals):
+            return [c for c, v in enumerate(vals) if v is not None]
+
+        if d['signed'][j] is not None:
+            nxt = bufs.pop(0)
+            signed_permute(x, nxt, *d['signed'][j])
+            x = nxt
+        if self._da5_moves(d, j)[1]:
+            nxt = bufs.pop(0)
+            median_filter(x, nxt, d['median'][j])
+            x = nxt
+        if d['blur'][j] is not None and selected(d['blur'][j]):
+            gaussian_blur_wide(x, d['blur'][j], st['blur'])
+        if d['noise'][j] is not None:
+            gaussian_noise(x, d['noise'][j][0], d['noise'][j][1])
+        if d['brightness'][j] is not None and selected(d['brightness'][j]):
+            da5_apply(x, OP_DA5_ADD, d['brightness'][j], channels=selected(d['brightness'][j]))
+        if d['contrast'][j] is not None and selected(d['contrast'][j]):
+            sel = selected(d['contrast'][j])
+            channel_stats(x, sa, st['ws'], channels=sel)
+            if d['oneof_contrast'] == 0:
+                intensity_apply(x, OP_CONTRAST, d['contrast'][j], sa, channels=sel)
+            else:
+                da5_apply(x, OP_DA5_CONTRAST_NOCLIP, d['contrast'][j], sa, channels=sel)
+        if d['lowres'][j] is not None:
+            for c, z in enumerate(d['lowres'][j]):
+                if z is None:
+                    continue
+                t = lowres_target_shape(shape, z)
+                dpad = st['dpad'][:int(np.prod([v + 2 * LOWRES_PAD for v in t]))].view(
+                    *[v + 2 * LOWRES_PAD for v in t])
+                lowres_gather(x[c], dpad, t, 0)
+                d4 = dpad.unsqueeze(0)
+                channel_stats(d4, st['stats1'][0], st['ws'])
+                bspline_prefilter(d4, 7)
+                spatial_transform_data(d4, x[c:c + 1], lowres_affine(shape, t), 0, 0.0)
+                intensity_apply(x[c:c + 1], OP_CLIP, None, st['stats1'][0])
+        for key in ('gamma1', 'gamma2'):
+            if d[key][j] is not None:
+                channel_stats(x, sa, st['ws'])
+                channel_stats(x, sb, st['ws'], pre_op=OP_GAMMA_INVERTED, gammas=d[key][j], pre_stats=sa)
+                intensity_apply(x, OP_GAMMA_INVERTED, d[key][j], sa, sb)
+        if d['mirror'][j] != 0:
+            nxt = bufs.pop(0)
+            signed_permute(x, nxt, (0, 1, 2), d['mirror'][j])
+            x = nxt
+        if bufs:
+            raise RuntimeError("apply_da5: more buffers than out-of-place passes")
+        if d['blank'][j] is not None:
+            for c, rects in enumerate(d['blank'][j]):
+                for lb, size in (rects or ()):
+                    blank_rectangle(x, c, lb, size, ds['rect'])
+        if d['gradient'][j] is not None and selected(d['gradient'][j]):
+            local_gauss(x, LOCAL_ADDITIVE, d['gradient'][j])
+        if d['local_gamma'][j] is not None and selected(d['local_gamma'][j]):
+            channel_stats(x, sa, st['ws'], channels=selected(d['local_gamma'][j]))
+            local_gauss(x, LOCAL_GAMMA, d['local_gamma'][j], sa)
+        if d['sharpen'][j] is not None and selected(d['sharpen'][j]):
+            channel_stats(x, sa, st['ws'], channels=selected(d['sharpen'][j]))
+            # every move is done, so the walk's first scratch buffer is free
+            sharpen(x, ds['a'], d['sharpen'][j], sa)
+        return x
+
     def _cascade_state(self):
         st = self._cstate
         if st is None:
@@ -876,6 +1286,32 @@ class DeviceDataLoader3D:
             cascade_remove(onehot[c], u, st['threshold'], st['ws'], st['chosen'],
                            other=None if other is None else onehot[other])
 
+    def _da5_sample(self, j, data, seg, mod, tgt, box, spatial, d, shift, remove):
+        """Sample j of a DA5 batch: crop (or crop + warp) un-mirrored into the head of the buffer walk, the recipe
+        (apply_da5) ending in the batch slot `mod`; the seg takes Rot90, Transpose and the mirror as ONE signed
+        permutation, since nothing touches it in between."""
+        ds = self._da5_state(int(mod.shape[0]), int(tgt.shape[0]))
+        n = sum(self._da5_moves(d, j))
+        bufs = [ds['a'], ds['b'], ds['a']][:n] + [mod]
+        sperm, smask = compose_signed_permutation(d['rot90'][j], d['transpose'][j], d['mirror'][j])
+        seg_moves = not (sperm == (0, 1, 2) and smask == 0)
+        sdst = ds['seg'] if seg_moves else tgt
+        if spatial is None:
+            lbs = [b + s for b, s in zip(box, shift)]
+            crop_pad_data(data, bufs[0], lbs, 0, 0.0)
+            crop_pad_seg(seg, sdst, lbs, 0, -1, replace=remove)
+        else:
+            pdata, pseg = self._scratch_for(data, seg)
+            crop_pad_data(data, pdata, box, 0, 0.0)
+            crop_pad_seg(seg, pseg, box, 0, -1)
+            bspline_prefilter(pdata, 7)
+            affine = spatial_affine(spatial, self.patch_size)
+            spatial_transform_data(pdata, bufs[0], affine, 0, 0.0)
+            spatial_transform_seg(pseg, sdst, affine, 0, replace=remove)
+        if seg_moves:
+            signed_permute(sdst, tgt, sperm, smask)
+        self.apply_da5(bufs, d, j)
+
     def generate_train_batch(self, plan=None):
         plan = plan if plan is not None else self.plan_batch()
         intensity = None
@@ -884,7 +1320,12 @@ class DeviceDataLoader3D:
             plan, cascade = plan[:-1], plan[-1]
             if self.cascade_labels is None:
                 raise ValueError("generate_train_batch: a cascade plan needs a loader in cascade mode")
-        if len(plan) == 3:
+        da5 = None
+        if len(plan) == 5 and isinstance(plan[3], dict) and plan[3].get('da5'):
+            if not self.da5:
+                raise ValueError("generate_train_batch: a DA5 plan needs a loader with da5=True")
+            keys, boxes, spatial, da5, flips = plan
+        elif len(plan) == 3:
             keys, boxes, flips = plan
             spatial = [None] * len(keys)
         elif len(plan) == 4:
@@ -906,6 +1347,12 @@ class DeviceDataLoader3D:
         for j, k in enumerate(keys):
             data, seg, properties = self._case(k)
             mod = data_all[j] if self.cascade_labels is None else data_all[j, :M]
+            if da5 is not None:
+                self._da5_sample(j, data, seg, mod, target[j], boxes[j], spatial[j], da5, shift, remove)
+                if self.mask_channels is not None:
+                    mask_remove_label(mod, target[j], self.mask_channels, replace=(-1, 0))
+                props.append(properties)
+                continue
             if spatial[j] is None:
                 lbs = [b + s for b, s in zip(boxes[j], shift)]
                 crop_pad_data(data, mod, lbs, flips[j], 0.0)

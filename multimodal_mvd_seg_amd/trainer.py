@@ -998,6 +998,80 @@ class nnUNetTrainerDiceTopK10LossMI355(nnUNetTrainerMI355):
         return _wrap_every_level(self, loss)
 
 
+# ------------------------------------------------------------------------------------------------ data augmentation variants
+class nnUNetTrainerDA5MI355(nnUNetTrainerMI355):
+    """variants/data_augmentation/nnUNetTrainerDA5.py: the heavier augmentation recipe, run by the device feed.
+    3-D plans without the dummy 2-D mode and without a cascade; everything else is refused with a message."""
+
+    def configure_rotation_dummyDA_mirroring_and_inital_patch_size(self):
+        """nnUNetTrainerDA5.py:36-91: the base trainer's rotations, mirroring and dummy-2-D rule; the initial patch is sized
+        with the scale range (0.7, 1.43)."""
+        rotation_for_DA, do_dummy_2d_data_aug, _, mirror_axes = \
+            super().configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+        patch_size = self.configuration_manager.patch_size
+        dim = len(patch_size)
+        initial_patch_size = get_patch_size(patch_size[-dim:], *rotation_for_DA.values(), (0.7, 1.43))
+        if do_dummy_2d_data_aug:
+            initial_patch_size[0] = patch_size[0]
+        return rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, mirror_axes
+
+    def get_device_dataloader(self, dataset_tr, device=None, intensity_augmentation=True, cascade_augmentation=True,
+                              da5_probabilities=None):
+        """The training loader with da5=True (nnUNetTrainerDA5.get_training_transforms:94-305): SpatialTransform with
+        p_rot_per_sample 0.4, p_rot_per_axis 0.5, p_scale_per_sample 0.2, scale (0.7, 1.43) independently per axis, then
+        the DA5 chain.  The intensity stage is implied."""
+        if len(self.configuration_manager.patch_size) != 3:
+            raise NotImplementedError("nnUNetTrainerDA5MI355: DA5 is built for 3-D plans only")
+        if self.is_cascaded:
+            raise NotImplementedError("nnUNetTrainerDA5MI355: DA5 with a cascade is not built")
+        rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, mirror_axes = \
+            self.configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+        if do_dummy_2d_data_aug:
+            raise NotImplementedError("nnUNetTrainerDA5MI355: DA5 for an anisotropic plan (do_dummy_2d_data_aug, the "
+                                      "in-plane form of the recipe) is not built")
+        use_mask_for_norm = getattr(self.configuration_manager, 'use_mask_for_norm', None)
+        return DeviceDataLoader3D(dataset_tr, self.batch_size, [int(i) for i in initial_patch_size],
+                                  self.configuration_manager.patch_size, self.label_manager,
+                                  oversample_foreground_percent=self.oversample_foreground_percent,
+                                  mirror_axes=mirror_axes, deep_supervision_scales=self._get_deep_supervision_scales(),
+                                  device=self.device if device is None else device, rotation_for_DA=rotation_for_DA,
+                                  scale_range=(0.7, 1.43), p_rot_per_sample=0.4, p_rot_per_axis=0.5,
+                                  p_scale_per_sample=0.2, mask_channels=use_mask_for_norm if use_mask_for_norm else None,
+                                  da5=True, da5_probabilities=da5_probabilities)
+
+
+class nnUNetTrainerDA5_10epochsMI355(nnUNetTrainerDA5MI355):
+    """nnUNetTrainerDA5.py: nnUNetTrainerDA5_10epochs."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.num_epochs = 10
+
+
+class nnUNetTrainerNoMirroringMI355(nnUNetTrainerMI355):
+    """variants/data_augmentation/nnUNetTrainerNoMirroring.py:4-10: no mirroring in training, none at inference."""
+
+    def configure_rotation_dummyDA_mirroring_and_inital_patch_size(self):
+        rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, _ = \
+            super().configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+        self.inference_allowed_mirroring_axes = None
+        return rotation_for_DA, do_dummy_2d_data_aug, initial_patch_size, None
+
+
+class nnUNetTrainerNoDAMI355(nnUNetTrainerMI355):
+    """variants/data_augmentation/nnUNetTrainerNoDA.py: the training loader runs the validation transforms -- final patch
+    straight from the case, no spatial, intensity or mirror stage -- and inference does not mirror."""
+
+    def configure_rotation_dummyDA_mirroring_and_inital_patch_size(self):
+        rotation_for_DA, do_dummy_2d_data_aug, _, _ = super().configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+        self.inference_allowed_mirroring_axes = None
+        return rotation_for_DA, do_dummy_2d_data_aug, self.configuration_manager.patch_size, None
+
+    def get_device_dataloader(self, dataset_tr, device=None, intensity_augmentation=False, cascade_augmentation=True):
+        self.configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+        return self.get_device_validation_dataloader(dataset_tr, device=device)
+
+
 # ------------------------------------------------------------------------------------------------ persistence topological loss
 class nnUNetTrainerTopoLossMI355(nnUNetTrainerMI355):
     """The base trainer's loss plus the reference's persistence topological loss (training/loss/Topo_Loss.py:16-85) on the
