@@ -13,161 +13,34 @@
 //                dies at the edge of value b that merges it into an older one: the bar (b, d).
 //   Dimension 1 needs a boundary-matrix reduction and is not built.
 //
-//   device: k_cub3d_keys -- one 64-bit key per (voxel, half-neighbour): ord(edge value of g) << 32 | (v * n_off + k) with
-//           g = f (dimension 0) or -f (dimension 2), -0 folded to +0 -- and one 64-bit radix sort per sample (persist.hip's
-//           order: vertices by (value, linear index), edges by (value, enumeration index));
-//   host:   mvd_cub3d_pair_host, plain C++: one elder-rule union-find sweep per sample, samples over <= 16 threads; the
-//           bars of non-zero length as (birth voxel, death voxel) rows;
+//   device: k_grid_edge_keys -- one 64-bit key per (voxel, half-neighbour): ord(edge value of g) << 32 | (v * n_off + k)
+//           with g = f (dimension 0) or -f (dimension 2), -0 folded to +0 -- and one 64-bit radix sort per sample (the
+//           order of persist_common.h: vertices by (value, linear index), edges by (value, enumeration index));
+//   host:   mvd_cub3d_pair_host, plain C++: one elder-rule union-find sweep per sample (grid_elder_sweep), samples over
+//           <= 16 threads; the bars of non-zero length as (birth voxel, death voxel) rows;
 //   device: the target's diagram is m copies of (0, 1): m is counted with mvd_cc_label and one border-flag pass;
 //           the optimal matching of n bars to m identical points is a selection of the <= m bars of largest positive gain
 //           (one stable descending radix sort of the fp64 gains per sample); the loss is reduced in fp64 in a fixed order;
 //           the gradient is scattered by voxel-sorted runs (one thread owns a voxel's run): no float atomics anywhere.
-#include "common.h"
-
-#include <hipcub/hipcub.hpp>
+#include "persist_common.h"
 
 #include <math.h>
-
-#include <thread>
-#include <vector>
 
 namespace mvd {
 
 #define CUB3D_MAX_SAMPLES 4096
 #define CUB3D_NO_KEY 0xffffffffu
 
-struct Cub3dOffsets {
-    int n;          // slots per voxel: 13 (dimension 0) or 4 (dimension 2: three grid edges + the edge to the outside)
-    int off[13][3];
-};
-
-static int cub3d_fill_offsets(int dim, Cub3dOffsets *o) {
-    o->n = 0;
-    if (dim == 0) {  // half of the 26-neighbourhood, the enumeration of persist.hip
-        for (int dz = 0; dz <= 1; dz++)
-            for (int dy = -1; dy <= 1; dy++)
-                for (int dx = -1; dx <= 1; dx++) {
-                    if (dz == 0 && (dy < 0 || (dy == 0 && dx <= 0))) continue;
-                    o->off[o->n][0] = dz;
-                    o->off[o->n][1] = dy;
-                    o->off[o->n][2] = dx;
-                    o->n++;
-                }
-    } else if (dim == 2) {
-        const int t[4][3] = {{0, 0, 1}, {0, 1, 0}, {1, 0, 0}, {0, 0, 0}};  // slot 3: the edge to the outside vertex
-        for (int i = 0; i < 4; i++) memcpy(o->off[o->n++], t[i], sizeof(int) * 3);
-    } else {
-        return 1;
+// dimension 0: half of the 26-neighbourhood, f swept upwards; dimension 2: half of the 6-neighbourhood plus slot 3, the
+// edge to the outside vertex, f swept downwards (negate = dim == 2)
+static int cub3d_offsets(int dim, GridOffsets *o) {
+    if (dim != 0 && dim != 2) return 1;
+    grid_half_offsets(dim == 0 ? 26 : 6, o);
+    if (dim == 2) {
+        o->outside = o->n++;
+        memset(o->off[o->outside], 0, sizeof(int) * 3);
     }
     return 0;
-}
-
-static long cub3d_valid_keys(int D, int H, int W, int dim, const Cub3dOffsets &o) {
-    long n = 0;
-    const int ng = dim == 2 ? 3 : o.n;
-    for (int k = 0; k < ng; k++) {
-        const long a = D - abs(o.off[k][0]), b = H - abs(o.off[k][1]), c = W - abs(o.off[k][2]);
-        if (a > 0 && b > 0 && c > 0) n += a * b * c;
-    }
-    if (dim == 2) {  // one outside edge per border voxel
-        const long a = D > 2 ? D - 2 : 0, b = H > 2 ? H - 2 : 0, c = W > 2 ? W - 2 : 0;
-        n += (long)D * H * W - a * b * c;
-    }
-    return n;
-}
-
-// monotone map float -> uint32, as in persist.hip
-__host__ __device__ inline uint32_t cub3d_f2ord(float v) {
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-// dimension 0 sweeps f upwards, dimension 2 sweeps f downwards (= -f upwards); -0 is folded to +0
-__host__ __device__ inline float cub3d_sign(float v, int dim) {
-    const float g = dim == 2 ? -v : v;
-    return g == 0.f ? 0.f : g;
-}
-
-// one thread per (voxel, slot) of ONE sample; slots that leave the grid carry ~0 and sort last
-__global__ void k_cub3d_keys(const float *__restrict__ f, uint64_t *__restrict__ keys, int D, int H, int W,
-                             const Cub3dOffsets o, int dim) {
-    const long V = (long)D * H * W, total = V * o.n;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const long v = e / o.n;
-        const int k = (int)(e - v * o.n);
-        const int x = (int)(v % W), y = (int)((v / W) % H), z = (int)(v / ((long)W * H));
-        uint64_t key = ~0ull;
-        if (dim == 2 && k == 3) {
-            if (x == 0 || x == W - 1 || y == 0 || y == H - 1 || z == 0 || z == D - 1)  // max(g[v], -inf) = g[v]
-                key = ((uint64_t)cub3d_f2ord(cub3d_sign(f[v], dim)) << 32) | (uint64_t)e;
-        } else {
-            const int zz = z + o.off[k][0], yy = y + o.off[k][1], xx = x + o.off[k][2];
-            if (zz >= 0 && zz < D && yy >= 0 && yy < H && xx >= 0 && xx < W) {
-                const long u = ((long)zz * H + yy) * W + xx;
-                const float a = cub3d_sign(f[v], dim), b = cub3d_sign(f[u], dim);
-                key = ((uint64_t)cub3d_f2ord(a < b ? b : a) << 32) | (uint64_t)e;
-            }
-        }
-        keys[e] = key;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------ host pairing
-static inline int32_t cub3d_find(int32_t *p, int32_t x) {
-    while (p[x] != x) {
-        p[x] = p[p[x]];
-        x = p[x];
-    }
-    return x;
-}
-
-// One sample.  f: the field as given (comparisons of floats already identify -0 and +0).  Returns the number of bars
-// written to rows (<= V), or -1 for keys that are no sorted filtration of this grid.
-static long cub3d_pair_one(const float *f, const uint64_t *keys, long n_keys, int D, int H, int W, int dim,
-                           const Cub3dOffsets &o, int32_t *rows) {
-    const long V = (long)D * H * W;
-    const int32_t OUT = (int32_t)V;  // dimension 2 only: the outside vertex, older than every voxel
-    std::vector<int32_t> p((size_t)V + 1);
-    for (long i = 0; i <= V; i++) p[(size_t)i] = (int32_t)i;
-    long doff[13];
-    for (int k = 0; k < o.n; k++) doff[k] = ((long)o.off[k][0] * H + o.off[k][1]) * W + o.off[k][2];
-    const uint64_t total = (uint64_t)V * (uint64_t)o.n;
-    long nb = 0, alive = dim == 2 ? V + 1 : V;
-    for (long e = 0; e < n_keys; e++) {
-        const uint64_t key = keys[e];
-        const uint32_t idx = (uint32_t)key;
-        if ((e > 0 && key < keys[e - 1]) || (uint64_t)idx >= total) return -1;
-        if (alive <= 1) continue;  // everything is one component: the rest of the keys is only checked
-        const long v = idx / (uint32_t)o.n;
-        const int k = (int)(idx - (uint32_t)v * (uint32_t)o.n);
-        const bool outside = dim == 2 && k == 3;
-        const long u = outside ? V : v + doff[k];
-        if (u < 0 || u > V || (!outside && u >= V)) return -1;
-        const int32_t a = cub3d_find(p.data(), (int32_t)v), b = cub3d_find(p.data(), (int32_t)u);
-        if (a == b) continue;
-        bool a_younger;
-        float val;       // the edge's value in f
-        int32_t crit;    // the edge's critical vertex: arg-max of f (dimension 0), arg-min of f (dimension 2)
-        if (dim == 0) {
-            a_younger = f[a] > f[b] || (f[a] == f[b] && a > b);
-            crit = (int32_t)(f[v] < f[u] ? u : v);
-            val = f[crit];
-        } else {
-            a_younger = b == OUT || (a != OUT && (f[a] < f[b] || (f[a] == f[b] && a > b)));
-            crit = (int32_t)(outside ? v : (f[u] < f[v] ? u : v));
-            val = f[crit];
-        }
-        const int32_t young = a_younger ? a : b, old = a_younger ? b : a;
-        if (dim == 0 ? val > f[young] : f[young] > val) {  // bars of non-zero length only
-            if (nb >= V) return -1;
-            rows[2 * nb] = dim == 0 ? young : crit;      // birth voxel
-            rows[2 * nb + 1] = dim == 0 ? crit : young;  // death voxel
-            nb++;
-        }
-        p[young] = old;
-        alive--;
-    }
-    return nb;
 }
 
 // ------------------------------------------------------------------------------------------------------ the target's m
@@ -337,13 +210,6 @@ __global__ void k_cub3d_scatter(const uint32_t *__restrict__ key, const uint32_t
     grad[k] = gdiag ? (float)sum : (float)(sum * (double)g_out[0]);
 }
 
-static inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
-static size_t cub3d_sort_temp_u64(long n) {
-    size_t t = 0;
-    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, t, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)n, 0, 64);
-    return t;
-}
 static size_t cub3d_pairs_temp_u64(long n) {
     size_t t = 0;
     (void)hipcub::DeviceRadixSort::SortPairsDescending(nullptr, t, (const uint64_t *)nullptr, (uint64_t *)nullptr,
@@ -357,11 +223,6 @@ static size_t cub3d_pairs_temp_u32(long n) {
     return t;
 }
 
-static long ew_blocks(long n) {
-    long b = cdiv(n, 256);
-    return b > 8192 ? 8192 : (b < 1 ? 1 : b);
-}
-
 }  // namespace mvd
 
 using namespace mvd;
@@ -371,42 +232,38 @@ extern "C" {
 /* slots per sample of the key array (V * 13 for dimension 0, V * 4 for dimension 2); *n_valid = the keys that are edges
  * (the rest carry ~0 and sort last).  < 0: dim is neither 0 nor 2, or the grid is empty. */
 long mvd_cub3d_num_keys(int D, int H, int W, int dim, long *n_valid) {
-    Cub3dOffsets o;
-    if (D <= 0 || H <= 0 || W <= 0 || cub3d_fill_offsets(dim, &o)) return -1;
-    if (n_valid) *n_valid = cub3d_valid_keys(D, H, W, dim, o);
+    GridOffsets o;
+    if (D <= 0 || H <= 0 || W <= 0 || cub3d_offsets(dim, &o)) return -1;
+    if (n_valid) *n_valid = grid_valid_edges(D, H, W, o);
     return (long)D * H * W * o.n;
 }
 
 size_t mvd_cub3d_workspace_bytes(int D, int H, int W, int dim) {
-    Cub3dOffsets o;
-    if (D <= 0 || H <= 0 || W <= 0 || cub3d_fill_offsets(dim, &o)) return 0;
+    GridOffsets o;
+    if (D <= 0 || H <= 0 || W <= 0 || cub3d_offsets(dim, &o)) return 0;
     const long total = (long)D * H * W * o.n;
     if (total >= (1L << 31)) return 0;
-    return al256((size_t)total * sizeof(uint64_t)) + cub3d_sort_temp_u64(total) + 512;
+    return sort_u64_workspace_bytes(total);
 }
 
 /* f [N][D][H][W] -> keys_sorted [N][num_keys], ascending per sample */
 int mvd_cub3d_sorted_keys(const float *f, int N, int D, int H, int W, int dim, uint64_t *keys_sorted, void *ws,
                           size_t ws_bytes, void *stream) {
-    Cub3dOffsets o;
+    GridOffsets o;
     MVD_REQUIRE(f && keys_sorted && ws, "cub3d_sorted_keys: null pointer");
     MVD_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "cub3d_sorted_keys: bad shape");
-    MVD_REQUIRE(cub3d_fill_offsets(dim, &o) == 0,
+    MVD_REQUIRE(cub3d_offsets(dim, &o) == 0,
                 "cub3d_sorted_keys: dimension %d is not built (0 and 2 are union-find; 1 needs a matrix reduction)", dim);
     const long V = (long)D * H * W, total = V * o.n;
     MVD_REQUIRE(total < (1L << 31), "cub3d_sorted_keys: grid too large (edge index must fit 31 bits)");
     const size_t need = mvd_cub3d_workspace_bytes(D, H, W, dim);
     MVD_REQUIRE(need && ws_bytes >= need, "cub3d_sorted_keys: workspace too small");
     hipStream_t s = as_stream(stream);
-    uint64_t *keys = reinterpret_cast<uint64_t *>(ws);
-    const size_t koff = al256((size_t)total * sizeof(uint64_t));
-    void *temp = reinterpret_cast<char *>(ws) + koff;
     for (int n = 0; n < N; n++) {  // the sorts share the unsorted keys and the temporary storage: stream order
-        hipLaunchKernelGGL(k_cub3d_keys, dim3(ew_blocks(total)), dim3(256), 0, s, f + (long)n * V, keys, D, H, W, o, dim);
+        hipLaunchKernelGGL(k_grid_edge_keys, dim3(ew_blocks(total, 8192)), dim3(256), 0, s, f + (long)n * V,
+                           reinterpret_cast<uint64_t *>(ws), D, H, W, o, dim == 2);
         if (check_launch("cub3d_keys")) return 1;
-        size_t temp_bytes = ws_bytes - koff;
-        hipError_t e = hipcub::DeviceRadixSort::SortKeys(temp, temp_bytes, keys, keys_sorted + (long)n * total, (int)total, 0,
-                                                         64, s);
+        hipError_t e = sort_u64_from_workspace(ws, ws_bytes, total, keys_sorted + (long)n * total, s);
         if (e != hipSuccess) {
             set_error("cub3d_sorted_keys: radix sort: %s", hipGetErrorString(e));
             return 1;
@@ -420,30 +277,31 @@ int mvd_cub3d_sorted_keys(const float *f, int N, int D, int H, int W, int dim, u
  * order, counts[n] of them in sample n.  Essential bars are dropped. */
 int mvd_cub3d_pair_host(const float *f_host, const uint64_t *keys_host, long n_keys, int N, int D, int H, int W, int dim,
                         int32_t *bars, int32_t *counts, int n_threads) {
-    Cub3dOffsets o;
+    GridOffsets o;
     MVD_REQUIRE(f_host && bars && counts && N > 0 && D > 0 && H > 0 && W > 0, "cub3d_pair_host: bad arguments");
-    MVD_REQUIRE(cub3d_fill_offsets(dim, &o) == 0,
+    MVD_REQUIRE(cub3d_offsets(dim, &o) == 0,
                 "cub3d_pair_host: dimension %d is not built (0 and 2 are union-find; 1 needs a matrix reduction)", dim);
     const long V = (long)D * H * W;
     MVD_REQUIRE(V * o.n < (1L << 31), "cub3d_pair_host: grid too large");
-    MVD_REQUIRE(n_keys == cub3d_valid_keys(D, H, W, dim, o) && (keys_host || n_keys == 0),
+    MVD_REQUIRE(n_keys == grid_valid_edges(D, H, W, o) && (keys_host || n_keys == 0),
                 "cub3d_pair_host: n_keys does not match the grid (%ld)", n_keys);
-    int nt = n_threads < 1 ? 1 : (n_threads > 16 ? 16 : n_threads);
-    if (nt > N) nt = N;
+    const int negate = dim == 2;
     std::vector<long> rc((size_t)N, 0);
-    auto work = [&](int t) {
-        for (int n = t; n < N; n += nt)
-            rc[n] = cub3d_pair_one(f_host + (long)n * V, keys_host + (long)n * n_keys, n_keys, D, H, W, dim, o,
-                                   bars + (long)n * V * 2);
-    };
-    if (nt == 1) {
-        work(0);
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nt; t++) pool.emplace_back(work, t);
-        work(0);
-        for (auto &th : pool) th.join();
-    }
+    host_pool(N, n_threads, [&](int n) {
+        const float *f = f_host + (long)n * V;
+        int32_t *rows = bars + (long)n * V * 2;
+        long nb = 0;
+        // the component of `young` is born at g[young] and dies at val = g[crit]: a bar of non-zero length iff val is
+        // above; in f that is (young, crit) for dimension 0 and, the sweep running downwards, (crit, young) for dimension 2
+        const long r = grid_elder_sweep(f, keys_host + (long)n * n_keys, n_keys, D, H, W, o, negate,
+                                        [&](int32_t young, int32_t crit, float val) {
+                                            if (!(val > fold_sign(f[young], negate))) return;
+                                            rows[2 * nb] = negate ? crit : young;      // birth voxel
+                                            rows[2 * nb + 1] = negate ? young : crit;  // death voxel
+                                            nb++;
+                                        });
+        rc[n] = r < 0 ? -1 : nb;
+    });
     for (int n = 0; n < N; n++) {
         MVD_REQUIRE(rc[n] >= 0, "cub3d_pair_host: the keys of sample %d are not a sorted filtration of the %dx%dx%d grid", n, W,
                     H, D);
@@ -473,7 +331,7 @@ int mvd_cub3d_target_count(const float *target, int N, int D, int H, int W, int 
     int32_t *labels = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(ws) + al256((size_t)V));
     int32_t *flags = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(labels) + al256((size_t)V * 4));  // [V] + 1 scratch
     for (int n = 0; n < N; n++) {
-        hipLaunchKernelGGL(k_cub3d_target_mask, dim3(ew_blocks(V)), dim3(256), 0, s, target + (long)n * V, mask, V, dim);
+        hipLaunchKernelGGL(k_cub3d_target_mask, dim3(ew_blocks(V, 8192)), dim3(256), 0, s, target + (long)n * V, mask, V, dim);
         if (check_launch("cub3d_target_mask")) return 1;
         if (dim == 0) {
             if (int rc = mvd_cc_label(mask, labels, m + n, D, H, W, 26, stream)) return rc;
@@ -484,8 +342,8 @@ int mvd_cub3d_target_count(const float *target, int N, int D, int H, int W, int 
                 set_error("cub3d_target_count: memset failed");
                 return 1;
             }
-            hipLaunchKernelGGL(k_cub3d_border_flags, dim3(ew_blocks(V)), dim3(256), 0, s, labels, flags, D, H, W);
-            hipLaunchKernelGGL(k_cub3d_count_enclosed, dim3(ew_blocks(V)), dim3(256), 0, s, labels, flags, V, m + n);
+            hipLaunchKernelGGL(k_cub3d_border_flags, dim3(ew_blocks(V, 8192)), dim3(256), 0, s, labels, flags, D, H, W);
+            hipLaunchKernelGGL(k_cub3d_count_enclosed, dim3(ew_blocks(V, 8192)), dim3(256), 0, s, labels, flags, V, m + n);
         }
         if (check_launch("cub3d_target_count")) return 1;
     }

@@ -22,14 +22,9 @@
 //   device: top-k bar lengths, the fused loss (fp64, fixed order), its gradient and the diagram gradient: every sum runs
 //           in a fixed order, without float atomics.
 // Comparison / integer work up to the lengths; each length is one fp32 subtraction.
-#include "common.h"
-
-#include <hipcub/hipcub.hpp>
+#include "persist_common.h"
 
 #include <math.h>
-
-#include <thread>
-#include <vector>
 
 namespace mvd {
 
@@ -59,22 +54,6 @@ __host__ __device__ inline Ls2dGeom ls2d_geom(int H, int W, int maxdim) {
     g.T = maxdim >= 1 ? 2 * g.Ed : 0;
     g.n = g.V + g.E + g.T;
     return g;
-}
-
-__host__ __device__ inline uint32_t ls2d_f2ord(float v) {
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__host__ __device__ inline float ls2d_ord2f(uint32_t k) {
-    uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    float v;
-    memcpy(&v, &u, 4);
-    return v;
-}
-__host__ __device__ inline float ls2d_sign(float v, int sublevel) {
-    float g = sublevel ? v : -v;
-    return g == 0.f ? 0.f : g;
 }
 
 // the two vertices of edge e (u < v)
@@ -115,35 +94,27 @@ __global__ void k_ls2d_keys(const float *__restrict__ x, uint64_t *__restrict__ 
         float val;
         uint32_t lo;
         if (c < g.V) {
-            val = ls2d_sign(f[c], sublevel);
+            val = fold_sign(f[c], !sublevel);
             lo = (uint32_t)c;
         } else if (c < g.V + g.E) {
             long u, v;
             ls2d_edge_vertices(g, c - g.V, &u, &v);
-            const float a = ls2d_sign(f[u], sublevel), d = ls2d_sign(f[v], sublevel);
+            const float a = fold_sign(f[u], !sublevel), d = fold_sign(f[v], !sublevel);
             val = a < d ? d : a;
             lo = (1u << 30) | (uint32_t)(c - g.V);
         } else {
             long u, v, w;
             ls2d_tri_vertices(g, c - g.V - g.E, &u, &v, &w);
-            const float a = ls2d_sign(f[u], sublevel), d = ls2d_sign(f[v], sublevel), e = ls2d_sign(f[w], sublevel);
+            const float a = fold_sign(f[u], !sublevel), d = fold_sign(f[v], !sublevel), e = fold_sign(f[w], !sublevel);
             val = a < d ? d : a;
             val = val < e ? e : val;
             lo = (2u << 30) | (uint32_t)(c - g.V - g.E);
         }
-        keys[q] = ((uint64_t)ls2d_f2ord(val) << 32) | lo;
+        keys[q] = ((uint64_t)f2ord(val) << 32) | lo;
     }
 }
 
 // ------------------------------------------------------------------------------------------------------------ host pairing
-static inline int32_t ls2d_find(int32_t *p, int32_t x) {
-    while (p[x] != x) {
-        p[x] = p[p[x]];
-        x = p[x];
-    }
-    return x;
-}
-
 // bars row r of one problem: {bits of the birth value, bits of the death value, birth critical vertex, death critical vertex}
 static inline void ls2d_put(int32_t *row, float birth, float death, int32_t bv, int32_t dv) {
     memcpy(row, &birth, 4);
@@ -162,7 +133,7 @@ static int ls2d_pair_one(const uint64_t *keys, const Ls2dGeom &g, int sublevel, 
     // dimension 0: forward sweep, the component founded later (larger position in the order) dies
     for (long i = 0; i < n; i++) {
         const uint32_t lo = (uint32_t)keys[i], dim = lo >> 30, idx = lo & LS2D_IDX_MASK;
-        const float val = ls2d_ord2f((uint32_t)(keys[i] >> 32));
+        const float val = ord2f((uint32_t)(keys[i] >> 32));
         if (dim > 2 || (i > 0 && keys[i] < keys[i - 1])) return 1;
         if ((dim == 0 && idx >= V) || (dim == 1 && idx >= E) || (dim == 2 && idx >= T)) return 1;
         seen[dim]++;
@@ -174,7 +145,7 @@ static int ls2d_pair_one(const uint64_t *keys, const Ls2dGeom &g, int sublevel, 
         } else if (dim == 1) {
             long u, v;
             ls2d_edge_vertices(g, idx, &u, &v);
-            const int32_t a = ls2d_find(par.data(), (int32_t)u), b = ls2d_find(par.data(), (int32_t)v);
+            const int32_t a = uf_find(par.data(), (int32_t)u), b = uf_find(par.data(), (int32_t)v);
             if (a == b) {
                 edge_row[idx] = -1;  // opens a 1-cycle: paired in the backward sweep
                 continue;
@@ -217,7 +188,7 @@ static int ls2d_pair_one(const uint64_t *keys, const Ls2dGeom &g, int sublevel, 
                 t1 = (int32_t)(2 * s);
                 t2 = (int32_t)(2 * s + 1);
             }
-            const int32_t a = ls2d_find(par.data(), t1), b = ls2d_find(par.data(), t2);
+            const int32_t a = uf_find(par.data(), t1), b = uf_find(par.data(), t2);
             if (a == b) return 1;  // a positive edge always separates two dual components
             const int32_t dying = tpos[a] < tpos[b] ? a : b, keep = dying == a ? b : a;
             long u, v, x, y, z;
@@ -225,7 +196,7 @@ static int ls2d_pair_one(const uint64_t *keys, const Ls2dGeom &g, int sublevel, 
             ls2d_tri_vertices(g, dying, &x, &y, &z);
             const int32_t bv = (int32_t)(gv[u] >= gv[v] ? u : v);
             const int32_t dv = (int32_t)((gv[x] >= gv[y] && gv[x] >= gv[z]) ? x : (gv[y] >= gv[z] ? y : z));
-            ls2d_put(bars + 4 * (V + dying), sgn * ls2d_ord2f((uint32_t)(keys[i] >> 32)), sgn * tval[dying], bv, dv);
+            ls2d_put(bars + 4 * (V + dying), sgn * ord2f((uint32_t)(keys[i] >> 32)), sgn * tval[dying], bv, dv);
             edge_row[idx] = (int32_t)(V + dying);
             par[dying] = keep;
         }
@@ -505,9 +476,7 @@ int mvd_ls2d_sorted_keys(const float *x, int B, int C, int H, int W, const int *
     const size_t need = mvd_ls2d_workspace_bytes(P, H, W, maxdim);
     MVD_REQUIRE(need && ws_bytes >= need, "ls2d_sorted_keys: workspace too small");
     hipStream_t s = as_stream(stream);
-    long bx = cdiv(total, 256);
-    if (bx > 8192) bx = 8192;
-    hipLaunchKernelGGL(k_ls2d_keys, dim3(bx), dim3(256), 0, s, x, keys_sorted, B, C, chs, g, sublevel);
+    hipLaunchKernelGGL(k_ls2d_keys, dim3(ew_blocks(total, 8192)), dim3(256), 0, s, x, keys_sorted, B, C, chs, g, sublevel);
     if (check_launch("ls2d_keys")) return 1;
     if (g.n < 2) return 0;
     for (int p = 0; p < P; p++) {  // the sorts share the temporary storage: they run in stream order
@@ -532,22 +501,11 @@ int mvd_ls2d_pair_host(const uint64_t *keys_host, int P, int H, int W, int suble
     const Ls2dGeom g = ls2d_geom(H, W, maxdim);
     MVD_REQUIRE(edge_row || g.E == 0, "ls2d_pair_host: edge_row is null");
     MVD_REQUIRE(g.V < (1L << 30) && g.E + g.T < (1L << 30), "ls2d_pair_host: too many cells");
-    int nt = n_threads < 1 ? 1 : (n_threads > 16 ? 16 : n_threads);
-    if (nt > P) nt = P;
     std::vector<int> rc((size_t)P, 0);
-    auto work = [&](int t) {
-        for (int p = t; p < P; p += nt)
-            rc[p] = ls2d_pair_one(keys_host + (long)p * g.n, g, sublevel, bars + (long)p * (g.V + g.T) * 4,
-                                  edge_row + (long)p * g.E);
-    };
-    if (nt == 1) {
-        work(0);
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nt; t++) pool.emplace_back(work, t);
-        work(0);
-        for (auto &th : pool) th.join();
-    }
+    host_pool(P, n_threads, [&](int p) {
+        rc[p] = ls2d_pair_one(keys_host + (long)p * g.n, g, sublevel, bars + (long)p * (g.V + g.T) * 4,
+                              edge_row + (long)p * g.E);
+    });
     for (int p = 0; p < P; p++)
         MVD_REQUIRE(rc[p] == 0, "ls2d_pair_host: the keys of problem %d are not a sorted filtration of the %dx%d grid", p, W, H);
     return 0;
@@ -642,9 +600,7 @@ int mvd_ls2d_count_bars(const int32_t *bars, int P, int H, int W, int sublevel, 
 int mvd_ls2d_onehot(const float *label, float *planes, int B, int C, long V, void *stream) {
     MVD_REQUIRE(label && planes && B > 0 && C > 0 && V > 0, "ls2d_onehot: bad arguments");
     hipStream_t s = as_stream(stream);
-    long bx = cdiv((long)B * C * V, 256);
-    if (bx > 8192) bx = 8192;
-    hipLaunchKernelGGL(k_ls2d_onehot, dim3(bx), dim3(256), 0, s, label, planes, B, C, V);
+    hipLaunchKernelGGL(k_ls2d_onehot, dim3(ew_blocks((long)B * C * V, 8192)), dim3(256), 0, s, label, planes, B, C, V);
     return check_launch("ls2d_onehot");
 }
 }

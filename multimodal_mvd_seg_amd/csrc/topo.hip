@@ -1,7 +1,7 @@
 // Soft-skeleton primitives (erode / dilate / skeleton update) on planar volumes and the integer
 // connected-component labelling (K12).  Compiled with -ffp-contract=off: `delta - skel*delta` must round the product
 // (torch does mul then sub) for bit-exact forward parity.
-#include "common.h"
+#include "persist_common.h"
 
 namespace mvd {
 
@@ -415,13 +415,8 @@ __device__ inline void cc_union(int32_t *parent, int32_t a, int32_t b) {
     }
 }
 
-struct CcOffsets {
-    int n;
-    int off[13][3];
-};
-
 __global__ void k_cc_merge(const uint8_t *__restrict__ mask, int32_t *__restrict__ parent, int D, int H, int W,
-                           CcOffsets offs) {
+                           GridOffsets offs) {
     const long HW = (long)H * W, total = (long)D * HW;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         if (!mask[i]) continue;
@@ -571,35 +566,6 @@ __global__ void k_seg_remove_components(const int32_t *__restrict__ seg, const i
 
 using namespace mvd;
 
-static inline long ew_grid(long n) {
-    long b = cdiv(n, 256);
-    return b > 4096 ? 4096 : (b < 1 ? 1 : b);
-}
-
-static int fill_offsets(int conn, CcOffsets *o) {
-    o->n = 0;
-    if (conn == 6) {
-        int t[3][3] = {{0, 0, 1}, {0, 1, 0}, {1, 0, 0}};
-        for (int i = 0; i < 3; i++) memcpy(o->off[o->n++], t[i], sizeof(int) * 3);
-    } else if (conn == 14) {
-        int t[7][3] = {{0, 0, 1}, {0, 1, 0}, {1, 0, 0}, {0, 1, 1}, {1, 0, 1}, {1, 1, 0}, {1, 1, 1}};
-        for (int i = 0; i < 7; i++) memcpy(o->off[o->n++], t[i], sizeof(int) * 3);
-    } else if (conn == 26) {
-        for (int dz = 0; dz <= 1; dz++)
-            for (int dy = -1; dy <= 1; dy++)
-                for (int dx = -1; dx <= 1; dx++) {
-                    if (dz == 0 && (dy < 0 || (dy == 0 && dx <= 0))) continue;
-                    o->off[o->n][0] = dz;
-                    o->off[o->n][1] = dy;
-                    o->off[o->n][2] = dx;
-                    o->n++;
-                }
-    } else {
-        return 1;
-    }
-    return 0;
-}
-
 extern "C" {
 
 #define VOL_CHECK(name)                                                                                        \
@@ -609,28 +575,28 @@ int mvd_soft_erode_fwd(const float *x, float *y, uint16_t *code, int NC, int D, 
     MVD_REQUIRE(x && y, "soft_erode_fwd: null pointer");
     VOL_CHECK("soft_erode_fwd");
     long total = (long)NC * D * H * W;
-    hipLaunchKernelGGL(k_erode_fwd, dim3(ew_grid(total)), dim3(256), 0, as_stream(stream), x, y, code, total, D, H, W);
+    hipLaunchKernelGGL(k_erode_fwd, dim3(ew_blocks(total, 4096)), dim3(256), 0, as_stream(stream), x, y, code, total, D, H, W);
     return check_launch("soft_erode_fwd");
 }
 int mvd_soft_erode_bwd(const uint16_t *code, const float *dy, float *dx, int NC, int D, int H, int W, void *stream) {
     MVD_REQUIRE(code && dy && dx, "soft_erode_bwd: null pointer");
     VOL_CHECK("soft_erode_bwd");
     long total = (long)NC * D * H * W;
-    hipLaunchKernelGGL(k_erode_bwd, dim3(ew_grid(total)), dim3(256), 0, as_stream(stream), code, dy, dx, total, D, H, W);
+    hipLaunchKernelGGL(k_erode_bwd, dim3(ew_blocks(total, 4096)), dim3(256), 0, as_stream(stream), code, dy, dx, total, D, H, W);
     return check_launch("soft_erode_bwd");
 }
 int mvd_soft_dilate_fwd(const float *x, float *y, uint8_t *code, int NC, int D, int H, int W, void *stream) {
     MVD_REQUIRE(x && y, "soft_dilate_fwd: null pointer");
     VOL_CHECK("soft_dilate_fwd");
     long total = (long)NC * D * H * W;
-    hipLaunchKernelGGL(k_dilate_fwd, dim3(ew_grid(total)), dim3(256), 0, as_stream(stream), x, y, code, total, D, H, W);
+    hipLaunchKernelGGL(k_dilate_fwd, dim3(ew_blocks(total, 4096)), dim3(256), 0, as_stream(stream), x, y, code, total, D, H, W);
     return check_launch("soft_dilate_fwd");
 }
 int mvd_soft_dilate_bwd(const uint8_t *code, const float *dy, float *dx, int NC, int D, int H, int W, void *stream) {
     MVD_REQUIRE(code && dy && dx, "soft_dilate_bwd: null pointer");
     VOL_CHECK("soft_dilate_bwd");
     long total = (long)NC * D * H * W;
-    hipLaunchKernelGGL(k_dilate_bwd, dim3(ew_grid(total)), dim3(256), 0, as_stream(stream), code, dy, dx, total, D, H,
+    hipLaunchKernelGGL(k_dilate_bwd, dim3(ew_blocks(total, 4096)), dim3(256), 0, as_stream(stream), code, dy, dx, total, D, H,
                        W);
     return check_launch("soft_dilate_bwd");
 }
@@ -638,7 +604,7 @@ int mvd_soft_dilate_bwd(const uint8_t *code, const float *dy, float *dx, int NC,
 int mvd_skel_update_fwd(const float *img, const float *opened, const float *skel_in, float *skel_out, long n, int init,
                         void *stream) {
     MVD_REQUIRE(img && opened && skel_out && (init || skel_in) && n > 0, "skel_update_fwd: bad arguments");
-    hipLaunchKernelGGL(k_skel_update_fwd, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), img, opened, skel_in,
+    hipLaunchKernelGGL(k_skel_update_fwd, dim3(ew_blocks(n, 4096)), dim3(256), 0, as_stream(stream), img, opened, skel_in,
                        skel_out, n, init);
     return check_launch("skel_update_fwd");
 }
@@ -646,7 +612,7 @@ int mvd_skel_update_bwd(const float *img, const float *opened, const float *skel
                         float *d_img, float *d_opened, float *d_skel_in, long n, int init, void *stream) {
     MVD_REQUIRE(img && opened && d_skel_out && d_img && d_opened && (init || (skel_in && d_skel_in)) && n > 0,
                 "skel_update_bwd: bad arguments");
-    hipLaunchKernelGGL(k_skel_update_bwd, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), img, opened, skel_in,
+    hipLaunchKernelGGL(k_skel_update_bwd, dim3(ew_blocks(n, 4096)), dim3(256), 0, as_stream(stream), img, opened, skel_in,
                        d_skel_out, d_img, d_opened, d_skel_in, n, init);
     return check_launch("skel_update_bwd");
 }
@@ -694,15 +660,15 @@ int mvd_cldice_combine(const float *sums, float *out, float smooth, void *stream
 
 int mvd_threshold_mask(const float *f, uint8_t *mask, long n, float thr, int ge, void *stream) {
     MVD_REQUIRE(f && mask && n > 0, "threshold_mask: bad arguments");
-    hipLaunchKernelGGL(k_threshold, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), f, mask, n, thr, ge);
+    hipLaunchKernelGGL(k_threshold, dim3(ew_blocks(n, 4096)), dim3(256), 0, as_stream(stream), f, mask, n, thr, ge);
     return check_launch("threshold_mask");
 }
 
 int mvd_cc_label(const uint8_t *mask, int32_t *labels, int32_t *count, int D, int H, int W, int conn, void *stream) {
     MVD_REQUIRE(mask && labels && count, "cc_label: null pointer");
     MVD_REQUIRE(D > 0 && H > 0 && W > 0 && (long)D * H * W < 2147483647L, "cc_label: bad grid (int32 labels)");
-    CcOffsets offs;
-    MVD_REQUIRE(fill_offsets(conn, &offs) == 0, "cc_label: conn must be 6, 14 or 26");
+    GridOffsets offs;
+    MVD_REQUIRE(grid_half_offsets(conn, &offs) == 0, "cc_label: conn must be 6, 14 or 26");
     long n = (long)D * H * W;
     hipStream_t s = as_stream(stream);
     if (hipMemsetAsync(count, 0, sizeof(int32_t), s) != hipSuccess) {
@@ -710,12 +676,12 @@ int mvd_cc_label(const uint8_t *mask, int32_t *labels, int32_t *count, int D, in
         return 1;
     }
     // `labels` doubles as the parent forest until the last two passes
-    hipLaunchKernelGGL(k_cc_init, dim3(ew_grid(n)), dim3(256), 0, s, mask, labels, n);
-    hipLaunchKernelGGL(k_cc_merge, dim3(ew_grid(n)), dim3(256), 0, s, mask, labels, D, H, W, offs);
-    hipLaunchKernelGGL(k_cc_flatten, dim3(ew_grid(n)), dim3(256), 0, s, labels, count, n);
+    hipLaunchKernelGGL(k_cc_init, dim3(ew_blocks(n, 4096)), dim3(256), 0, s, mask, labels, n);
+    hipLaunchKernelGGL(k_cc_merge, dim3(ew_blocks(n, 4096)), dim3(256), 0, s, mask, labels, D, H, W, offs);
+    hipLaunchKernelGGL(k_cc_flatten, dim3(ew_blocks(n, 4096)), dim3(256), 0, s, labels, count, n);
     if (check_launch("cc_label merge")) return 1;
-    hipLaunchKernelGGL(k_cc_compress, dim3(ew_grid(n)), dim3(256), 0, s, labels, n);
-    hipLaunchKernelGGL(k_cc_finish, dim3(ew_grid(n)), dim3(256), 0, s, labels, n);
+    hipLaunchKernelGGL(k_cc_compress, dim3(ew_blocks(n, 4096)), dim3(256), 0, s, labels, n);
+    hipLaunchKernelGGL(k_cc_finish, dim3(ew_blocks(n, 4096)), dim3(256), 0, s, labels, n);
     return check_launch("cc_label relabel");
 }
 
@@ -725,7 +691,7 @@ int mvd_seg_label_mask(const int32_t *seg, uint8_t *mask, long n, const int32_t 
     LabelSet ls;
     ls.n = nlabels;
     for (int i = 0; i < 16; i++) ls.v[i] = i < nlabels ? label_set[i] : 0;  // host array, passed by value
-    hipLaunchKernelGGL(k_seg_label_mask, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), seg, mask, n, ls);
+    hipLaunchKernelGGL(k_seg_label_mask, dim3(ew_blocks(n, 4096)), dim3(256), 0, as_stream(stream), seg, mask, n, ls);
     return check_launch("seg_label_mask");
 }
 
@@ -738,7 +704,7 @@ int mvd_cc_component_sizes(const int32_t *cc_labels, int32_t *sizes, long n, voi
         return 1;
     }
     constexpr int RUN = 16;
-    hipLaunchKernelGGL(k_cc_sizes<RUN>, dim3(ew_grid(cdiv(n, RUN))), dim3(256), 0, s, cc_labels, sizes, n);
+    hipLaunchKernelGGL(k_cc_sizes<RUN>, dim3(ew_blocks(cdiv(n, RUN), 4096)), dim3(256), 0, s, cc_labels, sizes, n);
     return check_launch("cc_component_sizes");
 }
 
@@ -762,7 +728,7 @@ int mvd_seg_remove_components(const int32_t *seg, const int32_t *cc_labels, cons
                               int background, void *stream) {
     MVD_REQUIRE(seg && cc_labels && kept && out, "seg_remove_components: null pointer");
     MVD_REQUIRE(n > 0, "seg_remove_components: empty");
-    hipLaunchKernelGGL(k_seg_remove_components, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), seg, cc_labels, kept,
+    hipLaunchKernelGGL(k_seg_remove_components, dim3(ew_blocks(n, 4096)), dim3(256), 0, as_stream(stream), seg, cc_labels, kept,
                        out, n, (int32_t)background);
     return check_launch("seg_remove_components");
 }

@@ -5,7 +5,9 @@ arithmetic operation of the hot path runs in libmvdseg_hip.so.  Activations are 
 [N,C,D,H,W] stored NDHWC (torch.channels_last_3d); logits / targets / volumes of the topology losses are planar.
 """
 import ctypes
+import functools
 import os
+import time
 import typing
 import weakref
 
@@ -2066,6 +2068,14 @@ def cc_label(mask, conn=6):
     return labels, count
 
 
+@functools.lru_cache(maxsize=None)
+def _h0_slots(conn):
+    """Key slots per vertex, from the library's own half-neighbourhood: the n offsets (dz, dy, dx), all in -1..1, give an
+    L^3 grid sum (L - |dz|)(L - |dy|)(L - |dx|) edges, a number in (n (L-1)^3, n L^3]; for n <= 13 and L = 64 the
+    intervals of different n are disjoint, so n = ceil(edges / L^3)."""
+    return -(-query("mvd_h0_num_edges", 64, 64, 64, conn) // 64 ** 3)
+
+
 def h0_persistence(f, conn=6, sublevel=True):
     """H0 persistence of a [D,H,W] device field: (birth [N], death [N], death_vertex [N]) as CPU tensors, one bar per
     vertex in linear-index order (the reference's C++ also returns its diagrams on the CPU, functional/sublevel.py:26-49).
@@ -2081,8 +2091,7 @@ def h0_persistence(f, conn=6, sublevel=True):
         raise RuntimeError("h0_persistence: conn must be 6, 14 or 26")
     nb = query("mvd_h0_workspace_bytes", D, H, W, int(conn))
     ws = _Workspace.get(nb, x.device)
-    noff = {6: 3, 14: 7, 26: 13}[int(conn)]
-    keys = torch.empty((D * H * W * noff,), dtype=torch.int64, device=x.device)
+    keys = torch.empty((D * H * W * _h0_slots(int(conn)),), dtype=torch.int64, device=x.device)
     call("mvd_h0_sorted_edges", _p(x), _p(keys), D, H, W, int(conn), int(bool(sublevel)), _p(ws), ws.numel(), _stream())
     keys_h = keys[:ne].cpu()          # synchronises the stream
     f_h = x.cpu()
@@ -2137,9 +2146,37 @@ def ls2d_num_cells(H, W, maxdim=1):
     return n, nv.value, ne.value, nt.value
 
 
+class _StageTimer:
+    """Optional split of one "device keys + sort -> one D2H -> host pairing -> one H2D" round trip into the four times that
+    `sink` (Ls2dTimes, Cub3dTimes) reports.  With `sink.on` false (the default) nothing is recorded and nothing waits.  Else
+    the device stage is timed by two events, the host stages by the clock, and the stream is drained after the sort and
+    after the H2D copy -- the two marks with device work in flight -- so that every stage is timed alone."""
+    KEYS = ("keys_sort_ms", "d2h_ms", "host_sweep_ms", "h2d_ms")
+
+    def __init__(self, sink):
+        self.sink, self.on, self.t = sink, sink.on, []
+        if self.on:
+            self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            self.ev[0].record()
+
+    def mark(self):
+        """the end of the next stage of KEYS"""
+        if not self.on:
+            return
+        if not self.t:
+            self.ev[1].record()
+        if len(self.t) in (0, 3):
+            torch.cuda.current_stream().synchronize()
+        self.t.append(time.perf_counter())
+
+    def store(self, **extra):
+        if self.on:
+            ms = [self.ev[0].elapsed_time(self.ev[1])] + [(b - a) * 1e3 for a, b in zip(self.t, self.t[1:])]
+            self.sink.last = dict(zip(self.KEYS, ms), **extra)
+
+
 class Ls2dTimes:
-    """Optional split of one levelset2d_persistence call (tools/bench_topoloss.py): set `Ls2dTimes.on = True`.  The timed
-    call synchronises after the sort, so that the D2H copy is timed alone."""
+    """Optional split of one levelset2d_persistence call (tools/bench_topoloss.py): set `Ls2dTimes.on = True`."""
     on = False
     last = None
 
@@ -2166,34 +2203,20 @@ def levelset2d_persistence(x, channels, sublevel, maxdim=1):
         raise RuntimeError(f"levelset2d_persistence: {P} problems of {W}x{H} do not fit one sort (2^31 cells)")
     ws = _Workspace.get(nb, x.device)
     keys = torch.empty((P, n), dtype=torch.int64, device=x.device)
-    timed = Ls2dTimes.on
-    if timed:
-        import time
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        ev[0].record()
+    tm = _StageTimer(Ls2dTimes)
     call("mvd_ls2d_sorted_keys", _p(x), B, C, H, W, ch, nch, int(bool(sublevel)), int(maxdim), _p(keys), _p(ws), ws.numel(),
          _stream())
-    if timed:
-        ev[1].record()
-        ev[1].synchronize()
-        tc = time.perf_counter()
+    tm.mark()
     keys_h = keys.cpu()               # the one D2H copy; synchronises the stream
-    if timed:
-        t0 = time.perf_counter()
+    tm.mark()
     out_h = torch.empty((P * (V + T) * 4 + P * E,), dtype=torch.int32)
     bars_h, er_h = out_h[:P * (V + T) * 4], out_h[P * (V + T) * 4:]
     call("mvd_ls2d_pair_host", _p(keys_h), P, H, W, int(bool(sublevel)), int(maxdim), _p(bars_h), _p(er_h),
          LS2D_HOST_THREADS)
-    if timed:
-        t1 = time.perf_counter()
-        ev[2].record()
+    tm.mark()
     out = out_h.to(x.device)          # the one H2D copy
-    if timed:
-        ev[3].record()
-        ev[3].synchronize()
-        t2 = time.perf_counter()
-        Ls2dTimes.last = {"keys_sort_ms": ev[0].elapsed_time(ev[1]), "d2h_ms": (t0 - tc) * 1e3,
-                          "host_sweep_ms": (t1 - t0) * 1e3, "h2d_ms": (t2 - t1) * 1e3}
+    tm.mark()
+    tm.store()
     return out[:P * (V + T) * 4].view(P, V + T, 4), out[P * (V + T) * 4:].view(P, E)
 
 
@@ -2348,8 +2371,7 @@ CUB3D_HOST_THREADS = 16   # upper bound of the host pairing pool (never sized by
 
 
 class Cub3dTimes:
-    """Optional split of one cubical loss step (tools/bench_cubical_topo.py): set `Cub3dTimes.on = True`.  The timed calls
-    synchronise between the parts, so that each is timed alone."""
+    """Optional split of one cubical loss step (tools/bench_cubical_topo.py): set `Cub3dTimes.on = True`."""
     on = False
     last = None
 
@@ -2388,35 +2410,24 @@ def _cub3d_bars(x, dim):
     nv = nv.value
     ws = _Workspace.get(nb, x.device)
     keys = torch.empty((N, slots), dtype=torch.int64, device=x.device)
-    timed = Cub3dTimes.on
-    if timed:
-        import time
-        torch.cuda.synchronize()
-        t = [time.perf_counter()]
+    tm = _StageTimer(Cub3dTimes)
     call("mvd_cub3d_sorted_keys", _p(x), N, D, H, W, dim, _p(keys), _p(ws), ws.numel(), _stream())
-    if timed:
-        torch.cuda.synchronize()
-        t.append(time.perf_counter())
+    tm.mark()
     keys_h = keys[:, :nv].cpu()       # synchronises the stream
     f_h = x.cpu()
-    if timed:
-        t.append(time.perf_counter())
+    tm.mark()
     bars_h = torch.empty((N, V, 2), dtype=torch.int32)
     counts = torch.empty((N,), dtype=torch.int32)
     call("mvd_cub3d_pair_host", _p(f_h), _p(keys_h), nv, N, D, H, W, dim, _p(bars_h), _p(counts), CUB3D_HOST_THREADS)
-    if timed:
-        t.append(time.perf_counter())
+    tm.mark()
     cnt = counts.numpy().astype(np.int64)
     offsets = np.zeros(N + 1, dtype=np.int32)
     offsets[1:] = np.cumsum(cnt)
     packed = torch.cat([bars_h[n, :int(cnt[n])] for n in range(N)]) if N > 1 else bars_h[0, :int(cnt[0])]
     bars = packed.contiguous().to(x.device)
     offsets_dev = torch.from_numpy(offsets).to(x.device)
-    if timed:
-        torch.cuda.synchronize()
-        t.append(time.perf_counter())
-        Cub3dTimes.last = {"keys_sort_ms": (t[1] - t[0]) * 1e3, "d2h_ms": (t[2] - t[1]) * 1e3,
-                           "host_sweep_ms": (t[3] - t[2]) * 1e3, "h2d_ms": (t[4] - t[3]) * 1e3, "bars": int(offsets[-1])}
+    tm.mark()
+    tm.store(bars=int(offsets[-1]))
     return bars, offsets, offsets_dev
 
 
@@ -2506,7 +2517,6 @@ class CubicalWassersteinFn(Function):
         bars, offsets, offsets_dev = _cub3d_bars(x, dim)
         timed = Cub3dTimes.on
         if timed:
-            import time
             t0 = time.perf_counter()
         N, V, n_total = x.shape[0], x[0].numel(), int(offsets[-1])
         ws = _Workspace.get(query("mvd_cub3d_match_workspace_bytes", n_total), x.device)

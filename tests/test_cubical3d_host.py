@@ -99,6 +99,30 @@ def test_host_pairing_equals_the_restatement(shape, dim, levels):
             assert got[n].tolist() == [list(r) for r in want]            # same tie rules: the same sweep
 
 
+def h0_rows(f, death, dv):
+    """the dimension-0 cubical rows read off the conn-26 sublevel H0 pairing: its finite bars of non-zero length"""
+    flat = np.asarray(f, dtype=np.float32).reshape(-1)
+    keep = (dv >= 0) & (death > flat)
+    return np.stack([np.nonzero(keep)[0], dv[keep]], 1).astype(np.int32)
+
+
+def test_dimension_0_is_the_26_connected_h0_pairing():
+    """mvd_cub3d_pair_host(dim 0) and mvd_h0_pair_host(conn 26, sublevel) run one sweep on one key array"""
+    import test_h0_host as H0
+    most = 0
+    for shape in SHAPES + [(1, 1, 7)]:
+        for levels in (None, 6):
+            f = R.field(shape, 100 + 7 * sum(shape), levels)
+            assert np.array_equal(R.sorted_keys(f, 0), H0.host_sorted_keys(f, 26, True))
+            rows = R.pair_host(f[None], 0)[0]
+            rows = rows[np.argsort(rows[:, 0], kind="stable")]
+            _, death, dv, _ = H0.pair(f, 26, True)
+            want = h0_rows(f, death, dv)
+            assert rows.dtype == want.dtype and np.array_equal(rows, want), (shape, levels)
+            most = max(most, len(rows))
+    assert most >= 20
+
+
 def test_host_pairing_is_the_same_over_the_thread_pool():
     f = np.stack([R.field((6, 7, 9), s, 6 if s % 2 else None) for s in range(20)])
     for dim in (0, 2):

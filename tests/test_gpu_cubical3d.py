@@ -52,6 +52,23 @@ def test_device_bars_equal_the_restatement(shape, dim, levels):
         assert (flat[g[:, 1]] > flat[g[:, 0]]).all()                       # the gather invariant: b < d, both from the field
 
 
+@pytest.mark.parametrize("shape", [(6, 7, 9), (1, 1, 7)])
+@pytest.mark.parametrize("levels", [None, 6])
+def test_dimension_0_equals_the_26_connected_h0_pairing(shape, levels):
+    """the one key kernel through both of its entry points: the dimension-0 rows are the finite bars of non-zero length of
+    ops.h0_persistence(conn 26, sublevel)"""
+    ops = _ops()
+    x = torch.from_numpy(R.field(shape, 100 + 7 * sum(shape), levels)).to(DEV)
+    rows = ops.cubical3d_persistence(x[None], 0)[0].cpu().numpy()
+    rows = rows[np.argsort(rows[:, 0], kind="stable")]
+    birth, death, dv = (t.numpy() for t in ops.h0_persistence(x, 26, True))
+    keep = (dv >= 0) & (death > birth)
+    want = np.stack([np.nonzero(keep)[0], dv[keep]], 1).astype(np.int32)
+    assert rows.dtype == want.dtype and np.array_equal(rows, want)
+    if shape == (6, 7, 9) and levels is None:
+        assert len(rows) >= 20
+
+
 @pytest.mark.parametrize("dim", [0, 2])
 def test_constant_field_and_negative_zero(dim):
     ops = _ops()

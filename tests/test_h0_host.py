@@ -1,6 +1,6 @@
 """CPU tests of the HOST half of the H0 pairing (mvd_h0_pair_host in libmvdseg_hip.so is plain C++; the device half --
 edge keys + radix sort -- is exercised by the -m gpu tests).  The edge keys are built here in numpy with the formula of
-csrc/persist.hip::k_h0_edge_keys and sorted with numpy, then paired by the library and compared with the reference's own
+csrc/persist_common.h::k_grid_edge_keys and sorted with numpy, then paired by the library and compared with the reference's own
 C++ diagrams (tests/golden/persistence_grid.json, multisets) and with oracle/cc_oracle.c (element for element)."""
 import ctypes
 import json
@@ -93,3 +93,15 @@ def test_host_pairing_rejects_inconsistent_input():
     P = lambda a: ctypes.c_void_p(a.ctypes.data)
     assert lib.mvd_h0_pair_host(P(f), P(keys), 5, 2, 2, 2, 6, 1, P(death), P(dv)) < 0   # 12 edges expected
     assert lib.mvd_h0_num_edges(2, 2, 2, 7) < 0
+    # with the right count: keys that are not ascending, and a slot index past V * n_off = 8 * 3
+    f = np.arange(8, dtype=np.float32).reshape(2, 2, 2)
+    good = np.ascontiguousarray(host_sorted_keys(f, 6))
+    assert good.size == 12
+    swapped = good.copy()
+    swapped[[4, 5]] = swapped[[5, 4]]
+    past = good.copy()
+    past[-1] = (past[-1] & np.uint64(0xFFFFFFFF00000000)) | np.uint64(8 * 3)
+    for bad in (swapped, past):
+        assert lib.mvd_h0_pair_host(P(f), P(bad), 12, 2, 2, 2, 6, 1, P(death), P(dv)) < 0
+        assert len(lib.mvd_last_error()) > 10
+    assert lib.mvd_h0_pair_host(P(f), P(good), 12, 2, 2, 2, 6, 1, P(death), P(dv)) == 1
