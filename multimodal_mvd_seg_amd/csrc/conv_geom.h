@@ -218,6 +218,34 @@ inline void convT_wgrad_geom(WgradGeom &g, int N, int D, int H, int W, int C, in
     g.transposed_out = 1;
 }
 
+// ------------------------------------------------------------------------------------------------ tile walk (k_wgrad_wino3)
+// A split of k_wgrad_wino3 visits the tiles split, split + nsplit, ...; tile = ((n * ntd + td) * nth + th) * ntw + tw.
+// The walk keeps (tw, th, td, n) and adds the host-computed digits of nsplit with carries instead of dividing the tile
+// index again for every tile: a digit is below its extent, so a sum with a carry is below twice the extent and one
+// conditional subtraction per digit is enough.  n is not bounded: past the last tile it only says "no tile".
+// tests/host/wgrad_walk_main.cpp checks the walk against plain division.
+struct TileWalk {
+    int tw, th, td, n;
+};
+__host__ __device__ inline TileWalk tile_walk_at(int tile, int ntw, int nth, int ntd) {
+    TileWalk p;
+    unsigned r = (unsigned)tile;
+    p.tw = (int)(r % (unsigned)ntw); r /= (unsigned)ntw;
+    p.th = (int)(r % (unsigned)nth); r /= (unsigned)nth;
+    p.td = (int)(r % (unsigned)ntd);
+    p.n = (int)(r / (unsigned)ntd);
+    return p;
+}
+__host__ __device__ inline void tile_walk_advance(TileWalk &p, const TileWalk &d, int ntw, int nth, int ntd) {
+    int v = p.tw + d.tw, c = v >= ntw;
+    p.tw = c ? v - ntw : v;
+    v = p.th + d.th + c; c = v >= nth;
+    p.th = c ? v - nth : v;
+    v = p.td + d.td + c; c = v >= ntd;
+    p.td = c ? v - ntd : v;
+    p.n += d.n + c;
+}
+
 // engines (return 0 ok, >0 error, -1 = shape not supported by this engine)
 int fwd_scalar(const FwdGeom &g, const float *a1, const float *a2, const float *w, const float *bias, float *y1,
                float *y2, hipStream_t s);

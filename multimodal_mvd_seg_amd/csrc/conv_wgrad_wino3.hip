@@ -9,7 +9,10 @@
 //     k index is the octet: lane half h takes octet row 2s + h, so one tile is 8 steps (s = 0..1, quad column 0..3) of
 //     v_mfma_f32_32x32x2_f32;
 //   * 16 waves (four per SIMD, one workgroup per CU); wave (pz, a) owns the positions (pz, a, 0..3): 4 accumulator
-//     tiles = 64 accumulator registers;
+//     tiles = 64 accumulator registers; pz = wave >> 2, a = (wave + pz) & 3, so that the four waves of a SIMD are four
+//     different position rows, two pair copies and two single copies;
+//   * a split walks its tiles on the scalar unit: one division for its first tile, then the digits of nsplit are added
+//     with carries (conv_geom.h: tile_walk_at / tile_walk_advance);
 //   * the D stage of the input transform runs once, at staging: the 4 halo planes of a (row, column, 4-channel) entry
 //     become the 4 D-transformed planes of the same LDS slots, so the image keeps the 2-D kernel's size and two images
 //     (double buffering, one barrier per tile) fit; the H and W stages run on the fly exactly as in k_wgrad_wino2w12
@@ -19,7 +22,8 @@
 //     parameter: 8 code copies instead of 16);
 //   * the minus signs of A (row 3) are not applied: E of a position with pz, a or b = 3 is the negated value, and the
 //     reduce flips the sign of those partials back (exact in any precision);
-//   * bias gradient: wave (pz = 1, a = 0) of the c-block-0 workgroups sums e(z0) + e(z1) of every quad it fetches.
+//   * bias gradient: wave (pz = 1, a = 1) of the c-block-0 workgroups sums e(z0) + e(z1) of every quad it fetches (row
+//     a = 1 needs the whole quad for E anyway).
 // Partials [nsplit][64][C][K] (+ bias rows [nsplit][2][K]); no atomics, the reduce sums the splits in a fixed order.
 #include "common.h"
 #include "conv_geom.h"
@@ -32,6 +36,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 struct Wg3Tile {
     int ntd, nth, ntw;  // 2 x 8 x 8 tiles along D, H, W
     int ntiles, nsplit, nkb;
+    TileWalk step;  // tile_walk_at(nsplit): what a split adds per tile (conv_geom.h)
 };
 
 constexpr int W3_EA = 10, W3_EB = 8;                                          // halo rows / columns of A and of dy
@@ -70,18 +75,22 @@ __device__ __forceinline__ void wgrad_wino3_body(const int pz, const WgradGeom &
     // half-entry q = t + 1024 ph < 1600 (halo row / column q >> 4, 2-channel part q & 15) in all four planes (4 x b64);
     // dy phase: thread t owns the entry (slot t >> 3, 4-channel part t & 7) of the 2 x 8 x 8 tile (b128)
     const int planeA = g.Hi * g.Wi * Cs;  // plane z of the halo adds z * planeA
-    const int zb = tid >> 9, yb = (tid >> 6) & 7, xb = (tid >> 3) & 7;
-    const int relB = ((zb * g.Hb + yb) * g.Wb + xb) * K + k0 + (tid & 7) * 4;
+    unsigned relA[2];                      // byte offset of the thread's half-entry in plane 0 of the halo, per phase
+#pragma unroll
+    for (int ph = 0; ph < 2; ph++) {
+        const int q = tid + 1024 * ph, slot = q >> 4;
+        const int ya = slot / W3_EA, xa = slot - ya * W3_EA;
+        relA[ph] = (unsigned)((ya * g.Wi + xa) * Cs + cofs + (q & 15) * 2) * 4u;
+    }
+    const int relB = (((tid >> 9) * g.Hb + ((tid >> 6) & 7)) * g.Wb + ((tid >> 3) & 7)) * K + k0 + (tid & 7) * 4;
 
     v2f ra[4];
     float4 rb;
-    auto load_tile = [&](int tile, bool valid) {
-        unsigned r_ = (unsigned)(valid ? tile : 0);
-        const int tw_ = (int)(r_ % (unsigned)tg.ntw); r_ /= (unsigned)tg.ntw;
-        const int th_ = (int)(r_ % (unsigned)tg.nth); r_ /= (unsigned)tg.nth;
-        const int td_ = (int)(r_ % (unsigned)tg.ntd);
-        const int n = (int)(r_ / (unsigned)tg.ntd);
-        const int z0 = td_ * 2, y0 = th_ * 8, x0 = tw_ * 8;  // first dy voxel; the A halo starts one voxel before it
+    // pos: (tw, th, td, n) of the tile, kept by the tile walk (scalar unit); past the last tile: tile 0, no records
+    auto load_tile = [&](const TileWalk &pos, bool valid) {
+        const int n = valid ? pos.n : 0;
+        const int z0 = valid ? pos.td * 2 : 0, y0 = valid ? pos.th * 8 : 0, x0 = valid ? pos.tw * 8 : 0;
+        // (z0, y0, x0): first dy voxel; the A halo starts one voxel before it
         const bool intA = z0 >= 1 && y0 >= 1 && x0 >= 1 && z0 + 3 <= g.Di && y0 - 1 + W3_EA <= g.Hi && x0 - 1 + W3_EA <= g.Wi;
         const bool intB = z0 + 2 <= g.Db && y0 + W3_EB <= g.Hb && x0 + W3_EB <= g.Wb;
         const float *baseA = asrc + ((((long)n * g.Di + (z0 - 1)) * g.Hi + (y0 - 1)) * g.Wi + (x0 - 1)) * (long)Cs;
@@ -92,24 +101,35 @@ __device__ __forceinline__ void wgrad_wino3_body(const int pz, const WgradGeom &
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(baseA), 0, valid ? 0x7fffffff : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rB =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(baseB), 0, valid ? 0x7fffffff : 0, 0x00020000);
+        int pl4 = planeA * 4;
+        asm volatile("" : "+s"(pl4));
         struct Ld {
             __amdgpu_buffer_rsrc_t rA, rB;
             bool intA, intB;
-            int z0, y0, x0;
+            int z0, y0, x0, pl4;
         };
-        return Ld{rA, rB, intA, intB, z0, y0, x0};
+        return Ld{rA, rB, intA, intB, z0, y0, x0, pl4};
     };
     auto issue_a = [&](const auto &L, int ph) {
-        const int q = tid + 1024 * ph, slot = q >> 4;
-        const int ya = slot / W3_EA, xa = slot - ya * W3_EA;
-        const unsigned rel = (unsigned)((ya * g.Wi + xa) * Cs + cofs + (q & 15) * 2);
+        const int q = tid + 1024 * ph;
+        if (q >= 16 * W3_EA * W3_EA) return;  // store_a skips these threads too
+        // one register per phase lives across the tile loop (relA[ph]); the plane offsets are added here (L.pl4 is
+        // opaque to the optimiser, which would otherwise hold all eight sums), and the halo coordinates of a tile
+        // that crosses the volume's border are recomputed from the thread index in that branch only
+        bool inhw = true;  // the thread's halo row and column lie inside the volume
+        if (!L.intA) {     // block-uniform; VALU only inside
+            int q_ = q;
+            asm volatile("" : "+v"(q_));
+            const int ya = (q_ >> 4) / W3_EA, xa = (q_ >> 4) - ya * W3_EA;
+            const int ih = L.y0 - 1 + ya, iw = L.x0 - 1 + xa;
+            inhw = ih >= 0 && ih < g.Hi && iw >= 0 && iw < g.Wi;
+        }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            unsigned o = q < 16 * W3_EA * W3_EA ? (rel + (unsigned)(u * planeA)) * 4u : 0xffffffffu;
-            if (!L.intA) {  // block-uniform; VALU only inside
-                const int id = L.z0 - 1 + u, ih = L.y0 - 1 + ya, iw = L.x0 - 1 + xa;
-                const bool ok = id >= 0 && id < g.Di && ih >= 0 && ih < g.Hi && iw >= 0 && iw < g.Wi;
-                o = ok ? o : 0xffffffffu;
+            unsigned o = relA[ph] + (unsigned)(u * L.pl4);
+            if (!L.intA) {
+                const int id = L.z0 - 1 + u;
+                o = (inhw && id >= 0 && id < g.Di) ? o : 0xffffffffu;
             }
             ra[u] = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(L.rA, (int)o, 0, 0));
         }
@@ -117,6 +137,9 @@ __device__ __forceinline__ void wgrad_wino3_body(const int pz, const WgradGeom &
     auto issue_b = [&](const auto &L) {
         unsigned o = (unsigned)relB * 4u;
         if (!L.intB) {
+            int t_ = tid;
+            asm volatile("" : "+v"(t_));
+            const int zb = t_ >> 9, yb = (t_ >> 6) & 7, xb = (t_ >> 3) & 7;
             const int id = L.z0 + zb, ih = L.y0 + yb, iw = L.x0 + xb;
             o = (id < g.Db && ih < g.Hb && iw < g.Wb) ? o : 0xffffffffu;
         }
@@ -177,14 +200,14 @@ __device__ __forceinline__ void wgrad_wino3_body(const int pz, const WgradGeom &
     float R[4];      // column ring: halo column x lives in slot x & 3
     float V[2][4];   // MFMA A operands, double buffered over the step parity
     float E[2][4];   // MFMA B operands
-    const bool bias_wave = PAIR && A == 0 && pz == 1 && pbias != nullptr && cb == 0;
-    const float bflag = bias_wave ? 1.f : 0.f;
+    const bool bias_wave = PAIR && A == 1 && pz == 1 && pbias != nullptr && cb == 0;  // wave-uniform
     float bsum = 0.f;
 
     int tile = split;
     int par = 0;
+    TileWalk pos = tile_walk_at(split, tg.ntw, tg.nth, tg.ntd);  // the only divisions: once, before the tile loop
     {
-        const auto L = load_tile(tile, tile < tg.ntiles);
+        const auto L = load_tile(pos, tile < tg.ntiles);
 #pragma unroll
         for (int ph = 0; ph < 2; ph++) {
             issue_a(L, ph);
@@ -196,7 +219,8 @@ __device__ __forceinline__ void wgrad_wino3_body(const int pz, const WgradGeom &
     }
     while (tile < tg.ntiles) {
         const int next = tile + tg.nsplit;
-        const auto L = load_tile(next, next < tg.ntiles);
+        tile_walk_advance(pos, tg.step, tg.ntw, tg.nth, tg.ntd);
+        const auto L = load_tile(pos, next < tg.ntiles);
         {   // window of the first octet: columns 0..3 of octet row h, and its dy quad
             float e[4], f[4];
             fetch_e(0, 0, e, f);
@@ -207,7 +231,7 @@ __device__ __forceinline__ void wgrad_wino3_body(const int pz, const WgradGeom &
                 R[c] = rcomb(pa, pb);
             }
             make_E(e, f, E[0]);
-            if (PAIR && A == 0) bsum += bflag * ((e[0] + e[1]) + (e[2] + e[3]));
+            if (PAIR && A == 1 && bias_wave) bsum += (e[0] + e[1]) + (e[2] + e[3]);
             V[0][0] = R[0] - R[2];
             V[0][1] = R[1] + R[2];
             V[0][2] = R[2] - R[1];
@@ -242,7 +266,7 @@ __device__ __forceinline__ void wgrad_wino3_body(const int pz, const WgradGeom &
             }
             if (!last) {  // window update + operands of the next step (VALU only; the MFMAs above read V[cur] / E[cur])
                 make_E(e, f, E[nxt]);
-                if (PAIR && A == 0) bsum += bflag * ((e[0] + e[1]) + (e[2] + e[3]));
+                if (PAIR && A == 1 && bias_wave) bsum += (e[0] + e[1]) + (e[2] + e[3]);
                 if (wq != 3) {
                     R[(2 * wq + 4) & 3] = rcomb(pa[0], pb[0]);
                     R[(2 * wq + 5) & 3] = rcomb(pa[1], pb[1]);
@@ -293,12 +317,14 @@ __global__ __launch_bounds__(1024, 1) void k_wgrad_wino3(const WgradGeom g, cons
                                                          float *__restrict__ partial, float *__restrict__ pbias) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pz = wave >> 2;
+    // consecutive waves go to the four SIMDs in turn (measured): rotating the position row by pz gives every
+    // SIMD all four rows a, two pair copies and two single copies, instead of the four waves of one row
+    const int pz = wave >> 2, a = (wave + pz) & 3;
     // one code copy per (one plane / two planes, position row): every wave runs the same trip counts, so the barriers
     // inside the copies pair up
 #define MVD_W3(PAIR, AA) wgrad_wino3_body<PAIR, AA>(pz, g, tg, a1, a2, b, partial, pbias, lds)
     const bool pair = pz == 1 || pz == 2;
-    switch (wave & 3) {
+    switch (a) {
         case 0: if (pair) MVD_W3(true, 0); else MVD_W3(false, 0); break;
         case 1: if (pair) MVD_W3(true, 1); else MVD_W3(false, 1); break;
         case 2: if (pair) MVD_W3(true, 2); else MVD_W3(false, 2); break;
@@ -419,6 +445,7 @@ int wgrad_wino3(const WgradGeom &g, const float *a1, const float *a2, const floa
     if (nsplit > ntiles) nsplit = (int)ntiles;
     if (nsplit < 1) nsplit = 1;
     tg.nsplit = nsplit;
+    tg.step = tile_walk_at(nsplit, tg.ntw, tg.nth, tg.ntd);
     // the buffer offsets of one tile (plane 3 of the A halo, the far corner of dy) must fit the 31-bit buffer range
     if ((long)4 * g.Hi * g.Wi * g.C1 * 4 >= (1L << 31) || (long)4 * g.Hi * g.Wi * g.C2 * 4 >= (1L << 31) ||
         (long)2 * g.Hb * g.Wb * g.K * 4 >= (1L << 31))
