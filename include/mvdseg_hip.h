@@ -390,6 +390,40 @@ int mvd_instnorm_lrelu_bwd_head(const float *x, const float *dlogits, const floa
                                 float *dbeta, int N, long V, int C, float slope, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The tail of a residual block (BasicBlockD of ResidualEncoderUNet), fp32, [N,V,C] NDHWC (csrc/resblock.hip):
+ *     y = LeakyReLU_slope( IN(a) * gamma_a + beta_a + R )
+ * a: the raw output of the block's second conv.  gamma_r == NULL: R = r, a finished tensor (identity skip, pool-only
+ * skip).  Otherwise R = IN(r) * gamma_r + beta_r with r the raw output of the 1x1x1 projection of the skip branch, normalised
+ * in the same pass (the normalised skip tensor is never written).  mean / rstd [N][C] of a (and of r in the projection form)
+ * are outputs, saved for the backward pass; have_stats bit 0 (a) / bit 1 (r): that pair was already filled by the caller
+ * (mvd_instnorm_stats_from_tiles on the producing conv's tile statistics) and its statistics pass is skipped.
+ * Statistics as the InstanceNorm entries: fp64 partial sums in a fixed order, biased variance, no atomics (results are
+ * bit-identical from run to run).  ws: mvd_resblock_workspace_bytes.
+ * mvd_resblock_bwd: da, dr [N,V,C], dgamma_a / dbeta_a (and dgamma_r / dbeta_r in the projection form) [C], overwritten.  The
+ * LeakyReLU branch is that of the forward pass: z is re-computed from a and r with the forward's arithmetic, z == 0 takes the
+ * slope.  dr is the masked gradient itself (identity form) or its InstanceNorm backward through r (projection form);
+ * accumulate != 0 adds it into dr instead of overwriting (the block input of the identity form feeds the first conv too).
+ * C % 4 == 0 loads four channels at a time under the alignment rule of the InstanceNorm entries (a, r, y, dy, da, dr 16-byte
+ * aligned, refused before any launch otherwise); every other C takes a scalar path.  N, V, C <= 0, V == 1 (no variance),
+ * N > 65535 and C > 1024 are refused before any launch. */
+size_t mvd_resblock_workspace_bytes(int N, long V, int C);
+int mvd_resblock_fwd(const float *a, const float *gamma_a, const float *beta_a, const float *r, const float *gamma_r,
+                     const float *beta_r, float *y, float *mean_a, float *rstd_a, float *mean_r, float *rstd_r, int N, long V,
+                     int C, float eps, float slope, int have_stats, void *ws, size_t ws_bytes, void *stream);
+int mvd_resblock_bwd(const float *a, const float *r, const float *dy, const float *gamma_a, const float *beta_a,
+                     const float *mean_a, const float *rstd_a, const float *gamma_r, const float *beta_r, const float *mean_r,
+                     const float *rstd_r, float *da, float *dr, float *dgamma_a, float *dbeta_a, float *dgamma_r, float *dbeta_r,
+                     int accumulate, int N, long V, int C, float slope, void *ws, size_t ws_bytes, void *stream);
+/* AvgPool3d(kernel = stride, stride) of the skip branch of a strided residual block, fp32 NDHWC: x [N,D,H,W,C] ->
+ * y [N,D/sd,H/sh,W/sw,C], stride 1 or 2 per axis (AvgPool2d on the [N,C,1,H,W] view with stride (1,s,s)).  An odd extent on a
+ * strided axis is refused: torch's pool floors where the strided conv beside it does not, so the block cannot run there.
+ * mvd_avgpool3d_bwd: dx = dy of the window / window size; accumulate != 0 adds into dx.  D, H, W are the INPUT extents in
+ * both calls.  Alignment as above. */
+int mvd_avgpool3d_fwd(const float *x, float *y, int N, int D, int H, int W, int C, const int stride[3], void *stream);
+int mvd_avgpool3d_bwd(const float *dy, float *dx, int N, int D, int H, int W, int C, const int stride[3], int accumulate,
+                      void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * BatchNorm3d(eps, affine, momentum, track_running_stats) + LeakyReLU(slope), fused.  Replaces the nn.BatchNorm3d +
  * nn.LeakyReLU of every ConvDropoutNormReLU of the BN trainer variant
  * (variants/network_architecture/nnUNetTrainerBN.py:31-32: norm_op = get_matching_batchnorm(conv_op), norm_op_kwargs =

@@ -516,6 +516,312 @@ class MI355PlainConvUNet(nn.Module):
         return uniq
 
 
+# ------------------------------------------------------------------------------------------------ ResidualEncoderUNet
+# The network class the ResEncUNetPlanner's plans name (resencUNet_planner.py, get_network_from_plans.py:34-37, 46-52, 61-65,
+# 90-91): dynamic_network_architectures' ResidualEncoderUNet restated -- a stem, per stage a stack of BasicBlockD, the plain
+# decoder.  fp32, InstanceNorm; the tail of every block (norm of conv2 + skip + LeakyReLU) is one kernel pair
+# (ops.ResidualAddNormActFn), the skip branch's pool another (ops.AvgPool3dFn).  DESIGN 36.
+def _refuse_resenc(what):
+    raise NotImplementedError(f"ResidualEncoderUNet: {what}")
+
+
+class ConvDropoutNorm(nn.Module):
+    """conv -> (no dropout) -> InstanceNorm with NO nonlinearity: conv2 and the skip projection of BasicBlockD (the package
+    builds them as ConvDropoutNormReLU(nonlin=None), so `all_modules` is Sequential(conv, norm)).  A sibling of
+    ConvDropoutNormReLU, which keeps refusing nonlin=None.  Inside a block only `conv` runs here: the norm's parameters go
+    into the block tail's kernel.  Called on its own it normalises with slope 1."""
+
+    def __init__(self, conv_op, input_channels, output_channels, kernel_size, stride, conv_bias=False, norm_op=None,
+                 norm_op_kwargs=None):
+        super().__init__()
+        self.dim = dim = _conv_dim(conv_op)
+        norm_ops = ConvDropoutNormReLU._norm_ops if dim == 3 else ConvDropoutNormReLU._norm_ops_2d
+        if not (isinstance(norm_op, type) and issubclass(norm_op, norm_ops[0])):
+            _refuse_resenc(f"norm_op {norm_op!r}: only nn.{norm_ops[0].__name__} is built (no BatchNorm residual blocks)")
+        if not dict(norm_op_kwargs or {'affine': True}).get('affine', False):
+            _refuse_resenc(f"{norm_ops[0].__name__}(affine=False) is not on the reference's path")
+        self.input_channels, self.output_channels = input_channels, output_channels
+        self.stride = _tup3(stride, dim)
+        k = _tup3(kernel_size, dim)
+        if len(k) != dim or len(self.stride) != dim:
+            _refuse_resenc(f"kernel size {k} / stride {self.stride} do not have the {dim} axes of {conv_op.__name__}")
+        if not (all(i in (1, 3) for i in k) and all(i in (1, 2) for i in self.stride)):
+            _refuse_resenc(f"kernel size 3 or 1 and stride 1 or 2 per axis are built (got {k}, {self.stride})")
+        self.conv = (HipConv3d if dim == 3 else HipConv2d)(input_channels, output_channels, k, self.stride,
+                                                           padding=[(i - 1) // 2 for i in k], dilation=1, bias=conv_bias)
+        self.norm = norm_ops[1](output_channels, **(norm_op_kwargs or {'eps': 1e-5, 'affine': True}))
+        self.all_modules = nn.Sequential(self.conv, self.norm)
+
+    def forward(self, x):
+        return self.norm(self.conv(x))
+
+
+class HipAvgPool3d(nn.AvgPool3d):
+    def forward(self, x):
+        return ops.AvgPool3dFn.apply(x, _tup3(self.stride, 3))
+
+
+class HipAvgPool2d(nn.AvgPool2d):
+    """AvgPool2d on the [N,C,1,H,W] view of a 2-D network's activation."""
+
+    def forward(self, x):
+        y = ops.AvgPool3dFn.apply(_as5(x), (1,) + _tup3(self.stride, 2))
+        return y.squeeze(2) if x.dim() == 4 else y
+
+
+class BasicBlockD(nn.Module):
+    """conv1 (conv, norm, LeakyReLU) -> conv2 (conv, norm) -> + skip(x) -> LeakyReLU.  skip: the identity when neither the
+    stride nor the channel count changes, else nn.Sequential of an average pool (kernel = stride) when strided, then a 1x1x1
+    conv (bias=False) + norm when the channels change -- so the parameter keys are skip.0.* or skip.1.*."""
+
+    def __init__(self, conv_op, input_channels, output_channels, kernel_size, stride, conv_bias=False, norm_op=None,
+                 norm_op_kwargs=None, dropout_op=None, dropout_op_kwargs=None, nonlin=None, nonlin_kwargs=None,
+                 stochastic_depth_p=0.0, squeeze_excitation=False, squeeze_excitation_reduction_ratio=1. / 16):
+        super().__init__()
+        self.dim = dim = _conv_dim(conv_op)
+        if stochastic_depth_p:
+            _refuse_resenc(f"stochastic depth (p = {stochastic_depth_p}) is not built")
+        if squeeze_excitation:
+            _refuse_resenc("squeeze-and-excitation is not built")
+        if dropout_op is not None:
+            _refuse_resenc("dropout is not on the reference's path (get_network_from_plans.py:43)")
+        if not (isinstance(nonlin, type) and issubclass(nonlin, nn.LeakyReLU)):
+            _refuse_resenc(f"nonlin {nonlin!r}: only nn.LeakyReLU is built")
+        if isinstance(norm_op, type) and issubclass(norm_op, (nn.BatchNorm2d, nn.BatchNorm3d)):
+            _refuse_resenc(f"norm_op {norm_op.__name__}: BatchNorm residual blocks are not built (InstanceNorm only)")
+        self.input_channels, self.output_channels = input_channels, output_channels
+        self.stride = _tup3(stride, dim)
+        self.conv1 = ConvDropoutNormReLU(conv_op, input_channels, output_channels, kernel_size, self.stride, conv_bias, norm_op,
+                                         norm_op_kwargs, None, None, nonlin, nonlin_kwargs)
+        self.conv2 = ConvDropoutNorm(conv_op, output_channels, output_channels, kernel_size, 1, conv_bias, norm_op,
+                                     norm_op_kwargs)
+        self.nonlin2 = nonlin(**dict(nonlin_kwargs or {'inplace': True}))
+        has_stride = any(i != 1 for i in self.stride)
+        requires_projection = input_channels != output_channels
+        if has_stride or requires_projection:
+            ops_ = []
+            if has_stride:
+                ops_.append((HipAvgPool3d if dim == 3 else HipAvgPool2d)(self.stride, self.stride))
+            if requires_projection:
+                ops_.append(ConvDropoutNorm(conv_op, input_channels, output_channels, 1, 1, False, norm_op, norm_op_kwargs))
+            self.skip = nn.Sequential(*ops_)
+        else:
+            self.skip = nn.Identity()   # (torch's `lambda x: x` in the package: no parameters, no keys either way)
+        self._pool = has_stride
+        self._proj = requires_projection
+
+    def forward(self, x):
+        x = _as5(x)
+        # x has two consumers here (conv1 and the skip branch): one gradient buffer (ops._GradShare).  A stage output the
+        # encoder tagged already (the decoder reads it as well) keeps its tag: the skip branch's pool / the block tail add
+        # into the decoder's buffer and leave it published for conv1.  The conv branch is built FIRST, so that in the backward
+        # pass the skip branch's node runs before conv1's: the pool / the tail add IN PLACE into the buffer autograd holds as
+        # the decoder's contribution, before any other contribution arrives and autograd sums (out of place).
+        tagged = ops._share_of(x) is not None
+        if tagged and self._proj and not self._pool:
+            # A projection conv directly on a tagged tensor (a later stage at stride 1 that changes channels) cannot take part
+            # in that: a Conv3dFn that finds a buffer it cannot join publishes its own OVER it and returns it, autograd sums
+            # the two out of place, and conv1 would then join a buffer nobody reads.  This block therefore works on a view of
+            # x with a share of its own (its two consumers); the view's backward hands their sum to autograd, which adds it
+            # to the decoder's contribution.
+            x, tagged = x.view_as(x), False
+        if not tagged and SHARE_GRADS[0]:
+            ops.share_grad(x)
+        a = self.conv2.conv(self.conv1(x))
+        r, gr, br = x, None, None
+        if self._pool:
+            r = ops.AvgPool3dFn.apply(r, self.stride if self.dim == 3 else (1,) + self.stride)
+        if self._proj:
+            p = self.skip[-1]
+            r = p.conv(r)
+            gr, br = p.norm.weight, p.norm.bias
+        n2 = self.conv2.norm
+        return ops.ResidualAddNormActFn.apply(a, n2.weight, n2.bias, r, gr, br, n2.eps, self.nonlin2.negative_slope)
+
+    def compute_conv_feature_map_size(self, input_size):
+        """Two maps of output_channels at the strided size (conv1, conv2), a third when the skip is not the identity."""
+        size_after_stride = [i // j for i, j in zip(input_size, self.stride)]
+        one = np.prod([self.output_channels, *size_after_stride], dtype=np.int64)
+        return one * (3 if (self._pool or self._proj) else 2)
+
+
+class StackedResidualBlocks(nn.Module):
+    """n_blocks residual blocks: the first takes the stride and the channel change, the rest run at stride 1."""
+
+    def __init__(self, n_blocks, conv_op, input_channels, output_channels, kernel_size, initial_stride, conv_bias=False,
+                 norm_op=None, norm_op_kwargs=None, dropout_op=None, dropout_op_kwargs=None, nonlin=None, nonlin_kwargs=None,
+                 block=BasicBlockD, bottleneck_channels=None, stochastic_depth_p=0.0, squeeze_excitation=False,
+                 squeeze_excitation_reduction_ratio=1. / 16):
+        super().__init__()
+        assert n_blocks > 0, 'n_blocks must be > 0'
+        if block is not BasicBlockD:
+            _refuse_resenc(f"block {getattr(block, '__name__', block)!r}: only BasicBlockD is built (no BottleneckD)")
+        if bottleneck_channels is not None:
+            _refuse_resenc("bottleneck_channels belong to BottleneckD, which is not built")
+        if not isinstance(output_channels, (tuple, list)):
+            output_channels = [output_channels] * n_blocks
+        dim = _conv_dim(conv_op)
+        extra = (stochastic_depth_p, squeeze_excitation, squeeze_excitation_reduction_ratio)
+        self.blocks = nn.Sequential(
+            block(conv_op, input_channels, output_channels[0], kernel_size, initial_stride, conv_bias, norm_op, norm_op_kwargs,
+                  dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs, *extra),
+            *[block(conv_op, output_channels[n - 1], output_channels[n], kernel_size, 1, conv_bias, norm_op, norm_op_kwargs,
+                    dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs, *extra) for n in range(1, n_blocks)])
+        self.initial_stride = _tup3(initial_stride, dim)
+        self.output_channels = output_channels[-1]
+
+    def forward(self, x):
+        return self.blocks(x)
+
+    def compute_conv_feature_map_size(self, input_size):
+        output = self.blocks[0].compute_conv_feature_map_size(input_size)
+        size_after_stride = [i // j for i, j in zip(input_size, self.initial_stride)]
+        for b in self.blocks[1:]:
+            output += b.compute_conv_feature_map_size(size_after_stride)
+        return output
+
+
+class ResidualEncoder(nn.Module):
+    def __init__(self, input_channels: int, n_stages: int, features_per_stage: Union[int, Sequence[int]],
+                 conv_op: Type = nn.Conv3d, kernel_sizes=3, strides=1, n_blocks_per_stage: Union[int, Sequence[int]] = 2,
+                 conv_bias: bool = False, norm_op=None, norm_op_kwargs=None, dropout_op=None, dropout_op_kwargs=None,
+                 nonlin=None, nonlin_kwargs=None, block=BasicBlockD, bottleneck_channels=None, return_skips: bool = False,
+                 disable_default_stem: bool = False, stem_channels: int = None, pool_type: str = 'conv',
+                 stochastic_depth_p: float = 0.0, squeeze_excitation: bool = False,
+                 squeeze_excitation_reduction_ratio: float = 1. / 16):
+        super().__init__()
+        dim = _conv_dim(conv_op)
+        if pool_type != 'conv':
+            _refuse_resenc(f"pool {pool_type!r}: the plans use strided convolutions (pool='conv')")
+        if disable_default_stem:
+            _refuse_resenc("disable_default_stem is not built (the plans keep the stem)")
+        if dropout_op is not None:
+            _refuse_resenc("dropout is not on the reference's path (get_network_from_plans.py:43)")
+        if isinstance(norm_op, type) and issubclass(norm_op, (nn.BatchNorm2d, nn.BatchNorm3d)):
+            _refuse_resenc(f"norm_op {norm_op.__name__}: BatchNorm residual blocks are not built (InstanceNorm only)")
+        if isinstance(kernel_sizes, int):
+            kernel_sizes = [kernel_sizes] * n_stages
+        if isinstance(features_per_stage, int):
+            features_per_stage = [features_per_stage] * n_stages
+        if isinstance(n_blocks_per_stage, int):
+            n_blocks_per_stage = [n_blocks_per_stage] * n_stages
+        if isinstance(strides, int):
+            strides = [strides] * n_stages
+        if bottleneck_channels is None or isinstance(bottleneck_channels, int):
+            bottleneck_channels = [bottleneck_channels] * n_stages
+        assert len(kernel_sizes) == n_stages and len(n_blocks_per_stage) == n_stages
+        assert len(features_per_stage) == n_stages and len(strides) == n_stages and len(bottleneck_channels) == n_stages
+        if stem_channels is None:
+            stem_channels = features_per_stage[0]
+        self.stem = StackedConvBlocks(1, conv_op, input_channels, stem_channels, kernel_sizes[0], 1, conv_bias, norm_op,
+                                      norm_op_kwargs, dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs)
+        input_channels = stem_channels
+        stages = []
+        for s in range(n_stages):
+            stages.append(StackedResidualBlocks(
+                n_blocks_per_stage[s], conv_op, input_channels, features_per_stage[s], kernel_sizes[s], strides[s], conv_bias,
+                norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs, nonlin, nonlin_kwargs, block=block,
+                bottleneck_channels=bottleneck_channels[s], stochastic_depth_p=stochastic_depth_p,
+                squeeze_excitation=squeeze_excitation,
+                squeeze_excitation_reduction_ratio=squeeze_excitation_reduction_ratio))
+            input_channels = features_per_stage[s]
+        self.stages = nn.Sequential(*stages)
+        self.output_channels = list(features_per_stage)
+        self.strides = [_tup3(i, dim) for i in strides]
+        self.return_skips = return_skips
+        # read by the decoder (UNetDecoder.py:39-65)
+        self.conv_op, self.norm_op, self.norm_op_kwargs = conv_op, norm_op, norm_op_kwargs
+        self.nonlin, self.nonlin_kwargs = nonlin, nonlin_kwargs
+        self.dropout_op, self.dropout_op_kwargs = dropout_op, dropout_op_kwargs
+        self.conv_bias, self.kernel_sizes = conv_bias, [_tup3(k, dim) for k in kernel_sizes]
+
+    def forward(self, x):
+        x = self.stem(x)
+        ret = []
+        last = len(self.stages) - 1
+        for i, s in enumerate(self.stages):
+            x = s(x)
+            if self.return_skips and i != last and SHARE_GRADS[0]:
+                ops.share_grad(x)   # a skip: read by the next stage AND by the decoder (as PlainConvEncoder.forward)
+            ret.append(x)
+        return ret if self.return_skips else ret[-1]
+
+    def compute_conv_feature_map_size(self, input_size):
+        output = self.stem.compute_conv_feature_map_size(input_size)
+        for s in range(len(self.stages)):
+            output += self.stages[s].compute_conv_feature_map_size(input_size)
+            input_size = [i // j for i, j in zip(input_size, self.strides[s])]
+        return output
+
+
+class MI355ResidualEncoderUNet(nn.Module):
+    """Drop-in for dynamic_network_architectures.architectures.unet.ResidualEncoderUNet: the PlainConvUNet signature with
+    n_blocks_per_stage in the place of n_conv_per_stage, plus block, bottleneck_channels and stem_channels.  fp32 only."""
+
+    def __init__(self, input_channels: int, n_stages: int, features_per_stage: Union[int, Sequence[int]],
+                 conv_op: Type = nn.Conv3d, kernel_sizes=3, strides=1, n_blocks_per_stage: Union[int, Sequence[int]] = 2,
+                 num_classes: int = 2, n_conv_per_stage_decoder: Union[int, Sequence[int]] = 2, conv_bias: bool = False,
+                 norm_op=None, norm_op_kwargs=None, dropout_op=None, dropout_op_kwargs=None, nonlin=None,
+                 nonlin_kwargs=None, deep_supervision: bool = False, block=BasicBlockD, bottleneck_channels=None,
+                 stem_channels: int = None, nonlin_first: bool = False, pool: str = 'conv'):
+        super().__init__()
+        if nonlin_first:
+            _refuse_resenc("nonlin_first is not built (the plans set nonlin_first=False)")
+        if isinstance(n_blocks_per_stage, int):
+            n_blocks_per_stage = [n_blocks_per_stage] * n_stages
+        if isinstance(n_conv_per_stage_decoder, int):
+            n_conv_per_stage_decoder = [n_conv_per_stage_decoder] * (n_stages - 1)
+        assert len(n_blocks_per_stage) == n_stages, "n_blocks_per_stage must have as many entries as we have resolution stages"
+        assert len(n_conv_per_stage_decoder) == (n_stages - 1)
+        self.encoder = ResidualEncoder(input_channels, n_stages, features_per_stage, conv_op, kernel_sizes, strides,
+                                       n_blocks_per_stage, conv_bias, norm_op, norm_op_kwargs, dropout_op, dropout_op_kwargs,
+                                       nonlin, nonlin_kwargs, block, bottleneck_channels, return_skips=True,
+                                       disable_default_stem=False, stem_channels=stem_channels, pool_type=pool)
+        self.decoder = UNetDecoder(self.encoder, num_classes, n_conv_per_stage_decoder, deep_supervision)
+
+    def forward(self, x, return_last_feature=False):
+        if not x.is_cuda:
+            raise RuntimeError("MI355ResidualEncoderUNet runs on the MI355X only (no CPU path); move the input to cuda")
+        if _conv_dim(self.encoder.conv_op) == 2:
+            # the 2d configuration: [N,C,H,W] in, [N,K,h,w] logits out; inside, every tensor is the [N,C,1,H,W] view
+            if x.dim() != 4:
+                raise RuntimeError(f"2-D MI355ResidualEncoderUNet: input must be [N,C,H,W], got {tuple(x.shape)}")
+            out = self.decoder(self.encoder(ops.to_ndhwc(x.unsqueeze(2))), return_last_feature)
+            sq = lambda o: [t.squeeze(2) for t in o] if isinstance(o, (list, tuple)) else o.squeeze(2)
+            if return_last_feature:
+                return sq(out[0]), (out[1].squeeze(2) if out[1] is not None else None)
+            return sq(out)
+        return self.decoder(self.encoder(ops.to_ndhwc(x)), return_last_feature)
+
+    def compute_conv_feature_map_size(self, input_size):
+        return self.encoder.compute_conv_feature_map_size(input_size) + \
+            self.decoder.compute_conv_feature_map_size(input_size)
+
+    def parameters_in_execution_order(self):
+        """Stem, stages, then per decoder level the transposed conv, the refining convs and the seg layer (see
+        MI355PlainConvUNet.parameters_in_execution_order); every parameter exactly once."""
+        out = list(self.encoder.stem.parameters()) + list(self.encoder.stages.parameters())
+        for up, refine, head in zip(self.decoder.transpconvs, self.decoder.stages, self.decoder.seg_layers):
+            out += list(up.parameters()) + list(refine.parameters()) + list(head.parameters())
+        seen, uniq = set(), []
+        for p in out + list(self.parameters()):
+            if id(p) not in seen:
+                seen.add(id(p))
+                uniq.append(p)
+        return uniq
+
+
+ResidualEncoderUNet = MI355ResidualEncoderUNet  # the name get_network_from_plans.py:36-37 maps 'ResidualEncoderUNet' to
+
+
+def init_last_bn_before_add_to_0(module):
+    """The package's second init of a residual network: the norm in front of each block's add starts at zero (weight AND
+    bias), so every block starts as the identity on its skip branch.  Restated from memory of the package."""
+    if isinstance(module, BasicBlockD):
+        nn.init.constant_(module.conv2.norm.weight, 0)
+        nn.init.constant_(module.conv2.norm.bias, 0)
+
+
 def set_precision(module: nn.Module, precision: str):
     """Mixed precision of the reference's autocast path (nnUNetTrainer.py:906; BASELINE cfg 4/5), MI355X style:
     "bf16" makes every fused InstanceNorm+LeakyReLU emit bf16, so every conv / transposed conv / seg head reads bf16
@@ -529,6 +835,9 @@ def set_precision(module: nn.Module, precision: str):
         # the generic bf16 engines take the (1,3,3) / (1,2,2) / (1,1,1) layers, but the 2-D network's forward misses the
         # project's bf16 bar against fp64: refused until the layer behind that is found
         raise NotImplementedError("bf16 mixed precision is not built for 2-D networks (the 2d configuration runs fp32)")
+    if precision == "bf16" and any(isinstance(m, BasicBlockD) for m in module.modules()):
+        raise NotImplementedError("bf16 mixed precision is not built for ResidualEncoderUNet: the residual block tail and the "
+                                  "skip branch's pool are fp32 only")
     if precision == "bf16" and any(isinstance(m, BottleneckFusion) for m in module.modules()):
         raise NotImplementedError("bf16 mixed precision is not built for FinalNetv2: its bottleneck fusion block (LayerNorm, "
                                   "token linears, attention) is fp32 only")

@@ -942,6 +942,129 @@ class InstanceNormLeakyReLUFn(Function):
         return dx, dg, db, None, None, None
 
 
+def _join_or_publish(share, shape, dev):
+    """Gradient buffer of a tensor with several consumers, for a kernel that can accumulate: (buffer, accumulate, joined).
+    joined: an earlier consumer's buffer exists, the kernel adds into it and the node returns None to autograd.  The buffer
+    stays published (a later consumer may join too).  Otherwise a fresh buffer, published for the consumers still to run."""
+    joined = _joinable(share, shape, torch.float32)
+    if joined is not None:
+        return joined, 1, True
+    return _publish(share, empty_cl3d(shape, dev)), 0, False
+
+
+class ResidualAddNormActFn(Function):
+    """The tail of a residual block (BasicBlockD): y = LeakyReLU(IN(a) * gamma_a + beta_a + R), fp32 (mvd_resblock_fwd / _bwd).
+    `a` is the raw output of conv2.  gamma_r is None: R = r (identity or pool-only skip); else r is the raw output of the
+    skip branch's 1x1x1 projection and R = IN(r) * gamma_r + beta_r, normalised in the same pass.  Statistics a producing conv
+    attached (`_mvd_tile_stats`) replace the pass over that tensor.  Backward: when r carries a shared gradient buffer
+    (share_grad: the block input of the identity form feeds conv1 too) the kernel adds dr into it (`accumulate`)."""
+
+    @staticmethod
+    def forward(ctx, a, gamma_a, beta_a, r, gamma_r, beta_r, eps, slope):
+        _require_cuda(a, gamma_a, beta_a, r, gamma_r, beta_r)
+        proj = gamma_r is not None
+        if proj and beta_r is None:
+            raise RuntimeError("ResidualAddNormActFn: the projection form needs gamma_r and beta_r")
+        if a.dtype != torch.float32 or r.dtype != torch.float32:
+            raise NotImplementedError("ResidualEncoderUNet: the residual block tail is fp32 only (no bf16 mixed precision)")
+        if tuple(a.shape) != tuple(r.shape) or a.dim() != 5:
+            raise RuntimeError(f"residual block: conv branch {tuple(a.shape)} and skip branch {tuple(r.shape)} differ in shape")
+        if any(p is not None and p.numel() != a.shape[1] for p in (gamma_a, beta_a, gamma_r, beta_r)):
+            raise RuntimeError(f"residual block: the norm parameters must have {a.shape[1]} channels")
+        ctx.share_r = _share_of(r)
+        pre_a, pre_r = getattr(a, '_mvd_tile_stats', None), (getattr(r, '_mvd_tile_stats', None) if proj else None)
+        a, r = to_ndhwc(a), to_ndhwc(r)
+        N, C = a.shape[:2]
+        V = a[0, 0].numel()
+        dev = a.device
+        y = empty_cl3d(a.shape, dev)
+        ga, ba = gamma_a.detach().contiguous(), beta_a.detach().contiguous()
+        gr, br = (gamma_r.detach().contiguous(), beta_r.detach().contiguous()) if proj else (None, None)
+        mean_a = torch.empty((N, C), dtype=torch.float32, device=dev)
+        rstd_a = torch.empty_like(mean_a)
+        mean_r, rstd_r = (torch.empty_like(mean_a), torch.empty_like(mean_a)) if proj else (None, None)
+        have = 0
+        for bit, pre, m, s in ((1, pre_a, mean_a, rstd_a), (2, pre_r, mean_r, rstd_r)):
+            if pre is not None and V > 1 and pre[0].shape[0] == N and pre[0].shape[2] == C:
+                wsn = _Workspace.get(query("mvd_instnorm_workspace_bytes", N, V, C), dev)
+                call("mvd_instnorm_stats_from_tiles", _p(pre[0]), pre[1], _p(m), _p(s), N, V, C, float(eps), _p(wsn), wsn.numel(),
+                     _stream())
+                have |= bit
+        ws = _Workspace.get(query("mvd_resblock_workspace_bytes", N, V, C), dev)
+        call("mvd_resblock_fwd", _p(a), _p(ga), _p(ba), _p(r), _p(gr), _p(br), _p(y), _p(mean_a), _p(rstd_a), _p(mean_r),
+             _p(rstd_r), N, V, C, float(eps), float(slope), have, _p(ws), ws.numel(), _stream())
+        ctx.proj = proj
+        ctx.slope = float(slope)
+        ctx.params = (gamma_a, beta_a, gamma_r, beta_r)
+        if proj:
+            ctx.save_for_backward(a, r, ga, ba, mean_a, rstd_a, gr, br, mean_r, rstd_r)
+        else:
+            ctx.save_for_backward(a, r, ga, ba, mean_a, rstd_a)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        if ctx.proj:
+            a, r, ga, ba, mean_a, rstd_a, gr, br, mean_r, rstd_r = ctx.saved_tensors
+        else:
+            a, r, ga, ba, mean_a, rstd_a = ctx.saved_tensors
+            gr = br = mean_r = rstd_r = None
+        dy = to_ndhwc(dy)
+        N, C = a.shape[:2]
+        V = a[0, 0].numel()
+        dev = a.device
+        da = empty_cl3d(a.shape, dev)
+        if ctx.needs_input_grad[3] and ctx.share_r is not None:
+            dr, acc, joined = _join_or_publish(ctx.share_r, tuple(r.shape), dev)
+        else:
+            dr, acc, joined = empty_cl3d(r.shape, dev), 0, False
+        params = ctx.params
+        sinks = [(_take_grad(p) if p is not None else None) for p in params]
+        outs = [(s if s is not None else torch.empty((C,), dtype=torch.float32, device=dev)) if p is not None else None
+                for p, s in zip(params, sinks)]
+        ws = _Workspace.get(query("mvd_resblock_workspace_bytes", N, V, C), dev)
+        call("mvd_resblock_bwd", _p(a), _p(r), _p(dy), _p(ga), _p(ba), _p(mean_a), _p(rstd_a), _p(gr), _p(br), _p(mean_r),
+             _p(rstd_r), _p(da), _p(dr), _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), acc, N, V, C, ctx.slope, _p(ws),
+             ws.numel(), _stream())
+        for i, (p, s) in enumerate(zip(params, sinks)):
+            if s is not None:
+                outs[i] = None
+                _grad_done(p)
+        return da, outs[0], outs[1], (None if joined else dr), outs[2], outs[3], None, None
+
+
+class AvgPool3dFn(Function):
+    """AvgPool3d(stride, stride) of a strided residual block's skip branch on NDHWC fp32 (mvd_avgpool3d_fwd / _bwd); stride 1
+    or 2 per axis, an odd extent on a strided axis is refused.  Backward joins a shared gradient buffer of x (`accumulate`)."""
+
+    @staticmethod
+    def forward(ctx, x, stride):
+        _require_cuda(x)
+        if x.dtype != torch.float32:
+            raise NotImplementedError("ResidualEncoderUNet: the skip branch's average pool is fp32 only")
+        stride = tuple(int(s) for s in stride)
+        if x.dim() != 5 or len(stride) != 3:
+            raise RuntimeError(f"avgpool3d: [N,C,D,H,W] and a 3-axis stride, got {tuple(x.shape)} and {stride}")
+        ctx.share = _share_of(x)
+        x = to_ndhwc(x)
+        N, C, D, H, W = x.shape
+        # (a stride other than 1 or 2 and an odd extent on a strided axis are refused by the library, before any launch)
+        y = empty_cl3d((N, C, *[max(e // max(s, 1), 1) for e, s in zip((D, H, W), stride)]), x.device)
+        call("mvd_avgpool3d_fwd", _p(x), _p(y), N, D, H, W, C, i3(stride), _stream())
+        ctx.geom = (N, C, D, H, W, stride)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        N, C, D, H, W, stride = ctx.geom
+        dy = to_ndhwc(dy)
+        dx, acc, joined = _join_or_publish(ctx.share, (N, C, D, H, W), dy.device)
+        call("mvd_avgpool3d_bwd", _p(dy), _p(dx), N, D, H, W, C, i3(stride), acc, _stream())
+        return (None if joined else dx), None
+
+
 class BatchNormLeakyReLUFn(Function):
     """BatchNorm3d(eps, affine, momentum, track_running_stats=True) + LeakyReLU(slope) fused (nnUNetTrainerBN.py:31-32).
     training: batch statistics over (N, D, H, W); the kernel updates running_mean / running_var / num_batches_tracked in

@@ -23,7 +23,8 @@ from torch import nn
 
 from . import losses, ops
 from .dataloading import DeviceDataLoader2D, DeviceDataLoader3D, get_patch_size
-from .network import InitWeights_He, MI355PlainConvUNet, MVDDualBranchNet, get_finalnet_from_plans, set_precision
+from .network import (InitWeights_He, MI355PlainConvUNet, MI355ResidualEncoderUNet, MVDDualBranchNet,
+                      get_finalnet_from_plans, init_last_bn_before_add_to_0, set_precision)
 from .optim import CosineAnnealingLR, FlatParams, FusedAdam, FusedSGDNesterov, PolyLRScheduler
 from .parallel import BucketedGradReducer, broadcast_parameters, ddp_batch_split
 
@@ -208,17 +209,24 @@ def determine_num_input_channels(plans_manager, configuration_manager, dataset_j
 
 def make_plans(patch_size, strides, batch_size=2, base_features=32, max_features=320, n_conv=2, batch_dice=False,
                conv_kernel_sizes=None, configuration='3d_fullres', spacing=None, previous_stage_name=None,
-               next_stage_names=None, cascade_configuration=None, cascade_spacing=None):
+               next_stage_names=None, cascade_configuration=None, cascade_spacing=None, unet_class_name='PlainConvUNet',
+               n_blocks_per_stage=None, n_conv_per_stage_decoder=None):
     """A minimal nnUNetPlans.json-shaped dict for the synthetic configurations of BASELINE.json.  `configuration`: the name
     of the entry ('2d' with a 2-tuple patch size and 2-tuple strides writes a 2-D plan).  spacing / previous_stage_name /
     next_stage_names are written into the entry when given.  cascade_configuration names a second entry that inherits
     from the first (`inherits_from`, as the planner writes 3d_cascade_fullres), has it as its previous stage and is
-    listed as its next stage: a two-stage plan."""
+    listed as its next stage: a two-stage plan.  unet_class_name 'ResidualEncoderUNet' with n_blocks_per_stage (written as
+    n_conv_per_stage_encoder, the key the ResEnc planner uses for its block counts) and n_conv_per_stage_decoder writes a
+    residual-encoder plan; left at None both keep [n_conv] per stage."""
     n = len(strides)
+    enc = [n_conv] * n if n_blocks_per_stage is None else [int(b) for b in n_blocks_per_stage]
+    dec = [n_conv] * (n - 1) if n_conv_per_stage_decoder is None else [int(b) for b in n_conv_per_stage_decoder]
+    if len(enc) != n or len(dec) != n - 1:
+        raise ValueError(f"n_blocks_per_stage needs {n} entries and n_conv_per_stage_decoder {n - 1}")
     cfg = {
-        'patch_size': list(patch_size), 'batch_size': batch_size, 'UNet_class_name': 'PlainConvUNet',
+        'patch_size': list(patch_size), 'batch_size': batch_size, 'UNet_class_name': unet_class_name,
         'UNet_base_num_features': base_features, 'unet_max_num_features': max_features,
-        'n_conv_per_stage_encoder': [n_conv] * n, 'n_conv_per_stage_decoder': [n_conv] * (n - 1),
+        'n_conv_per_stage_encoder': enc, 'n_conv_per_stage_decoder': dec,
         'conv_kernel_sizes': conv_kernel_sizes or [[3] * len(patch_size)] * n,
         'pool_op_kernel_sizes': [list(s) for s in strides],
         'batch_dice': batch_dice}
@@ -241,7 +249,8 @@ def make_plans(patch_size, strides, batch_size=2, base_features=32, max_features
 
 def get_network_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
                            deep_supervision=True, norm_op=nn.InstanceNorm3d, norm_op_kwargs=None):
-    """get_network_from_plans.py:15-92 for UNet_class_name == 'PlainConvUNet'.  norm_op / norm_op_kwargs: what the
+    """get_network_from_plans.py:15-92: 'PlainConvUNet', and 'ResidualEncoderUNet' (:36, :46-52, :61-65, :90-91) with
+    n_blocks_per_stage = n_conv_per_stage_encoder and the second init pass.  norm_op / norm_op_kwargs: what the
     network_architecture trainer variants replace (nnUNetTrainerBN.py:31-32); the default is the builder's own.
     dim = len(conv_kernel_sizes[0]) picks the conv (:21-23): 3 -> nn.Conv3d, 2 -> nn.Conv2d (the 2d configuration) with the
     norm of the same family in two dimensions (InstanceNorm2d; get_matching_batchnorm for the BN variant)."""
@@ -252,21 +261,32 @@ def get_network_from_plans(plans_manager, dataset_json, configuration_manager, n
     conv_op = nn.Conv3d if dim == 3 else nn.Conv2d
     if dim == 2:
         norm_op = {nn.InstanceNorm3d: nn.InstanceNorm2d, nn.BatchNorm3d: nn.BatchNorm2d}.get(norm_op, norm_op)
-    if configuration_manager.UNet_class_name != 'PlainConvUNet':
-        raise NotImplementedError("north_star names PlainConvUNet; ResidualEncoderUNet is out of scope")
+    name = configuration_manager.UNet_class_name
+    if name not in ('PlainConvUNet', 'ResidualEncoderUNet'):
+        raise NotImplementedError(f"UNet_class_name {name!r}: PlainConvUNet and ResidualEncoderUNet are built")
+    residual = name == 'ResidualEncoderUNet'
     label_manager = plans_manager.get_label_manager(dataset_json)
-    model = MI355PlainConvUNet(
+    blocks = {'n_blocks_per_stage' if residual else 'n_conv_per_stage': configuration_manager.n_conv_per_stage_encoder}
+    model = (MI355ResidualEncoderUNet if residual else MI355PlainConvUNet)(
         input_channels=num_input_channels, n_stages=num_stages,
         features_per_stage=[min(configuration_manager.UNet_base_num_features * 2 ** i,
                                 configuration_manager.unet_max_num_features) for i in range(num_stages)],
         conv_op=conv_op, kernel_sizes=configuration_manager.conv_kernel_sizes,
         strides=configuration_manager.pool_op_kernel_sizes, num_classes=label_manager.num_segmentation_heads,
-        deep_supervision=deep_supervision, n_conv_per_stage=configuration_manager.n_conv_per_stage_encoder,
+        deep_supervision=deep_supervision, **blocks,
         n_conv_per_stage_decoder=configuration_manager.n_conv_per_stage_decoder, conv_bias=True,
         norm_op=norm_op, norm_op_kwargs=dict(norm_op_kwargs or {'eps': 1e-5, 'affine': True}), dropout_op=None,
         dropout_op_kwargs=None, nonlin=nn.LeakyReLU, nonlin_kwargs={'inplace': True})
     model.apply(InitWeights_He(1e-2))
+    if residual:
+        model.apply(init_last_bn_before_add_to_0)   # (:90-91)
     return model
+
+
+def _refuse_residual_plans(configuration_manager, who):
+    if getattr(configuration_manager, 'UNet_class_name', 'PlainConvUNet') == 'ResidualEncoderUNet':
+        raise NotImplementedError(f"{who}: ResidualEncoderUNet plans are built for the single-network InstanceNorm trainers "
+                                  f"only")
 
 
 # ------------------------------------------------------------------------------------------------ trainer
@@ -1183,6 +1203,7 @@ class ContrastiveTrainerMI355(nnUNetTrainerMI355):
     @staticmethod
     def build_network_architecture(plans_manager, dataset_json, configuration_manager, num_input_channels,
                                    enable_deep_supervision: bool = True) -> nn.Module:
+        _refuse_residual_plans(configuration_manager, "ContrastiveTrainerMI355 (dual-branch)")
         b1 = get_network_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
                                     enable_deep_supervision)
         b2 = get_network_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
@@ -1273,5 +1294,6 @@ class FinalNetTrainerMI355(ContrastiveTrainerMI355):
     @staticmethod
     def build_network_architecture(plans_manager, dataset_json, configuration_manager, num_input_channels,
                                    enable_deep_supervision: bool = True) -> nn.Module:
+        _refuse_residual_plans(configuration_manager, "FinalNetTrainerMI355 (FinalNetv2 has plain encoders)")
         return get_finalnet_from_plans(plans_manager, dataset_json, configuration_manager, num_input_channels,
                                        enable_deep_supervision)
