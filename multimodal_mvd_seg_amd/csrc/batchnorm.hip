@@ -3,86 +3,17 @@
 // HBM-bound like instnorm.hip: training fwd = read x (stats) + read x + write y; eval fwd = read x + write y;
 // bwd = read x,dy (sums) + read x,dy + write dx.  Statistics are over the batch AND the volume (M = N * V values per
 // channel): per-thread fp64 accumulation -> fixed-order LDS reduce -> per-block partials [n][b][c][2] -> ONE wave per
-// channel sums all N * nblk partials in a fixed order.  No float atomics: run-to-run bit-identical.  Self-contained: shares
-// only common.h with instnorm.hip.
-#include "common.h"
+// channel sums all N * nblk partials in a fixed order.  No float atomics: run-to-run bit-identical.  The geometry, the
+// row walk, the pre-activation and the reductions are those of norm_common.h, shared with instnorm.hip and resblock.hip;
+// the kernels and the epilogues (running buffers, step counter, the EVAL root) are this file's own.
+#include "norm_common.h"
 
 namespace mvd {
 
-struct BnGeom {
-    int C, VEC, CG, R, threads, nblk;
-    long V, chunk;
-};
-
-// thread = (channel group g of VEC channels, row r); a block owns `chunk` voxels of one sample
-static BnGeom bn_geom(int N, long V, int C) {
-    BnGeom g;
-    g.C = C;
-    g.V = V;
-    g.VEC = (C % 4 == 0) ? 4 : 1;
-    g.CG = C / g.VEC;  // C <= 1024: at most 256 groups of four, or up to 1023 scalar columns
-    g.R = 256 / g.CG;
-    if (g.R < 1) g.R = 1;
-    g.threads = ((g.R * g.CG + 63) / 64) * 64;
-    long want = 2048 / (N > 0 ? N : 1);
-    if (want < 1) want = 1;
-    long rows_min = (long)g.R * 16;  // at least 16 voxels per thread
-    long nblk = V / rows_min;
-    if (nblk < 1) nblk = 1;
-    if (nblk > want) nblk = want;
-    g.chunk = cdiv(V, nblk);
-    g.nblk = (int)cdiv(V, g.chunk);  // (no empty trailing block)
+static NormGeom bn_geom(int N, long V, int C) {
+    NormGeom g = norm_geom(N, V, C);
+    g.nblk = (int)cdiv(V, g.chunk);  // (no empty trailing block: one wave per channel sums ALL N * nblk partials)
     return g;
-}
-
-// the streaming passes take more, smaller chunks than the reducing ones (no reduction to amortise)
-static long bn_apply_chunk(const BnGeom &g, int N) {
-    long nb2 = g.V / ((long)g.R * 8);
-    if (nb2 < 1) nb2 = 1;
-    long cap2 = 8192 / N > 0 ? 8192 / N : 1;
-    if (nb2 > cap2) nb2 = cap2;
-    return cdiv(g.V, nb2);
-}
-
-// VEC consecutive channels at element e, as fp32
-template <int VEC, bool BF>
-__device__ __forceinline__ void bn_ld(const void *p, size_t e, float (&f)[VEC]) {
-    if constexpr (VEC == 4) {
-        const float4 q = ld4<BF>(p, e);
-        f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
-    } else
-        f[0] = ld1<BF>(p, e);
-}
-template <int VEC, bool BF>
-__device__ __forceinline__ void bn_st(void *p, size_t e, const float (&f)[VEC]) {
-    if constexpr (VEC == 4)
-        st4<BF>(p, e, f[0], f[1], f[2], f[3]);
-    else
-        st1<BF>(p, e, f[0]);
-}
-
-// rows r < R of the block -> partial[(n * nblk + b)][c][2], rows added in ascending order
-template <int VEC>
-__device__ __forceinline__ void bn_block_reduce(const double (&s)[VEC], const double (&ss)[VEC], double *sm,
-                                                double *__restrict__ partial, int C, int R, int g, int r) {
-    if (r < R) {
-#pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            sm[((size_t)r * C + g * VEC + i) * 2 + 0] = s[i];
-            sm[((size_t)r * C + g * VEC + i) * 2 + 1] = ss[i];
-        }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        double a = 0, q = 0;
-        for (int rr = 0; rr < R; rr++) {
-            a += sm[((size_t)rr * C + c) * 2 + 0];
-            q += sm[((size_t)rr * C + c) * 2 + 1];
-        }
-        const size_t o = (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * C + c) * 2;
-        partial[o] = a;
-        partial[o + 1] = q;
-    }
 }
 
 // ---- fwd pass 1: partial[n][b][c][2] = (sum x, sum x^2) in fp64
@@ -90,60 +21,13 @@ template <int VEC, bool XB>
 __global__ __launch_bounds__(1024) void k_bn_stats(const void *__restrict__ x, double *__restrict__ partial, int C, int CG,
                                                    int R, long V, long chunk) {
     extern __shared__ double sm[];  // [R][C][2]
-    const int n = blockIdx.y, t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    const long v0 = (long)blockIdx.x * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
-    double s[VEC], ss[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; i++) s[i] = ss[i] = 0.0;
-    if (r < R) {
-        const size_t base = ((size_t)n * V) * C + (size_t)g * VEC;
-        long v = v0 + r;
-        for (; v + 3L * R < v1; v += 4L * R) {  // four rows in flight per thread, accumulated in row order
-            float f[4][VEC];
-#pragma unroll
-            for (int u = 0; u < 4; u++) bn_ld<VEC, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-#pragma unroll
-                for (int i = 0; i < VEC; i++) {
-                    s[i] += (double)f[u][i];
-                    ss[i] += (double)f[u][i] * (double)f[u][i];
-                }
-        }
-        for (; v < v1; v += R) {
-            float f[VEC];
-            bn_ld<VEC, XB>(x, base + (size_t)v * C, f);
-#pragma unroll
-            for (int i = 0; i < VEC; i++) {
-                s[i] += (double)f[i];
-                ss[i] += (double)f[i] * (double)f[i];
-            }
-        }
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r < R) {
+        double s[VEC] = {}, ss[VEC] = {};
+        norm_moments<VEC, XB>(x, t.base(V, C), t.v0 + t.r, t.v1, R, C, s, ss);
+        norm_row_store<VEC>(sm, C, t.c0(), t.r, s, ss);
     }
-    bn_block_reduce<VEC>(s, ss, sm, partial, C, R, g, r);
-}
-
-// all `total` = N * nblk block partials of channel c, summed by one wave: lanes stride over them (two in flight), then the
-// fixed shuffle tree.  Valid in lane 0.
-__device__ __forceinline__ void bn_channel_sum(const double *__restrict__ partial, int C, int c, long total, double &a,
-                                               double &q) {
-    double a0 = 0, q0 = 0, a1 = 0, q1 = 0;
-    long j = threadIdx.x;
-    for (; j + 64 < total; j += 128) {
-        const size_t o = ((size_t)j * C + c) * 2, o1 = ((size_t)(j + 64) * C + c) * 2;
-        const double va = partial[o], vq = partial[o + 1], wa = partial[o1], wq = partial[o1 + 1];
-        a0 += va; q0 += vq; a1 += wa; q1 += wq;
-    }
-    for (; j < total; j += 64) {
-        const size_t o = ((size_t)j * C + c) * 2;
-        a0 += partial[o];
-        q0 += partial[o + 1];
-    }
-    a = wave_sum(a0 + a1);
-    q = wave_sum(q0 + q1);
+    norm_block_reduce<2>(sm, partial, C, R, (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // one wave per channel: mean, rstd (biased variance, formed in fp64, clamped at 0), the running buffers
@@ -153,11 +37,11 @@ __global__ void k_bn_finalize(const double *__restrict__ partial, float *__restr
                               long long *__restrict__ num_batches_tracked, int C, long total, long M, float eps,
                               double momentum) {
     const int c = blockIdx.x;
-    double a, q;
-    bn_channel_sum(partial, C, c, total, a, q);
+    double s[2];
+    norm_wave_sum<2>(partial, C, c, 0, (int)total, s);  // (total = N * nblk <= max(2048, N))
     if (threadIdx.x != 0) return;
-    const double m = a / (double)M;
-    double var = q / (double)M - m * m;
+    const double m = s[0] / (double)M;
+    double var = s[1] / (double)M - m * m;
     if (var < 0) var = 0;
     mean[c] = (float)m;
     rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -175,48 +59,40 @@ __global__ __launch_bounds__(1024) void k_bn_apply(const void *__restrict__ x, c
                                                    const float *__restrict__ beta, const float *__restrict__ mean,
                                                    const float *__restrict__ rstd_or_var, void *__restrict__ y, int C, int CG,
                                                    int R, long V, long chunk, float eps, float slope) {
-    const int n = blockIdx.y, t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    if (r >= R) return;
-    const long v0 = (long)blockIdx.x * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r >= R) return;
+    const size_t base = t.base(V, C);
     float mu[VEC], rs[VEC], ga[VEC], be[VEC];
+    norm_consts<VEC>(mu, rs, ga, be, mean, rstd_or_var, gamma, beta, 0, t.c0());
+    if (EVAL)
 #pragma unroll
-    for (int i = 0; i < VEC; i++) {
-        const int c = g * VEC + i;
-        mu[i] = mean[c];
-        rs[i] = EVAL ? (float)(1.0 / sqrt((double)rstd_or_var[c] + (double)eps)) : rstd_or_var[c];
-        ga[i] = gamma[c];
-        be[i] = beta[c];
-    }
-    const size_t base = ((size_t)n * V) * C + (size_t)g * VEC;
-    long v = v0 + r;
-    for (; v + 3L * R < v1; v += 4L * R) {  // four independent rows in flight
+        for (int i = 0; i < VEC; i++) rs[i] = (float)(1.0 / sqrt((double)rs[i] + (double)eps));
+    long v = t.v0 + t.r;
+    for (; v + 3L * R < t.v1; v += 4L * R) {  // four independent rows in flight
         float f[4][VEC];
 #pragma unroll
-        for (int u = 0; u < 4; u++) bn_ld<VEC, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
+        for (int u = 0; u < 4; u++) norm_ld<VEC, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
 #pragma unroll
         for (int u = 0; u < 4; u++) {
 #pragma unroll
             for (int i = 0; i < VEC; i++) {
-                const float xh = (f[u][i] - mu[i]) * rs[i];
-                const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
+                float xh;
+                const float z = norm_z(f[u][i], mu[i], rs[i], ga[i], be[i], xh);
                 f[u][i] = z > 0.f ? z : z * slope;
             }
-            bn_st<VEC, YB>(y, base + (size_t)(v + (long)u * R) * C, f[u]);
+            norm_st<VEC, YB>(y, base + (size_t)(v + (long)u * R) * C, f[u]);
         }
     }
-    for (; v < v1; v += R) {
+    for (; v < t.v1; v += R) {
         float f[VEC];
-        bn_ld<VEC, XB>(x, base + (size_t)v * C, f);
+        norm_ld<VEC, XB>(x, base + (size_t)v * C, f);
 #pragma unroll
         for (int i = 0; i < VEC; i++) {
-            const float xh = (f[i] - mu[i]) * rs[i];
-            const float z = fmaf(xh, ga[i], be[i]);
+            float xh;
+            const float z = norm_z(f[i], mu[i], rs[i], ga[i], be[i], xh);
             f[i] = z > 0.f ? z : z * slope;
         }
-        bn_st<VEC, YB>(y, base + (size_t)v * C, f);
+        norm_st<VEC, YB>(y, base + (size_t)v * C, f);
     }
 }
 
@@ -228,72 +104,60 @@ __global__ __launch_bounds__(1024) void k_bn_bwd_stats(const void *__restrict__ 
                                                        double *__restrict__ partial, int C, int CG, int R, long V,
                                                        long chunk, float slope) {
     extern __shared__ double sm[];  // [R][C][2]
-    const int n = blockIdx.y, t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    const long v0 = (long)blockIdx.x * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
-    double s[VEC], ss[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; i++) s[i] = ss[i] = 0.0;
-    if (r < R) {
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r < R) {
+        double s[VEC] = {}, ss[VEC] = {};
+        const size_t base = t.base(V, C);
         float mu[VEC], rs[VEC], ga[VEC], be[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            const int c = g * VEC + i;
-            mu[i] = mean[c];
-            rs[i] = rstd[c];
-            ga[i] = gamma[c];
-            be[i] = beta[c];
-        }
-        const size_t base = ((size_t)n * V) * C + (size_t)g * VEC;
-        long v = v0 + r;
-        for (; v + R < v1; v += 2L * R) {  // two rows (four loads) in flight per thread, accumulated in row order
+        norm_consts<VEC>(mu, rs, ga, be, mean, rstd, gamma, beta, 0, t.c0());
+        long v = t.v0 + t.r;
+        for (; v + R < t.v1; v += 2L * R) {  // two rows (four loads) in flight per thread, accumulated in row order
             float f[2][VEC], d[2][VEC];
 #pragma unroll
             for (int u = 0; u < 2; u++) {
-                bn_ld<VEC, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
-                bn_ld<VEC, YB>(dy, base + (size_t)(v + (long)u * R) * C, d[u]);
+                norm_ld<VEC, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
+                norm_ld<VEC, YB>(dy, base + (size_t)(v + (long)u * R) * C, d[u]);
             }
 #pragma unroll
             for (int u = 0; u < 2; u++)
 #pragma unroll
                 for (int i = 0; i < VEC; i++) {
-                    const float xh = (f[u][i] - mu[i]) * rs[i];
-                    const float z = fmaf(xh, ga[i], be[i]);
+                    float xh;
+                    const float z = norm_z(f[u][i], mu[i], rs[i], ga[i], be[i], xh);
                     const float dz = z > 0.f ? d[u][i] : d[u][i] * slope;
                     s[i] += (double)dz;
                     ss[i] += (double)dz * (double)xh;
                 }
         }
-        for (; v < v1; v += R) {
+        for (; v < t.v1; v += R) {
             float f[VEC], d[VEC];
-            bn_ld<VEC, XB>(x, base + (size_t)v * C, f);
-            bn_ld<VEC, YB>(dy, base + (size_t)v * C, d);
+            norm_ld<VEC, XB>(x, base + (size_t)v * C, f);
+            norm_ld<VEC, YB>(dy, base + (size_t)v * C, d);
 #pragma unroll
             for (int i = 0; i < VEC; i++) {
-                const float xh = (f[i] - mu[i]) * rs[i];
-                const float z = fmaf(xh, ga[i], be[i]);
+                float xh;
+                const float z = norm_z(f[i], mu[i], rs[i], ga[i], be[i], xh);
                 const float dz = z > 0.f ? d[i] : d[i] * slope;
                 s[i] += (double)dz;
                 ss[i] += (double)dz * (double)xh;
             }
         }
+        norm_row_store<VEC>(sm, C, t.c0(), t.r, s, ss);
     }
-    bn_block_reduce<VEC>(s, ss, sm, partial, C, R, g, r);
+    norm_block_reduce<2>(sm, partial, C, R, (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // one wave per channel over all n: sums[c][2] (float) = (sum dz, sum dz * xhat) = (dbeta, dgamma)
 __global__ void k_bn_bwd_finalize(const double *__restrict__ partial, float *__restrict__ sums, float *__restrict__ dgamma,
                                   float *__restrict__ dbeta, int C, long total) {
     const int c = blockIdx.x;
-    double a, q;
-    bn_channel_sum(partial, C, c, total, a, q);
+    double s[2];
+    norm_wave_sum<2>(partial, C, c, 0, (int)total, s);
     if (threadIdx.x != 0) return;
-    sums[(size_t)c * 2 + 0] = (float)a;
-    sums[(size_t)c * 2 + 1] = (float)q;
-    dgamma[c] = (float)q;  // (scalar stores: the gradients may be slices of a flat buffer)
-    dbeta[c] = (float)a;
+    sums[(size_t)c * 2 + 0] = (float)s[0];
+    sums[(size_t)c * 2 + 1] = (float)s[1];
+    dgamma[c] = (float)s[1];  // (scalar stores: the gradients may be slices of a flat buffer)
+    dbeta[c] = (float)s[0];
 }
 
 // ---- bwd pass 2: dx = gamma * rstd * (dz - sum dz / M - xhat * sum dz xhat / M), in x's dtype
@@ -303,56 +167,48 @@ __global__ __launch_bounds__(1024) void k_bn_bwd_apply(const void *__restrict__ 
                                                        const float *__restrict__ mean, const float *__restrict__ rstd,
                                                        const float *__restrict__ sums, void *__restrict__ dx, int C, int CG,
                                                        int R, long V, long chunk, float invM, float slope) {
-    const int n = blockIdx.y, t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    if (r >= R) return;
-    const long v0 = (long)blockIdx.x * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r >= R) return;
+    const size_t base = t.base(V, C);
     float mu[VEC], rs[VEC], ga[VEC], be[VEC], m1[VEC], m2[VEC];
+    norm_consts<VEC>(mu, rs, ga, be, mean, rstd, gamma, beta, 0, t.c0());
 #pragma unroll
     for (int i = 0; i < VEC; i++) {
-        const int c = g * VEC + i;
-        mu[i] = mean[c];
-        rs[i] = rstd[c];
-        ga[i] = gamma[c];
-        be[i] = beta[c];
-        m1[i] = sums[(size_t)c * 2 + 0] * invM;
-        m2[i] = sums[(size_t)c * 2 + 1] * invM;
+        m1[i] = sums[(size_t)(t.c0() + i) * 2 + 0] * invM;
+        m2[i] = sums[(size_t)(t.c0() + i) * 2 + 1] * invM;
     }
-    const size_t base = ((size_t)n * V) * C + (size_t)g * VEC;
-    long v = v0 + r;
-    for (; v + 3L * R < v1; v += 4L * R) {  // four rows (eight loads) in flight
+    long v = t.v0 + t.r;
+    for (; v + 3L * R < t.v1; v += 4L * R) {  // four rows (eight loads) in flight
         float f[4][VEC], d[4][VEC];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            bn_ld<VEC, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
-            bn_ld<VEC, YB>(dy, base + (size_t)(v + (long)u * R) * C, d[u]);
+            norm_ld<VEC, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
+            norm_ld<VEC, YB>(dy, base + (size_t)(v + (long)u * R) * C, d[u]);
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
 #pragma unroll
             for (int i = 0; i < VEC; i++) {
-                const float xh = (f[u][i] - mu[i]) * rs[i];
-                const float z = fmaf(xh, ga[i], be[i]);
+                float xh;
+                const float z = norm_z(f[u][i], mu[i], rs[i], ga[i], be[i], xh);
                 const float dz = z > 0.f ? d[u][i] : d[u][i] * slope;
                 f[u][i] = ga[i] * rs[i] * (dz - m1[i] - xh * m2[i]);
             }
-            bn_st<VEC, XB>(dx, base + (size_t)(v + (long)u * R) * C, f[u]);
+            norm_st<VEC, XB>(dx, base + (size_t)(v + (long)u * R) * C, f[u]);
         }
     }
-    for (; v < v1; v += R) {
+    for (; v < t.v1; v += R) {
         float f[VEC], d[VEC];
-        bn_ld<VEC, XB>(x, base + (size_t)v * C, f);
-        bn_ld<VEC, YB>(dy, base + (size_t)v * C, d);
+        norm_ld<VEC, XB>(x, base + (size_t)v * C, f);
+        norm_ld<VEC, YB>(dy, base + (size_t)v * C, d);
 #pragma unroll
         for (int i = 0; i < VEC; i++) {
-            const float xh = (f[i] - mu[i]) * rs[i];
-            const float z = fmaf(xh, ga[i], be[i]);
+            float xh;
+            const float z = norm_z(f[i], mu[i], rs[i], ga[i], be[i], xh);
             const float dz = z > 0.f ? d[i] : d[i] * slope;
             f[i] = ga[i] * rs[i] * (dz - m1[i] - xh * m2[i]);
         }
-        bn_st<VEC, XB>(dx, base + (size_t)v * C, f);
+        norm_st<VEC, XB>(dx, base + (size_t)v * C, f);
     }
 }
 
@@ -375,7 +231,7 @@ int mvd_batchnorm_nblk(int N, long V, int C) { return bn_shape_ok(N, V, C) ? bn_
 
 size_t mvd_batchnorm_workspace_bytes(int N, long V, int C) {
     if (!bn_shape_ok(N, V, C)) return 0;
-    const BnGeom g = bn_geom(N, V, C);
+    const NormGeom g = bn_geom(N, V, C);
     // partials [N][nblk][C][2] doubles + sums [C][2] floats
     return (size_t)N * g.nblk * C * 2 * sizeof(double) + (size_t)C * 2 * sizeof(float) + 256;
 }
@@ -390,8 +246,8 @@ int mvd_batchnorm_lrelu_fwd(const void *x, int x_is_bf16, const float *gamma, co
     MVD_REQUIRE((long)N * V > 1, "batchnorm_fwd: expected more than 1 value per channel when training (N * V == 1)");
     MVD_REQUIRE(momentum >= 0.0 && momentum <= 1.0, "batchnorm_fwd: momentum %g outside [0, 1]", momentum);
     MVD_REQUIRE(ws_bytes >= mvd_batchnorm_workspace_bytes(N, V, C), "batchnorm_fwd: workspace too small");
-    const BnGeom g = bn_geom(N, V, C);
-    const bool v4 = g.VEC == 4, xb = x_is_bf16 != 0, yb = y_is_bf16 != 0;
+    const NormGeom g = bn_geom(N, V, C);
+    const bool v4 = g.vec == 4, xb = x_is_bf16 != 0, yb = y_is_bf16 != 0;
     hipStream_t s = as_stream(stream);
     double *partial = reinterpret_cast<double *>(ws);
     const size_t sm = (size_t)g.R * C * 2 * sizeof(double);  // <= 16 KiB for C <= 1024
@@ -401,7 +257,7 @@ int mvd_batchnorm_lrelu_fwd(const void *x, int x_is_bf16, const float *gamma, co
     hipLaunchKernelGGL(k_bn_finalize, dim3(C), dim3(64), 0, s, partial, mean, rstd, running_mean, running_var,
                        reinterpret_cast<long long *>(num_batches_tracked), C, (long)N * g.nblk, (long)N * V, eps, momentum);
     if (check_launch("batchnorm finalize")) return 1;
-    const long chunk2 = bn_apply_chunk(g, N);
+    const long chunk2 = norm_apply_chunk(g, 8192 / N);
     auto apply = MVD_BN_PICK(k_bn_apply, v4, xb, yb, , false);
     hipLaunchKernelGGL(apply, dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, s, x, gamma, beta, mean, rstd, y, C, g.CG,
                        g.R, V, chunk2, eps, slope);
@@ -414,9 +270,9 @@ int mvd_batchnorm_lrelu_eval(const void *x, int x_is_bf16, const float *gamma, c
     MVD_REQUIRE(x && gamma && beta && y && running_mean && running_var,
                 "batchnorm_eval: null pointer (affine parameters and running buffers are required)");
     MVD_REQUIRE(bn_shape_ok(N, V, C), "batchnorm_eval: bad shape N=%d V=%ld C=%d", N, V, C);
-    const BnGeom g = bn_geom(N, V, C);
-    const bool v4 = g.VEC == 4, xb = x_is_bf16 != 0, yb = y_is_bf16 != 0;
-    const long chunk2 = bn_apply_chunk(g, N);
+    const NormGeom g = bn_geom(N, V, C);
+    const bool v4 = g.vec == 4, xb = x_is_bf16 != 0, yb = y_is_bf16 != 0;
+    const long chunk2 = norm_apply_chunk(g, 8192 / N);
     auto apply = MVD_BN_PICK(k_bn_apply, v4, xb, yb, , true);
     hipLaunchKernelGGL(apply, dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, as_stream(stream), x, gamma, beta,
                        running_mean, running_var, y, C, g.CG, g.R, V, chunk2, eps, slope);
@@ -430,8 +286,8 @@ int mvd_batchnorm_lrelu_bwd(const void *x, int x_is_bf16, const void *dy, int y_
     MVD_REQUIRE(bn_shape_ok(N, V, C), "batchnorm_bwd: bad shape N=%d V=%ld C=%d", N, V, C);
     MVD_REQUIRE((long)N * V > 1, "batchnorm_bwd: expected more than 1 value per channel (N * V == 1)");
     MVD_REQUIRE(ws_bytes >= mvd_batchnorm_workspace_bytes(N, V, C), "batchnorm_bwd: workspace too small");
-    const BnGeom g = bn_geom(N, V, C);
-    const bool v4 = g.VEC == 4, xb = x_is_bf16 != 0, yb = y_is_bf16 != 0;
+    const NormGeom g = bn_geom(N, V, C);
+    const bool v4 = g.vec == 4, xb = x_is_bf16 != 0, yb = y_is_bf16 != 0;
     hipStream_t s = as_stream(stream);
     double *partial = reinterpret_cast<double *>(ws);
     float *sums = reinterpret_cast<float *>(partial + (size_t)N * g.nblk * C * 2);
@@ -442,7 +298,7 @@ int mvd_batchnorm_lrelu_bwd(const void *x, int x_is_bf16, const void *dy, int y_
     if (check_launch("batchnorm bwd stats")) return 1;
     hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(C), dim3(64), 0, s, partial, sums, dgamma, dbeta, C, (long)N * g.nblk);
     if (check_launch("batchnorm bwd finalize")) return 1;
-    const long chunk2 = bn_apply_chunk(g, N);
+    const long chunk2 = norm_apply_chunk(g, 8192 / N);
     auto apply = MVD_BN_PICK(k_bn_bwd_apply, v4, xb, yb);
     hipLaunchKernelGGL(apply, dim3((unsigned)cdiv(V, chunk2), N), dim3(g.threads), 0, s, x, dy, gamma, beta, mean, rstd, sums, dx,
                        C, g.CG, g.R, V, chunk2, (float)(1.0 / (double)((long)N * V)), slope);

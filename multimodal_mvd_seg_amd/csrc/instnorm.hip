@@ -1,101 +1,24 @@
 // Fused InstanceNorm3d(affine) + LeakyReLU on NDHWC fp32 activations  (SURVEY K3/K4).
 // HBM-bound: fwd = read x (stats) + read x + write y; bwd = read x,dy (sums) + read x,dy + write dx.
-// Statistics: per-thread fp64 accumulation -> fixed-order LDS reduce -> per-block partials -> fixed-order finalize.
-#include "common.h"
+// Statistics: per-thread fp64 accumulation -> fixed-order LDS reduce -> per-block partials -> fixed-order finalize; the
+// geometry, the row walk, the pre-activation and these reductions are those of norm_common.h (shared with batchnorm.hip and
+// resblock.hip).  The single-launch (small), tile-statistics and scale / shift kernels are this file's own.
+#include "norm_common.h"
 
 namespace mvd {
-
-struct NormGeom {
-    int C, CG, R, threads, nblk;
-    long V, chunk;
-};
-
-static NormGeom norm_geom(int N, long V, int C) {
-    NormGeom g;
-    g.C = C;
-    g.V = V;
-    int vec = (C % 4 == 0) ? 4 : 1;
-    g.CG = C / vec;  // at most 256 for C % 4 == 0 and at most 1024 otherwise: every entry point requires C <= 1024
-    g.R = 256 / g.CG;
-    if (g.R < 1) g.R = 1;
-    g.threads = ((g.R * g.CG + 63) / 64) * 64;
-    if (g.threads > 1024) g.threads = 1024;
-    long want = 2048 / (N > 0 ? N : 1);
-    if (want < 1) want = 1;
-    long rows_min = (long)g.R * 16;  // at least 16 voxels per thread
-    long nblk = V / rows_min;
-    if (nblk < 1) nblk = 1;
-    if (nblk > want) nblk = want;
-    g.nblk = (int)nblk;
-    g.chunk = cdiv(V, nblk);
-    return g;
-}
 
 // ---- pass 1 (fwd): partial[n][b][c][2] = (sum x, sum x^2) in fp64
 template <int VEC, bool XB>
 __global__ void k_in_stats(const float *__restrict__ x, double *__restrict__ partial, int C, int CG, int R, long V,
                            long chunk) {
     extern __shared__ double sm[];  // [R][C][2]
-    const int n = blockIdx.y, b = blockIdx.x, nblk = gridDim.x;
-    const int t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    const long v0 = (long)b * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
-    double s[VEC], ss[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; i++) s[i] = ss[i] = 0.0;
-    if (r < R) {
-        const float *xp = x + ((size_t)n * V) * C + (size_t)g * VEC;
-        long v = v0 + r;
-        if (VEC == 4) {
-            for (; v + 3L * R < v1; v += 4L * R) {  // four rows in flight per thread, accumulated in row order
-                float4 q4[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) q4[u] = ld4<XB>(x, ((size_t)n * V + v + (long)u * R) * C + (size_t)g * 4);
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const float f[4] = {q4[u].x, q4[u].y, q4[u].z, q4[u].w};
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        s[i] += (double)f[i];
-                        ss[i] += (double)f[i] * (double)f[i];
-                    }
-                }
-            }
-        }
-        for (; v < v1; v += R) {
-            if (VEC == 4) {
-                float4 q = ld4<XB>(x, ((size_t)n * V + v) * C + (size_t)g * 4);
-                float f[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    s[i] += (double)f[i];
-                    ss[i] += (double)f[i] * (double)f[i];
-                }
-            } else {
-                float f = xp[(size_t)v * C];
-                s[0] += (double)f;
-                ss[0] += (double)f * (double)f;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            sm[((size_t)r * C + g * VEC + i) * 2 + 0] = s[i];
-            sm[((size_t)r * C + g * VEC + i) * 2 + 1] = ss[i];
-        }
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r < R) {
+        double s[VEC] = {}, ss[VEC] = {};
+        norm_moments<VEC, XB>(x, t.base(V, C), t.v0 + t.r, t.v1, R, C, s, ss);
+        norm_row_store<VEC>(sm, C, t.c0(), t.r, s, ss);
     }
-    __syncthreads();
-    for (int c = t; c < C; c += blockDim.x) {
-        double a = 0, q = 0;
-        for (int rr = 0; rr < R; rr++) {
-            a += sm[((size_t)rr * C + c) * 2 + 0];
-            q += sm[((size_t)rr * C + c) * 2 + 1];
-        }
-        size_t o = (((size_t)n * nblk + b) * C + c) * 2;
-        partial[o] = a;
-        partial[o + 1] = q;
-    }
+    norm_block_reduce<2>(sm, partial, C, R, (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // scale / shift (optional): the fused form scale = gamma * rstd, shift = beta - mean * scale of the bf16 path (the expression
@@ -106,23 +29,11 @@ __global__ void k_in_finalize(const double *__restrict__ partial, float *__restr
                               float *__restrict__ shift = nullptr) {
     // one wave per (n, c): lanes stride over the block partials, fixed shuffle tree (deterministic)
     const int n = blockIdx.y, c = blockIdx.x;
-    double a = 0, q = 0, a1 = 0, q1 = 0;
-    int b = threadIdx.x;
-    for (; b + 64 < nblk; b += 128) {  // two block partials (four loads) in flight per lane, fixed order
-        const size_t o = (((size_t)n * nblk + b) * C + c) * 2, o1 = (((size_t)n * nblk + b + 64) * C + c) * 2;
-        const double va = partial[o], vq = partial[o + 1], wa = partial[o1], wq = partial[o1 + 1];
-        a += va; q += vq; a1 += wa; q1 += wq;
-    }
-    for (; b < nblk; b += 64) {
-        size_t o = (((size_t)n * nblk + b) * C + c) * 2;
-        a += partial[o];
-        q += partial[o + 1];
-    }
-    a = wave_sum(a + a1);
-    q = wave_sum(q + q1);
+    double s[2];
+    norm_wave_sum<2>(partial, C, c, (size_t)n * nblk, nblk, s);
     if (threadIdx.x != 0) return;
-    double m = a / (double)V;
-    double var = q / (double)V - m * m;
+    double m = s[0] / (double)V;
+    double var = s[1] / (double)V - m * m;
     if (var < 0) var = 0;
     const float mf = (float)m, rf = (float)(1.0 / sqrt(var + (double)eps));
     mean[(size_t)n * C + c] = mf;
@@ -201,14 +112,14 @@ __global__ void k_in_apply(const float *__restrict__ x, const float *__restrict_
             float f[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                float xh = (f[k] - mean[(size_t)n * C + c + k]) * rstd[(size_t)n * C + c + k];
-                float z = fmaf(xh, gamma[c + k], beta[c + k]);
+                float xh;
+                const float z = norm_z(f[k], mean[(size_t)n * C + c + k], rstd[(size_t)n * C + c + k], gamma[c + k], beta[c + k], xh);
                 f[k] = z > 0.f ? z : z * slope;
             }
             reinterpret_cast<float4 *>(yn)[i] = make_float4(f[0], f[1], f[2], f[3]);
         } else {
-            float xh = (xn[i] - mean[(size_t)n * C + c]) * rstd[(size_t)n * C + c];
-            float z = fmaf(xh, gamma[c], beta[c]);
+            float xh;
+            const float z = norm_z(xn[i], mean[(size_t)n * C + c], rstd[(size_t)n * C + c], gamma[c], beta[c], xh);
             yn[i] = z > 0.f ? z : z * slope;
         }
     }
@@ -221,49 +132,37 @@ __global__ void k_in_apply_rows(const float *__restrict__ x, const float *__rest
                                 const float *__restrict__ beta, const float *__restrict__ mean,
                                 const float *__restrict__ rstd, float *__restrict__ y, int C, int CG, int R, long V,
                                 long chunk, float slope) {
-    const int n = blockIdx.y, t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    if (r >= R) return;
-    const long v0 = (long)blockIdx.x * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
+    const NormThread<4> t(CG, V, chunk);
+    if (t.r >= R) return;
+    const size_t base = t.base(V, C);
     float mu[4], rs[4], ga[4], be[4];
+    norm_consts<4>(mu, rs, ga, be, mean, rstd, gamma, beta, (size_t)blockIdx.y * C, t.c0());
+    long v = t.v0 + t.r;
+    for (; v + 3L * R < t.v1; v += 4L * R) {  // four independent rows in flight
+        float f[4][4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int c = g * 4 + i;
-        mu[i] = mean[(size_t)n * C + c];
-        rs[i] = rstd[(size_t)n * C + c];
-        ga[i] = gamma[c];
-        be[i] = beta[c];
-    }
-    const size_t base = ((size_t)n * V) * C + (size_t)g * 4;
-    long v = v0 + r;
-    for (; v + 3L * R < v1; v += 4L * R) {  // four independent rows in flight
-        float4 q[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) q[u] = ld4<XB>(x, base + (size_t)(v + (long)u * R) * C);
+        for (int u = 0; u < 4; u++) norm_ld<4, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            float f[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float xh = (f[i] - mu[i]) * rs[i];
-                const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
-                f[i] = z > 0.f ? z : z * slope;
+                float xh;
+                const float z = norm_z(f[u][i], mu[i], rs[i], ga[i], be[i], xh);
+                f[u][i] = z > 0.f ? z : z * slope;
             }
-            st4<YB>(y, base + (size_t)(v + (long)u * R) * C, f[0], f[1], f[2], f[3]);
+            norm_st<4, YB>(y, base + (size_t)(v + (long)u * R) * C, f[u]);
         }
     }
-    for (; v < v1; v += R) {
-        float4 q = ld4<XB>(x, base + (size_t)v * C);
-        float f[4] = {q.x, q.y, q.z, q.w};
+    for (; v < t.v1; v += R) {
+        float f[4];
+        norm_ld<4, XB>(x, base + (size_t)v * C, f);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const float xh = (f[i] - mu[i]) * rs[i];
-            const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
+            float xh;
+            const float z = norm_z(f[i], mu[i], rs[i], ga[i], be[i], xh);
             f[i] = z > 0.f ? z : z * slope;
         }
-        st4<YB>(y, base + (size_t)v * C, f[0], f[1], f[2], f[3]);
+        norm_st<4, YB>(y, base + (size_t)v * C, f);
     }
 }
 
@@ -295,6 +194,11 @@ __device__ __forceinline__ float4 head_da(const float (&dq)[HK], const float4 (&
     }
     return a;
 }
+template <int HK>  // (into the float[4] of norm_ld)
+__device__ __forceinline__ void head_da(float (&d)[4], const float (&dq)[HK], const float4 (&wk)[HK]) {
+    const float4 a = head_da(dq, wk);
+    d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
+}
 
 #ifndef MVD_IN_NRB
 #define MVD_IN_NRB 4
@@ -308,78 +212,69 @@ __global__ __launch_bounds__(HK > 0 ? 256 : 1024) void k_in_bwd_apply_rows(const
                                     const float *__restrict__ mean, const float *__restrict__ rstd,
                                     const float *__restrict__ sums, float *__restrict__ dx, int C, int CG, int R, long V,
                                     long chunk, float slope, const float *__restrict__ hw = nullptr) {
-    const int n = blockIdx.y, t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    if (r >= R) return;
-    const long v0 = (long)blockIdx.x * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
+    const int n = blockIdx.y;
+    const NormThread<4> t(CG, V, chunk);
+    if (t.r >= R) return;
+    const size_t base = t.base(V, C);
     const float invV = 1.0f / (float)V;
     float mu[4], rs[4], ga[4], be[4], m1[4], m2[4];
+    norm_consts<4>(mu, rs, ga, be, mean, rstd, gamma, beta, (size_t)n * C, t.c0());
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        const int c = g * 4 + i;
-        const size_t nc = (size_t)n * C + c;
-        mu[i] = mean[nc];
-        rs[i] = rstd[nc];
-        ga[i] = gamma[c];
-        be[i] = beta[c];
+        const size_t nc = (size_t)n * C + t.c0() + i;
         m1[i] = sums[nc * 2 + 0] * invV;
         m2[i] = sums[nc * 2 + 1] * invV;
     }
-    const size_t base = ((size_t)n * V) * C + (size_t)g * 4;
     float4 wk[HK > 0 ? HK : 1];
-    if constexpr (HK > 0) head_w_load(wk, hw, C, g);
-    long v = v0 + r;
-    for (; v + (NRB - 1L) * R < v1; v += (long)NRB * R) {  // NRB rows (2 NRB loads) in flight
-        float4 q[NRB], e[NRB];
+    if constexpr (HK > 0) head_w_load(wk, hw, C, t.g);
+    long v = t.v0 + t.r;
+    for (; v + (NRB - 1L) * R < t.v1; v += (long)NRB * R) {  // NRB rows (2 NRB loads) in flight
+        float f[NRB][4], d[NRB][4];
         if constexpr (HK > 0) {
             float dq[NRB][HK];
 #pragma unroll
             for (int u = 0; u < NRB; u++) {
-                q[u] = ld4<XB>(x, base + (size_t)(v + (long)u * R) * C);
+                norm_ld<4, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
                 head_dl_load(dq[u], dy, n, V, v + (long)u * R);
             }
 #pragma unroll
-            for (int u = 0; u < NRB; u++) e[u] = head_da(dq[u], wk);
+            for (int u = 0; u < NRB; u++) head_da(d[u], dq[u], wk);
         } else {
 #pragma unroll
             for (int u = 0; u < NRB; u++) {
-                q[u] = ld4<XB>(x, base + (size_t)(v + (long)u * R) * C);
-                e[u] = ld4<YB>(dy, base + (size_t)(v + (long)u * R) * C);
+                norm_ld<4, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
+                norm_ld<4, YB>(dy, base + (size_t)(v + (long)u * R) * C, d[u]);
             }
         }
 #pragma unroll
         for (int u = 0; u < NRB; u++) {
-            float f[4] = {q[u].x, q[u].y, q[u].z, q[u].w}, d[4] = {e[u].x, e[u].y, e[u].z, e[u].w};
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float xh = (f[i] - mu[i]) * rs[i];
-                const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
-                const float dz = z > 0.f ? d[i] : d[i] * slope;
-                f[i] = ga[i] * rs[i] * (dz - m1[i] - xh * m2[i]);
+                float xh;
+                const float z = norm_z(f[u][i], mu[i], rs[i], ga[i], be[i], xh);
+                const float dz = z > 0.f ? d[u][i] : d[u][i] * slope;
+                f[u][i] = ga[i] * rs[i] * (dz - m1[i] - xh * m2[i]);
             }
-            st4<XB>(dx, base + (size_t)(v + (long)u * R) * C, f[0], f[1], f[2], f[3]);
+            norm_st<4, XB>(dx, base + (size_t)(v + (long)u * R) * C, f[u]);
         }
     }
-    for (; v < v1; v += R) {
-        float4 q = ld4<XB>(x, base + (size_t)v * C);
-        float4 e;
+    for (; v < t.v1; v += R) {
+        float f[4], d[4];
+        norm_ld<4, XB>(x, base + (size_t)v * C, f);
         if constexpr (HK > 0) {
             float dq[HK];
             head_dl_load(dq, dy, n, V, v);
-            e = head_da(dq, wk);
+            head_da(d, dq, wk);
         } else
-            e = ld4<YB>(dy, base + (size_t)v * C);
-        float f[4] = {q.x, q.y, q.z, q.w}, d[4] = {e.x, e.y, e.z, e.w};
+            norm_ld<4, YB>(dy, base + (size_t)v * C, d);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const float xh = (f[i] - mu[i]) * rs[i];
-            const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
+            float xh;
+            const float z = norm_z(f[i], mu[i], rs[i], ga[i], be[i], xh);
             const float dz = z > 0.f ? d[i] : d[i] * slope;
             f[i] = ga[i] * rs[i] * (dz - m1[i] - xh * m2[i]);
         }
-        st4<XB>(dx, base + (size_t)v * C, f[0], f[1], f[2], f[3]);
+        norm_st<4, XB>(dx, base + (size_t)v * C, f);
     }
 }
 
@@ -392,101 +287,68 @@ __global__ __launch_bounds__(HK > 0 ? 256 : 1024) void k_in_bwd_stats(const floa
                                double *__restrict__ partial, int C, int CG, int R, long V, long chunk, float slope,
                                const float *__restrict__ hw = nullptr) {
     static_assert(HK == 0 || VEC == 4, "the head form works on 4-channel groups");
-    extern __shared__ double sm[];
-    const int n = blockIdx.y, b = blockIdx.x, nblk = gridDim.x;
-    const int t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    const long v0 = (long)b * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
-    double s[VEC], ss[VEC];
-    float mu[VEC], rs[VEC], ga[VEC], be[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; i++) s[i] = ss[i] = 0.0;
-    if (r < R) {
-#pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            int c = g * VEC + i;
-            mu[i] = mean[(size_t)n * C + c];
-            rs[i] = rstd[(size_t)n * C + c];
-            ga[i] = gamma[c];
-            be[i] = beta[c];
-        }
-        const size_t base = ((size_t)n * V) * C + (size_t)g * VEC;
+    extern __shared__ double sm[];  // [R][C][2]
+    const int n = blockIdx.y;
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r < R) {
+        double s[VEC] = {}, ss[VEC] = {};
+        const size_t base = t.base(V, C);
+        float mu[VEC], rs[VEC], ga[VEC], be[VEC];
+        norm_consts<VEC>(mu, rs, ga, be, mean, rstd, gamma, beta, (size_t)n * C, t.c0());
         float4 wk[HK > 0 ? HK : 1];
-        if constexpr (HK > 0) head_w_load(wk, hw, C, g);
-        long v = v0 + r;
+        if constexpr (HK > 0) head_w_load(wk, hw, C, t.g);
+        long v = t.v0 + t.r;
         if (VEC == 4) {
-            for (; v + R < v1; v += 2L * R) {  // two rows (four loads) in flight per thread, accumulated in row order
-                const float4 q0 = ld4<XB>(x, base + (size_t)v * C), q1 = ld4<XB>(x, base + (size_t)(v + R) * C);
-                float4 e0, e1;
+            for (; v + R < t.v1; v += 2L * R) {  // two rows (four loads) in flight per thread, accumulated in row order
+                float f[2][VEC], d[2][VEC];
                 if constexpr (HK > 0) {
-                    float d0[HK], d1[HK];
-                    head_dl_load(d0, dy, n, V, v);
-                    head_dl_load(d1, dy, n, V, v + R);
-                    e0 = head_da(d0, wk);
-                    e1 = head_da(d1, wk);
+                    float dq[2][HK];
+#pragma unroll
+                    for (int u = 0; u < 2; u++) norm_ld<VEC, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
+#pragma unroll
+                    for (int u = 0; u < 2; u++) head_dl_load(dq[u], dy, n, V, v + (long)u * R);
+#pragma unroll
+                    for (int u = 0; u < 2; u++) head_da(d[u], dq[u], wk);
                 } else {
-                    e0 = ld4<YB>(dy, base + (size_t)v * C);
-                    e1 = ld4<YB>(dy, base + (size_t)(v + R) * C);
+#pragma unroll
+                    for (int u = 0; u < 2; u++) {
+                        norm_ld<VEC, XB>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
+                        norm_ld<VEC, YB>(dy, base + (size_t)(v + (long)u * R) * C, d[u]);
+                    }
                 }
-                const float fx[2][4] = {{q0.x, q0.y, q0.z, q0.w}, {q1.x, q1.y, q1.z, q1.w}};
-                const float dd[2][4] = {{e0.x, e0.y, e0.z, e0.w}, {e1.x, e1.y, e1.z, e1.w}};
 #pragma unroll
                 for (int u = 0; u < 2; u++)
 #pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        const float xh = (fx[u][i] - mu[i]) * rs[i];
-                        const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
-                        const float dz = z > 0.f ? dd[u][i] : dd[u][i] * slope;
+                    for (int i = 0; i < VEC; i++) {
+                        float xh;
+                        const float z = norm_z(f[u][i], mu[i], rs[i], ga[i], be[i], xh);
+                        const float dz = z > 0.f ? d[u][i] : d[u][i] * slope;
                         s[i] += (double)dz;
                         ss[i] += (double)dz * (double)xh;
                     }
             }
         }
-        for (; v < v1; v += R) {
+        for (; v < t.v1; v += R) {
             float f[VEC], d[VEC];
-            if constexpr (VEC == 4) {
-                float4 q = ld4<XB>(x, base + (size_t)v * C);
-                float4 e;
-                if constexpr (HK > 0) {
-                    float dq[HK];
-                    head_dl_load(dq, dy, n, V, v);
-                    e = head_da(dq, wk);
-                } else
-                    e = ld4<YB>(dy, base + (size_t)v * C);
-                f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
-                d[0] = e.x; d[1] = e.y; d[2] = e.z; d[3] = e.w;
-            } else {
-                f[0] = x[base + (size_t)v * C];
-                d[0] = dy[base + (size_t)v * C];
-            }
+            norm_ld<VEC, XB>(x, base + (size_t)v * C, f);
+            if constexpr (HK > 0) {
+                float dq[HK];
+                head_dl_load(dq, dy, n, V, v);
+                head_da(d, dq, wk);
+            } else
+                norm_ld<VEC, YB>(dy, base + (size_t)v * C, d);
 #pragma unroll
             for (int i = 0; i < VEC; i++) {
-                float xh = (f[i] - mu[i]) * rs[i];
-                float z = fmaf(xh, ga[i], be[i]);
-                float dz = z > 0.f ? d[i] : d[i] * slope;
+                float xh;
+                const float z = norm_z(f[i], mu[i], rs[i], ga[i], be[i], xh);
+                const float dz = z > 0.f ? d[i] : d[i] * slope;
                 s[i] += (double)dz;
                 ss[i] += (double)dz * (double)xh;
             }
         }
-#pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            sm[((size_t)r * C + g * VEC + i) * 2 + 0] = s[i];
-            sm[((size_t)r * C + g * VEC + i) * 2 + 1] = ss[i];
-        }
+        norm_row_store<VEC>(sm, C, t.c0(), t.r, s, ss);
     }
-    __syncthreads();
-    for (int c = t; c < C; c += blockDim.x) {
-        double a = 0, q = 0;
-        for (int rr = 0; rr < R; rr++) {
-            a += sm[((size_t)rr * C + c) * 2 + 0];
-            q += sm[((size_t)rr * C + c) * 2 + 1];
-        }
-        size_t o = (((size_t)n * nblk + b) * C + c) * 2;
-        partial[o] = a;
-        partial[o + 1] = q;
-    }
+    norm_block_reduce<2>(sm, partial, C, R, (size_t)n * gridDim.x + blockIdx.x);
 }
 
 // sums[n][c][2] (float) = (sum dz, sum dz*xhat); dgamma/dbeta over n
@@ -496,26 +358,14 @@ __global__ void k_in_bwd_finalize(const double *__restrict__ partial, float *__r
     const int c = blockIdx.x;
     double tg = 0, tb = 0;
     for (int n = 0; n < N; n++) {
-        double a = 0, q = 0, a1 = 0, q1 = 0;
-        int b = threadIdx.x;
-        for (; b + 64 < nblk; b += 128) {  // (as k_in_finalize)
-            const size_t o = (((size_t)n * nblk + b) * C + c) * 2, o1 = (((size_t)n * nblk + b + 64) * C + c) * 2;
-            const double va = partial[o], vq = partial[o + 1], wa = partial[o1], wq = partial[o1 + 1];
-            a += va; q += vq; a1 += wa; q1 += wq;
-        }
-        for (; b < nblk; b += 64) {
-            size_t o = (((size_t)n * nblk + b) * C + c) * 2;
-            a += partial[o];
-            q += partial[o + 1];
-        }
-        a = wave_sum(a + a1);
-        q = wave_sum(q + q1);
+        double s[2];
+        norm_wave_sum<2>(partial, C, c, (size_t)n * nblk, nblk, s);
         if (threadIdx.x == 0) {
-            sums[((size_t)n * C + c) * 2 + 0] = (float)a;
-            sums[((size_t)n * C + c) * 2 + 1] = (float)q;
+            sums[((size_t)n * C + c) * 2 + 0] = (float)s[0];
+            sums[((size_t)n * C + c) * 2 + 1] = (float)s[1];
         }
-        tb += a;
-        tg += q;
+        tb += s[0];
+        tg += s[1];
     }
     if (threadIdx.x == 0) {
         dgamma[c] = (float)tg;
@@ -567,46 +417,40 @@ __global__ void k_in_finalize_tiles(const float *__restrict__ tile, const float 
 __global__ void k_in_apply_ss16(const unsigned short *__restrict__ x, const float *__restrict__ scale,
                                 const float *__restrict__ shift, unsigned short *__restrict__ y, int C, int CG, int R, long V,
                                 long chunk, float slope) {
-    const int n = blockIdx.y, t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    if (r >= R) return;
-    const long v0 = (long)blockIdx.x * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
+    const int n = blockIdx.y;
+    const NormThread<4> t(CG, V, chunk);
+    if (t.r >= R) return;
+    const size_t base = t.base(V, C);
     float sc[4], sh[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        sc[i] = scale[(size_t)n * C + g * 4 + i];
-        sh[i] = shift[(size_t)n * C + g * 4 + i];
+        sc[i] = scale[(size_t)n * C + t.c0() + i];
+        sh[i] = shift[(size_t)n * C + t.c0() + i];
     }
-    const float *xf = reinterpret_cast<const float *>(x);
-    float *yf = reinterpret_cast<float *>(y);
-    const size_t base = ((size_t)n * V) * C + (size_t)g * 4;
-    long v = v0 + r;
-    for (; v + 3L * R < v1; v += 4L * R) {  // four independent rows in flight
-        float4 q[4];
+    long v = t.v0 + t.r;
+    for (; v + 3L * R < t.v1; v += 4L * R) {  // four independent rows in flight
+        float f[4][4];
 #pragma unroll
-        for (int u = 0; u < 4; u++) q[u] = ld4<true>(xf, base + (size_t)(v + (long)u * R) * C);
+        for (int u = 0; u < 4; u++) norm_ld<4, true>(x, base + (size_t)(v + (long)u * R) * C, f[u]);
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            float f[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float z = fmaf(f[i], sc[i], sh[i]);
-                f[i] = fmaxf(z, z * slope);
+                const float z = fmaf(f[u][i], sc[i], sh[i]);
+                f[u][i] = fmaxf(z, z * slope);
             }
-            st4<true>(yf, base + (size_t)(v + (long)u * R) * C, f[0], f[1], f[2], f[3]);
+            norm_st<4, true>(y, base + (size_t)(v + (long)u * R) * C, f[u]);
         }
     }
-    for (; v < v1; v += R) {
-        float4 q = ld4<true>(xf, base + (size_t)v * C);
-        float f[4] = {q.x, q.y, q.z, q.w};
+    for (; v < t.v1; v += R) {
+        float f[4];
+        norm_ld<4, true>(x, base + (size_t)v * C, f);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const float z = fmaf(f[i], sc[i], sh[i]);
             f[i] = fmaxf(z, z * slope);
         }
-        st4<true>(yf, base + (size_t)v * C, f[0], f[1], f[2], f[3]);
+        norm_st<4, true>(y, base + (size_t)v * C, f);
     }
 }
 
@@ -634,9 +478,8 @@ __global__ void k_in_bwd_apply(const float *__restrict__ x, const float *__restr
 #pragma unroll
         for (int k = 0; k < VEC; k++) {
             size_t nc = (size_t)n * C + c + k;
-            float rs = rstd[nc];
-            float xh = (f[k] - mean[nc]) * rs;
-            float z = fmaf(xh, gamma[c + k], beta[c + k]);
+            float rs = rstd[nc], xh;
+            float z = norm_z(f[k], mean[nc], rs, gamma[c + k], beta[c + k], xh);
             float dz = z > 0.f ? d[k] : d[k] * slope;
             float m1 = sums[nc * 2 + 0] * invV, m2 = sums[nc * 2 + 1] * invV;
             f[k] = gamma[c + k] * rs * (dz - m1 - xh * m2);
@@ -736,8 +579,8 @@ __global__ __launch_bounds__(256) void k_in_small_fwd(const float *__restrict__ 
             float f[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float xh = (f[i] - mu[i]) * rs[i];
-                const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
+                float xh;
+                const float z = norm_z(f[i], mu[i], rs[i], ga[i], be[i], xh);
                 f[i] = z > 0.f ? z : z * slope;
             }
             st4<false>(y, base + (size_t)v * C, f[0], f[1], f[2], f[3]);
@@ -786,8 +629,8 @@ __global__ __launch_bounds__(256) void k_in_small_bwd(const float *__restrict__ 
             float f[4] = {q[j].x, q[j].y, q[j].z, q[j].w}, d[4] = {e[j].x, e[j].y, e[j].z, e[j].w};
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float xh = (f[i] - mu[i]) * rs[i];
-                const float z = fmaf(xh, ga[i], be[i]);  // (explicit: the same rounding in every kernel that re-computes z)
+                float xh;
+                const float z = norm_z(f[i], mu[i], rs[i], ga[i], be[i], xh);
                 const float dz = z > 0.f ? d[i] : d[i] * slope;
                 s[i] += (double)dz;
                 ss[i] += (double)dz * (double)xh;
@@ -867,16 +710,6 @@ struct InPlan {
     int wblk = 0;                                  // norm_geom's nblk: the workspace holds N * wblk * C * 2 doubles
     size_t lds = 0;                                // LDS bytes of the statistics kernels
 };
-
-// row-mapped apply passes: more, smaller voxel chunks than the statistics pass (pure streaming, no reduction)
-static void plan_apply_rows(InPlan &p, int N, long V) {
-    long nb = V / ((long)p.R * 8);
-    if (nb < 1) nb = 1;
-    const long cap = 8192 / N > 0 ? 8192 / N : 1;
-    if (nb > cap) nb = cap;
-    p.achunk = cdiv(V, nb);
-    p.agrid = cdiv(V, p.achunk);
-}
 
 static void plan_apply_scalar(InPlan &p, int N, long V, int C) {  // C % 4 != 0: 256 threads, grid stride over the elements
     const long bx = cdiv(V * C, 256), cap = 4096 / N > 0 ? 4096 / N : 1;
@@ -961,9 +794,10 @@ static int in_plan(InPlan &p, const char *who, int dir, int N, long V, int C, bo
         // networks agree bit for bit whichever kernel produced the statistics
         p.apply = !v4 ? MVD_IN_APPLY1 : xb ? MVD_IN_APPLY_SS16 : MVD_IN_APPLY_ROWS;
     }
-    if (v4)
-        plan_apply_rows(p, N, V);
-    else
+    if (v4) {  // row-mapped apply passes: at most 8192 blocks over the batch
+        p.achunk = norm_apply_chunk(g, 8192 / N);
+        p.agrid = cdiv(V, p.achunk);
+    } else
         plan_apply_scalar(p, N, V, C);
     return 0;
 }

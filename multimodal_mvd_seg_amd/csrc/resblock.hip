@@ -5,57 +5,13 @@
 //   backward  g = dy * lrelu'(z) with z re-computed by the forward's arithmetic (rb_z below, one function for both passes);
 //             da = InstanceNorm backward of g through a; dr = g (identity form) or InstanceNorm backward of g through r
 // HBM-bound.  Identity form: forward = read a (statistics) + read a, r + write y; backward = read a, r, dy (sums) + read a,
-// r, dy + write da, dr.  Statistics as in instnorm.hip: per-thread fp64 accumulation in row order -> fixed-order LDS reduce
-// -> per-block partials -> fixed-order finalize (one wave per channel, fixed shuffle tree).  No atomics anywhere: a graph
-// replay repeats the eager step bit for bit.
-#include "common.h"
+// r, dy + write da, dr.  Geometry, row walk and statistics are those of norm_common.h, shared with instnorm.hip and
+// batchnorm.hip: per-thread fp64 accumulation in row order -> fixed-order LDS reduce -> per-block partials -> fixed-order
+// finalize (one wave per channel, fixed shuffle tree).  No atomics anywhere: a graph replay repeats the eager step bit
+// for bit.
+#include "norm_common.h"
 
 namespace mvd {
-
-struct RbGeom {
-    int vec, CG, R, threads, nblk, agrid;
-    long chunk, achunk;
-};
-
-// thread = (channel group g of `vec` channels, row r); a block walks the rows v0 + r, v0 + r + R, ... of its voxel chunk
-static RbGeom rb_geom(int N, long V, int C) {
-    RbGeom g;
-    g.vec = (C % 4 == 0) ? 4 : 1;
-    g.CG = C / g.vec;  // <= 256 (vec 4) or <= 1024 (scalar): the entry points require C <= 1024
-    g.R = 256 / g.CG;
-    if (g.R < 1) g.R = 1;
-    g.threads = ((g.R * g.CG + 63) / 64) * 64;  // <= 1024
-    long want = 2048 / (N > 0 ? N : 1);
-    if (want < 1) want = 1;
-    long nblk = V / ((long)g.R * 16);  // statistics: at least 16 rows per thread
-    if (nblk < 1) nblk = 1;
-    if (nblk > want) nblk = want;
-    g.nblk = (int)nblk;
-    g.chunk = cdiv(V, nblk);
-    long agrid = V / ((long)g.R * 8);  // apply passes: about 8 rows per thread
-    if (agrid < 1) agrid = 1;
-    if (agrid > 65535) agrid = 65535;
-    g.agrid = (int)agrid;
-    g.achunk = cdiv(V, agrid);
-    return g;
-}
-
-template <int VEC>
-__device__ __forceinline__ void rb_load(float (&f)[VEC], const float *__restrict__ p, size_t e) {
-    if (VEC == 4) {
-        const float4 q = *reinterpret_cast<const float4 *>(p + e);
-        f[0] = q.x; f[1 % VEC] = q.y; f[2 % VEC] = q.z; f[3 % VEC] = q.w;
-    } else {
-        f[0] = p[e];
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void rb_store(const float (&f)[VEC], float *__restrict__ p, size_t e) {
-    if (VEC == 4)
-        *reinterpret_cast<float4 *>(p + e) = make_float4(f[0], f[1 % VEC], f[2 % VEC], f[3 % VEC]);
-    else
-        p[e] = f[0];
-}
 
 // per-channel constants of one thread
 template <int VEC, bool PROJ>
@@ -64,36 +20,23 @@ struct RbCh {
     __device__ __forceinline__ void load(int n, int C, int c0, const float *mean_a, const float *rstd_a, const float *gamma_a,
                                          const float *beta_a, const float *mean_r, const float *rstd_r, const float *gamma_r,
                                          const float *beta_r) {
+        norm_consts<VEC>(mu, rs, ga, be, mean_a, rstd_a, gamma_a, beta_a, (size_t)n * C, c0);
+        if (PROJ)
+            norm_consts<VEC>(mur, rsr, gr, br, mean_r, rstd_r, gamma_r, beta_r, (size_t)n * C, c0);
+        else
 #pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            const int c = c0 + i;
-            mu[i] = mean_a[(size_t)n * C + c];
-            rs[i] = rstd_a[(size_t)n * C + c];
-            ga[i] = gamma_a[c];
-            be[i] = beta_a[c];
-            if (PROJ) {
-                mur[i] = mean_r[(size_t)n * C + c];
-                rsr[i] = rstd_r[(size_t)n * C + c];
-                gr[i] = gamma_r[c];
-                br[i] = beta_r[c];
-            } else {
+            for (int i = 0; i < VEC; i++) {
                 mur[i] = 0.f; rsr[i] = 1.f; gr[i] = 1.f; br[i] = 0.f;
             }
-        }
     }
 };
 
-// THE pre-activation of the block tail; xa / xr return the normalised values.  Explicit fmaf: the same rounding in the
-// forward and in both backward passes, whatever the compiler contracts elsewhere.
-template <bool PROJ>
-__device__ __forceinline__ float rb_z(float a, float r, float mu, float rs, float ga, float be, float mur, float rsr, float gr,
-                                      float br, float &xa, float &xr) {
-    xa = (a - mu) * rs;
-    const float za = fmaf(xa, ga, be);
-    if (PROJ) {
-        xr = (r - mur) * rsr;
-        return za + fmaf(xr, gr, br);
-    }
+// the pre-activation of the block tail, channel i of the thread: norm_z of a, plus r or norm_z of r; xa / xr return the
+// normalised values
+template <int VEC, bool PROJ>
+__device__ __forceinline__ float rb_z(const RbCh<VEC, PROJ> &ch, int i, float a, float r, float &xa, float &xr) {
+    const float za = norm_z(a, ch.mu[i], ch.rs[i], ch.ga[i], ch.be[i], xa);
+    if (PROJ) return za + norm_z(r, ch.mur[i], ch.rsr[i], ch.gr[i], ch.br[i], xr);
     xr = 0.f;
     return za + r;
 }
@@ -103,74 +46,24 @@ template <int VEC>
 __global__ void k_rb_stats(const float *__restrict__ a, const float *__restrict__ r_, double *__restrict__ partial, int C, int CG,
                            int R, long V, long chunk) {
     extern __shared__ double sm[];  // [R][C][2]
-    const int n = blockIdx.y, b = blockIdx.x, nblk = gridDim.x, N = gridDim.y;
-    const float *__restrict__ x = blockIdx.z ? r_ : a;
-    const int t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    const long v0 = (long)b * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
-    if (r < R) {
-        double s[VEC], ss[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; i++) s[i] = ss[i] = 0.0;
-        const size_t base = (size_t)n * V * C + (size_t)g * VEC;
-        long v = v0 + r;
-        for (; v + 3L * R < v1; v += 4L * R) {  // four rows in flight per thread, accumulated in row order
-            float f[4][VEC];
-#pragma unroll
-            for (int u = 0; u < 4; u++) rb_load<VEC>(f[u], x, base + (size_t)(v + (long)u * R) * C);
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-#pragma unroll
-                for (int i = 0; i < VEC; i++) {
-                    s[i] += (double)f[u][i];
-                    ss[i] += (double)f[u][i] * (double)f[u][i];
-                }
-        }
-        for (; v < v1; v += R) {
-            float f[VEC];
-            rb_load<VEC>(f, x, base + (size_t)v * C);
-#pragma unroll
-            for (int i = 0; i < VEC; i++) {
-                s[i] += (double)f[i];
-                ss[i] += (double)f[i] * (double)f[i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            sm[((size_t)r * C + g * VEC + i) * 2 + 0] = s[i];
-            sm[((size_t)r * C + g * VEC + i) * 2 + 1] = ss[i];
-        }
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r < R) {
+        double s[VEC] = {}, ss[VEC] = {};
+        norm_moments<VEC, false>(blockIdx.z ? r_ : a, t.base(V, C), t.v0 + t.r, t.v1, R, C, s, ss);
+        norm_row_store<VEC>(sm, C, t.c0(), t.r, s, ss);
     }
-    __syncthreads();
-    for (int c = t; c < C; c += blockDim.x) {
-        double sa = 0, sq = 0;
-        for (int rr = 0; rr < R; rr++) {
-            sa += sm[((size_t)rr * C + c) * 2 + 0];
-            sq += sm[((size_t)rr * C + c) * 2 + 1];
-        }
-        const size_t o = ((((size_t)blockIdx.z * N + n) * nblk + b) * C + c) * 2;
-        partial[o] = sa;
-        partial[o + 1] = sq;
-    }
+    norm_block_reduce<2>(sm, partial, C, R, ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
 }
 
 // one wave per (c, n, tensor): lanes stride over the block partials, fixed shuffle tree; biased variance, eps inside the root
 __global__ void k_rb_finalize(const double *__restrict__ partial, float *__restrict__ mean_a, float *__restrict__ rstd_a,
                               float *__restrict__ mean_r, float *__restrict__ rstd_r, int C, int nblk, long V, float eps) {
     const int c = blockIdx.x, n = blockIdx.y, N = gridDim.y;
-    double s = 0, q = 0;
-    for (int b = threadIdx.x; b < nblk; b += 64) {
-        const size_t o = ((((size_t)blockIdx.z * N + n) * nblk + b) * C + c) * 2;
-        s += partial[o];
-        q += partial[o + 1];
-    }
-    s = wave_sum(s);
-    q = wave_sum(q);
+    double s[2];
+    norm_wave_sum<2>(partial, C, c, ((size_t)blockIdx.z * N + n) * nblk, nblk, s);
     if (threadIdx.x != 0) return;
-    const double m = s / (double)V;
-    double var = q / (double)V - m * m;
+    const double m = s[0] / (double)V;
+    double var = s[1] / (double)V - m * m;
     if (var < 0) var = 0;
     float *mean = blockIdx.z ? mean_r : mean_a, *rstd = blockIdx.z ? rstd_r : rstd_a;
     mean[(size_t)n * C + c] = (float)m;
@@ -184,47 +77,42 @@ __global__ void k_rb_apply(const float *__restrict__ a, const float *__restrict_
                            const float *__restrict__ gamma_r, const float *__restrict__ beta_r, const float *__restrict__ mean_r,
                            const float *__restrict__ rstd_r, float *__restrict__ y, int C, int CG, int R, long V, long chunk,
                            float slope) {
-    const int n = blockIdx.y, t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    if (r >= R) return;
-    const long v0 = (long)blockIdx.x * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
+    const int n = blockIdx.y;
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r >= R) return;
+    const size_t base = t.base(V, C);
     RbCh<VEC, PROJ> ch;
-    ch.load(n, C, g * VEC, mean_a, rstd_a, gamma_a, beta_a, mean_r, rstd_r, gamma_r, beta_r);
-    const size_t base = (size_t)n * V * C + (size_t)g * VEC;
-    long v = v0 + r;
-    for (; v + (long)R < v1; v += 2L * R) {  // two rows of both tensors in flight
+    ch.load(n, C, t.c0(), mean_a, rstd_a, gamma_a, beta_a, mean_r, rstd_r, gamma_r, beta_r);
+    long v = t.v0 + t.r;
+    for (; v + (long)R < t.v1; v += 2L * R) {  // two rows of both tensors in flight
         float fa[2][VEC], fr[2][VEC];
 #pragma unroll
         for (int u = 0; u < 2; u++) {
-            rb_load<VEC>(fa[u], a, base + (size_t)(v + (long)u * R) * C);
-            rb_load<VEC>(fr[u], r_, base + (size_t)(v + (long)u * R) * C);
+            norm_ld<VEC, false>(a, base + (size_t)(v + (long)u * R) * C, fa[u]);
+            norm_ld<VEC, false>(r_, base + (size_t)(v + (long)u * R) * C, fr[u]);
         }
 #pragma unroll
         for (int u = 0; u < 2; u++) {
 #pragma unroll
             for (int i = 0; i < VEC; i++) {
                 float xa, xr;
-                const float z = rb_z<PROJ>(fa[u][i], fr[u][i], ch.mu[i], ch.rs[i], ch.ga[i], ch.be[i], ch.mur[i], ch.rsr[i],
-                                           ch.gr[i], ch.br[i], xa, xr);
+                const float z = rb_z(ch, i, fa[u][i], fr[u][i], xa, xr);
                 fa[u][i] = z > 0.f ? z : z * slope;
             }
-            rb_store<VEC>(fa[u], y, base + (size_t)(v + (long)u * R) * C);
+            norm_st<VEC, false>(y, base + (size_t)(v + (long)u * R) * C, fa[u]);
         }
     }
-    for (; v < v1; v += R) {
+    for (; v < t.v1; v += R) {
         float fa[VEC], fr[VEC];
-        rb_load<VEC>(fa, a, base + (size_t)v * C);
-        rb_load<VEC>(fr, r_, base + (size_t)v * C);
+        norm_ld<VEC, false>(a, base + (size_t)v * C, fa);
+        norm_ld<VEC, false>(r_, base + (size_t)v * C, fr);
 #pragma unroll
         for (int i = 0; i < VEC; i++) {
             float xa, xr;
-            const float z = rb_z<PROJ>(fa[i], fr[i], ch.mu[i], ch.rs[i], ch.ga[i], ch.be[i], ch.mur[i], ch.rsr[i], ch.gr[i],
-                                       ch.br[i], xa, xr);
+            const float z = rb_z(ch, i, fa[i], fr[i], xa, xr);
             fa[i] = z > 0.f ? z : z * slope;
         }
-        rb_store<VEC>(fa, y, base + (size_t)v * C);
+        norm_st<VEC, false>(y, base + (size_t)v * C, fa);
     }
 }
 
@@ -238,77 +126,55 @@ __global__ void k_rb_bwd_stats(const float *__restrict__ a, const float *__restr
                                int C, int CG, int R, long V, long chunk, float slope) {
     constexpr int NS = PROJ ? 3 : 2;
     extern __shared__ double sm[];  // [R][C][NS]
-    const int n = blockIdx.y, b = blockIdx.x, nblk = gridDim.x;
-    const int t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    const long v0 = (long)b * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
-    if (r < R) {
+    const int n = blockIdx.y;
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r < R) {
+        double s1[VEC] = {}, s2[VEC] = {}, s3[VEC] = {};
+        const size_t base = t.base(V, C);
         RbCh<VEC, PROJ> ch;
-        ch.load(n, C, g * VEC, mean_a, rstd_a, gamma_a, beta_a, mean_r, rstd_r, gamma_r, beta_r);
-        double s1[VEC], s2[VEC], s3[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; i++) s1[i] = s2[i] = s3[i] = 0.0;
-        const size_t base = (size_t)n * V * C + (size_t)g * VEC;
-        long v = v0 + r;
-        for (; v + (long)R < v1; v += 2L * R) {  // two rows of the three tensors in flight, accumulated in row order
+        ch.load(n, C, t.c0(), mean_a, rstd_a, gamma_a, beta_a, mean_r, rstd_r, gamma_r, beta_r);
+        long v = t.v0 + t.r;
+        for (; v + (long)R < t.v1; v += 2L * R) {  // two rows of the three tensors in flight, accumulated in row order
             float fa[2][VEC], fr[2][VEC], fd[2][VEC];
 #pragma unroll
             for (int u = 0; u < 2; u++) {
-                rb_load<VEC>(fa[u], a, base + (size_t)(v + (long)u * R) * C);
-                rb_load<VEC>(fr[u], r_, base + (size_t)(v + (long)u * R) * C);
-                rb_load<VEC>(fd[u], dy, base + (size_t)(v + (long)u * R) * C);
+                norm_ld<VEC, false>(a, base + (size_t)(v + (long)u * R) * C, fa[u]);
+                norm_ld<VEC, false>(r_, base + (size_t)(v + (long)u * R) * C, fr[u]);
+                norm_ld<VEC, false>(dy, base + (size_t)(v + (long)u * R) * C, fd[u]);
             }
 #pragma unroll
             for (int u = 0; u < 2; u++)
 #pragma unroll
                 for (int i = 0; i < VEC; i++) {
                     float xa, xr;
-                    const float z = rb_z<PROJ>(fa[u][i], fr[u][i], ch.mu[i], ch.rs[i], ch.ga[i], ch.be[i], ch.mur[i], ch.rsr[i],
-                                               ch.gr[i], ch.br[i], xa, xr);
+                    const float z = rb_z(ch, i, fa[u][i], fr[u][i], xa, xr);
                     const float gz = z > 0.f ? fd[u][i] : fd[u][i] * slope;
                     s1[i] += (double)gz;
                     s2[i] += (double)gz * (double)xa;
                     if (PROJ) s3[i] += (double)gz * (double)xr;
                 }
         }
-        for (; v < v1; v += R) {
+        for (; v < t.v1; v += R) {
             float fa[VEC], fr[VEC], fd[VEC];
-            rb_load<VEC>(fa, a, base + (size_t)v * C);
-            rb_load<VEC>(fr, r_, base + (size_t)v * C);
-            rb_load<VEC>(fd, dy, base + (size_t)v * C);
+            norm_ld<VEC, false>(a, base + (size_t)v * C, fa);
+            norm_ld<VEC, false>(r_, base + (size_t)v * C, fr);
+            norm_ld<VEC, false>(dy, base + (size_t)v * C, fd);
 #pragma unroll
             for (int i = 0; i < VEC; i++) {
                 float xa, xr;
-                const float z = rb_z<PROJ>(fa[i], fr[i], ch.mu[i], ch.rs[i], ch.ga[i], ch.be[i], ch.mur[i], ch.rsr[i], ch.gr[i],
-                                           ch.br[i], xa, xr);
+                const float z = rb_z(ch, i, fa[i], fr[i], xa, xr);
                 const float gz = z > 0.f ? fd[i] : fd[i] * slope;
                 s1[i] += (double)gz;
                 s2[i] += (double)gz * (double)xa;
                 if (PROJ) s3[i] += (double)gz * (double)xr;
             }
         }
-#pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            const size_t o = ((size_t)r * C + g * VEC + i) * NS;
-            sm[o] = s1[i];
-            sm[o + 1] = s2[i];
-            if (PROJ) sm[o + 2] = s3[i];
-        }
+        if constexpr (PROJ)
+            norm_row_store<VEC>(sm, C, t.c0(), t.r, s1, s2, s3);
+        else
+            norm_row_store<VEC>(sm, C, t.c0(), t.r, s1, s2);
     }
-    __syncthreads();
-    for (int c = t; c < C; c += blockDim.x) {
-        double q[NS];
-#pragma unroll
-        for (int k = 0; k < NS; k++) q[k] = 0;
-        for (int rr = 0; rr < R; rr++)
-#pragma unroll
-            for (int k = 0; k < NS; k++) q[k] += sm[((size_t)rr * C + c) * NS + k];
-        const size_t o = (((size_t)n * nblk + b) * C + c) * NS;
-#pragma unroll
-        for (int k = 0; k < NS; k++) partial[o + k] = q[k];
-    }
+    norm_block_reduce<NS>(sm, partial, C, R, (size_t)n * gridDim.x + blockIdx.x);
 }
 
 // sums[n][c][NS] (float); dgamma / dbeta over n in ascending order.  One wave per channel.
@@ -323,16 +189,9 @@ __global__ void k_rb_bwd_finalize(const double *__restrict__ partial, float *__r
     for (int k = 0; k < NS; k++) tot[k] = 0;
     for (int n = 0; n < N; n++) {
         double q[NS];
-#pragma unroll
-        for (int k = 0; k < NS; k++) q[k] = 0;
-        for (int b = threadIdx.x; b < nblk; b += 64) {
-            const size_t o = (((size_t)n * nblk + b) * C + c) * NS;
-#pragma unroll
-            for (int k = 0; k < NS; k++) q[k] += partial[o + k];
-        }
+        norm_wave_sum<NS>(partial, C, c, (size_t)n * nblk, nblk, q);
 #pragma unroll
         for (int k = 0; k < NS; k++) {
-            q[k] = wave_sum(q[k]);
             if (threadIdx.x == 0) sums[((size_t)n * C + c) * NS + k] = (float)q[k];
             tot[k] += q[k];
         }
@@ -357,45 +216,41 @@ __global__ void k_rb_bwd_apply(const float *__restrict__ a, const float *__restr
                                float *__restrict__ da, float *dr, int accumulate, int C, int CG, int R, long V, long chunk,
                                float slope) {
     constexpr int NS = PROJ ? 3 : 2;
-    const int n = blockIdx.y, t = threadIdx.x;
-    const int g = t % CG, r = t / CG;
-    if (r >= R) return;
-    const long v0 = (long)blockIdx.x * chunk;
-    long v1 = v0 + chunk;
-    if (v1 > V) v1 = V;
+    const int n = blockIdx.y;
+    const NormThread<VEC> t(CG, V, chunk);
+    if (t.r >= R) return;
+    const size_t base = t.base(V, C);
     RbCh<VEC, PROJ> ch;
-    ch.load(n, C, g * VEC, mean_a, rstd_a, gamma_a, beta_a, mean_r, rstd_r, gamma_r, beta_r);
+    ch.load(n, C, t.c0(), mean_a, rstd_a, gamma_a, beta_a, mean_r, rstd_r, gamma_r, beta_r);
     const float invV = 1.0f / (float)V;
     float m1[VEC], m2[VEC], m3[VEC], ka[VEC], kr[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; i++) {
-        const size_t o = ((size_t)n * C + g * VEC + i) * NS;
+        const size_t o = ((size_t)n * C + t.c0() + i) * NS;
         m1[i] = sums[o] * invV;
         m2[i] = sums[o + 1] * invV;
         m3[i] = PROJ ? sums[o + 2] * invV : 0.f;
         ka[i] = ch.ga[i] * ch.rs[i];
         kr[i] = ch.gr[i] * ch.rsr[i];
     }
-    const size_t base = (size_t)n * V * C + (size_t)g * VEC;
-    for (long v = v0 + r; v < v1; v += R) {
+    for (long v = t.v0 + t.r; v < t.v1; v += R) {
         const size_t e = base + (size_t)v * C;
         float fa[VEC], fr[VEC], fd[VEC], fo[VEC];
-        rb_load<VEC>(fa, a, e);
-        rb_load<VEC>(fr, r_, e);
-        rb_load<VEC>(fd, dy, e);
-        if (accumulate) rb_load<VEC>(fo, dr, e);
+        norm_ld<VEC, false>(a, e, fa);
+        norm_ld<VEC, false>(r_, e, fr);
+        norm_ld<VEC, false>(dy, e, fd);
+        if (accumulate) norm_ld<VEC, false>(dr, e, fo);
 #pragma unroll
         for (int i = 0; i < VEC; i++) {
             float xa, xr;
-            const float z = rb_z<PROJ>(fa[i], fr[i], ch.mu[i], ch.rs[i], ch.ga[i], ch.be[i], ch.mur[i], ch.rsr[i], ch.gr[i],
-                                       ch.br[i], xa, xr);
+            const float z = rb_z(ch, i, fa[i], fr[i], xa, xr);
             const float gz = z > 0.f ? fd[i] : fd[i] * slope;
             fa[i] = ka[i] * (gz - m1[i] - xa * m2[i]);
             const float d = PROJ ? kr[i] * (gz - m1[i] - xr * m3[i]) : gz;
             fr[i] = accumulate ? fo[i] + d : d;
         }
-        rb_store<VEC>(fa, da, e);
-        rb_store<VEC>(fr, dr, e);
+        norm_st<VEC, false>(da, e, fa);
+        norm_st<VEC, false>(dr, e, fr);
     }
 }
 
@@ -424,13 +279,13 @@ __global__ void k_avgpool_fwd(const float *__restrict__ x, float *__restrict__ y
                     const size_t e =
                         ((((size_t)n * D + (zo * sd + dz)) * H + (yo * sh + dyy)) * W + (xo * sw + dx)) * C + (size_t)g * VEC;
                     float f[VEC];
-                    rb_load<VEC>(f, x, e);
+                    norm_ld<VEC, false>(x, e, f);
 #pragma unroll
                     for (int k = 0; k < VEC; k++) acc[k] += f[k];
                 }
 #pragma unroll
         for (int k = 0; k < VEC; k++) acc[k] *= inv;
-        rb_store<VEC>(acc, y, (size_t)i * VEC);
+        norm_st<VEC, false>(y, (size_t)i * VEC, acc);
     }
 }
 
@@ -451,11 +306,11 @@ __global__ void k_avgpool_bwd(const float *__restrict__ dy, float *dx, long tota
         const long n = p / D;
         const size_t e = ((((size_t)n * od + zi / sd) * oh + yi / sh) * ow + xi / sw) * C + (size_t)g * VEC;
         float f[VEC], o[VEC];
-        rb_load<VEC>(f, dy, e);
-        if (accumulate) rb_load<VEC>(o, dx, (size_t)i * VEC);
+        norm_ld<VEC, false>(dy, e, f);
+        if (accumulate) norm_ld<VEC, false>(dx, (size_t)i * VEC, o);
 #pragma unroll
         for (int k = 0; k < VEC; k++) f[k] = accumulate ? o[k] + f[k] * inv : f[k] * inv;
-        rb_store<VEC>(f, dx, (size_t)i * VEC);
+        norm_st<VEC, false>(dx, (size_t)i * VEC, f);
     }
 }
 
@@ -495,7 +350,7 @@ extern "C" {
 
 size_t mvd_resblock_workspace_bytes(int N, long V, int C) {
     if (N <= 0 || V <= 0 || C <= 0) return 256;
-    const RbGeom g = rb_geom(N, V, C);
+    const NormGeom g = norm_geom(N, V, C);
     // block partials: 2 tensors x 2 sums (forward) or 3 sums (backward) -> 4 doubles; then sums [N][C][3] floats
     return (size_t)N * g.nblk * C * 4 * sizeof(double) + (size_t)N * C * 3 * sizeof(float) + 256;
 }
@@ -511,7 +366,7 @@ int mvd_resblock_fwd(const float *a, const float *gamma_a, const float *beta_a, 
     MVD_REQUIRE(rb_aligned(a, C) && rb_aligned(r, C) && rb_aligned(y, C),
                 "resblock_fwd: a, r and y must be 16-byte aligned for C %% 4 == 0");
     hipStream_t s = as_stream(stream);
-    const RbGeom g = rb_geom(N, V, C);
+    const NormGeom g = norm_geom(N, V, C);
     double *partial = reinterpret_cast<double *>(ws);
     // have_stats: bit 0 mean_a / rstd_a, bit 1 mean_r / rstd_r are already filled (mvd_instnorm_stats_from_tiles)
     const bool need_a = !(have_stats & 1), need_r = proj && !(have_stats & 2);
@@ -530,10 +385,11 @@ int mvd_resblock_fwd(const float *a, const float *gamma_a, const float *beta_a, 
                            need_a ? rstd_a : rstd_r, mean_r, rstd_r, C, g.nblk, V, eps);
         if (check_launch("resblock finalize")) return 1;
     }
-    const dim3 agrid(g.agrid, N);
+    const long achunk = norm_apply_chunk(g, 65535);  // (the cap: grid.x)
+    const dim3 agrid((unsigned)cdiv(V, achunk), N);
 #define MVD_RB_APPLY(VV, PP)                                                                                                   \
     hipLaunchKernelGGL((k_rb_apply<VV, PP>), agrid, dim3(g.threads), 0, s, a, r, gamma_a, beta_a, mean_a, rstd_a, gamma_r, beta_r, \
-                       mean_r, rstd_r, y, C, g.CG, g.R, V, g.achunk, slope)
+                       mean_r, rstd_r, y, C, g.CG, g.R, V, achunk, slope)
     if (g.vec == 4) {
         if (proj) MVD_RB_APPLY(4, true); else MVD_RB_APPLY(4, false);
     } else {
@@ -557,10 +413,11 @@ int mvd_resblock_bwd(const float *a, const float *r, const float *dy, const floa
     MVD_REQUIRE(rb_aligned(a, C) && rb_aligned(r, C) && rb_aligned(dy, C) && rb_aligned(da, C) && rb_aligned(dr, C),
                 "resblock_bwd: a, r, dy, da and dr must be 16-byte aligned for C %% 4 == 0");
     hipStream_t s = as_stream(stream);
-    const RbGeom g = rb_geom(N, V, C);
+    const NormGeom g = norm_geom(N, V, C);
     double *partial = reinterpret_cast<double *>(ws);
     float *sums = reinterpret_cast<float *>(partial + (size_t)N * g.nblk * C * 4);
-    const dim3 grid(g.nblk, N), agrid(g.agrid, N);
+    const long achunk = norm_apply_chunk(g, 65535);
+    const dim3 grid(g.nblk, N), agrid((unsigned)cdiv(V, achunk), N);
     const size_t lds = (size_t)g.R * C * (proj ? 3 : 2) * sizeof(double);
 #define MVD_RB_BSTATS(VV, PP)                                                                                                  \
     hipLaunchKernelGGL((k_rb_bwd_stats<VV, PP>), grid, dim3(g.threads), lds, s, a, r, dy, gamma_a, beta_a, mean_a, rstd_a,     \
@@ -581,7 +438,7 @@ int mvd_resblock_bwd(const float *a, const float *r, const float *dy, const floa
     if (check_launch("resblock bwd finalize")) return 1;
 #define MVD_RB_BAPPLY(VV, PP)                                                                                                  \
     hipLaunchKernelGGL((k_rb_bwd_apply<VV, PP>), agrid, dim3(g.threads), 0, s, a, r, dy, gamma_a, beta_a, mean_a, rstd_a,      \
-                       gamma_r, beta_r, mean_r, rstd_r, sums, da, dr, accumulate ? 1 : 0, C, g.CG, g.R, V, g.achunk, slope)
+                       gamma_r, beta_r, mean_r, rstd_r, sums, da, dr, accumulate ? 1 : 0, C, g.CG, g.R, V, achunk, slope)
     if (g.vec == 4) {
         if (proj) MVD_RB_BAPPLY(4, true); else MVD_RB_BAPPLY(4, false);
     } else {

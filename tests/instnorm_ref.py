@@ -44,7 +44,7 @@ def norm_geom(N, V, C):
     """(CG, R, threads, nblk, chunk)"""
     CG = C // 4 if C % 4 == 0 else C
     R = max(256 // CG, 1)
-    threads = min(cdiv(R * CG, 64) * 64, 1024)
+    threads = cdiv(R * CG, 64) * 64        # <= 1024 for C <= 1024 (tests/test_norm_geom_host.py)
     want = max(2048 // N, 1)
     nblk = min(max(V // (R * 16), 1), want)
     return CG, R, threads, nblk, cdiv(V, nblk)
