@@ -159,6 +159,50 @@ long mvd_wgrad_wino3_launches(void);
  * column-sum pass runs otherwise).  MVD_WGRAD_BIAS_FOLD=0 / mvd_set_wgrad_bias_fold(0) restore the separate pass (< 0:
  * back to the environment); dw does not depend on it. */
 int mvd_set_wgrad_bias_fold(int on);
+/* What a weight-gradient entry point runs for a shape: the host-only plan the launch code itself consumes (no device call).
+ * transposed 0: mvd_conv3d_wgrad[_bf16] (prologue 1: mvd_conv3d_wgrad_bf16_fused); 1: mvd_convT3d_wgrad[_bf16] of an
+ * [N,D,H,W,C1] input (ksize ignored, C2 = 0).  ws_bytes 0 = what the matching workspace query returns.  want_bias: dbias is
+ * asked for.  Returns 0, or 2 with mvd_last_error for arguments the entry points refuse.  plan[MVD_WG_PLAN_LEN]:
+ *   0 kernel (MVD_WG_*), 1 reduce kernel (MVD_WGR_*), 2 source of the bias gradient (MVD_WGB_*),
+ *   3..7 template configuration TPW, NA, NB, SH, TRI (k_wgrad_wino<NA, NB, NQ>: NQ as TPW; 0 where a kernel has none),
+ *   8..10 tile TD, TH, TW and 11..13 tiles ntd, nth, ntw per sample, 14 ntiles (the z-marching kernels: planes per chunk
+ *   zc x 8 (stride 2: 4) x 32 columns, chunks nzc and column tiles per sample, 14 their units; the scalar kernel: 14 voxels),
+ *   15 nsplit (split-K workgroups), 16 partial tensors each of them writes, 17 ncb, 18 nkb (channel blocks of the grid),
+ *   19 bias rows [K] behind the partials (0: none), 20 workspace bytes the path touches, 21 workspace bytes planned for,
+ *   22.. the switches it read: 22 MVD_WINO mode, 23 wino3 enabled, 24 wino3 minimum items, 25 bias fold, 26 bf16 kernel
+ *   (mvd_set_bf16_wgrad_kernel), 27 scalar engine mode, 28 MVD_WGRAD16_BIG, 29 MVD_WGRAD16_TRI, 30 MVD_WGRAD_DB,
+ *   31 MVD_WGRAD16Z, 32 MVD_WGRAD16ZS, 33 MVD_WGRAD_REDUCE_G16.
+ * fp32 operands that are not 16-byte aligned take MVD_WG_SCALAR whatever the plan says (bf16: refused).
+ * mvd_conv_wgrad_last_kernel: the MVD_WG_* id stored at the launch site by the latest weight-gradient call of the process. */
+#define MVD_WG_NONE 0
+#define MVD_WG_WINO3 1     /* k_wgrad_wino3: fp32 F(2x2x2,3x3x3) */
+#define MVD_WG_WINO2W12 2  /* k_wgrad_wino2w12: fp32 F(2x2,3x3) */
+#define MVD_WG_WINO 3      /* k_wgrad_wino: fp32 F(2,3) along W (MVD_WINO=1) */
+#define MVD_WG_SMALLC 4    /* k_wgrad_smallc: fp32 narrow input */
+#define MVD_WG_MFMA 5      /* k_wgrad_mfma: fp32 generic */
+#define MVD_WG_WGRAD16 6   /* k_wgrad16: bf16 tiled */
+#define MVD_WG_WGRAD16Z 7  /* k_wgrad16z: bf16 z-marching, stride 1 */
+#define MVD_WG_WGRAD16ZS 8 /* k_wgrad16zs: bf16 z-marching, stride 2 */
+#define MVD_WG_SCALAR 9    /* k_wgrad_scalar */
+#define MVD_WG_PLAN_LEN 34
+#define MVD_WGR_F4 1    /* k_wgrad_reduce_f<4> */
+#define MVD_WGR_F16 2   /* k_wgrad_reduce_f<16> */
+#define MVD_WGR_WINO 3  /* k_wgrad_reduce_wino */
+#define MVD_WGR_WINO2 4 /* k_wgrad_reduce_wino2 */
+#define MVD_WGR_WINO3 5 /* k_wgrad_reduce_wino3 */
+#define MVD_WGR_D 6     /* k_wgrad_reduce_d (fp64 partials of the scalar kernel) */
+#define MVD_WGB_NONE 0     /* no dbias asked for */
+#define MVD_WGB_COLSUM 1   /* the column-sum pass over dy */
+#define MVD_WGB_GENERIC 2  /* k_wgrad_mfma, every tap on one dy slot: 4 rows per split */
+#define MVD_WGB_CONVT 3    /* k_wgrad_mfma, transposed conv: 16 rows per split */
+#define MVD_WGB_SMALLC 4   /* k_wgrad_smallc: the idle GEMM row */
+#define MVD_WGB_WINO3 5    /* k_wgrad_wino3: 2 rows per split */
+#define MVD_WGB_WINO2W12 6 /* k_wgrad_wino2w12: 2 rows per split */
+#define MVD_WGB_SLOT28 7   /* k_wgrad16: the idle 28th tap slot */
+#define MVD_WGB_ZMARCH 8   /* k_wgrad16z: one row per split */
+int mvd_conv_wgrad_plan(int transposed, int is_bf16, int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3],
+                        const int stride[3], size_t ws_bytes, int want_bias, int prologue, long *plan);
+int mvd_conv_wgrad_last_kernel(void);
 size_t mvd_conv3d_wgrad_workspace_bytes(int C, int K, int T, int N, int Do, int Ho, int Wo);
 int mvd_conv3d_wgrad(const float *x1, int C1, const float *x2, int C2, const float *dy, float *dw, float *dbias,
                      int N, int D, int H, int W, int K, const int ksize[3], const int stride[3], void *ws,

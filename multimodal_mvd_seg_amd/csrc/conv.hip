@@ -175,7 +175,7 @@ __global__ void k_wgrad_reduce_d(WgradGeom g, const double *__restrict__ partial
     dw[o] = (float)s;
 }
 
-static int wgrad_scalar_split(const WgradGeom &g, long *chunk) {
+int wgrad_scalar_split(const WgradGeom &g, long *chunk) {
     long total = (long)g.N * g.Do * g.Ho * g.Wo;
     long per = (long)g.ntaps * (g.C1 + g.C2) * g.K;
     long nsplit = cdiv(total, 512);
@@ -194,13 +194,14 @@ size_t wgrad_scalar_ws(const WgradGeom &g) {
     return (size_t)ns * g.ntaps * (g.C1 + g.C2) * g.K * sizeof(double) + 256;
 }
 
-int wgrad_scalar(const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws,
-                 size_t ws_bytes, hipStream_t s) {
-    long chunk;
-    int ns = wgrad_scalar_split(g, &chunk);
-    MVD_REQUIRE(ws_bytes >= wgrad_scalar_ws(g), "conv wgrad (scalar): workspace too small");
+int wgrad_scalar(const WgradPlan &p, const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws,
+                 hipStream_t s) {
+    const long chunk = p.chunk;
+    const int ns = p.nsplit;
+    MVD_REQUIRE(p.ws_bytes >= p.needed_ws, "conv wgrad (scalar): workspace too small");
     long per = (long)g.ntaps * (g.C1 + g.C2) * g.K;
     double *partial = reinterpret_cast<double *>(ws);
+    g_wgrad_last_kernel = WG_SCALAR;
     hipLaunchKernelGGL(k_wgrad_scalar, dim3(cdiv(per, 256), ns), dim3(256), 0, s, g, a1, a2, b, partial, chunk);
     if (check_launch("conv wgrad (scalar)")) return 1;
     hipLaunchKernelGGL(k_wgrad_reduce_d, dim3(cdiv(per, 256)), dim3(256), 0, s, g, partial, dw, ns);
@@ -367,15 +368,21 @@ static int run_fwd(const FwdGeom &g, const float *a1, const float *a2, const flo
     return fwd_scalar(g, a1, a2, w, bias, y1, y2, s);
 }
 
+int conv_engine_mode() { return g_engine_mode; }
+
+// the MFMA kernels read 16 bytes at a time: other pointers take the scalar kernel (fp32) or are refused (bf16)
+static bool wgrad_aligned(const void *a1, const void *a2, const void *b) {
+    return (((uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)b) & 15) == 0;
+}
+
 static int run_wgrad(const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws,
                      size_t ws_bytes, hipStream_t s, float *dbias = nullptr, int *dbias_done = nullptr) {
     if (dbias_done) *dbias_done = 0;
-    if (g_engine_mode == 0) {
-        int r = wgrad_mfma(g, a1, a2, b, dw, ws, ws_bytes, s, false, dbias, dbias_done);
-        if (r >= 0) return r;
-        if (dbias_done) *dbias_done = 0;
-    }
-    return wgrad_scalar(g, a1, a2, b, dw, ws, ws_bytes, s);
+    WgradPlan p;
+    int r = wgrad_plan(g, false, ws_bytes, dbias && dbias_done, false, &p);
+    if (r) return r;
+    if (p.kernel != WG_SCALAR && !wgrad_aligned(a1, a2, b)) wgrad_plan_scalar(g, ws_bytes, dbias && dbias_done, &p);
+    return wgrad_launch(p, g, a1, a2, b, dw, ws, s, dbias, dbias_done);
 }
 
 static int run_fwd16(const FwdGeom &g, const uint16_t *a1, const uint16_t *a2, const uint16_t *w, const float *bias,
@@ -396,13 +403,16 @@ static int run_fwd16(const FwdGeom &g, const uint16_t *a1, const uint16_t *a2, c
 
 static int run_wgrad16(const WgradGeom &g, const uint16_t *a1, const uint16_t *a2, const uint16_t *b, float *dw, void *ws,
                        size_t ws_bytes, hipStream_t s, float *dbias = nullptr, int *dbias_done = nullptr) {
-    int r = wgrad_mfma(g, reinterpret_cast<const float *>(a1), reinterpret_cast<const float *>(a2),
-                       reinterpret_cast<const float *>(b), dw, ws, ws_bytes, s, true, dbias, dbias_done);
-    if (r < 0) {
+    if (dbias_done) *dbias_done = 0;
+    WgradPlan p;
+    int r = wgrad_plan(g, true, ws_bytes, dbias && dbias_done, false, &p);
+    if (r == 3 || (r == 0 && !wgrad_aligned(a1, a2, b))) {
         set_error("bf16 wgrad: unsupported shape (needs C %% 32 == 0 and K %% 32 == 0; C=%d+%d K=%d)", g.C1, g.C2, g.K);
         return 3;
     }
-    return r;
+    if (r) return r;
+    return wgrad_launch(p, g, reinterpret_cast<const float *>(a1), reinterpret_cast<const float *>(a2),
+                        reinterpret_cast<const float *>(b), dw, ws, s, dbias, dbias_done);
 }
 
 static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
@@ -624,6 +634,56 @@ int mvd_conv_wgrad_wino3_applicable(int N, int D, int H, int W, int C1, int C2, 
 }
 
 long mvd_wgrad_wino3_launches(void) { return wgrad_wino3_launches(); }
+
+static_assert(MVD_WG_NONE == WG_NONE && MVD_WG_WINO3 == WG_WINO3 && MVD_WG_WINO2W12 == WG_WINO2W12 && MVD_WG_WINO == WG_WINO &&
+                  MVD_WG_SMALLC == WG_SMALLC && MVD_WG_MFMA == WG_MFMA && MVD_WG_WGRAD16 == WG_WGRAD16 &&
+                  MVD_WG_WGRAD16Z == WG_WGRAD16Z && MVD_WG_WGRAD16ZS == WG_WGRAD16ZS && MVD_WG_SCALAR == WG_SCALAR,
+              "kernel ids of the header and of conv_geom.h");
+static_assert(MVD_WGR_F4 == WGR_F4 && MVD_WGR_F16 == WGR_F16 && MVD_WGR_WINO == WGR_WINO && MVD_WGR_WINO2 == WGR_WINO2 &&
+                  MVD_WGR_WINO3 == WGR_WINO3 && MVD_WGR_D == WGR_D,
+              "reduce ids of the header and of conv_geom.h");
+static_assert(MVD_WGB_NONE == WGB_NONE && MVD_WGB_COLSUM == WGB_COLSUM && MVD_WGB_GENERIC == WGB_GENERIC &&
+                  MVD_WGB_CONVT == WGB_CONVT && MVD_WGB_SMALLC == WGB_SMALLC && MVD_WGB_WINO3 == WGB_WINO3 &&
+                  MVD_WGB_WINO2W12 == WGB_WINO2W12 && MVD_WGB_SLOT28 == WGB_SLOT28 && MVD_WGB_ZMARCH == WGB_ZMARCH,
+              "bias-source ids of the header and of conv_geom.h");
+
+int mvd_conv_wgrad_last_kernel(void) { return g_wgrad_last_kernel; }
+
+int mvd_conv_wgrad_plan(int transposed, int is_bf16, int N, int D, int H, int W, int C1, int C2, int K, const int ksize[3],
+                        const int stride[3], size_t ws_bytes, int want_bias, int prologue, long *plan) {
+    MVD_REQUIRE(plan && stride && (transposed || ksize), "conv_wgrad_plan: null pointer");
+    MVD_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && K > 0 && C1 > 0 && C2 >= 0, "conv_wgrad_plan: bad shape");
+    MVD_REQUIRE(!transposed || (C2 == 0 && !prologue), "conv_wgrad_plan: a transposed conv has one input and no loader prologue");
+    MVD_REQUIRE(!prologue || (is_bf16 && C2 == 0), "conv_wgrad_plan: the loader prologue is bf16 with one input");
+    WgradGeom g;
+    size_t query;
+    if (transposed) {
+        for (int a = 0; a < 3; a++) MVD_REQUIRE(stride[a] == 1 || stride[a] == 2, "conv_wgrad_plan: stride must be 1 or 2");
+        convT_wgrad_geom(g, N, D, H, W, C1, K, stride);
+        query = mvd_convT3d_wgrad_workspace_bytes(C1, K, g.T, N, D, H, W);
+    } else {
+        if (check_ks(ksize, stride, "conv_wgrad_plan")) return 2;
+        conv_wgrad_geom(g, N, D, H, W, C1, C2, K, ksize, stride);
+        query = mvd_conv3d_wgrad_workspace_bytes(C1 + C2, K, g.T, N, g.Do, g.Ho, g.Wo);
+    }
+    if (ws_bytes == 0) ws_bytes = query;
+    MVD_REQUIRE(ws_bytes >= query, "conv_wgrad_plan: workspace too small");
+    WgradPlan p;
+    // the bf16 transposed entry point runs the column sums itself, before the weight gradient
+    const bool in_kernel_bias = want_bias && !(transposed && is_bf16);
+    const int r = wgrad_plan(g, is_bf16 != 0, ws_bytes, in_kernel_bias, prologue != 0, &p);
+    if (r == 3 && prologue) set_error("conv_wgrad_plan: shape not served by the z-marching kernel");
+    else if (r == 3) set_error("conv_wgrad_plan: bf16 needs C %% 32 == 0 and K %% 32 == 0 (C=%d+%d K=%d)", C1, C2, K);
+    if (r) return 2;
+    if (want_bias && !in_kernel_bias) p.bias_src = WGB_COLSUM;
+    const long out[MVD_WG_PLAN_LEN] = {p.kernel, p.reduce, p.bias_src, p.TPW, p.NA, p.NB, p.SH, p.TRI, p.TD, p.TH, p.TW,
+                                       p.ntd, p.nth, p.ntw, p.ntiles, p.nsplit, p.partials, p.ncb, p.nkb, p.bias_rows,
+                                       (long)p.needed_ws, (long)p.ws_bytes, p.wino_mode, p.wino3_on, p.wino3_min_items,
+                                       p.bias_fold, p.bf16_kernel, p.engine_mode, p.env_big16, p.env_tri16, p.env_db,
+                                       p.env_16z, p.env_16zs, p.env_reduce_g16};
+    for (int i = 0; i < MVD_WG_PLAN_LEN; i++) plan[i] = out[i];
+    return 0;
+}
 
 int mvd_set_wgrad_bias_fold(int on) {
     set_wgrad_bias_fold(on);
@@ -945,11 +1005,13 @@ int mvd_conv3d_wgrad_bf16_fused(const uint16_t *x1, int C1, const uint16_t *dy, 
                 "conv3d_wgrad_bf16_fused: workspace too small");
     hipStream_t s = as_stream(stream);
     int dbias_done = 0;
-    const int r = wgrad16z_run(g, x1, nullptr, dy, dw, ws, ws_bytes, s, dbias, &dbias_done, in_scale, in_shift, slope);
-    if (r < 0) {
+    WgradPlan p;
+    if (wgrad_plan(g, true, ws_bytes, dbias != nullptr, true, &p)) {
         set_error("conv3d_wgrad_bf16_fused: the z-marching kernel refused the launch (workspace?)");
         return 2;
     }
+    const int r = wgrad_launch(p, g, reinterpret_cast<const float *>(x1), nullptr, reinterpret_cast<const float *>(dy), dw, ws, s,
+                               dbias, &dbias_done, in_scale, in_shift, slope);
     if (r) return r;
     if (dbias && !dbias_done) return colsum(reinterpret_cast<const float *>(dy), dbias, (long)N * g.Do * g.Ho * g.Wo, K, ws, s, true);
     return 0;

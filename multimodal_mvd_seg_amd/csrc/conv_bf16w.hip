@@ -58,10 +58,7 @@ constexpr int WZ_APARTS = (WZ_TH + 2) * WZ_SROW * 4;  // 1360 16-byte parts per 
 static_assert(WZ_LDS <= 160 * 1024, "k_wgrad16z: LDS budget");
 static_assert((WZ_TH - 1) * WZ_ROWB + 16 * 64 + 384 < 65536, "ds_read immediates");
 
-struct WgZTile {
-    int nty, ntx, nzc, zc;   // column tiles, z chunks per column, planes per chunk
-    int nunits, nsplit, nkb;
-};
+// (WgZTile: conv_geom.h)
 
 __device__ inline s16x4w wz_trd(unsigned addr) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4w *)addr);
@@ -655,14 +652,21 @@ __global__ __launch_bounds__(256, 1) void k_wgrad16zs(const WgradGeom g, const W
         }
 }
 
+int wgrad16z_env() {
+    static const int v = getenv("MVD_WGRAD16Z") ? atoi(getenv("MVD_WGRAD16Z")) : 1;
+    return v;
+}
 static int &wgrad16z_mode() {
-    static int v = getenv("MVD_WGRAD16Z") ? atoi(getenv("MVD_WGRAD16Z")) : 1;
+    static int v = wgrad16z_env();
     return v;
 }
 void wgrad16z_enable(int on) { wgrad16z_mode() = on; }
+int wgrad16z_mode_now() { return wgrad16z_mode(); }
+int wgrad16zs_env() {
+    static const int on = getenv("MVD_WGRAD16ZS") ? atoi(getenv("MVD_WGRAD16ZS")) : 1;
+    return on;
+}
 
-// Returns -1 when the problem is not this kernel's (the caller falls through to k_wgrad16), 0 after a launch (the partials
-// [nsplit][27][C][K] and, when pbias_out is set, the bias rows [nsplit][K] are in ws), > 0 on error.
 static bool wgrad16z_shape_ok(const WgradGeom &g) {
     const int C = g.C1 + g.C2;
     if (g.ntaps != 27 || g.T != 27 || g.C1 % 32 != 0 || g.C2 % 32 != 0 || g.K % 32 != 0 || C < 32) return false;
@@ -681,12 +685,24 @@ static bool wgrad16z_shape_ok(const WgradGeom &g) {
 
 bool wgrad16z_prologue_ok(const WgradGeom &g) { return wgrad16z_shape_ok(g) && g.C2 == 0; }
 
-int wgrad16z(const WgradGeom &g, const unsigned short *a1, const unsigned short *a2, const unsigned short *b, void *ws,
-             size_t ws_bytes, bool want_bias, int *nsplit_out, float **pbias_out, hipStream_t s, const float *in_scale,
-             const float *in_shift, float slope) {
-    const bool pro = in_scale != nullptr && in_shift != nullptr;
-    if (!wgrad16z_mode() && !pro) return -1;
-    if (!wgrad16z_shape_ok(g) || (pro && g.C2 != 0)) return -1;
+static void wgz_fill(WgradPlan *p, const WgZTile &tg, int kernel, int th, int ncb, long units) {
+    p->kernel = kernel;
+    p->TPW = 7; p->NA = 0; p->NB = 0; p->SH = 1; p->TRI = 0;
+    p->TD = tg.zc; p->TH = th; p->TW = 32;
+    p->ntd = tg.nzc; p->nth = tg.nty; p->ntw = tg.ntx;
+    p->ntiles = units;
+    p->nsplit = tg.nsplit;
+    p->partials = 1;
+    p->ncb = ncb; p->nkb = tg.nkb;
+    p->tz = tg;
+}
+
+// false when the problem is not k_wgrad16z's (wgrad_plan goes on to k_wgrad16zs and k_wgrad16).  The kernel leaves the
+// partials [nsplit][27][C][K] and, with want_bias, the bias rows [nsplit][K] behind them in the workspace.  pro: the loader
+// prologue -- x is the RAW output of the producing conv and the operand is lrelu(x * scale + shift) (ops.NormActConv3dFn)
+bool wgrad16z_plan(const WgradGeom &g, bool pro, bool want_bias, size_t ws_bytes, WgradPlan *p) {
+    if (!wgrad16z_mode() && !pro) return false;
+    if (!wgrad16z_shape_ok(g) || (pro && g.C2 != 0)) return false;
     const int C = g.C1 + g.C2;
     WgZTile tg;
     tg.nty = (g.Ho + WZ_TH - 1) / WZ_TH;
@@ -694,7 +710,7 @@ int wgrad16z(const WgradGeom &g, const unsigned short *a1, const unsigned short 
     const int ncb = C / 32;
     tg.nkb = g.K / 32;
     const long blocks = (long)ncb * tg.nkb;
-    if (blocks > 65535) return -1;
+    if (blocks > 65535) return false;
     const long columns = (long)g.N * tg.nty * tg.ntx;
     const long per_round = blocks >= 256 ? 1 : 256 / blocks;
     // z chunks per column: the count that minimises rounds x (planes per chunk + the pipeline fill of a chunk)
@@ -714,15 +730,27 @@ int wgrad16z(const WgradGeom &g, const unsigned short *a1, const unsigned short 
     tg.zc = (g.Do + best_nzc - 1) / best_nzc;
     tg.nzc = (g.Do + tg.zc - 1) / tg.zc;
     const long units = columns * tg.nzc;
-    if (units > (1L << 30)) return -1;
+    if (units > (1L << 30)) return false;
     tg.nunits = (int)units;
     const long rounds = (units + per_round - 1) / per_round;
     tg.nsplit = (int)((units + rounds - 1) / rounds);
     const size_t need = (size_t)tg.nsplit * 27 * C * g.K * sizeof(float);
     const size_t need_b = want_bias ? (size_t)tg.nsplit * g.K * sizeof(float) : 0;
-    if (need + need_b > ws_bytes) return -1;
+    if (need + need_b > ws_bytes) return false;
+    wgz_fill(p, tg, WG_WGRAD16Z, WZ_TH, ncb, units);
+    p->pro = pro;
+    p->bias_src = want_bias ? WGB_ZMARCH : WGB_NONE;
+    p->bias_rows = want_bias ? tg.nsplit : 0;
+    p->bias_off = need;
+    p->needed_ws = need + need_b;
+    return true;
+}
+
+int wgrad16z_launch(const WgradPlan &p, const WgradGeom &g, const unsigned short *a1, const unsigned short *a2,
+                    const unsigned short *b, void *ws, hipStream_t s, const float *in_scale, const float *in_shift, float slope) {
+    const bool pro = p.pro != 0;
     float *partial = reinterpret_cast<float *>(ws);
-    float *pbias = want_bias ? partial + need / sizeof(float) : nullptr;
+    float *pbias = p.bias_rows ? reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + p.bias_off) : nullptr;
     typedef void (*kfn_t)(const WgradGeom, const WgZTile, const unsigned short *, const unsigned short *, const unsigned short *,
                           float *, float *, const float *, const float *, float);
     kfn_t kfn = pro ? k_wgrad16z<true> : k_wgrad16z<false>;
@@ -735,38 +763,34 @@ int wgrad16z(const WgradGeom &g, const unsigned short *a1, const unsigned short 
         }
         cf() = true;
     }
-    hipLaunchKernelGGL(kfn, dim3(tg.nsplit, (unsigned)blocks), dim3(256), WZ_LDS, s, g, tg, a1, a2, b, partial, pbias, in_scale, in_shift,
-                       slope);
-    if (check_launch("conv wgrad (bf16 z-marching)")) return 1;
-    *nsplit_out = tg.nsplit;
-    *pbias_out = pbias;
-    return 0;
+    g_wgrad_last_kernel = WG_WGRAD16Z;
+    hipLaunchKernelGGL(kfn, dim3(p.nsplit, (unsigned)(p.ncb * p.nkb)), dim3(256), WZ_LDS, s, g, p.tz, a1, a2, b, partial, pbias,
+                       in_scale, in_shift, slope);
+    return check_launch("conv wgrad (bf16 z-marching)");
 }
 
-
-// stride-2 twin: -1 when the problem is not this kernel's, 0 after a launch (partials [nsplit][27][C][K] in ws; no bias rows)
-int wgrad16zs(const WgradGeom &g, const unsigned short *a1, const unsigned short *a2, const unsigned short *b, void *ws,
-              size_t ws_bytes, int *nsplit_out, hipStream_t s) {
-    static const int on = getenv("MVD_WGRAD16ZS") ? atoi(getenv("MVD_WGRAD16ZS")) : 1;
-    if (!on || !wgrad16z_mode()) return -1;
-    if (g.ntaps != 27 || g.T != 27 || g.C1 % 32 != 0 || g.C2 != 0 || a2 != nullptr || g.K % 64 != 0) return -1;
+// stride-2 twin: false when the problem is not this kernel's; partials [nsplit][27][C][K] in the workspace, no bias rows (the
+// caller runs the column sums)
+bool wgrad16zs_plan(const WgradGeom &g, size_t ws_bytes, WgradPlan *p) {
+    if (!wgrad16zs_env() || !wgrad16z_mode()) return false;
+    if (g.ntaps != 27 || g.T != 27 || g.C1 % 32 != 0 || g.C2 != 0 || g.K % 64 != 0) return false;
     for (int a = 0; a < 3; a++)
-        if (g.sa[a] != 2 || g.sb[a] != 1) return -1;
+        if (g.sa[a] != 2 || g.sb[a] != 1) return false;
     for (int t = 0; t < 27; t++)
         if (g.off[t][0] != t / 9 - 1 || g.off[t][1] != (t / 3) % 3 - 1 || g.off[t][2] != t % 3 - 1 || g.ob[t][0] != 0 ||
             g.ob[t][1] != 0 || g.ob[t][2] != 0)
-            return -1;
-    if (g.Db != g.Do || g.Hb != g.Ho || g.Wb != g.Wo) return -1;
-    if (g.Do != (g.Di - 1) / 2 + 1 || g.Ho != (g.Hi - 1) / 2 + 1 || g.Wo != (g.Wi - 1) / 2 + 1) return -1;
-    if (g.Wo < 32 || g.Ho < 4 || g.Do < 4) return -1;
-    if ((long)g.Hi * g.Wi * g.C1 * 2 >= (1L << 31) || (long)g.Ho * g.Wo * g.K * 2 >= (1L << 31)) return -1;
+            return false;
+    if (g.Db != g.Do || g.Hb != g.Ho || g.Wb != g.Wo) return false;
+    if (g.Do != (g.Di - 1) / 2 + 1 || g.Ho != (g.Hi - 1) / 2 + 1 || g.Wo != (g.Wi - 1) / 2 + 1) return false;
+    if (g.Wo < 32 || g.Ho < 4 || g.Do < 4) return false;
+    if ((long)g.Hi * g.Wi * g.C1 * 2 >= (1L << 31) || (long)g.Ho * g.Wo * g.K * 2 >= (1L << 31)) return false;
     WgZTile tg;
     tg.nty = (g.Ho + WS_TH - 1) / WS_TH;
     tg.ntx = (g.Wo + WS_TW - 1) / WS_TW;
     const int ncb = g.C1 / 32;
     tg.nkb = g.K / 64;
     const long blocks = (long)ncb * tg.nkb;
-    if (blocks > 65535) return -1;
+    if (blocks > 65535) return false;
     const long columns = (long)g.N * tg.nty * tg.ntx;
     const long per_round = blocks >= 256 ? 1 : 256 / blocks;
     long best_cost = -1;
@@ -785,12 +809,19 @@ int wgrad16zs(const WgradGeom &g, const unsigned short *a1, const unsigned short
     tg.zc = (g.Do + best_nzc - 1) / best_nzc;
     tg.nzc = (g.Do + tg.zc - 1) / tg.zc;
     const long units = columns * tg.nzc;
-    if (units > (1L << 30) || units * blocks < 128) return -1;   // (small problems: the tiled kernel)
+    if (units > (1L << 30) || units * blocks < 128) return false;   // (small problems: the tiled kernel)
     tg.nunits = (int)units;
     const long rounds = (units + per_round - 1) / per_round;
     tg.nsplit = (int)((units + rounds - 1) / rounds);
     const size_t need = (size_t)tg.nsplit * 27 * g.C1 * g.K * sizeof(float);
-    if (need > ws_bytes) return -1;
+    if (need > ws_bytes) return false;
+    wgz_fill(p, tg, WG_WGRAD16ZS, WS_TH, ncb, units);
+    p->needed_ws = need;
+    return true;
+}
+
+int wgrad16zs_launch(const WgradPlan &p, const WgradGeom &g, const unsigned short *a1, const unsigned short *b, void *ws,
+                     hipStream_t s) {
     static PerDeviceFlag cfgd;
     if (!cfgd()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_wgrad16zs), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS) !=
@@ -800,10 +831,10 @@ int wgrad16zs(const WgradGeom &g, const unsigned short *a1, const unsigned short
         }
         cfgd() = true;
     }
-    hipLaunchKernelGGL(k_wgrad16zs, dim3(tg.nsplit, (unsigned)blocks), dim3(256), WS_LDS, s, g, tg, a1, b, reinterpret_cast<float *>(ws));
-    if (check_launch("conv wgrad (bf16 z-marching, stride 2)")) return 1;
-    *nsplit_out = tg.nsplit;
-    return 0;
+    g_wgrad_last_kernel = WG_WGRAD16ZS;
+    hipLaunchKernelGGL(k_wgrad16zs, dim3(p.nsplit, (unsigned)(p.ncb * p.nkb)), dim3(256), WS_LDS, s, g, p.tz, a1, b,
+                       reinterpret_cast<float *>(ws));
+    return check_launch("conv wgrad (bf16 z-marching, stride 2)");
 }
 
 }  // namespace mvd

@@ -246,6 +246,84 @@ __host__ __device__ inline void tile_walk_advance(TileWalk &p, const TileWalk &d
     p.n += d.n + c;
 }
 
+// ------------------------------------------------------------------------------------------------ weight-gradient plan
+// The tile descriptors the weight-gradient kernels take by value (k_wgrad_mfma / k_wgrad16 / k_wgrad_smallc / k_wgrad_wino*:
+// WgTile; k_wgrad16z / k_wgrad16zs: WgZTile; k_wgrad_wino3: Wg3Tile) and the plan that fills them.
+struct WgTile {
+    int TD, TH, TW, lTH, lTW;
+    int EAh, EAw, nslotsA, minA[3];
+    int EBh, EBw, nslotsB, minB[3];
+    int magAw, magAhw, magBw, magBhw;  // 16-bit reciprocal multipliers: q = (n * mag) >> 16 (exact, host-verified)
+    int ntd, nth, ntw, nsplit, nkb;
+    int ntiles;
+    int toffA[27], toffB[27];
+    int dbg;
+};
+struct WgZTile {
+    int nty, ntx, nzc, zc;   // column tiles, z chunks per column, planes per chunk
+    int nunits, nsplit, nkb;
+};
+struct Wg3Tile {
+    int ntd, nth, ntw;  // 2 x 8 x 8 tiles along D, H, W
+    int ntiles, nsplit, nkb;
+    TileWalk step;  // tile_walk_at(nsplit): what a split adds per tile
+};
+
+// kernel / reduce / bias-source ids: MVD_WG_*, MVD_WGR_*, MVD_WGB_* of include/mvdseg_hip.h (conv.hip checks they agree)
+enum { WG_NONE = 0, WG_WINO3, WG_WINO2W12, WG_WINO, WG_SMALLC, WG_MFMA, WG_WGRAD16, WG_WGRAD16Z, WG_WGRAD16ZS, WG_SCALAR };
+enum { WGR_NONE = 0, WGR_F4, WGR_F16, WGR_WINO, WGR_WINO2, WGR_WINO3, WGR_D };
+enum { WGB_NONE = 0, WGB_COLSUM, WGB_GENERIC, WGB_CONVT, WGB_SMALLC, WGB_WINO3, WGB_WINO2W12, WGB_SLOT28, WGB_ZMARCH };
+
+// What one weight-gradient call runs: filled by wgrad_plan (conv_mfma.hip; host arithmetic only, no device call, no
+// pointer) and consumed by the launch code -- wgrad_launch launches plan.kernel with plan.tg / tz / t3 and nothing else.
+// The z-marching kernels report their column tile as (TD, TH, TW) = (zc, 8 or 4, 32), (ntd, nth, ntw) = (nzc, nty, ntx)
+// and their units as ntiles.
+struct WgradPlan {
+    int kernel, reduce, bias_src;
+    int TPW, NA, NB, SH, TRI;
+    int TD, TH, TW, ntd, nth, ntw;
+    long ntiles;
+    int nsplit, partials;       // split-K workgroups along grid x; partial tensors each of them writes (2: k_wgrad_mfma)
+    int ncb, nkb;
+    int bias_rows;              // rows [K] behind the partials that the reduce sums into dbias (0: none)
+    size_t bias_off;            // their byte offset in the workspace
+    size_t needed_ws, ws_bytes; // bytes the chosen path touches; the workspace the plan was made for
+    int cfg, pro;               // tile configuration of the tiled kernels; the loader prologue of k_wgrad16z
+    long chunk;                 // k_wgrad_scalar: voxels per split
+    // the switches it read
+    int wino_mode, wino3_on, bias_fold, bf16_kernel, engine_mode;
+    long wino3_min_items;
+    int env_big16, env_tri16, env_db, env_16z, env_16zs, env_reduce_g16;
+    WgTile tg;
+    WgZTile tz;
+    Wg3Tile t3;
+};
+// 0: planned; 1: an error (message set: a workspace below what the tiled kernels need); 3: bf16 and no kernel takes the shape
+int wgrad_plan(const WgradGeom &g, bool bf16_in, size_t ws_bytes, bool want_bias, bool prologue, WgradPlan *plan);
+// k_wgrad_scalar whatever the shape (fp32 operands that are not 16-byte aligned)
+void wgrad_plan_scalar(const WgradGeom &g, size_t ws_bytes, bool want_bias, WgradPlan *plan);
+// launches what the plan says (fp32 operands for bf16_in == false, bf16 bits behind the same pointers otherwise)
+int wgrad_launch(const WgradPlan &p, const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws,
+                 hipStream_t s, float *dbias, int *dbias_done, const float *in_scale = nullptr, const float *in_shift = nullptr,
+                 float slope = 0.f);
+extern int g_wgrad_last_kernel;  // plan.kernel of the most recent launch (one host store beside each hipLaunchKernelGGL)
+// the per-file halves of the plan and of the launch
+int conv_engine_mode();                                     // conv.hip: 0 auto, 1 scalar only
+int wgrad_scalar_split(const WgradGeom &g, long *chunk);    // conv.hip
+bool wgrad16z_plan(const WgradGeom &g, bool pro, bool want_bias, size_t ws_bytes, WgradPlan *p);   // conv_bf16w.hip
+bool wgrad16zs_plan(const WgradGeom &g, size_t ws_bytes, WgradPlan *p);
+int wgrad16z_launch(const WgradPlan &p, const WgradGeom &g, const unsigned short *a1, const unsigned short *a2,
+                    const unsigned short *b, void *ws, hipStream_t s, const float *in_scale, const float *in_shift, float slope);
+int wgrad16zs_launch(const WgradPlan &p, const WgradGeom &g, const unsigned short *a1, const unsigned short *b, void *ws,
+                     hipStream_t s);
+int wgrad16z_mode_now();
+int wgrad16z_env();
+int wgrad16zs_env();
+bool wgrad_wino3_plan(const WgradGeom &g, int nsplit, bool want_bias, size_t ws_bytes, WgradPlan *p);  // conv_wgrad_wino3.hip
+int wgrad_wino3_launch(const WgradPlan &p, const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw,
+                       void *ws, hipStream_t s, float *dbias, int *dbias_done);
+long wgrad_wino3_min_items();
+
 // engines (return 0 ok, >0 error, -1 = shape not supported by this engine)
 int fwd_scalar(const FwdGeom &g, const float *a1, const float *a2, const float *w, const float *bias, float *y1,
                float *y2, hipStream_t s);
@@ -258,13 +336,9 @@ int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w,
              void *ws, size_t ws_bytes, hipStream_t s, float *stats = nullptr, long stats_tiles = 0, int *stats_done = nullptr,
              long *plan = nullptr);
 size_t wgrad_scalar_ws(const WgradGeom &g);
-int wgrad_scalar(const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws,
-                 size_t ws_bytes, hipStream_t s);
+int wgrad_scalar(const WgradPlan &p, const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws,
+                 hipStream_t s);
 size_t wgrad_mfma_ws(const WgradGeom &g);
-// dbias / dbias_done (optional): engines that see every dy value anyway (the 2-D Winograd kernel) also produce the bias
-// gradient and set *dbias_done = 1; otherwise the caller runs the column-sum kernel
-int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws, size_t ws_bytes,
-               hipStream_t s, bool bf16_in = false, float *dbias = nullptr, int *dbias_done = nullptr);
 
 // fp32 Winograd F(2,3)-along-W engine for plain 3x3x3 stride-1 problems (conv_wino.hip); u = Winograd-domain weights
 // stats / stats_done (optional): the F(2x2,3x3) kernel can also emit per-tile (sum y, sum y^2) per output channel,
@@ -293,29 +367,17 @@ int dgrad16s(int N, int D, int H, int W, int C, int K, int Do, int Ho, int Wo, c
 // bf16 z-marching stride-2 forward conv 32 -> 64 channels (conv_bf16s.hip): -1 = not this kernel's shape
 int launch_fwd16ys(const FwdGeom &g, const unsigned short *a1, const unsigned short *a2, const unsigned short *w, const float *bias,
                    unsigned short *y1, unsigned short *y2, hipStream_t s, int ncu);
-// bf16 z-marching weight gradient of the plain 3x3x3 stride-1 conv (conv_bf16w.hip): -1 = not this kernel's problem, 0 = the
-// partials [nsplit][27][C][K] (and, if asked, bias rows [nsplit][K] at *pbias_out) are in ws
-int wgrad16z(const WgradGeom &g, const unsigned short *a1, const unsigned short *a2, const unsigned short *b, void *ws,
-             size_t ws_bytes, bool want_bias, int *nsplit_out, float **pbias_out, hipStream_t s, const float *in_scale = nullptr,
-             const float *in_shift = nullptr, float slope = 0.f);
-// the same + the split reduce into dw / dbias (conv_mfma.hip)
-int wgrad16z_run(const WgradGeom &g, const unsigned short *a1, const unsigned short *a2, const unsigned short *b, float *dw, void *ws,
-                 size_t ws_bytes, hipStream_t s, float *dbias, int *dbias_done, const float *in_scale, const float *in_shift,
-                 float slope);
+// bf16 z-marching weight gradient of the plain 3x3x3 stride-1 conv and its stride-2 twin (conv_bf16w.hip): wgrad16z_plan /
+// wgrad16zs_plan above
 bool wgrad16z_prologue_ok(const WgradGeom &g);
-// stride-2 twin (k_wgrad16zs): partials only, the bias gradient stays with the caller's column-sum pass
-int wgrad16zs(const WgradGeom &g, const unsigned short *a1, const unsigned short *a2, const unsigned short *b, void *ws,
-              size_t ws_bytes, int *nsplit_out, hipStream_t s);
 void wgrad16z_enable(int on);
 int pack_weights_batch(int n, const float *const *w, float *const *wf, float *const *wb, float *const *uf, float *const *ub,
                        const int *K, const int *C, const int *T, const int *transposed, hipStream_t s,
                        float *const *vf = nullptr, float *const *vb = nullptr);
 int wino_mode();                          // MVD_WINO: 0 off, 1 F(2,3) along W, 2 F(2x2,3x3) (default)
-// F(2x2x2,3x3x3) weight gradient (conv_wgrad_wino3.hip): plain 3x3x3 stride-1 conv, 32-multiple channels; -1 = not
-// run (shape, workspace), else the contract of wgrad_mfma.  wgrad_wino3_selected: the engine is on and the layer has the
-// minimum of work items per sample; wgrad_wino3_ws: partials + bias rows for nsplit splits
-int wgrad_wino3(const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws, size_t ws_bytes,
-                int nsplit, hipStream_t s, float *dbias, int *dbias_done);
+// F(2x2x2,3x3x3) weight gradient (conv_wgrad_wino3.hip): plain 3x3x3 stride-1 conv, 32-multiple channels (wgrad_wino3_plan
+// above).  wgrad_wino3_selected: the engine is on and the layer has the minimum of work items per sample;
+// wgrad_wino3_ws: partials + bias rows for nsplit splits
 bool wgrad_wino3_selected(const WgradGeom &g);
 size_t wgrad_wino3_ws(int nsplit, int C, int K);
 int wgrad_wino3_enabled();  // MVD_WGRAD_WINO3: 0 off, 1 (default) on

@@ -1179,16 +1179,7 @@ int fwd_mfma(const FwdGeom &g, const float *a1, const float *a2, const float *w,
 }
 
 // ================================================================================================ wgrad
-struct WgTile {
-    int TD, TH, TW, lTH, lTW;
-    int EAh, EAw, nslotsA, minA[3];
-    int EBh, EBw, nslotsB, minB[3];
-    int magAw, magAhw, magBw, magBhw;  // 16-bit reciprocal multipliers: q = (n * mag) >> 16 (exact, host-verified)
-    int ntd, nth, ntw, nsplit, nkb;
-    int ntiles;
-    int toffA[27], toffB[27];
-    int dbg;
-};
+// (WgTile: conv_geom.h)
 
 // NA / NB: float4 per thread of the A halo / B tile (512 threads: LDS regions are NA*8 KiB and NB*8 KiB).  The NEXT
 // tile's A and B are prefetched into registers while the current tile's MFMAs run.
@@ -2716,10 +2707,16 @@ __global__ __launch_bounds__(64 * G) void k_wgrad_reduce_f(WgradGeom g, const fl
     dw[o] = (float)s;
 }
 
-static void launch_wgrad_reduce_f(unsigned blocks, hipStream_t s, const WgradGeom &g, const float *partial, float *dw, int nsplit,
-                                  const float *pbias, float *dbias, int nrows, int wblocks) {
+// k_wgrad_reduce_f<16> from 64 partials up (MVD_WGRAD_REDUCE_G16=0: always <4>)
+static int wgrad_reduce_g16_env() {
     static const int g16 = getenv("MVD_WGRAD_REDUCE_G16") ? atoi(getenv("MVD_WGRAD_REDUCE_G16")) : 1;
-    if (g16 && nsplit >= 64)
+    return g16;
+}
+static int wgrad_reduce_f_id(int nsplit) { return wgrad_reduce_g16_env() && nsplit >= 64 ? WGR_F16 : WGR_F4; }
+
+static void launch_wgrad_reduce_f(int which, unsigned blocks, hipStream_t s, const WgradGeom &g, const float *partial, float *dw,
+                                  int nsplit, const float *pbias, float *dbias, int nrows, int wblocks) {
+    if (which == WGR_F16)
         hipLaunchKernelGGL(k_wgrad_reduce_f<16>, dim3(blocks), dim3(1024), 0, s, g, partial, dw, nsplit, pbias, dbias, nrows, wblocks);
     else
         hipLaunchKernelGGL(k_wgrad_reduce_f<4>, dim3(blocks), dim3(256), 0, s, g, partial, dw, nsplit, pbias, dbias, nrows, wblocks);
@@ -2761,8 +2758,13 @@ size_t wgrad_mfma_ws(const WgradGeom &g) {
     // split-K partials + the bias-gradient rows (two lane halves per partial; per wave as well for transposed convs: 16 rows
     // per fp32 split = 8 per split counted here)
     size_t ws = (size_t)wgrad_max_split(g) * (g.ntaps * (size_t)(g.C1 + g.C2) + 8) * g.K * sizeof(float) + 256;
-    // the F(2x2x2,3x3x3) kernel: 64 positions at the fp32 split count (one workgroup per CU)
     const int C = g.C1 + g.C2;
+    // the fp32 generic kernel: two partials and up to 16 bias rows per split at ITS split count.  The same bytes as above
+    // while the bf16 count is twice the fp32 one; with more than 256 channel-block pairs both are 1 and the line above is
+    // half of this (the shape then kept its kernel on the scalar kernel's share but lost its in-kernel bias rows)
+    const size_t g2 = (size_t)wgrad_max_split(g, 1) * (2 * g.ntaps * (size_t)C + 16) * g.K * sizeof(float) + 256;
+    if (g2 > ws) ws = g2;
+    // the F(2x2x2,3x3x3) kernel: 64 positions at the fp32 split count (one workgroup per CU)
     if (g.ntaps == 27 && C % 32 == 0 && g.K % 32 == 0) {
         const size_t w3 = wgrad_wino3_ws(wgrad_max_split(g, 1), C, g.K) + 256;
         if (w3 > ws) ws = w3;
@@ -2770,52 +2772,65 @@ size_t wgrad_mfma_ws(const WgradGeom &g) {
     return ws;
 }
 
-// k_wgrad16z + the split reduce.  -1 = not that kernel's problem.  in_scale / in_shift (optional, [N][C1] fp32): the loader
-// prologue -- x is the RAW output of the producing conv and the operand is lrelu(x * scale + shift) (ops.NormActConv3dFn)
-int wgrad16z_run(const WgradGeom &g, const unsigned short *a1, const unsigned short *a2, const unsigned short *b, float *dw, void *ws,
-                 size_t ws_bytes, hipStream_t s, float *dbias, int *dbias_done, const float *in_scale, const float *in_shift,
-                 float slope) {
-    int nsplit_z = 0;
-    float *pbias_z = nullptr;
-    const int C = g.C1 + g.C2;
-    const int rz = wgrad16z(g, a1, a2, b, ws, ws_bytes, dbias && dbias_done, &nsplit_z, &pbias_z, s, in_scale, in_shift, slope);
-    if (rz != 0) return rz;
-    float *partial_z = reinterpret_cast<float *>(ws);
-    const int wblocks = (int)cdiv((long)27 * C * g.K, 64);
-    if (pbias_z) {
-        launch_wgrad_reduce_f((unsigned)(wblocks + cdiv(g.K, 64)), s, g, partial_z, dw, nsplit_z, pbias_z, dbias,
-                           nsplit_z, wblocks);
-        *dbias_done = 1;
-    } else {
-        launch_wgrad_reduce_f((unsigned)(wblocks), s, g, partial_z, dw, nsplit_z, (const float *)nullptr,
-                           (float *)nullptr, 0, 0);
-    }
-    return check_launch("conv wgrad reduce (bf16 z-marching)");
+// process-start A/B switches of the tiled kernels
+static int wgrad16_big_env() {  // bf16, 3x3x3 stride 1 on large volumes: 256-voxel tiles (MVD_WGRAD16_BIG=0: 128)
+    static const int v = getenv("MVD_WGRAD16_BIG") ? atoi(getenv("MVD_WGRAD16_BIG")) : 1;
+    return v;
+}
+static int wgrad16_tri_env() {  // TRI form of k_wgrad16
+    static const int v = getenv("MVD_WGRAD16_TRI") ? atoi(getenv("MVD_WGRAD16_TRI")) : 1;
+    return v;
+}
+static int wgrad_db_env() {  // two LDS images (k_wgrad_mfma)
+    static const int v = getenv("MVD_WGRAD_DB") ? atoi(getenv("MVD_WGRAD_DB")) : 1;
+    return v;
 }
 
-int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws, size_t ws_bytes,
-               hipStream_t s, bool bf16_in, float *dbias, int *dbias_done) {
-    if (dbias_done) *dbias_done = 0;
+int g_wgrad_last_kernel = WG_NONE;
+
+static void wgrad_plan_reset(WgradPlan *P, size_t ws_bytes) {
+    memset(P, 0, sizeof(*P));
+    P->ws_bytes = ws_bytes;
+    P->wino_mode = wino_mode();
+    P->wino3_on = wgrad_wino3_enabled();
+    P->wino3_min_items = wgrad_wino3_min_items();
+    P->bias_fold = wgrad_bias_fold() ? 1 : 0;
+    P->bf16_kernel = wgrad16z_mode_now();
+    P->engine_mode = conv_engine_mode();
+    P->env_big16 = wgrad16_big_env();
+    P->env_tri16 = wgrad16_tri_env();
+    P->env_db = wgrad_db_env();
+    P->env_16z = wgrad16z_env();
+    P->env_16zs = wgrad16zs_env();
+    P->env_reduce_g16 = wgrad_reduce_g16_env();
+}
+
+// the tile of the tiled kernels and the (TPW, NA, NB, SH, TRI) of the template that runs
+static void wgrad_plan_tiled(WgradPlan *P, int kernel, int TPW, int NA, int NB, int SH, int TRI, int ncb, long ntiles) {
+    const WgTile &tg = P->tg;
+    P->kernel = kernel;
+    P->TPW = TPW; P->NA = NA; P->NB = NB; P->SH = SH; P->TRI = TRI;
+    P->TD = tg.TD; P->TH = tg.TH; P->TW = tg.TW;
+    P->ntd = tg.ntd; P->nth = tg.nth; P->ntw = tg.ntw;
+    P->ntiles = ntiles;
+    P->nsplit = tg.nsplit;
+    P->ncb = ncb; P->nkb = tg.nkb;
+}
+
+// The MFMA kernels.  -1 = none of them takes the problem (fp32: the scalar kernel; bf16: an error), 1 = error.
+static int wgrad_plan_mfma(const WgradGeom &g, bool bf16_in, size_t ws_bytes, bool want_bias, WgradPlan *P) {
     if (!wgrad_mfma_ok(g)) return -1;
-    if (((uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)b) & 15) return -1;
     if (bf16_in && (g.C1 % 32 != 0 || g.C2 % 32 != 0 || g.K % 32 != 0)) return -1;
     const int C = g.C1 + g.C2;
     if (bf16_in) {  // plain 3x3x3 stride 1 on volumes at least 32 wide: the z-marching kernel (conv_bf16w.hip)
-        const int rz = wgrad16z_run(g, reinterpret_cast<const unsigned short *>(a1), reinterpret_cast<const unsigned short *>(a2),
-                                    reinterpret_cast<const unsigned short *>(b), dw, ws, ws_bytes, s, dbias, dbias_done, nullptr,
-                                    nullptr, 0.f);
-        if (rz >= 0) return rz;
-        int nsplit_s = 0;   // stride 2: k_wgrad16zs (no bias rows: dbias_done stays 0, the caller runs the column sums)
-        const int rs2 = wgrad16zs(g, reinterpret_cast<const unsigned short *>(a1), reinterpret_cast<const unsigned short *>(a2),
-                                  reinterpret_cast<const unsigned short *>(b), ws, ws_bytes, &nsplit_s, s);
-        if (rs2 > 0) return rs2;
-        if (rs2 == 0) {
-            launch_wgrad_reduce_f((unsigned)cdiv((long)27 * C * g.K, 64), s, g, reinterpret_cast<float *>(ws), dw, nsplit_s,
-                                  (const float *)nullptr, (float *)nullptr, 0, 0);
-            return check_launch("conv wgrad reduce (bf16 z-marching, stride 2)");
+        if (wgrad16z_plan(g, false, want_bias, ws_bytes, P) ||
+            wgrad16zs_plan(g, ws_bytes, P)) {  // stride 2: k_wgrad16zs (no bias rows: the caller runs the column sums)
+            P->reduce = wgrad_reduce_f_id(P->nsplit);
+            if (want_bias && !P->bias_rows) P->bias_src = WGB_COLSUM;
+            return 0;
         }
     }
-    WgTile tg;
+    WgTile &tg = P->tg;
     memset(&tg, 0, sizeof(tg));
     tg.dbg = getenv("MVD_CONV_DBG") ? atoi(getenv("MVD_CONV_DBG")) : 0;
     int mnA[3] = {127, 127, 127}, mxA[3] = {-127, -127, -127}, mnB[3] = {127, 127, 127}, mxB[3] = {-127, -127, -127};
@@ -2831,7 +2846,7 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
     const int cand[5][3] = {{4, 8, 8}, {2, 8, 8}, {2, 4, 8}, {2, 4, 4}, {1, 4, 4}};
     // bf16, 3x3x3 stride 1 on large volumes: 256-voxel tiles (MVD_WGRAD16_BIG=0: 128) -- half the barriers and staging
     // per MFMA, a 6x10x10 halo for 256 voxels instead of 4x10x10 for 128
-    static const int big16 = getenv("MVD_WGRAD16_BIG") ? atoi(getenv("MVD_WGRAD16_BIG")) : 1;
+    const int big16 = wgrad16_big_env();
     int cfg = -1;
     for (int ci = 0; ci < 5 && cfg < 0; ci++) {
         const int T3[3] = {cand[ci][0], cand[ci][1], cand[ci][2]};
@@ -2865,6 +2880,7 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
         tg.EBh = EB[1]; tg.EBw = EB[2]; tg.nslotsB = nB;
     }
     if (cfg < 0) return -1;
+    P->cfg = cfg;
     {   // 16-bit reciprocal multipliers, verified exhaustively for the slot range they are used on
         auto magic = [](int d, int nmax) -> int {
             int m = (1 << 16) / d + 1;
@@ -2905,11 +2921,279 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
         return 1;
     }
     if ((long)ncb * tg.nkb > 65535) return -1;
-    float *partial = reinterpret_cast<float *>(ws);
     const int tpw = (g.ntaps + 3) / 4;
-    dim3 grid(tg.nsplit, ncb * tg.nkb);
-    static const int db_mfma = getenv("MVD_WGRAD_DB") ? atoi(getenv("MVD_WGRAD_DB")) : 1;  // two LDS images (k_wgrad_mfma)
-    if (!bf16_in) tg.dbg = (tg.dbg & ~16) | (db_mfma ? 0 : 16);
+    const int TPW = tpw <= 1 ? 1 : tpw == 2 ? 2 : tpw <= 4 ? 4 : 7;  // the instantiated tap counts per wave
+    if (!bf16_in) tg.dbg = (tg.dbg & ~16) | (wgrad_db_env() ? 0 : 16);
+    bool sameA = true, sameB = true;
+    for (int t = 1; t < g.ntaps; t++) {
+        sameA = sameA && tg.toffA[t] == tg.toffA[0];
+        sameB = sameB && tg.toffB[t] == tg.toffB[0];
+    }
+    P->partials = 1;
+    if (bf16_in) {
+        // bias gradient from the idle 28th tap slot (k_wgrad16): 27 taps, 7 slots per wave, one dy fragment for all taps
+        const bool bias16 = want_bias && (cfg == 0 || cfg == 2) && sameB && tpw == 7 && g.ntaps < 28 &&
+                            need_ws + (size_t)tg.nsplit * g.K * sizeof(float) <= ws_bytes;
+        // TRI: the x-triples of the plain 27-tap stride-1 gather share their halo-row reads (see k_wgrad16)
+        bool tri = wgrad16_tri_env() != 0 && sameB && tpw == 7 && g.ntaps == 27 && tg.TW == 8 && g.sa[2] == 1 &&
+                   tg.TD * tg.TH * tg.TW == (cfg == 2 ? 256 : 128);
+        for (int t = 0; t < 27 && tri; t++) tri = tg.toffA[t] == tg.toffA[t - t % 3] + t % 3;
+        // (the third read of a triple runs two slots past its 10-slot halo row: inside the A image except for the very
+        // last row, where it reads the first bytes of the B image -- both inside the allocation, values never used)
+        if (cfg == 2)  // (chosen only for 27 taps, stride 1, one dy slot for all taps: sameB, tpw == 7)
+            wgrad_plan_tiled(P, WG_WGRAD16, 7, 10, 4, 1, tri, ncb, ntiles);
+        else if (cfg == 0)
+            wgrad_plan_tiled(P, WG_WGRAD16, sameB && tri ? 7 : TPW, 7, 2, sameB ? 1 : 0, sameB && tri, ncb, ntiles);
+        else
+            wgrad_plan_tiled(P, WG_WGRAD16, TPW, 1, 8, sameA ? 2 : 0, 0, ncb, ntiles);
+        P->reduce = wgrad_reduce_f_id(tg.nsplit);
+        P->bias_src = bias16 ? WGB_SLOT28 : want_bias ? WGB_COLSUM : WGB_NONE;
+        P->bias_rows = bias16 ? tg.nsplit : 0;
+        P->bias_off = need_ws;
+        P->needed_ws = need_ws + (bias16 ? (size_t)tg.nsplit * g.K * sizeof(float) : 0);
+        return 0;
+    }
+    const int wino_off = wino_mode() == 0;
+    if (!wino_off && cfg == 0 && g.ntaps == 27 && g.T == 27 && !g.transposed_out && g.C1 % 32 == 0 &&
+        g.C2 % 32 == 0 && g.K % 32 == 0 && tg.TD == 2) {
+        bool plain = true;
+        for (int a = 0; a < 3; a++) plain = plain && g.sa[a] == 1 && g.sb[a] == 1;
+        for (int t = 0; t < 27 && plain; t++)
+            plain = g.wt[t] == t && g.off[t][0] == t / 9 - 1 && g.off[t][1] == (t / 3) % 3 - 1 && g.off[t][2] == t % 3 - 1 &&
+                    g.ob[t][0] == 0 && g.ob[t][1] == 0 && g.ob[t][2] == 0;
+        // F(2x2x2,3x3x3): 64 positions over octets (conv_wgrad_wino3.hip)
+        if (plain && wgrad_wino3_selected(g) && wgrad_wino3_plan(g, wgrad_max_split(g, 1), want_bias, ws_bytes, P)) return 0;
+        const size_t need_w = (size_t)tg.nsplit * 36 * C * g.K * sizeof(float);
+        if (plain && need_w <= ws_bytes) {
+            // Winograd F(2,3)-transposed weight gradient: 36 position tiles over pairs instead of 27 taps over voxels
+            const size_t need_m2 = (size_t)tg.nsplit * 48 * C * g.K * sizeof(float);
+            const size_t need_w2 = need_m2 + (size_t)tg.nsplit * 2 * g.K * sizeof(float);
+            if (wino_mode() == 2 && tg.TH == 8 && tg.TW == 8 && tg.EAh == 10 && tg.EAw == 10 && tg.EBh == 8 && tg.EBw == 8 &&
+                need_w2 <= ws_bytes) {
+                // twelve waves (one plane per wave, 3 per SIMD), two LDS images
+                wgrad_plan_tiled(P, WG_WINO2W12, 0, 5, 2, 1, 0, ncb, ntiles);
+                P->reduce = WGR_WINO2;
+                P->bias_src = want_bias ? WGB_WINO2W12 : WGB_NONE;
+                P->bias_rows = want_bias ? tg.nsplit * 2 : 0;
+                P->bias_off = need_m2;
+                P->needed_ws = need_w2;
+                return 0;
+            }
+            wgrad_plan_tiled(P, WG_WINO, tg.TW == 8 ? 4 : 2, 13, 4, 1, 0, ncb, ntiles);  // k_wgrad_wino<NA, NB, NQ>: NQ as TPW
+            P->reduce = WGR_WINO;
+            P->bias_src = want_bias ? WGB_COLSUM : WGB_NONE;
+            P->needed_ws = need_w;
+            return 0;
+        }
+    }
+    if (cfg == 0 && sameB && g.C2 == 0 && C <= 8 && C % 4 == 0 && g.ntaps * C <= 128 && tg.nslotsA * (C / 4) <= 2 * 256) {
+        // narrow-input layer: rows of the GEMM are (tap, channel) pairs
+        long ns2 = 512 / tg.nkb;
+        if (ns2 < 1) ns2 = 1;
+        if (ns2 > tg.nsplit * 2) ns2 = tg.nsplit * 2;
+        if (ns2 > ntiles) ns2 = ntiles;
+        if ((size_t)ns2 * g.ntaps * C * g.K * sizeof(float) <= ws_bytes) tg.nsplit = (int)ns2;
+        // bias gradient from the idle GEMM row behind the (tap, channel) pairs, one row of K sums per split
+        const size_t need_s = (size_t)tg.nsplit * g.ntaps * C * g.K * sizeof(float);
+        const bool bias_s = wgrad_bias_fold() && want_bias && g.ntaps * C < 128 && g.sb[0] == 1 && g.sb[1] == 1 &&
+                            g.sb[2] == 1 && need_s + (size_t)tg.nsplit * g.K * sizeof(float) <= ws_bytes;
+        wgrad_plan_tiled(P, WG_SMALLC, 0, 2, 4, 1, 0, 1, ntiles);
+        P->reduce = wgrad_reduce_f_id(tg.nsplit);
+        P->bias_src = bias_s ? WGB_SMALLC : want_bias ? WGB_COLSUM : WGB_NONE;
+        P->bias_rows = bias_s ? tg.nsplit : 0;
+        P->bias_off = need_s;
+        P->needed_ws = need_s + (bias_s ? (size_t)tg.nsplit * g.K * sizeof(float) : 0);
+        return 0;
+    }
+    // the generic kernel runs two wave groups per workgroup, each with its own split-K partial
+    const size_t need_g = (size_t)2 * tg.nsplit * g.ntaps * C * g.K * sizeof(float);
+    if (need_g > ws_bytes) {
+        set_error("conv wgrad (mfma): workspace too small for two partials per split");
+        return 1;
+    }
+    // bias gradient inside the kernel when every tap reads the same dy slot and the rows fit behind the partials
+    const bool bias_g = want_bias && cfg == 0 && sameB && need_g + (size_t)4 * tg.nsplit * g.K * sizeof(float) <= ws_bytes;
+    // transposed conv with kernel == stride: the taps' dy slots are disjoint and tile dy (ob = every offset of the stride
+    // box once), and with ntaps a multiple of 4 no wave carries an alias tap -- each wave sums the fragments it stages
+    bool bias_t = false;
+    if (wgrad_bias_fold() && want_bias && cfg == 1 && sameA && g.ntaps == 4 * tpw &&
+        g.ntaps == g.sb[0] * g.sb[1] * g.sb[2] && need_g + (size_t)16 * tg.nsplit * g.K * sizeof(float) <= ws_bytes) {
+        bool box = true;  // tap t <-> offset (pd, ph, pw) of the stride box, each once (convT_wgrad_geom's order)
+        for (int t = 0; t < g.ntaps; t++)
+            box = box && g.ob[t][0] == t / (g.sb[1] * g.sb[2]) && g.ob[t][1] == (t / g.sb[2]) % g.sb[1] &&
+                  g.ob[t][2] == t % g.sb[2];
+        bias_t = box;
+    }
+    if (cfg == 0) wgrad_plan_tiled(P, WG_MFMA, TPW, 7, 2, sameB ? 1 : 0, 0, ncb, ntiles);
+    else wgrad_plan_tiled(P, WG_MFMA, TPW, 1, 8, sameA ? 2 : 0, 0, ncb, ntiles);
+    P->partials = 2;
+    P->reduce = wgrad_reduce_f_id(2 * tg.nsplit);
+    P->bias_src = bias_g ? WGB_GENERIC : bias_t ? WGB_CONVT : want_bias ? WGB_COLSUM : WGB_NONE;
+    P->bias_rows = bias_g ? 4 * tg.nsplit : bias_t ? 16 * tg.nsplit : 0;
+    P->bias_off = need_g;
+    P->needed_ws = need_g + (size_t)P->bias_rows * g.K * sizeof(float);
+    return 0;
+}
+
+int wgrad_plan(const WgradGeom &g, bool bf16_in, size_t ws_bytes, bool want_bias, bool prologue, WgradPlan *P) {
+    wgrad_plan_reset(P, ws_bytes);
+    if (prologue) {  // the fused entry point: k_wgrad16z with the loader prologue or nothing
+        if (!bf16_in || !wgrad16z_plan(g, true, want_bias, ws_bytes, P)) return 3;
+        P->reduce = wgrad_reduce_f_id(P->nsplit);
+        return 0;
+    }
+    if (bf16_in || conv_engine_mode() == 0) {
+        const int r = wgrad_plan_mfma(g, bf16_in, ws_bytes, want_bias, P);
+        if (r >= 0) return r;
+        wgrad_plan_reset(P, ws_bytes);
+    }
+    if (bf16_in) return 3;
+    wgrad_plan_scalar(g, ws_bytes, want_bias, P);
+    return 0;
+}
+
+void wgrad_plan_scalar(const WgradGeom &g, size_t ws_bytes, bool want_bias, WgradPlan *P) {
+    wgrad_plan_reset(P, ws_bytes);
+    long chunk;
+    const int ns = wgrad_scalar_split(g, &chunk);
+    P->kernel = WG_SCALAR;
+    P->reduce = WGR_D;
+    P->bias_src = want_bias ? WGB_COLSUM : WGB_NONE;
+    P->ntiles = (long)g.N * g.Do * g.Ho * g.Wo;
+    P->nsplit = ns;
+    P->partials = 1;
+    P->chunk = chunk;
+    P->needed_ws = wgrad_scalar_ws(g);
+}
+
+int wgrad_launch(const WgradPlan &p, const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws,
+                 hipStream_t s, float *dbias, int *dbias_done, const float *in_scale, const float *in_shift, float slope) {
+    if (dbias_done) *dbias_done = 0;
+    const int C = g.C1 + g.C2;
+    const WgTile &tg = p.tg;
+    float *partial = reinterpret_cast<float *>(ws);
+    float *pbias = p.bias_rows ? reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + p.bias_off) : nullptr;
+    const unsigned short *h1 = reinterpret_cast<const unsigned short *>(a1);
+    const unsigned short *h2 = reinterpret_cast<const unsigned short *>(a2);
+    const unsigned short *hb = reinterpret_cast<const unsigned short *>(b);
+    dim3 grid(p.nsplit, p.ncb * p.nkb);
+    switch (p.kernel) {
+    case WG_SCALAR: return wgrad_scalar(p, g, a1, a2, b, dw, ws, s);
+    case WG_WINO3: return wgrad_wino3_launch(p, g, a1, a2, b, dw, ws, s, dbias, dbias_done);
+    case WG_WGRAD16Z: {
+        const int r = wgrad16z_launch(p, g, h1, h2, hb, ws, s, in_scale, in_shift, slope);
+        if (r) return r;
+        break;
+    }
+    case WG_WGRAD16ZS: {
+        const int r = wgrad16zs_launch(p, g, h1, hb, ws, s);
+        if (r) return r;
+        break;
+    }
+    case WG_WGRAD16: {
+#define WG16T(TPW, NA, NB, SH, TRI)                                                                                          \
+    hipLaunchKernelGGL((k_wgrad16<TPW, NA, NB, SH, TRI>), grid, dim3(256),                                                  \
+                       (size_t)(NA + NB) * 4096 + (size_t)(tg.TD * tg.TH * tg.TW) * 64 + ((TRI) ? 64 : 0), s, g, tg, h1, h2, \
+                       hb, partial,                                                                                          \
+                       (TPW) == 7 && (SH) == 1 ? pbias : nullptr)
+#define WG16(TPW, NA, NB, SH) WG16T(TPW, NA, NB, SH, false)
+#define WG16_TPW(NA, NB, SH)                  \
+    {                                         \
+        if (p.TPW == 1) WG16(1, NA, NB, SH);    \
+        else if (p.TPW == 2) WG16(2, NA, NB, SH); \
+        else if (p.TPW == 4) WG16(4, NA, NB, SH); \
+        else WG16(7, NA, NB, SH);             \
+    }
+        g_wgrad_last_kernel = WG_WGRAD16;
+        if (p.NA == 10) {
+            static PerDeviceFlag cfgd_big;
+            if (!cfgd_big()) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_wgrad16<7, 10, 4, 1>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess) {
+                    set_error("conv wgrad (bf16 mfma): cannot raise the dynamic LDS limit");
+                    return 1;
+                }
+                cfgd_big() = true;
+            }
+            if (p.TRI) {
+                static PerDeviceFlag cfgd_tri;
+                if (!cfgd_tri()) {
+                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_wgrad16<7, 10, 4, 1, true>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess) {
+                        set_error("conv wgrad (bf16 mfma): cannot raise the dynamic LDS limit");
+                        return 1;
+                    }
+                    cfgd_tri() = true;
+                }
+                WG16T(7, 10, 4, 1, true);
+            } else {
+                WG16(7, 10, 4, 1);
+            }
+        } else if (p.NA == 7) {
+            if (p.TRI) WG16T(7, 7, 2, 1, true);
+            else if (p.SH == 1) WG16_TPW(7, 2, 1)
+            else WG16_TPW(7, 2, 0)
+        } else {
+            if (p.SH == 2) WG16_TPW(1, 8, 2)
+            else WG16_TPW(1, 8, 0)
+        }
+#undef WG16_TPW
+#undef WG16
+#undef WG16T
+        if (check_launch("conv wgrad (bf16 mfma)")) return 1;
+        break;
+    }
+    case WG_WINO2W12: {
+        auto kern2 = k_wgrad_wino2w12<5, 2>;  // twelve waves (one plane per wave, 3 per SIMD), two LDS images
+        static PerDeviceFlag cfgd_w2;
+        if (!cfgd_w2()) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern2), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)LDS_LIMIT) != hipSuccess) {
+                set_error("conv wgrad (winograd 2-D): cannot raise the dynamic LDS limit");
+                return 1;
+            }
+            cfgd_w2() = true;
+        }
+        g_wgrad_last_kernel = WG_WINO2W12;
+        hipLaunchKernelGGL(kern2, grid, dim3(768), (size_t)2 * (4 * 100 + 2 * 64) * 128, s, g, tg, a1, a2, b, partial, pbias);
+        if (check_launch("conv wgrad (winograd 2-D)")) return 1;
+        if (pbias) {
+            hipLaunchKernelGGL(k_dbias_reduce, dim3(cdiv(g.K, 64)), dim3(1024), 0, s, pbias, dbias, g.K, p.bias_rows);
+            if (check_launch("conv wgrad dbias reduce")) return 1;
+            *dbias_done = 1;
+        }
+        hipLaunchKernelGGL(k_wgrad_reduce_wino2, dim3(cdiv((long)3 * C * g.K, 64)), dim3(1024), 0, s, partial, dw, C, g.K,
+                           tg.nsplit);
+        return check_launch("conv wgrad reduce (winograd 2-D)");
+    }
+    case WG_WINO: {
+        auto kern = tg.TW == 8 ? k_wgrad_wino<13, 4, 4> : k_wgrad_wino<13, 4, 2>;
+        static PerDeviceFlag cfgd_w[2];
+        if (!cfgd_w[tg.TW == 8]()) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)LDS_LIMIT) != hipSuccess) {
+                set_error("conv wgrad (winograd): cannot raise the dynamic LDS limit");
+                return 1;
+            }
+            cfgd_w[tg.TW == 8]() = true;
+        }
+        g_wgrad_last_kernel = WG_WINO;
+        hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)(13 + 4) * 4096, s, g, tg, a1, a2, b, partial);
+        if (check_launch("conv wgrad (winograd)")) return 1;
+        hipLaunchKernelGGL(k_wgrad_reduce_wino, dim3(cdiv((long)9 * C * g.K, 64)), dim3(256), 0, s, partial, dw, C, g.K,
+                           tg.nsplit);
+        return check_launch("conv wgrad reduce (winograd)");
+    }
+    case WG_SMALLC: {
+        auto kern = k_wgrad_smallc<2, 4>;
+        const size_t lds2 = (size_t)(2 + 4) * 4096 + 32 * 4;
+        g_wgrad_last_kernel = WG_SMALLC;
+        hipLaunchKernelGGL(kern, dim3(tg.nsplit, tg.nkb), dim3(256), lds2, s, g, tg, a1, b, partial, pbias);
+        if (check_launch("conv wgrad (mfma, narrow input)")) return 1;
+        break;
+    }
+    case WG_MFMA: {
+        const int db_mfma = wgrad_db_env();
 #define WG_LAUNCH(TPW, NA, NB, SH)                                                                                   \
     {                                                                                                              \
         auto kern = k_wgrad_mfma<TPW, NA, NB, SH>;                                                                 \
@@ -2926,228 +3210,40 @@ int wgrad_mfma(const WgradGeom &g, const float *a1, const float *a2, const float
         hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, g, tg, a1, a2, b, partial,                               \
                            (SH) == 1 ? pbias_g : (SH) == 2 ? pbias_t : nullptr);                                    \
     }
-    bool sameA = true, sameB = true;
-    for (int t = 1; t < g.ntaps; t++) {
-        sameA = sameA && tg.toffA[t] == tg.toffA[0];
-        sameB = sameB && tg.toffB[t] == tg.toffB[0];
-    }
-    if (bf16_in) {
-        const unsigned short *h1 = reinterpret_cast<const unsigned short *>(a1);
-        const unsigned short *h2 = reinterpret_cast<const unsigned short *>(a2);
-        const unsigned short *hb = reinterpret_cast<const unsigned short *>(b);
-        // bias gradient from the idle 28th tap slot (k_wgrad16): 27 taps, 7 slots per wave, one dy fragment for all taps
-        float *pbias16 = nullptr;
-        if (dbias && dbias_done && (cfg == 0 || cfg == 2) && sameB && tpw == 7 && g.ntaps < 28 &&
-            need_ws + (size_t)tg.nsplit * g.K * sizeof(float) <= ws_bytes)
-            pbias16 = partial + need_ws / sizeof(float);
-        // TRI: the x-triples of the plain 27-tap stride-1 gather share their halo-row reads (see k_wgrad16)
-        static int tri_env = -1;
-        if (tri_env < 0) tri_env = getenv("MVD_WGRAD16_TRI") ? atoi(getenv("MVD_WGRAD16_TRI")) : 1;
-        bool tri = tri_env != 0 && sameB && tpw == 7 && g.ntaps == 27 && tg.TW == 8 && g.sa[2] == 1 &&
-                   tg.TD * tg.TH * tg.TW == (cfg == 2 ? 256 : 128);
-        for (int t = 0; t < 27 && tri; t++) tri = tg.toffA[t] == tg.toffA[t - t % 3] + t % 3;
-        // (the third read of a triple runs two slots past its 10-slot halo row: inside the A image except for the very
-        // last row, where it reads the first bytes of the B image -- both inside the allocation, values never used)
-#define WG16T(TPW, NA, NB, SH, TRI)                                                                                          \
-    hipLaunchKernelGGL((k_wgrad16<TPW, NA, NB, SH, TRI>), grid, dim3(256),                                                  \
-                       (size_t)(NA + NB) * 4096 + (size_t)(tg.TD * tg.TH * tg.TW) * 64 + ((TRI) ? 64 : 0), s, g, tg, h1, h2, \
-                       hb, partial,                                                                                          \
-                       (TPW) == 7 && (SH) == 1 ? pbias16 : nullptr)
-#define WG16(TPW, NA, NB, SH) WG16T(TPW, NA, NB, SH, false)
-#define WG16_TPW(NA, NB, SH)                  \
-    {                                         \
-        if (tpw <= 1) WG16(1, NA, NB, SH);    \
-        else if (tpw == 2) WG16(2, NA, NB, SH); \
-        else if (tpw <= 4) WG16(4, NA, NB, SH); \
-        else WG16(7, NA, NB, SH);             \
-    }
-        if (cfg == 2) {  // (chosen only for 27 taps, stride 1, one dy slot for all taps: sameB, tpw == 7)
-            static PerDeviceFlag cfgd_big;
-            if (!cfgd_big()) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_wgrad16<7, 10, 4, 1>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess) {
-                    set_error("conv wgrad (bf16 mfma): cannot raise the dynamic LDS limit");
-                    return 1;
-                }
-                cfgd_big() = true;
-            }
-            if (tri) {
-                static PerDeviceFlag cfgd_tri;
-                if (!cfgd_tri()) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_wgrad16<7, 10, 4, 1, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess) {
-                        set_error("conv wgrad (bf16 mfma): cannot raise the dynamic LDS limit");
-                        return 1;
-                    }
-                    cfgd_tri() = true;
-                }
-                WG16T(7, 10, 4, 1, true);
-            } else {
-                WG16(7, 10, 4, 1);
-            }
-        } else if (cfg == 0) {
-            if (sameB && tri) WG16T(7, 7, 2, 1, true);
-            else if (sameB) WG16_TPW(7, 2, 1)
-            else WG16_TPW(7, 2, 0)
-        } else {
-            if (sameA) WG16_TPW(1, 8, 2)
-            else WG16_TPW(1, 8, 0)
-        }
-#undef WG16_TPW
-#undef WG16
-#undef WG16T
-        if (check_launch("conv wgrad (bf16 mfma)")) return 1;
-        const long per16 = (long)g.ntaps * C * g.K;
-        const int wblocks = (int)cdiv(per16, 64);
-        if (pbias16) {  // the bias rows ride in the same reduce launch
-            launch_wgrad_reduce_f((unsigned)(wblocks + cdiv(g.K, 64)), s, g, partial, dw, tg.nsplit, pbias16,
-                               dbias, tg.nsplit, wblocks);
-            *dbias_done = 1;
-        } else {
-            launch_wgrad_reduce_f((unsigned)(wblocks), s, g, partial, dw, tg.nsplit, (const float *)nullptr,
-                               (float *)nullptr, 0, 0);
-        }
-        return check_launch("conv wgrad reduce (bf16 mfma)");
-    }
-    const int wino_off = wino_mode() == 0;
-    if (!bf16_in && !wino_off && cfg == 0 && g.ntaps == 27 && g.T == 27 && !g.transposed_out && g.C1 % 32 == 0 &&
-        g.C2 % 32 == 0 && g.K % 32 == 0 && tg.TD == 2) {
-        bool plain = true;
-        for (int a = 0; a < 3; a++) plain = plain && g.sa[a] == 1 && g.sb[a] == 1;
-        for (int t = 0; t < 27 && plain; t++)
-            plain = g.wt[t] == t && g.off[t][0] == t / 9 - 1 && g.off[t][1] == (t / 3) % 3 - 1 && g.off[t][2] == t % 3 - 1 &&
-                    g.ob[t][0] == 0 && g.ob[t][1] == 0 && g.ob[t][2] == 0;
-        if (plain && wgrad_wino3_selected(g)) {  // F(2x2x2,3x3x3): 64 positions over octets (conv_wgrad_wino3.hip)
-            const int r3 = wgrad_wino3(g, a1, a2, b, dw, ws, ws_bytes, wgrad_max_split(g, 1), s, dbias, dbias_done);
-            if (r3 >= 0) return r3;
-        }
-        const size_t need_w = (size_t)tg.nsplit * 36 * C * g.K * sizeof(float);
-        if (plain && need_w <= ws_bytes) {
-            // Winograd F(2,3)-transposed weight gradient: 36 position tiles over pairs instead of 27 taps over voxels
-            const size_t need_m2 = (size_t)tg.nsplit * 48 * C * g.K * sizeof(float);
-            const size_t need_w2 = need_m2 + (size_t)tg.nsplit * 2 * g.K * sizeof(float);
-            if (wino_mode() == 2 && tg.TH == 8 && tg.TW == 8 && tg.EAh == 10 && tg.EAw == 10 && tg.EBh == 8 && tg.EBw == 8 &&
-                need_w2 <= ws_bytes) {
-                float *pbias = (dbias && dbias_done) ? partial + need_m2 / sizeof(float) : nullptr;
-                auto kern2 = k_wgrad_wino2w12<5, 2>;  // twelve waves (one plane per wave, 3 per SIMD), two LDS images
-                static PerDeviceFlag cfgd_w2;
-                if (!cfgd_w2()) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern2), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)LDS_LIMIT) != hipSuccess) {
-                        set_error("conv wgrad (winograd 2-D): cannot raise the dynamic LDS limit");
-                        return 1;
-                    }
-                    cfgd_w2() = true;
-                }
-                hipLaunchKernelGGL(kern2, grid, dim3(768), (size_t)2 * (4 * 100 + 2 * 64) * 128, s, g, tg, a1, a2, b, partial,
-                                   pbias);
-                if (check_launch("conv wgrad (winograd 2-D)")) return 1;
-                if (pbias) {
-                    hipLaunchKernelGGL(k_dbias_reduce, dim3(cdiv(g.K, 64)), dim3(1024), 0, s, pbias, dbias, g.K, tg.nsplit * 2);
-                    if (check_launch("conv wgrad dbias reduce")) return 1;
-                    *dbias_done = 1;
-                }
-                hipLaunchKernelGGL(k_wgrad_reduce_wino2, dim3(cdiv((long)3 * C * g.K, 64)), dim3(1024), 0, s, partial, dw, C,
-                                   g.K, tg.nsplit);
-                return check_launch("conv wgrad reduce (winograd 2-D)");
-            }
-            auto kern = tg.TW == 8 ? k_wgrad_wino<13, 4, 4> : k_wgrad_wino<13, 4, 2>;
-            static PerDeviceFlag cfgd_w[2];
-            if (!cfgd_w[tg.TW == 8]()) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)LDS_LIMIT) != hipSuccess) {
-                    set_error("conv wgrad (winograd): cannot raise the dynamic LDS limit");
-                    return 1;
-                }
-                cfgd_w[tg.TW == 8]() = true;
-            }
-            hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)(13 + 4) * 4096, s, g, tg, a1, a2, b, partial);
-            if (check_launch("conv wgrad (winograd)")) return 1;
-            hipLaunchKernelGGL(k_wgrad_reduce_wino, dim3(cdiv((long)9 * C * g.K, 64)), dim3(256), 0, s, partial, dw, C, g.K,
-                               tg.nsplit);
-            return check_launch("conv wgrad reduce (winograd)");
-        }
-    }
-    if (cfg == 0 && sameB && g.C2 == 0 && C <= 8 && C % 4 == 0 && g.ntaps * C <= 128 && tg.nslotsA * (C / 4) <= 2 * 256) {
-        // narrow-input layer: rows of the GEMM are (tap, channel) pairs
-        long ns2 = 512 / tg.nkb;
-        if (ns2 < 1) ns2 = 1;
-        if (ns2 > tg.nsplit * 2) ns2 = tg.nsplit * 2;
-        if (ns2 > ntiles) ns2 = ntiles;
-        if ((size_t)ns2 * g.ntaps * C * g.K * sizeof(float) <= ws_bytes) tg.nsplit = (int)ns2;
-        auto kern = k_wgrad_smallc<2, 4>;
-        const size_t lds2 = (size_t)(2 + 4) * 4096 + 32 * 4;
-        // bias gradient from the idle GEMM row behind the (tap, channel) pairs, one row of K sums per split
-        const size_t need_s = (size_t)tg.nsplit * g.ntaps * C * g.K * sizeof(float);
-        float *pbias_s = nullptr;
-        if (wgrad_bias_fold() && dbias && dbias_done && g.ntaps * C < 128 && g.sb[0] == 1 && g.sb[1] == 1 && g.sb[2] == 1 &&
-            need_s + (size_t)tg.nsplit * g.K * sizeof(float) <= ws_bytes)
-            pbias_s = partial + need_s / sizeof(float);
-        hipLaunchKernelGGL(kern, dim3(tg.nsplit, tg.nkb), dim3(256), lds2, s, g, tg, a1, b, partial, pbias_s);
-        if (check_launch("conv wgrad (mfma, narrow input)")) return 1;
-        const long per2 = (long)g.ntaps * C * g.K;
-        const int wblocks2 = (int)cdiv(per2, 64);
-        if (pbias_s) {  // the bias rows ride in the same reduce launch
-            launch_wgrad_reduce_f((unsigned)(wblocks2 + cdiv(g.K, 64)), s, g, partial, dw, tg.nsplit, (const float *)pbias_s,
-                               dbias, tg.nsplit, wblocks2);
-            *dbias_done = 1;
-        } else {
-            launch_wgrad_reduce_f((unsigned)wblocks2, s, g, partial, dw, tg.nsplit, (const float *)nullptr, (float *)nullptr, 0,
-                               0);
-        }
-        return check_launch("conv wgrad reduce (mfma)");
-    }
 #define WG_TPW(NA, NB, SH)                     \
     {                                          \
-        if (tpw <= 1) WG_LAUNCH(1, NA, NB, SH) \
-        else if (tpw == 2) WG_LAUNCH(2, NA, NB, SH) \
-        else if (tpw <= 4) WG_LAUNCH(4, NA, NB, SH) \
+        if (p.TPW == 1) WG_LAUNCH(1, NA, NB, SH) \
+        else if (p.TPW == 2) WG_LAUNCH(2, NA, NB, SH) \
+        else if (p.TPW == 4) WG_LAUNCH(4, NA, NB, SH) \
         else WG_LAUNCH(7, NA, NB, SH)          \
     }
-    // the generic kernel runs two wave groups per workgroup, each with its own split-K partial
-    if ((size_t)2 * tg.nsplit * g.ntaps * C * g.K * sizeof(float) > ws_bytes) {
-        set_error("conv wgrad (mfma): workspace too small for two partials per split");
-        return 1;
-    }
-    // bias gradient inside the kernel when every tap reads the same dy slot and the rows fit behind the partials
-    const size_t need_g = (size_t)2 * tg.nsplit * g.ntaps * C * g.K * sizeof(float);
-    float *pbias_g = nullptr;
-    if (dbias && dbias_done && cfg == 0 && sameB && need_g + (size_t)4 * tg.nsplit * g.K * sizeof(float) <= ws_bytes)
-        pbias_g = partial + need_g / sizeof(float);
-    // transposed conv with kernel == stride: the taps' dy slots are disjoint and tile dy (ob = every offset of the stride
-    // box once), and with ntaps a multiple of 4 no wave carries an alias tap -- each wave sums the fragments it stages
-    float *pbias_t = nullptr;
-    if (wgrad_bias_fold() && dbias && dbias_done && cfg == 1 && sameA && g.ntaps == 4 * tpw &&
-        g.ntaps == g.sb[0] * g.sb[1] * g.sb[2] && need_g + (size_t)16 * tg.nsplit * g.K * sizeof(float) <= ws_bytes) {
-        bool box = true;  // tap t <-> offset (pd, ph, pw) of the stride box, each once (convT_wgrad_geom's order)
-        for (int t = 0; t < g.ntaps; t++)
-            box = box && g.ob[t][0] == t / (g.sb[1] * g.sb[2]) && g.ob[t][1] == (t / g.sb[2]) % g.sb[1] &&
-                  g.ob[t][2] == t % g.sb[2];
-        if (box) pbias_t = partial + need_g / sizeof(float);
-    }
-    if (cfg == 0) {
-        if (sameB) WG_TPW(7, 2, 1)
-        else WG_TPW(7, 2, 0)
-    } else {
-        if (sameA) WG_TPW(1, 8, 2)
-        else WG_TPW(1, 8, 0)
-    }
+        float *pbias_g = p.bias_src == WGB_GENERIC ? pbias : nullptr, *pbias_t = p.bias_src == WGB_CONVT ? pbias : nullptr;
+        g_wgrad_last_kernel = WG_MFMA;
+        if (p.NA == 7) {
+            if (p.SH == 1) WG_TPW(7, 2, 1)
+            else WG_TPW(7, 2, 0)
+        } else {
+            if (p.SH == 2) WG_TPW(1, 8, 2)
+            else WG_TPW(1, 8, 0)
+        }
 #undef WG_TPW
 #undef WG_LAUNCH
-    if (check_launch("conv wgrad (mfma)")) return 1;
-    const long per = (long)g.ntaps * C * g.K;
-    const int wblocks = (int)cdiv(per, 64);
-    if (pbias_g) {  // the bias rows ride in the same reduce launch
-        launch_wgrad_reduce_f((unsigned)(wblocks + cdiv(g.K, 64)), s, g, partial, dw, 2 * tg.nsplit,
-                           (const float *)pbias_g, dbias, tg.nsplit * 4, wblocks);
-        *dbias_done = 1;
-    } else if (pbias_t && cfg == 1) {
-        launch_wgrad_reduce_f((unsigned)(wblocks + cdiv(g.K, 64)), s, g, partial, dw, 2 * tg.nsplit,
-                           (const float *)pbias_t, dbias, tg.nsplit * 16, wblocks);
+        if (check_launch("conv wgrad (mfma)")) return 1;
+        break;
+    }
+    default:
+        set_error("conv wgrad: no kernel planned");
+        return 1;
+    }
+    // k_wgrad_reduce_f: the split-K partials and, behind the weight blocks of the same launch, the bias rows
+    const int wblocks = (int)cdiv((long)g.ntaps * C * g.K, 64);
+    const int np = p.nsplit * p.partials;
+    if (pbias) {
+        launch_wgrad_reduce_f(p.reduce, (unsigned)(wblocks + cdiv(g.K, 64)), s, g, partial, dw, np, pbias, dbias, p.bias_rows,
+                              wblocks);
         *dbias_done = 1;
     } else {
-        launch_wgrad_reduce_f((unsigned)(wblocks), s, g, partial, dw, 2 * tg.nsplit, (const float *)nullptr,
-                           (float *)nullptr, 0, 0);
+        launch_wgrad_reduce_f(p.reduce, (unsigned)wblocks, s, g, partial, dw, np, (const float *)nullptr, (float *)nullptr, 0, 0);
     }
     return check_launch("conv wgrad reduce (mfma)");
 }

@@ -33,11 +33,7 @@ namespace mvd {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-struct Wg3Tile {
-    int ntd, nth, ntw;  // 2 x 8 x 8 tiles along D, H, W
-    int ntiles, nsplit, nkb;
-    TileWalk step;  // tile_walk_at(nsplit): what a split adds per tile (conv_geom.h)
-};
+// (Wg3Tile: conv_geom.h)
 
 constexpr int W3_EA = 10, W3_EB = 8;                                          // halo rows / columns of A and of dy
 constexpr int W3_ABYTES = 4 * W3_EA * W3_EA * 128, W3_BBYTES = 2 * W3_EB * W3_EB * 128;
@@ -428,20 +424,21 @@ static long g_wgrad_wino3_launches = 0;
 long wgrad_wino3_launches() { return g_wgrad_wino3_launches; }
 
 size_t wgrad_wino3_ws(int nsplit, int C, int K) { return (size_t)nsplit * ((size_t)64 * C + 2) * K * sizeof(float); }
+long wgrad_wino3_min_items() { return g_wgrad_wino3_min_items; }
 
-int wgrad_wino3(const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw, void *ws, size_t ws_bytes,
-                int nsplit, hipStream_t s, float *dbias, int *dbias_done) {
+// false = not run (tile or block count, buffer range, workspace): wgrad_plan goes on to the F(2x2,3x3) kernels
+bool wgrad_wino3_plan(const WgradGeom &g, int nsplit, bool want_bias, size_t ws_bytes, WgradPlan *p) {
     const int C = g.C1 + g.C2;
     Wg3Tile tg;
     tg.ntd = (g.Do + 1) / 2;
     tg.nth = (g.Ho + 7) / 8;
     tg.ntw = (g.Wo + 7) / 8;
     const long ntiles = (long)g.N * tg.ntd * tg.nth * tg.ntw;
-    if (ntiles > (1L << 30)) return -1;
+    if (ntiles > (1L << 30)) return false;
     tg.ntiles = (int)ntiles;
     tg.nkb = g.K / 32;
     const int ncb = C / 32;
-    if ((long)ncb * tg.nkb > 65535) return -1;
+    if ((long)ncb * tg.nkb > 65535) return false;
     if (nsplit > ntiles) nsplit = (int)ntiles;
     if (nsplit < 1) nsplit = 1;
     tg.nsplit = nsplit;
@@ -449,11 +446,29 @@ int wgrad_wino3(const WgradGeom &g, const float *a1, const float *a2, const floa
     // the buffer offsets of one tile (plane 3 of the A halo, the far corner of dy) must fit the 31-bit buffer range
     if ((long)4 * g.Hi * g.Wi * g.C1 * 4 >= (1L << 31) || (long)4 * g.Hi * g.Wi * g.C2 * 4 >= (1L << 31) ||
         (long)2 * g.Hb * g.Wb * g.K * 4 >= (1L << 31))
-        return -1;
-    if (wgrad_wino3_ws(nsplit, C, g.K) > ws_bytes) return -1;
+        return false;
+    if (wgrad_wino3_ws(nsplit, C, g.K) > ws_bytes) return false;
+    p->kernel = WG_WINO3;
+    p->reduce = WGR_WINO3;
+    p->bias_src = want_bias ? WGB_WINO3 : WGB_NONE;
+    p->bias_rows = want_bias ? nsplit * 2 : 0;
+    p->bias_off = (size_t)nsplit * 64 * C * g.K * sizeof(float);
+    p->TD = 2; p->TH = 8; p->TW = 8;
+    p->ntd = tg.ntd; p->nth = tg.nth; p->ntw = tg.ntw;
+    p->ntiles = ntiles;
+    p->nsplit = nsplit;
+    p->partials = 1;
+    p->ncb = ncb; p->nkb = tg.nkb;
+    p->needed_ws = wgrad_wino3_ws(nsplit, C, g.K);
+    p->t3 = tg;
+    return true;
+}
+
+int wgrad_wino3_launch(const WgradPlan &p, const WgradGeom &g, const float *a1, const float *a2, const float *b, float *dw,
+                       void *ws, hipStream_t s, float *dbias, int *dbias_done) {
+    const int C = g.C1 + g.C2, nsplit = p.nsplit;
     float *partial = reinterpret_cast<float *>(ws);
-    const size_t nm = (size_t)nsplit * 64 * C * g.K;
-    float *pbias = (dbias && dbias_done) ? partial + nm : nullptr;
+    float *pbias = p.bias_rows ? reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + p.bias_off) : nullptr;
     static PerDeviceFlag cfgd;
     if (!cfgd()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_wgrad_wino3), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -463,12 +478,13 @@ int wgrad_wino3(const WgradGeom &g, const float *a1, const float *a2, const floa
         }
         cfgd() = true;
     }
-    hipLaunchKernelGGL(k_wgrad_wino3, dim3(nsplit, ncb * tg.nkb), dim3(1024), (size_t)2 * W3_IMG, s, g, tg, a1, a2, b,
+    g_wgrad_last_kernel = WG_WINO3;
+    hipLaunchKernelGGL(k_wgrad_wino3, dim3(nsplit, p.ncb * p.nkb), dim3(1024), (size_t)2 * W3_IMG, s, g, p.t3, a1, a2, b,
                        partial, pbias);
     if (check_launch("conv wgrad (winograd 3-D)")) return 1;
     g_wgrad_wino3_launches++;
     if (pbias) {
-        if (dbias_reduce(pbias, dbias, g.K, nsplit * 2, s)) return 1;
+        if (dbias_reduce(pbias, dbias, g.K, p.bias_rows, s)) return 1;
         *dbias_done = 1;
     }
     hipLaunchKernelGGL(k_wgrad_reduce_wino3, dim3(cdiv((long)C * g.K, 64)), dim3(1024), 0, s, partial, dw, C, g.K, nsplit);
